@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: training iterations/sec (+ MAD) of the Dual-DMP step on a synthetic 1M-face mesh.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f32|bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f32|bf16] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,7 +15,10 @@ same mesh.  N > 1: the same mesh is face/vertex-partitioned over N ranks with 1-
 dual-dmp_amd/dist.py); `--gpus N` without a torchrun environment starts the N ranks itself (child processes, before
 this process touches a GPU).
 
-Rank 0 prints ONE JSON line (schema in the task contract) with extra objects:
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs DIR is given (see
+dump_outputs), and prints ONE JSON line on rank 0: value (iters/s), ms_per_step, the MAD of the trained positions and the
+f16x3 scale check of the timed iterations.  --full adds the side measurements below to the same line (each one is
+switched by its own option; the objects are null in a plain run):
   roofline            dominant kernel family of the step (by summed time), measured with HIP events on the launch
                       stream in a separate profiled pass of the same step; + "roofline_gather" for the GCN gather
   cpu_baseline        the oracle's PyG-shaped PyTorch-CPU training step timed on this host (bounded sample)
@@ -58,6 +61,12 @@ def parse_args(argv=None):
                     help="feature dtype: f32 (headline line, BASELINE configs[2]) or bf16 features (configs[1] arithmetic)")
     ap.add_argument("--overlap", type=int, default=1, help="1: PosNet on a second stream beside NormalNet")
     ap.add_argument("--graph", type=int, default=1, help="1: replay the iteration as one hipGraph (single-GPU path)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write what the last timed step computed (loss, positions, normals, both parameter arenas) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (CPU baseline + parity, bf16 line, profiled pass / roofline, GEMM arithmetics, "
+                         "randomly numbered and irregular meshes, eval block, other gate, device copy); the options below "
+                         "switch them one by one and have no effect without --full")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-faces", type=int, default=0,
                     help="faces of the CPU-baseline sample; 0 = the bench size when the host has >= 128 GB, else 250,000")
@@ -83,7 +92,13 @@ def parse_args(argv=None):
                          "each float32 path is from it")
     ap.add_argument("--parity", type=int, default=1,
                     help="1: compare the HIP path's first iterations with the oracle iterations the CPU baseline runs (same mesh, same weights)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:
+        if args.kernel_table:
+            ap.error("--kernel-table needs --full (the per-kernel table comes from the profiled pass)")
+        args.no_cpu_baseline, args.bf16_extra, args.extras, args.profile_steps = True, 0, 0, 0
+        args.mode_ab = args.irregular = args.parity = args.parity_f64 = 0
+    return args
 
 
 def self_launch(args):
@@ -612,6 +627,31 @@ def timed_steps(tr, n, sync):
     return (time.perf_counter() - t0) / n * 1e3, loss
 
 
+DUMP_CAP_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(path, loss, pos, norm, params):
+    """--dump-outputs: what the last timed step hands its caller, as <path>/<name>.npy -- loss (float64, shape (1,)), pos
+    (V x 3 float32: PosNet's vertex positions), norm (F x 3 float32: NormalNet's face normals), posnet_params /
+    normalnet_params (the flat float32 parameter arenas after the step's Adam update).  At most DUMP_CAP_BYTES in all: beyond
+    it pos and norm are cut to the same fixed, seeded sample of rows, whose indices go to pos_rows / norm_rows (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {"loss": np.array([loss], dtype=np.float64), "posnet_params": params[0], "normalnet_params": params[1]}
+    rows = {"pos": pos, "norm": norm}
+    budget = DUMP_CAP_BYTES - sum(a.nbytes for a in out.values()) - 65536          # (.npy headers)
+    if sum(a.nbytes for a in rows.values()) <= budget:
+        out.update(rows)
+    else:
+        per_row = sum((a.nbytes // len(a) + 8) * len(a) for a in rows.values())      # (+ a float64 index per kept row)
+        rng = np.random.default_rng(0)
+        for k, a in rows.items():
+            keep = np.sort(rng.choice(len(a), int(budget / per_row * len(a)), replace=False))
+            out[k], out[k + "_rows"] = a[keep], keep.astype(np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def main():
     args = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -702,6 +742,13 @@ def main():
         if float(t[1].item()) > 0 and not scale_overflow:
             scale_overflow = "raised on another rank"
     ms_per_step = elapsed / args.steps * 1e3
+
+    if args.dump_outputs:                # before anything below runs another step on this trainer
+        pos_d = tr.gather_pos() if multi else tr.pos           # (collectives in the partitioned path: every rank calls them)
+        norm_d = tr.gather_norm() if multi else tr.norm
+        if rank == 0:
+            dump_outputs(args.dump_outputs, float(loss), pos_d.float().cpu().numpy(), norm_d.float().cpu().numpy(),
+                         [net.arena.data.float().cpu().numpy() for net in (tr.posnet, tr.normnet)])
 
     # ---- MAD (outside the timed region): float32 positions -> face normals -> mean angular difference
     out = {}
@@ -887,7 +934,7 @@ def main():
     # context for the fractions of the 8 TB/s peak above (outside the timed region).  The yardstick is the library's OWN
     # streaming copy (ddmp_copy_probe: 16 bytes per lane, XCD-contiguous, plain and nontemporal -- the better of the two), next to
     # the guide's 6.29 TB/s float4 copy; torch's copy_ (which round 4 divided by: 4.7-5.1 TB/s) is reported beside it.
-    if rank == 0:
+    if rank == 0 and args.full:
         src = torch.empty(512 * 1024 * 1024, dtype=torch.float32, device=dev).normal_()        # 2 GiB read + 2 GiB written
         dst = torch.empty_like(src)
 

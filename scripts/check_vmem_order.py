@@ -10,7 +10,8 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) > 1:
     asm = sys.argv[1]
 else:
-    asm = os.path.join(tempfile.gettempdir(), "ddmp_gemm_dev.s")
+    tmp = tempfile.TemporaryDirectory(prefix="ddmp_asm_")       # (a fixed name in /tmp collides with other users' runs)
+    asm = os.path.join(tmp.name, "ddmp_gemm_dev.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only",
                            "-S", os.path.join(root, "dual-dmp_amd", "csrc", "gemm.hip"), "-o", asm], stderr=subprocess.DEVNULL)
 lines = open(asm).read().split("\n")

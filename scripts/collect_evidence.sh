@@ -40,7 +40,7 @@ python3 scripts/pmc_traffic.py "$FD" "$WD" "bench.py $PROF: the $STEPS timed ite
 mkdir -p $R/profiles
 cp $O/${TAG}${SUF}_pmc_hbm_traffic.json $R/profiles/
 NOCPU=""; [ "$DT" = "bf16" ] && NOCPU="--no-cpu-baseline"      # (the CPU baseline / parity leg belongs to the f32 line)
-python3 bench.py --dtype $DT --steps 20 --warmup 5 $NOCPU --kernel-table $O/${TAG}${SUF}_bench_kernel_table_hip_events.json > $O/${TAG}${SUF}_bench_line.json 2> $O/${TAG}${SUF}_bench.err
+python3 bench.py --full --dtype $DT --steps 20 --warmup 5 $NOCPU --kernel-table $O/${TAG}${SUF}_bench_kernel_table_hip_events.json > $O/${TAG}${SUF}_bench_line.json 2> $O/${TAG}${SUF}_bench.err
 tail -1 $O/${TAG}${SUF}_bench_line.json | cut -c1-400
 # keep the merge-back small: the raw databases stay on the box
 rm -rf $O/${TAG}${SUF}_prof $O/${TAG}${SUF}_prof_ser $O/${TAG}${SUF}_pmc_F $O/${TAG}${SUF}_pmc_W

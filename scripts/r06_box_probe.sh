@@ -3,7 +3,7 @@
 # with the family times of the profiled pass.   gpurun -- 'bash scripts/r06_box_probe.sh'   (one box per call; appended by hand to profiles/r06_box_probe.txt)
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
-python3 bench.py --no-cpu-baseline --extras 0 --bf16-extra 0 --mode-ab 0 --parity 0 --steps 20 --warmup 5 2>/dev/null | python3 -c "
+python3 bench.py --full --no-cpu-baseline --extras 0 --bf16-extra 0 --mode-ab 0 --parity 0 --steps 20 --warmup 5 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 g = d['roofline']; s = d['roofline_gather']

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R
 mkdir -p gpurun_out
-timeout 600 python3 bench.py --no-cpu-baseline --mode-ab 0 --parity 0 --bf16-extra 0 --extras 0 --steps 20 --warmup 5 2>/dev/null | python3 -c "
+timeout 600 python3 bench.py --full --no-cpu-baseline --mode-ab 0 --parity 0 --bf16-extra 0 --extras 0 --steps 20 --warmup 5 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().split('\n')[-1])
 r, g = d['roofline'], d['roofline_gather']

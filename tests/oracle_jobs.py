@@ -129,36 +129,58 @@ def teacher_forced_oracle(which, k, bnfloop, ep0, iters, check_at, threads=0, me
 # the two cases worth a worker process (tests/test_gpu_path.py: *_at_144k), keyed by the arguments the tests pass
 DEFAULT_K = (3.0, 4.0, 4.0, 4.0, 1.0)                    # main.py:22-26
 BIG_JOBS = {"torus144k": ("torus144k", DEFAULT_K, 1, 0, 2, (1, 2)), "flip144k": ("flip144k", DEFAULT_K, 1, 0, 1, (1,))}
-_FUTURES = {}
-_POOL = None
+_JOBS = {}
+_TMP = None
+
+
+def _run_job(args, threads, path):
+    import torch
+    recs = teacher_forced_oracle(*args, threads)
+    torch.save(recs, path + ".part")
+    os.replace(path + ".part", path)
 
 
 def start_big_jobs(threads=12):
-    """Submit BIG_JOBS to two spawned worker processes (idempotent).  The parent may already hold a GPU context: spawn, not fork."""
-    global _POOL
-    if _POOL is not None:
+    """Start BIG_JOBS in two spawned worker processes (idempotent).  The parent may already hold a GPU context: spawn, not fork.
+    Each worker writes its record to a file and exits: no worker outlives its job, since every process that has loaded
+    PyTorch-ROCm counts against the number of processes a GPU box lets a test session hold open."""
+    global _TMP
+    if _JOBS:
         return
     import multiprocessing as mp
-    from concurrent.futures import ProcessPoolExecutor
-    _POOL = ProcessPoolExecutor(max_workers=len(BIG_JOBS), mp_context=mp.get_context("spawn"))
+    import tempfile
+    _TMP = tempfile.mkdtemp(prefix="ddmp_oracle_jobs_")
+    ctx = mp.get_context("spawn")
     for name, a in BIG_JOBS.items():
-        _FUTURES[name] = _POOL.submit(teacher_forced_oracle, *a, threads)
+        path = os.path.join(_TMP, name + ".pt")
+        p = ctx.Process(target=_run_job, args=(a, threads, path), daemon=True)
+        p.start()
+        _JOBS[name] = (p, path)
 
 
 def big_job(name):
     """The record of a BIG_JOBS case: from its worker when start_big_jobs() ran, else None (the caller computes it inline)."""
-    f = _FUTURES.get(name)
-    if f is None:
+    job = _JOBS.get(name)
+    if job is None:
         return None
-    try:
-        return f.result(timeout=3000)
-    except Exception as e:      # noqa: BLE001  (a worker that could not start must not fail the comparison: compute inline)
-        print("oracle_jobs: worker for %s failed (%s: %s); computing inline" % (name, type(e).__name__, e), file=sys.stderr)
+    p, path = job
+    p.join(timeout=3000)
+    if p.is_alive() or p.exitcode != 0 or not os.path.exists(path):
+        # (a worker that could not finish must not fail the comparison: compute inline)
+        print("oracle_jobs: worker for %s failed (exit code %s); computing inline" % (name, p.exitcode), file=sys.stderr)
         return None
+    import torch
+    return torch.load(path, weights_only=False)
 
 
 def shutdown():
-    global _POOL
-    if _POOL is not None:
-        _POOL.shutdown(wait=False, cancel_futures=True)
-        _POOL = None
+    global _TMP
+    for p, _ in _JOBS.values():
+        if p.is_alive():
+            p.terminate()
+        p.join(timeout=10)
+    _JOBS.clear()
+    if _TMP is not None:
+        import shutil
+        shutil.rmtree(_TMP, ignore_errors=True)
+        _TMP = None

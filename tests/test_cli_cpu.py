@@ -252,6 +252,62 @@ def test_bench_parity_object_bounds():
     assert not out["vs_float64"]["hip_within_2x_of_the_float32_reference"] and not out["ok"]
 
 
+def _load_bench():
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("ddmp_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_run_switches_the_side_measurements_off():
+    """A plain bench.py run times the steps only; --full runs every side measurement by default, each switchable."""
+    bench = _load_bench()
+    a = bench.parse_args(["--steps", "7", "--irregular", "1"])
+    assert a.steps == 7 and not a.full and a.no_cpu_baseline
+    assert (a.extras, a.bf16_extra, a.profile_steps, a.mode_ab, a.irregular, a.parity) == (0, 0, 0, 0, 0, 0)
+    a = bench.parse_args(["--full"])
+    assert a.full and not a.no_cpu_baseline and a.profile_steps > 0
+    assert (a.extras, a.bf16_extra, a.mode_ab, a.irregular, a.parity) == (1, 1, 1, 1, 1)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--kernel-table", "table.json"])
+
+
+def test_bench_inputs_are_identical_from_run_to_run():
+    """--dump-outputs compares two builds output for output: the bench mesh, its features and targets must not vary."""
+    bench = _load_bench()
+    a, b = bench.build_case(2000, "native"), bench.build_case(2000, "native")
+    for m, n in zip(a[:3], b[:3]):
+        assert np.array_equal(m.vs, n.vs) and np.array_equal(m.faces, n.faces)
+    for k, v in vars(a[3]).items():
+        if isinstance(v, (torch.Tensor, np.ndarray)):
+            assert np.array_equal(np.asarray(v), np.asarray(vars(b[3])[k])), k
+
+
+def test_bench_dump_is_capped_by_a_fixed_sample(tmp_path):
+    """Beyond 64 MB the per-row outputs are cut to the same seeded sample of rows every time, with their indices beside them."""
+    bench = _load_bench()
+    rng = np.random.default_rng(5)
+    pos, norm = rng.random((2_000_000, 3), dtype=np.float32), rng.random((4_000_000, 3), dtype=np.float32)
+    params = [rng.random(750_000, dtype=np.float32), rng.random(750_000, dtype=np.float32)]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), 2.5, pos, norm, params)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(["loss.npy", "pos.npy", "norm.npy", "pos_rows.npy", "norm_rows.npy", "posnet_params.npy",
+                            "normalnet_params.npy"])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 1024 * 1024
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f)) for f in files)
+    assert got["loss"].dtype == np.float64 and got["loss"][0] == 2.5 and np.array_equal(got["posnet_params"], params[0])
+    for k, full in (("pos", pos), ("norm", norm)):
+        rows = got[k + "_rows"].astype(np.int64)
+        assert 0 < len(rows) < len(full) and np.all(np.diff(rows) > 0) and np.array_equal(got[k], full[rows])
+    bench.dump_outputs(str(tmp_path / "small"), 2.5, pos[:1000], norm[:2000], params)
+    assert sorted(os.listdir(tmp_path / "small")) == sorted(["loss.npy", "pos.npy", "norm.npy", "posnet_params.npy",
+                                                             "normalnet_params.npy"])
+
+
 def test_self_launch_builds_the_launcher_command(monkeypatch):
     """`main.py --gpus N` outside a launcher starts torch.distributed.run as a CHILD (never an exec: this process may not have
     touched a GPU, the children do) with a standalone loopback rendezvous -- the launcher picks its own port -- and hands the

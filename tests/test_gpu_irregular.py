@@ -370,28 +370,44 @@ SWITCHES = [{"DDMP_SPMM_PATCH": "1"}, {"DDMP_SPMM_PATCH": "0"}, {"DDMP_SPMM_PATC
 
 
 _SWITCH_RUNS = {}
+SWITCH_RUNS_AT_ONCE = 2      # each switched run is a process with the GPU open, beside this one: a GPU box limits how many
 
 
-def _switch_runs():
-    """All five switched re-runs are started TOGETHER, by whichever of the parametrised tests below runs first (each is a pytest
-    process of ~60 s, most of it start-up and host-side mesh building: one after the other they were 300 of the suite's 810 s)."""
-    if not _SWITCH_RUNS:
-        for env in SWITCHES:
-            e = dict(os.environ)
-            e.update(env)
-            key = tuple(sorted(env.items()))
-            _SWITCH_RUNS[key] = subprocess.Popen(
+def _switch_run(request, env):
+    """The switched run of `env`, started together with the next selected ones up to SWITCH_RUNS_AT_ONCE (each is a pytest
+    process of ~60 s, most of it start-up and host-side mesh building: one after the other they were 300 of the suite's 810 s).
+    Every test waits for its own run, so no more than SWITCH_RUNS_AT_ONCE are ever alive."""
+    key = lambda e: tuple(sorted(e.items()))
+    selected = [it.callspec.params["env"] for it in request.session.items
+                if getattr(it, "originalname", "") == "test_irregular_graphs_under_switch" and hasattr(it, "callspec")]
+    keys = [key(e) for e in selected]
+    i = keys.index(key(env)) if key(env) in keys else 0
+    for e in ([env] + selected[i + 1: i + SWITCH_RUNS_AT_ONCE])[:SWITCH_RUNS_AT_ONCE]:
+        if key(e) not in _SWITCH_RUNS:
+            full = dict(os.environ)
+            full.update(e)
+            _SWITCH_RUNS[key(e)] = subprocess.Popen(
                 [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-x", "-q", "-m", "gpu", "-k", "not under_switch",
-                 "-p", "no:cacheprovider"], env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=os.path.dirname(HERE))
-    return _SWITCH_RUNS
+                 "-p", "no:cacheprovider"], env=full, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                cwd=os.path.dirname(HERE))
+    return _SWITCH_RUNS[key(env)]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _no_switch_run_outlives_the_module():
+    yield
+    for proc in _SWITCH_RUNS.values():
+        if proc.poll() is None:
+            proc.kill()
+            proc.communicate()
 
 
 @pytest.mark.parametrize("env", SWITCHES, ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
-def test_irregular_graphs_under_switch(env):
+def test_irregular_graphs_under_switch(request, env):
     """The tests above once more, in their own process, with the gather's kernel selection switched (read once per process)."""
     if any(k.startswith("DDMP_SPMM") for k in os.environ):
         pytest.skip("already inside a switched run")
-    proc = _switch_runs()[tuple(sorted(env.items()))]
+    proc = _switch_run(request, env)
     try:
         out, err = proc.communicate(timeout=1500)
     except subprocess.TimeoutExpired:

@@ -443,13 +443,18 @@ def test_gemm_nn_with_bn_backward_reductions(dev, n, M, K):
 @pytest.mark.parametrize("n,K,M", [(20777, 512, 512), (70001, 64, 256), (21000, 96, 384), (513, 256, 128), (130, 8, 32),
                                    (30001, 64, 128), (20480, 32, 64), (22222, 128, 32)])
 def test_gemm_nt_stats_matches_bn_stats(dev, gemm_mode, n, K, M):
-    """Statistics from the GEMM epilogue (panel shapes) or from the fallback pass == bn_stats of the stored output."""
+    """Statistics from the GEMM epilogue (panel shapes) or from the fallback pass == bn_stats of the stored output.  Where only
+    the fallback pass runs (f32-input MFMA, or the row panels switched off) a width it does not take is refused."""
     from dual_dmp_amd import ops
-    if M & (M - 1) and (gemm_mode == 0 or os.environ.get("DDMP_GEMM_PANEL") == "0"):
-        pytest.skip("the fallback pass (ddmp_bn_stats_f32) takes power-of-two widths only")
     torch.manual_seed(n + M)
     a, w, bias = torch.randn(n, K) + 0.3, torch.randn(M, K) / K ** 0.5, torch.randn(M)
     sums = torch.zeros(2 * M, dtype=torch.float64, device=dev)
+    if M & (M - 1) and (gemm_mode == 0 or os.environ.get("DDMP_GEMM_PANEL") == "0"):
+        # the fallback pass (ddmp_bn_stats_f32) takes power-of-two widths only: DDMP_EINVAL, no statistics it did not compute
+        with pytest.raises(ops.DdmpError, match=r"ddmp_gemm_nt_stats_f32 failed: status -1 "):
+            ops.gemm_nt_stats(a.to(dev), w.to(dev), sums, bias=bias.to(dev))
+        assert not sums.any()
+        return
     y = ops.gemm_nt_stats(a.to(dev), w.to(dev), sums, bias=bias.to(dev))
     ref = a.double() @ w.double().t() + bias.double()
     assert relerr(y, ref) < GEMM_TOL[gemm_mode]
