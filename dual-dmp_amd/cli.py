@@ -51,6 +51,9 @@ def get_parser(real: bool):
     if not real:
         p.add_argument("--viewer", action="store_true", default=True)
         p.add_argument("--port", type=int, default=8080)
+        p.add_argument("--hd", action="store_true",
+                       help="print hd=<two-sided mean surface distance / bbox diagonal> (check/hausdorff_checker.py's figure, "
+                            "on the GPU) whenever an OBJ is saved and at the end; off by default")
     p.add_argument("--no_graph", action="store_true", help="launch every kernel eagerly on one stream (default: one hipGraph per iteration, PosNet and NormalNet on two streams)")
     p.add_argument("--seed", type=int, default=None, help="torch seed for the weight init (the reference is unseeded)")
     p.add_argument("--gpus", type=int, default=1,
@@ -85,6 +88,7 @@ def train_loop(tr, args, mesh_dic, real, rank=0, world=1, evaluator=None, out_di
     gt_mesh, n_mesh, o1_mesh = mesh_dic["gt_mesh"], mesh_dic["n_mesh"], mesh_dic["o1_mesh"]
     get_pos = tr.gather_pos if world > 1 else (lambda: tr.pos)
     mad_value = None
+    want_hd = getattr(args, "hd", False) and evaluator is not None
     if gt_mesh is not None and not real:
         mad_value = Loss.mad(n_mesh.fn, gt_mesh.fn)
         if rank == 0:
@@ -107,8 +111,14 @@ def train_loop(tr, args, mesh_dic, real, rank=0, world=1, evaluator=None, out_di
                         o1_mesh.vs = pos.to("cpu").detach().numpy().copy()
                         name = "_ddmp.obj" if real or evaluator is None else "_ddmp={:.3f}.obj".format(mad_value)
                         Mesh.save(o1_mesh, out_dir + "/" + str(epoch) + name)
+                    if save and want_hd:
+                        log("hd={:.7f}".format(evaluator.hausdorff(pos)["hd"]))
     if mad_value is not None and rank == 0:
         log("final_mad: {:.3f}".format(mad_value))
+    if want_hd:
+        pos = get_pos()                                          # (with peers: every rank enters the all-gather)
+        if rank == 0:
+            log("hd={:.7f}".format(evaluator.hausdorff(pos)["hd"]))
     return mad_value
 
 
@@ -122,6 +132,8 @@ def run(argv=None, real: bool = False):
     rank, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     if rank == 0:
         for k, v in vars(args).items():
+            if k == "hd" and not v:                              # (opt-in: without it the output stays as it was)
+                continue
             print("{:12s}: {}".format(k, v))
     from . import datamaker
     from .evaluate import Evaluator
@@ -162,7 +174,8 @@ def run(argv=None, real: bool = False):
     out_dir = "datasets/" + mesh_name + "/output"
     if rank == 0:
         os.makedirs(out_dir, exist_ok=True)
-    ev = Evaluator(n_mesh, gt_mesh.fn, device) if (gt_mesh is not None and not real and rank == 0) else None
+    ev = Evaluator(n_mesh, gt_mesh.fn, device, gt_mesh=gt_mesh if getattr(args, "hd", False) else None) \
+        if (gt_mesh is not None and not real and rank == 0) else None
     # (ranks > 0 pass a stand-in so that they enter the evaluation's all-gather at the same epochs)
     evaluator = ev if rank == 0 else (object() if (gt_mesh is not None and not real) else None)
     train_loop(tr, args, mesh_dic, real, rank, world, evaluator, out_dir)

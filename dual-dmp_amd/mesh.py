@@ -50,6 +50,14 @@ def _csr_from_pairs(rows: np.ndarray, cols: np.ndarray, n: int):
     return ptr, idx.astype(np.int64, copy=False)
 
 
+def _write_rows(fp, row_fmt, cols, chunk=1 << 16):
+    """Text rows of the column blocks ``cols`` (float32 / integer arrays, widened to float64 exactly): one %-formatting
+    call per chunk of rows, no Python loop per row."""
+    for i in range(0, len(cols[0]), chunk):
+        rows = np.concatenate([np.asarray(c[i:i + chunk], dtype=np.float64) for c in cols], 1)
+        fp.write((row_fmt * len(rows)) % tuple(rows.ravel().tolist()))
+
+
 class Mesh:
     """``Mesh(path)`` parses an OBJ like the reference (``util/mesh.py:23-43``);
     ``Mesh(vs=..., faces=...)`` wraps in-memory arrays (used for the synthetic
@@ -111,6 +119,41 @@ class Mesh:
         with open(filename, "w") as fp:
             fp.write("".join("v {0:.8f} {1:.8f} {2:.8f}\n".format(x, y, z) for x, y, z in v))
             fp.write("".join("f {0} {1} {2}\n".format(a, b, c) for a, b, c in f))
+
+    def save_as_ply(self, filename, face_colors=None, vertex_colors=None):
+        """ASCII PLY in the header layout of ``util/mesh.py:287-317``: float32 positions printed with ``%.6f``, faces as
+        ``3 i j k`` followed by ``uchar red green blue alpha`` per face (colours in [0, 1]: ``int(255 c)`` truncated, then
+        clipped to 0..255; alpha 255).  With ``vertex_colors`` instead, the colour properties belong to the vertices.
+        Written with numpy's text formatter, not a Python loop per face."""
+        assert len(self.vs) > 0
+        if face_colors is not None and vertex_colors is not None:
+            raise ValueError("face_colors or vertex_colors, not both")
+        v = np.asarray(self.vs, dtype=np.float32)
+        f = np.asarray(self.faces, dtype=np.uint32).astype(np.int64)
+
+        def rgba(c, n):
+            c = np.asarray(c, dtype=np.float32).reshape(n, -1)[:, :3]
+            u = np.clip((255 * c).astype(np.int64), 0, 255)                 # int(): toward zero, as the reference
+            return np.concatenate([u, np.full((n, 1), 255, dtype=np.int64)], 1)
+
+        colour = "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n"
+        head = ["ply\nformat ascii 1.0\nelement vertex {}\n".format(len(v)), "property float x\nproperty float y\nproperty float z\n"]
+        if vertex_colors is not None:
+            head.append(colour)
+        head += ["element face {}\n".format(len(f)), "property list uchar int vertex_indices\n"]
+        if face_colors is not None:
+            head.append(colour)
+        head.append("end_header\n")
+        with open(filename, "w") as fp:
+            fp.write("".join(head))
+            if vertex_colors is not None:
+                _write_rows(fp, "%.6f %.6f %.6f %d %d %d %d\n", [v, rgba(vertex_colors, len(v))])
+            else:
+                _write_rows(fp, "%.6f %.6f %.6f\n", [v])
+            if face_colors is not None:
+                _write_rows(fp, "3 %d %d %d %d %d %d %d\n", [f, rgba(face_colors, len(f))])
+            else:
+                _write_rows(fp, "3 %d %d %d\n", [f])
 
     # ------------------------------------------------------- per-face geometry
     def compute_face_normals(self):

@@ -355,6 +355,28 @@ size_t ddmp_mad_workspace_bytes(void);
 int ddmp_mad_f64(int64_t F, const float* n1 /*[F,3] f32*/, const double* n2 /*[F,3] f64*/, double* out /*[1]*/,
                  void* workspace, size_t workspace_bytes, ddmp_stream stream);
 
+/* ------------------------------------------------------------------ point-to-surface distance (check/hausdorff_checker.py)
+ * A uniform grid over the triangles of a target mesh, built on the device, and the exact distance from query points to
+ * that surface (closest point by Voronoi region, f32).  The grid is one caller-owned buffer:
+ *   ddmp_surfdist_grid_bytes(F, max_refs): bytes for F faces and up to max_refs cell references (0 on bad sizes);
+ *   ddmp_surfdist_build: packs the triangles, sizes the cells (about the mean edge length, grown until the cell count is
+ *     at most 4F), lists every face in every cell its bounding box overlaps.  SYNCHRONISES the stream once, to read the
+ *     reference count: DDMP_EWORKSPACE when it exceeds the buffer (*refs_needed_host then says how many are needed),
+ *     DDMP_ERANGE for a face index outside [0, V), DDMP_EINVAL for a non-finite coordinate of a face's vertex or an extent
+ *     beyond the float32 range (no grid is built then).  Nothing is written past grid_bytes.
+ *   ddmp_surfdist_query: one distance per point, stats[12] (f64) = count, sum, sum of squares, min, max of the kept
+ *     distances, number dropped, bbox min xyz and bbox max xyz of the points.  max_dist > 0: points farther than max_dist
+ *     from the surface are dropped (dist = +inf); 0 keeps all.  sort_queries = 1 orders the points by grid cell first
+ *     (same results).  dist may be null (the workspace holds them).  A non-finite point gets dist = NaN and makes the
+ *     sum NaN (it is not dropped).  Deterministic: no float atomics. */
+size_t ddmp_surfdist_grid_bytes(int64_t F, int64_t max_refs);
+int ddmp_surfdist_build(int64_t V, int64_t F, const float* pos /*[V,3]*/, const int32_t* faces /*[F,3]*/, void* grid,
+                        size_t grid_bytes, int64_t* refs_needed_host /*nullable*/, ddmp_stream stream);
+size_t ddmp_surfdist_query_workspace_bytes(int64_t Q, int64_t F);
+int ddmp_surfdist_query(int64_t F, const void* grid, size_t grid_bytes, int64_t Q, const float* points /*[Q,3]*/,
+                        float max_dist, int sort_queries, float* dist /*[Q] nullable*/, double* stats /*[12]*/,
+                        void* workspace, size_t workspace_bytes, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ bfloat16-feature mode (SURVEY.md §8b `dtype`)
  * BASELINE.json configs[1] ("bf16 features"): node features, saved activations and activation gradients [N, C] are
  * bfloat16 in HBM (raw uint16_t bits here; rows 16-byte aligned: C and every leading dimension a multiple of 8);

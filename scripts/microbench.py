@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|all] [--rows N] [--iters K]"""
+usage: microbench.py [gemm|spmm|bn|hd|all] [--rows N] [--iters K]
+hd (not part of all): surface-distance grid build and queries on torus(1000, 500) (1M faces), native and randomly
+permuted vertex order, with and without the counting sort of the queries; CPU brute-force rate from a subset."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -125,3 +127,43 @@ if a.what in ("bn", "all"):
                              ("bwd_apply", lambda: ops.bn_bwd_apply(dZ, Y, bn4, c10, dY, sums), 12.0)):
             us = timeit(fn)
             print("bn_%-10s C=%3d %8.0f us  %7.1f GB/s" % (name, C, us, by * n * C / us / 1e3))
+
+if a.what == "hd":
+    import time
+    from dual_dmp_amd import evaluate
+    from dual_dmp_amd.evaluate import SurfaceDistance
+    tv, tf = synth.torus(1000, 500)
+    gt, noisy, _ = synth.make_triplet(tv, tf, steps=1)
+    rng = np.random.default_rng(0)
+    perm = rng.permutation(len(tv)); inv = np.empty_like(perm); inv[perm] = np.arange(len(perm))
+    for order in ("native", "permuted"):
+        A, B = (noisy.vs, gt.vs) if order == "native" else (noisy.vs[perm], gt.vs[perm])
+        F_ = tf if order == "native" else inv[tf]
+        pa = torch.from_numpy(A.astype(np.float32)).to(dev); pb = torch.from_numpy(B.astype(np.float32)).to(dev)
+        sa, sb = SurfaceDistance(pa, F_, dev), SurfaceDistance(pb, F_, dev)
+        us_b = timeit(lambda: sb.update(pb))
+        print("hd %-8s F=%d grid build %8.0f us" % (order, len(tf), us_b))
+        for sort in (False, True):
+            us_ab = timeit(lambda: sb.query(pa, sort=sort))
+            us_ba = timeit(lambda: sa.query(pb, sort=sort))
+            print("hd %-8s sort=%d  noisy->gt %8.0f us  gt->noisy %8.0f us" % (order, sort, us_ab, us_ba))
+        sort = evaluate.SORT_QUERIES
+        us_t = timeit(lambda: (sa.update(pa), sb.update(pb), sb.query(pa, sort=sort), sa.query(pb, sort=sort)))
+        print("hd %-8s two-sided (2 builds + 2 queries, sort=%d) %8.0f us" % (order, sort, us_t))
+    # meshes that do not overlap (an output in another frame): the queries start outside the grid box
+    diag = float(np.linalg.norm(gt.vs.max(0) - gt.vs.min(0)))
+    far = torch.from_numpy((noisy.vs + (2.0 * diag, 0.0, 0.0)).astype(np.float32)).to(dev)
+    sg = SurfaceDistance(torch.from_numpy(gt.vs.astype(np.float32)).to(dev), tf, dev)
+    print("hd disjoint (noisy moved by 2 bbox diagonals) -> gt %8.0f us" % timeit(lambda: sg.query(far)))
+    # CPU brute force: float64 numpy, 16 queries against all 1M triangles, extrapolated to V queries per direction
+    a0, b0, c0 = (gt.vs[tf[:, k]] for k in range(3))
+    n_ = np.cross(b0 - a0, c0 - a0)
+    t0 = time.perf_counter()
+    for q in noisy.vs[:16]:
+        ap = q - a0
+        s = (ap * n_).sum(1)                                         # plane distance + 3 segment distances per triangle
+        for u, w in ((a0, b0), (b0, c0), (c0, a0)):
+            d = w - u; t = np.clip(((q - u) * d).sum(1) / (d * d).sum(1), 0, 1)
+            e = q - u - t[:, None] * d; (e * e).sum(1)
+    dt = (time.perf_counter() - t0) / 16
+    print("hd cpu brute force (numpy f64, 1 thread-ish): %.3f s per query -> %.0f s per direction at V=%d" % (dt, dt * len(tv), len(tv)))
