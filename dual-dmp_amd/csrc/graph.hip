@@ -24,8 +24,10 @@ extern "C" const char* ddmp_status_string(int status) {
     return "unknown status";
 }
 
-extern "C" int ddmp_csr_build_host(int64_t n, int64_t nnz, const int64_t* ei, int32_t* rowptr,
-                                   int32_t* col, float* dinv, int64_t* nnz_out) {
+// self_loops: GCN's A + I (exactly one loop per node, dinv = (1 + in-degree)^-1/2) | ChebConv's A (none, dinv = in-degree^-1/2,
+// 0 for a node without edges)
+static int csr_build(int64_t n, int64_t nnz, const int64_t* ei, int32_t* rowptr, int32_t* col, float* dinv, int64_t* nnz_out,
+                     bool self_loops) {
     ARG_TRY(n > 0 && nnz >= 0 && rowptr && col && dinv && nnz_out);
     ARG_TRY(nnz == 0 || ei);
     ARG_TRY(n < (int64_t)INT32_MAX && nnz + n < (int64_t)INT32_MAX);
@@ -41,12 +43,13 @@ extern "C" int ddmp_csr_build_host(int64_t n, int64_t nnz, const int64_t* ei, in
         cnt[(size_t)d + 1]++;
         kept++;
     }
-    if (*nnz_out < kept + n) return DDMP_EWORKSPACE;
+    const int64_t used = kept + (self_loops ? n : 0);
+    if (*nnz_out < used) return DDMP_EWORKSPACE;
     rowptr[0] = 0;
     for (int64_t i = 0; i < n; ++i) {
-        const int32_t deg = cnt[(size_t)i + 1] + 1;   // + the self loop
+        const int32_t deg = cnt[(size_t)i + 1] + (self_loops ? 1 : 0);
         rowptr[i + 1] = rowptr[i] + deg;
-        dinv[i] = (float)(1.0 / std::sqrt((double)deg));
+        dinv[i] = deg > 0 ? (float)(1.0 / std::sqrt((double)deg)) : 0.f;
     }
     // fill: cursor per row
     for (int64_t i = 0; i < n; ++i) cnt[(size_t)i] = rowptr[i];
@@ -56,11 +59,21 @@ extern "C" int ddmp_csr_build_host(int64_t n, int64_t nnz, const int64_t* ei, in
         col[cnt[(size_t)d]++] = (int32_t)s;
     }
     for (int64_t i = 0; i < n; ++i) {
-        col[cnt[(size_t)i]++] = (int32_t)i;
+        if (self_loops) col[cnt[(size_t)i]++] = (int32_t)i;
         std::sort(col + rowptr[i], col + rowptr[i + 1]);
     }
-    *nnz_out = kept + n;
+    *nnz_out = used;
     return DDMP_OK;
+}
+
+extern "C" int ddmp_csr_build_host(int64_t n, int64_t nnz, const int64_t* ei, int32_t* rowptr,
+                                   int32_t* col, float* dinv, int64_t* nnz_out) {
+    return csr_build(n, nnz, ei, rowptr, col, dinv, nnz_out, true);
+}
+
+extern "C" int ddmp_csr_build_sym_host(int64_t n, int64_t nnz, const int64_t* ei, int32_t* rowptr,
+                                       int32_t* col, float* dinv, int64_t* nnz_out) {
+    return csr_build(n, nnz, ei, rowptr, col, dinv, nnz_out, false);
 }
 
 extern "C" int ddmp_csr_bfs_order_host(int64_t n, const int32_t* rowptr, const int32_t* col,
@@ -303,15 +316,14 @@ extern "C" int ddmp_graph_create_csr_rows_host(int64_t n_rows_all, int64_t n_col
     return upload_graph(row1 - row0, n_cols, rp.data(), col + rowptr[row0], dinv, out, row0);
 }
 
-extern "C" int ddmp_graph_create(int64_t n, int64_t nnz, const int64_t* edge_index, int on_device,
-                                 ddmp_graph** out) {
+static int graph_create(int64_t n, int64_t nnz, const int64_t* edge_index, int on_device, ddmp_graph** out, bool self_loops) {
     ARG_TRY(out && n > 0 && nnz >= 0 && (nnz == 0 || edge_index));
     std::vector<int64_t> host_ei;
     std::vector<int32_t> rowptr, col;
     std::vector<float> dinv;
     try {
         rowptr.resize((size_t)n + 1);
-        col.resize((size_t)(nnz + n));
+        col.resize((size_t)std::max<int64_t>(nnz + (self_loops ? n : 0), 1));
         dinv.resize((size_t)n);
         if (on_device && nnz > 0) host_ei.resize((size_t)(2 * nnz));
     } catch (const std::bad_alloc&) {
@@ -322,10 +334,21 @@ extern "C" int ddmp_graph_create(int64_t n, int64_t nnz, const int64_t* edge_ind
         HIP_TRY(hipMemcpy(host_ei.data(), edge_index, sizeof(int64_t) * (size_t)(2 * nnz), hipMemcpyDeviceToHost));
         ei = host_ei.data();
     }
-    int64_t used = nnz + n;
-    int st = ddmp_csr_build_host(n, nnz, ei, rowptr.data(), col.data(), dinv.data(), &used);
+    int64_t used = nnz + (self_loops ? n : 0);
+    int st = csr_build(n, nnz, ei, rowptr.data(), col.data(), dinv.data(), &used, self_loops);
     if (st != DDMP_OK) return st;
     return upload_graph(n, n, rowptr.data(), col.data(), dinv.data(), out);
+}
+
+extern "C" int ddmp_graph_create(int64_t n, int64_t nnz, const int64_t* edge_index, int on_device,
+                                 ddmp_graph** out) {
+    return graph_create(n, nnz, edge_index, on_device, out, true);
+}
+
+// S = D^-1/2 A D^-1/2 without self loops (ChebConv, normalization = "sym"); rows without entries are legal in every gather
+extern "C" int ddmp_graph_create_sym(int64_t n, int64_t nnz, const int64_t* edge_index, int on_device,
+                                     ddmp_graph** out) {
+    return graph_create(n, nnz, edge_index, on_device, out, false);
 }
 
 extern "C" int ddmp_graph_destroy(ddmp_graph* g) {

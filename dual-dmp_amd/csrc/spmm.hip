@@ -25,12 +25,43 @@ using namespace ddmp;
 constexpr int kRB = 64;            // rows per workgroup chunk
 constexpr int kMaxE = kRB * 16;    // staged CSR entries per chunk (mesh graphs: ~7 resp. 4 per row)
 
-template <int LANES, int CHUNKS, bool PRO>
+// AXP: the affine epilogue of ddmp_spmm_axpby_f32 (one step of a three-term recurrence per launch):
+//     Y[i,:] = a * (dinv_i * sum_e dinv_col X[col,:]) + b * X[i,:] + c * Z[i,:] + d * Z2[i,:]
+// The output row's own rows of X (b != 0), Z and Z2 (nullable) are plain row-streaming loads requested BEFORE the neighbour loop,
+// so they travel under the gather.  Y may alias Z or Z2: the AXP forms store through `Y` of this struct, which carries no
+// __restrict__ (the kernels' own Y argument is not dereferenced then), and a lane reads its 16 bytes of Z before it writes them.
+// One expression in every kernel, so the routes agree bit for bit.
+struct Axpby {
+    const float* Z;
+    int64_t ldz;
+    const float* Z2;
+    int64_t ldz2;
+    float* Y;
+    float a, b, c, d;
+};
+__device__ __forceinline__ float axpby1(const Axpby& ax, float s, float x, float z, float z2) {
+    return fmaf(ax.d, z2, fmaf(ax.c, z, fmaf(ax.b, x, ax.a * s)));
+}
+__device__ __forceinline__ float4 axpby4(const Axpby& ax, float4 acc, float di, float4 x, float4 z, float4 z2) {
+    return make_float4(axpby1(ax, acc.x * di, x.x, z.x, z2.x), axpby1(ax, acc.y * di, x.y, z.y, z2.y),
+                       axpby1(ax, acc.z * di, x.z, z.z, z2.z), axpby1(ax, acc.w * di, x.w, z.w, z2.w));
+}
+// the output row's own 16 bytes of X / Z / Z2 (zeros where the operand is absent)
+__device__ __forceinline__ void axpby_rows(const Axpby& ax, const float* X, int64_t ldx, int row, int off, float4& x, float4& z,
+                                           float4& z2) {
+    x = z = z2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ax.b != 0.f) x = *reinterpret_cast<const float4*>(X + (int64_t)row * ldx + off);
+    if (ax.Z) z = *reinterpret_cast<const float4*>(ax.Z + (int64_t)row * ax.ldz + off);
+    if (ax.Z2) z2 = *reinterpret_cast<const float4*>(ax.Z2 + (int64_t)row * ax.ldz2 + off);
+}
+
+template <int LANES, int CHUNKS, bool PRO, bool AXP = false>
 __global__ __launch_bounds__(256) void spmm_vec_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ dinv, const float* __restrict__ dinv_r,
     const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int n_rows,
     const float* __restrict__ bias, const float* __restrict__ pscale, const float* __restrict__ pshift,
-    float slope, int chunks_per_xcd, int n_chunks) {
+    float slope, int chunks_per_xcd, int n_chunks, Axpby ax = Axpby()) {
+    static_assert(!AXP || !PRO, "the affine epilogue has no prologue form");
     constexpr int RPW = 64 / LANES;         // rows per wave step
     constexpr int RPB = 4 * RPW;            // rows per block step
     __shared__ int s_rowptr[kRB + 1];
@@ -77,6 +108,12 @@ __global__ __launch_bounds__(256) void spmm_vec_kernel(
         float4 acc[CHUNKS];
 #pragma unroll
         for (int c = 0; c < CHUNKS; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 ox[AXP ? CHUNKS : 1], oz[AXP ? CHUNKS : 1], oz2[AXP ? CHUNKS : 1];
+        if (AXP) {
+#pragma unroll
+            for (int c = 0; c < CHUNKS; ++c)
+                axpby_rows(ax, X, ldx, row, c * LANES * 4 + sl * 4, ox[AXP ? c : 0], oz[AXP ? c : 0], oz2[AXP ? c : 0]);
+        }
 
         for (int e = es; e < ee; e += 4) {
             int cj[4];
@@ -115,7 +152,7 @@ __global__ __launch_bounds__(256) void spmm_vec_kernel(
             }
         }
         const float di = dinv_r[row];
-        float* yr = Y + (int64_t)row * ldy + sl * 4;
+        float* yr = (AXP ? ax.Y : Y) + (int64_t)row * ldy + sl * 4;
 #pragma unroll
         for (int c = 0; c < CHUNKS; ++c) {
             float4 o;
@@ -123,29 +160,37 @@ __global__ __launch_bounds__(256) void spmm_vec_kernel(
             o.y = fmaf(acc[c].y, di, bs[c].y);
             o.z = fmaf(acc[c].z, di, bs[c].z);
             o.w = fmaf(acc[c].w, di, bs[c].w);
+            if (AXP) o = axpby4(ax, acc[c], di, ox[AXP ? c : 0], oz[AXP ? c : 0], oz2[AXP ? c : 0]);
             *reinterpret_cast<float4*>(yr + c * LANES * 4) = o;
         }
     }
 }
 
 // any width: one thread per (row, channel)
-template <bool PRO>
+template <bool PRO, bool AXP = false>
 __global__ __launch_bounds__(256) void spmm_scalar_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ dinv, const float* __restrict__ dinv_r,
     const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int n_rows, int C,
     const float* __restrict__ bias, const float* __restrict__ pscale, const float* __restrict__ pshift,
-    float slope) {
+    float slope, Axpby ax = Axpby()) {
+    static_assert(!AXP || !PRO, "the affine epilogue has no prologue form");
     const int64_t total = (int64_t)n_rows * C;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
         const int row = (int)(idx / C), c = (int)(idx % C);
-        float acc = 0.f;
+        float acc = 0.f, ox = 0.f, oz = 0.f, oz2 = 0.f;
+        if (AXP) {
+            if (ax.b != 0.f) ox = X[(int64_t)row * ldx + c];
+            if (ax.Z) oz = ax.Z[(int64_t)row * ax.ldz + c];
+            if (ax.Z2) oz2 = ax.Z2[(int64_t)row * ax.ldz2 + c];
+        }
         for (int e = rowptr[row]; e < rowptr[row + 1]; ++e) {
             const int j = col[e];
             float t = X[(int64_t)j * ldx + c];
             if (PRO) t = lrelu(fmaf(t, pscale[c], pshift[c]), slope);
             acc = fmaf(dinv[j], t, acc);
         }
-        Y[(int64_t)row * ldy + c] = fmaf(acc, dinv_r[row], bias ? bias[c] : 0.f);
+        if (AXP) ax.Y[(int64_t)row * ldy + c] = axpby1(ax, acc * dinv_r[row], ox, oz, oz2);
+        else Y[(int64_t)row * ldy + c] = fmaf(acc, dinv_r[row], bias ? bias[c] : 0.f);
     }
 }
 
@@ -184,13 +229,14 @@ struct BnBwdGather {
     const float *c1, *c0;
 };
 
-template <int LANES, int U, int NR, bool PRO, int SL, bool RED = false, bool BWD = false>
+template <int LANES, int U, int NR, bool PRO, int SL, bool RED = false, bool BWD = false, bool AXP = false>
 __global__ __launch_bounds__(256) void spmm_slab_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ dinv, const float* __restrict__ dinv_r,
     const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int n_rows, int C,
     const float* __restrict__ bias, const float* __restrict__ pscale, const float* __restrict__ pshift,
-    float slope, int chunks_per_xcd, int n_chunks, BnRed red = BnRed(), BnBwdGather bwd = BnBwdGather()) {
+    float slope, int chunks_per_xcd, int n_chunks, BnRed red = BnRed(), BnBwdGather bwd = BnBwdGather(), Axpby ax = Axpby()) {
     static_assert(!BWD || (PRO && SL == 1 && !RED), "BWD: coefficients a, b come as the prologue's, one slab per pass");
+    static_assert(!AXP || (!PRO && !RED && !BWD && NR == 1 && SL == 1), "the affine epilogue: plain gather, one row and slab per pass");
     constexpr int CS = LANES * 4;
     constexpr int RPW = 64 / LANES;
     constexpr int RPB = 4 * RPW;
@@ -260,6 +306,8 @@ __global__ __launch_bounds__(256) void spmm_slab_kernel(
                 for (int s = 0; s < SL; ++s) acc[q][s] = make_float4(0.f, 0.f, 0.f, 0.f);
                 more |= (ee[q] > es[q]);
             }
+            float4 ox, oz, oz2;
+            if (AXP) axpby_rows(ax, X, ldx, r0 + min(lr0, nr - 1), off, ox, oz, oz2);
             while (more) {
                 int cj[NR][U];
                 float wj[NR][U];
@@ -324,7 +372,8 @@ __global__ __launch_bounds__(256) void spmm_slab_kernel(
                         o.y = fmaf(acc[q][s].y, di, bs[s].y);
                         o.z = fmaf(acc[q][s].z, di, bs[s].z);
                         o.w = fmaf(acc[q][s].w, di, bs[s].w);
-                        nt_store4(Y + (int64_t)row * ldy + off + s * CS, o);
+                        if (AXP) o = axpby4(ax, acc[q][s], di, ox, oz, oz2);
+                        nt_store4((AXP ? ax.Y : Y) + (int64_t)row * ldy + off + s * CS, o);
                         if (RED) {
                             const float4 y = *reinterpret_cast<const float4*>(red.Yp + (int64_t)row * red.ldyp + off);
                             const float g0 = o.x * lrelu_grad(fmaf(y.x, ra.x, rb.x), slope);
@@ -360,10 +409,10 @@ __global__ __launch_bounds__(256) void spmm_slab_kernel(
 #include "spmm_lean.inc"
 
 // chunk_list / n_list: only these chunks (the LDS-patch kernel's heavy list), one workgroup each
-template <bool PRO, int RED, bool BWD>
+template <bool PRO, int RED, bool BWD, bool AXP = false>
 int launch_lean(const LeanPlan& lp, const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, int C,
                 const float* bias, const float* ps, const float* psh, float slope, hipStream_t st, BnRed red = BnRed(),
-                BnBwdGather bwd = BnBwdGather(), const int* chunk_list = nullptr, int n_list = 0) {
+                BnBwdGather bwd = BnBwdGather(), const int* chunk_list = nullptr, int n_list = 0, Axpby ax = Axpby()) {
     const int n = (int)g->n_rows;
     if (chunk_list) {
         if (n_list <= 0) return DDMP_OK;
@@ -374,8 +423,8 @@ int launch_lean(const LeanPlan& lp, const ddmp_graph* g, const float* X, int64_t
         const int want = std::min(n_sl, std::max(1, 2048 / n_list));
         const int per = (n_sl + want - 1) / want;
         const int groups_l = (n_sl + per - 1) / per;
-        hipLaunchKernelGGL((spmm_lean_kernel<PRO, RED, BWD>), dim3(n_list, groups_l), dim3(256), 0, st, g->rowptr, g->col, g->ew, g->dinv, g->dinv_r, X,
-                           ldx, Y, ldy, n, C, bias, ps, psh, slope, 0, n_list, chunk_list, red, bwd);
+        hipLaunchKernelGGL((spmm_lean_kernel<PRO, RED, BWD, AXP>), dim3(n_list, groups_l), dim3(256), 0, st, g->rowptr, g->col, g->ew, g->dinv, g->dinv_r, X,
+                           ldx, Y, ldy, n, C, bias, ps, psh, slope, 0, n_list, chunk_list, red, bwd, ax);
         LAUNCH_TRY();
         return DDMP_OK;
     }
@@ -389,8 +438,8 @@ int launch_lean(const LeanPlan& lp, const ddmp_graph* g, const float* X, int64_t
         const int per = (n_slabs + want - 1) / want;
         groups = (n_slabs + per - 1) / per;
     }
-    hipLaunchKernelGGL((spmm_lean_kernel<PRO, RED, BWD>), dim3(cpx * kXcd, groups), dim3(256), 0, st, g->rowptr, g->col, g->ew, g->dinv, g->dinv_r, X, ldx,
-                       Y, ldy, n, C, bias, ps, psh, slope, cpx, lp.n_chunks, (const int*)nullptr, red, bwd);
+    hipLaunchKernelGGL((spmm_lean_kernel<PRO, RED, BWD, AXP>), dim3(cpx * kXcd, groups), dim3(256), 0, st, g->rowptr, g->col, g->ew, g->dinv, g->dinv_r, X, ldx,
+                       Y, ldy, n, C, bias, ps, psh, slope, cpx, lp.n_chunks, (const int*)nullptr, red, bwd, ax);
     LAUNCH_TRY();
     return DDMP_OK;
 }
@@ -485,6 +534,57 @@ extern "C" int ddmp_spmm_f32(const ddmp_graph* g, const float* X, int64_t ldx, f
     else
         hipLaunchKernelGGL((spmm_scalar_kernel<false>), dim3(grid), dim3(256), 0, st, g->rowptr, g->col, g->dinv, g->dinv_r,
                            X, ldx, Y, ldy, (int)g->n_rows, C, bias, pro_scale, pro_shift, slope);
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
+
+
+// One step of a three-term recurrence per launch (ChebConv forward: T_k = 2 L^ T_{k-1} - T_{k-2}; its Clenshaw backward): the
+// gather with the affine epilogue Axpby.  Routes: the lean gather (C % 32 == 0; spmm_slab_kernel where its 32-bit offsets do not
+// reach), the row kernel (C = 8 | 16), the scalar kernel (anything else).  The LDS-patch kernel has no such epilogue: its slab loop
+// counts every VMEM operation in flight, and patch-gather + a streaming pass over Y, Z would move 5 streams of N x C where this
+// moves 3 -- the lean gather takes those shapes too.
+extern "C" int ddmp_spmm_axpby_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, const float* Z,
+                                   int64_t ldz, const float* Z2, int64_t ldz2, int C, float a, float b, float c, float d,
+                                   ddmp_stream stream) {
+    ARG_TRY(g && X && Y && C > 0 && ldx >= C && ldy >= C);
+    ARG_TRY(X != Y);
+    ARG_TRY((!Z || ldz >= C) && (!Z2 || ldz2 >= C));
+    hipStream_t st = (hipStream_t)stream;
+    const Axpby ax{Z, Z ? ldz : 0, Z2, Z2 ? ldz2 : 0, Y, a, b, Z ? c : 0.f, Z2 ? d : 0.f};
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && al16(X) && al16(Y) && (!Z || (ldz % 4 == 0 && al16(Z))) &&
+                     (!Z2 || (ldz2 % 4 == 0 && al16(Z2)));
+    const int n = (int)g->n_rows;
+    const int n_chunks = (int)cdiv(n, kRB);
+    const int cpx = (int)cdiv(n_chunks, kXcd);
+    if (vec && C % 32 == 0) {
+        const LeanPlan lp = lean_plan(g, ldx, ldy, C);
+        if (lp.kind)
+            return launch_lean<false, 0, false, true>(lp, g, X, ldx, Y, ldy, C, nullptr, nullptr, nullptr, 0.f, st, BnRed(), BnBwdGather(),
+                                                      nullptr, 0, ax);
+        hipLaunchKernelGGL((spmm_slab_kernel<8, 4, 1, false, 1, false, false, true>), dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr,
+                           g->col, g->dinv, g->dinv_r, X, ldx, Y, ldy, n, C, (const float*)nullptr, (const float*)nullptr,
+                           (const float*)nullptr, 0.f, cpx, n_chunks, BnRed(), BnBwdGather(), ax);
+        LAUNCH_TRY();
+        return DDMP_OK;
+    }
+    if (vec && (C == 8 || C == 16)) {
+        if (C == 8)
+            hipLaunchKernelGGL((spmm_vec_kernel<2, 1, false, true>), dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->dinv,
+                               g->dinv_r, X, ldx, Y, ldy, n, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f,
+                               cpx, n_chunks, ax);
+        else
+            hipLaunchKernelGGL((spmm_vec_kernel<4, 1, false, true>), dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->dinv,
+                               g->dinv_r, X, ldx, Y, ldy, n, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f,
+                               cpx, n_chunks, ax);
+        LAUNCH_TRY();
+        return DDMP_OK;
+    }
+    const int64_t total = g->n_rows * (int64_t)C;
+    const int grid = (int)std::min<int64_t>(cdiv(total, 256), 256 * 16);
+    hipLaunchKernelGGL((spmm_scalar_kernel<false, true>), dim3(grid), dim3(256), 0, st, g->rowptr, g->col, g->dinv, g->dinv_r, X,
+                       ldx, Y, ldy, n, C, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f, ax);
     LAUNCH_TRY();
     return DDMP_OK;
 }

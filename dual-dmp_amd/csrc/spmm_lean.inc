@@ -26,15 +26,18 @@
 // per row on average -- a hub of several hundred neighbours) reads its entries from global memory instead (same sums in the
 // same order; slow, correct): one hub vertex costs its own chunk, not the graph.  `chunk_list` (nullable): the chunks to
 // process, one per workgroup -- the LDS-patch kernel's heavy list (ddmp_graph::heavy).
+// AXP (ddmp_spmm_axpby_f32): the affine epilogue a * (gather) + b * X[row] + c * Z[row] + d * Z2[row] -- see Axpby in spmm.hip; the
+// row's own operands are requested where RED = 1 requests its Yp row: before the neighbour loop.
 constexpr int kLeanSlots = kRB * 16;
-template <bool PRO, int RED, bool BWD>
+template <bool PRO, int RED, bool BWD, bool AXP = false>
 __global__ __launch_bounds__(256) void spmm_lean_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ ew, const float* __restrict__ dinv,
     const float* __restrict__ dinv_r, const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int n_rows, int C,
     const float* __restrict__ bias, const float* __restrict__ pscale, const float* __restrict__ pshift,
     float slope, int chunks_per_xcd, int n_chunks, const int* __restrict__ chunk_list, BnRed red = BnRed(),
-    BnBwdGather bwd = BnBwdGather()) {
+    BnBwdGather bwd = BnBwdGather(), Axpby ax = Axpby()) {
     static_assert(!BWD || (PRO && !RED), "BWD: coefficients a, b come as the prologue's");
+    static_assert(!AXP || (!PRO && !RED && !BWD), "the affine epilogue: plain gather only");
     static_assert(RED >= 0 && RED <= 2, "epilogue reduction");
     constexpr int LANES = 8, CS = 32, RPW = 8, RPB = 32;
     __shared__ int s_rowptr[kRB + 1];
@@ -141,7 +144,7 @@ __global__ __launch_bounds__(256) void spmm_lean_kernel(
         }
         const char* xb = reinterpret_cast<const char*>(X + off);
         const char* yb = BWD ? reinterpret_cast<const char*>(bwd.Yb + off) : nullptr;
-        char* ob = reinterpret_cast<char*>(Y + off);
+        char* ob = reinterpret_cast<char*>((AXP ? ax.Y : Y) + off);
         const unsigned ldy16 = (unsigned)(ldy >> 2);
 #pragma unroll
         for (int qq = 0; qq < 2; ++qq) {
@@ -161,6 +164,8 @@ __global__ __launch_bounds__(256) void spmm_lean_kernel(
             // (RED = 1: the row of Yp the epilogue needs does not depend on the gather -- requested before it, not behind it)
             float4 yred = make_float4(0.f, 0.f, 0.f, 0.f);
             if (RED == 1) yred = *reinterpret_cast<const float4*>(red.Yp + (int64_t)(r0 + lr) * red.ldyp + off);
+            float4 ox, oz, oz2;
+            if (AXP) axpby_rows(ax, X, ldx, r0 + lr, off, ox, oz, oz2);
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
             for (int q = 0; q < nq; ++q) {
                 unsigned o[4];
@@ -217,6 +222,7 @@ __global__ __launch_bounds__(256) void spmm_lean_kernel(
             o4.y = fmaf(acc.y, di, bs.y);
             o4.z = fmaf(acc.z, di, bs.z);
             o4.w = fmaf(acc.w, di, bs.w);
+            if (AXP) o4 = axpby4(ax, acc, di, ox, oz, oz2);
             nt_store4(reinterpret_cast<float*>(ob + ((uint64_t)((unsigned)row * ldy16) << 4)), o4);
             if (RED == 2) {
                 const float d0 = o4.x - rmu.x, d1 = o4.y - rmu.y, d2 = o4.z - rmu.z, d3 = o4.w - rmu.w;

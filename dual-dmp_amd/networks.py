@@ -14,7 +14,10 @@ Two interchangeable forms, both taking the reference's ``Dataset`` object (field
 ``PosNet(device, fused=False)`` / ``NormalNet(device, fused=False)``
     the reference's module structure verbatim -- 12 x (``GCNConv`` -> ``nn.BatchNorm1d`` ->
     ``nn.LeakyReLU``) + two ``nn.Linear`` -- with our drop-in :class:`nn_ops.GCNConv` standing where
-    ``torch_geometric.nn.GCNConv`` stands in ``util/networks.py:4``.
+    ``torch_geometric.nn.GCNConv`` stands in ``util/networks.py:4``.  ``conv="cheb", K=3`` builds the twelve
+    convolutions from :class:`nn_ops.ChebConv` instead (spectral layers of order K; parameters
+    ``convN.lins.k.weight``).  The fused engine, the trainer, the CLI, the partitioned path and bf16
+    features are GCN-only: ``fused=True`` with ``conv="cheb"`` raises.
 
 The reference's unused ``torch.randn(V,3)*1e-5`` draw (``util/networks.py:50``) is dropped: it only
 advances the RNG.  ``z1``/``z2`` carry ``requires_grad=True`` in the reference but are never
@@ -30,7 +33,7 @@ import torch.nn as nn
 
 from . import ops
 from .engine import ArenaLayout, GcnEngine, NORM_WIDTHS, POS_WIDTHS
-from .nn_ops import GCNConv
+from .nn_ops import ChebConv, GCNConv
 
 
 class _EngineFn(torch.autograd.Function):
@@ -255,12 +258,14 @@ class NormalNetFused(_FusedNet):
 class _ModularNet(nn.Module):
     _widths = None
 
-    def __init__(self, device):
+    def __init__(self, device, conv="gcn", K=3):
         super().__init__()
         self.device = torch.device(device)
         h = self._widths
+        if conv not in ("gcn", "cheb"):
+            raise ValueError("conv must be 'gcn' or 'cheb', got %r" % (conv,))
         for i in range(12):
-            setattr(self, "conv%d" % (i + 1), GCNConv(h[i], h[i + 1]))
+            setattr(self, "conv%d" % (i + 1), GCNConv(h[i], h[i + 1]) if conv == "gcn" else ChebConv(h[i], h[i + 1], K))
         self.linear1 = nn.Linear(h[12], h[13])
         self.linear2 = nn.Linear(h[13], h[14])
         for i in range(12):
@@ -308,9 +313,20 @@ class NormalNetModular(_ModularNet):
         return torch.mul(dx, dx_norm)
 
 
-def PosNet(device, fused=True, **kw):
-    return PosNetFused(device, **kw) if fused else PosNetModular(device)
+def _make_net(fused_cls, modular_cls, device, fused, conv, K, kw):
+    if conv not in ("gcn", "cheb"):
+        raise ValueError("conv must be 'gcn' or 'cheb', got %r" % (conv,))
+    if fused:
+        if conv != "gcn":
+            raise ValueError("conv=%r needs fused=False: the fused engine (and with it the trainer, the CLI, the partitioned "
+                             "path and bf16 features) is GCN-only" % (conv,))
+        return fused_cls(device, **kw)
+    return modular_cls(device, conv=conv, K=K)
 
 
-def NormalNet(device, fused=True, **kw):
-    return NormalNetFused(device, **kw) if fused else NormalNetModular(device)
+def PosNet(device, fused=True, conv="gcn", K=3, **kw):
+    return _make_net(PosNetFused, PosNetModular, device, fused, conv, K, kw)
+
+
+def NormalNet(device, fused=True, conv="gcn", K=3, **kw):
+    return _make_net(NormalNetFused, NormalNetModular, device, fused, conv, K, kw)

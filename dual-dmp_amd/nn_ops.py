@@ -1,4 +1,4 @@
-"""Drop-in ``GCNConv`` on the HIP kernels.
+"""Drop-in ``GCNConv`` and ``ChebConv`` on the HIP kernels.
 
 Same constructor / call signature, parameter names and initialisation as
 ``torch_geometric.nn.GCNConv`` 2.2.0 with the defaults the reference uses
@@ -8,6 +8,14 @@ Same constructor / call signature, parameter names and initialisation as
 
 The normalised graph is built once per ``edge_index`` tensor (cached on its storage + version)
 instead of on every call; aggregation runs on min(in, out) channels.
+
+``ChebConv(in_channels, out_channels, K, normalization="sym", bias=True)`` restates
+``torch_geometric.nn.ChebConv`` 2.2.0: parameters ``lins.0.weight`` ... ``lins.{K-1}.weight`` [out, in]
+Glorot-uniform and ``bias`` [out] zeros, ``forward(x, edge_index, edge_weight=None, batch=None,
+lambda_max=None)`` with ``lambda_max`` a float (default 2.0),
+``Y = sum_k T_k W_k^T + b``, ``T_0 = X``, ``T_1 = L^ X``, ``T_k = 2 L^ T_{k-1} - T_{k-2}``,
+``L^ = -(2 / lambda_max) D^-1/2 A D^-1/2 + (2 / lambda_max - 1) I`` (no self loops; symmetric
+``edge_index`` only).  ``edge_weight``, ``batch``, a tensor ``lambda_max`` and other normalisations raise.
 """
 from __future__ import annotations
 
@@ -118,3 +126,114 @@ class GCNConv(nn.Module):
 
     def extra_repr(self):
         return "%d, %d" % (self.in_channels, self.out_channels)
+
+
+class _ChebConvFn(torch.autograd.Function):
+    """K - 1 fused Chebyshev steps (``ops.spmm_axpby``: gather + three-term recurrence in one launch) into the column
+    blocks of ONE [N, K * Cp] buffer, then ONE GEMM against the packed [out, K * Cp] weight.  Backward: one dgrad GEMM,
+    one wgrad GEMM, and dX by the Clenshaw recurrence on the same (symmetric) graph, in place in the dgrad's buffer."""
+
+    @staticmethod
+    def forward(ctx, x, bias, graph, alpha, beta, *weights):
+        K = len(weights)
+        cout, cin = weights[0].shape
+        cp = (cin + 3) // 4 * 4
+        n = x.shape[0]
+        t = torch.empty((n, K * cp), dtype=torch.float32, device=x.device)
+        if cp != cin:
+            t[:, cin:cp] = 0
+        t[:, :cin] = x.detach()
+        wp = torch.zeros((cout, K * cp), dtype=torch.float32, device=x.device)
+        for k, w in enumerate(weights):
+            wp[:, k * cp:k * cp + cin] = w.detach()
+        blk = lambda m, k: m[:, k * cp:(k + 1) * cp]
+        for k in range(1, K):
+            if k == 1:
+                ops.spmm_axpby(graph, blk(t, 0), out=blk(t, 1), a=alpha, b=beta)
+            else:
+                ops.spmm_axpby(graph, blk(t, k - 1), out=blk(t, k), z=blk(t, k - 2), a=2 * alpha, b=2 * beta, c=-1.0)
+        y = ops.gemm_nt(t, wp, bias=None if bias is None else bias.detach().contiguous())
+        ctx.save_for_backward(t, wp)
+        ctx.graph, ctx.coef, ctx.dims, ctx.has_bias = graph, (alpha, beta), (K, cin, cp), bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        with ops.on_device(dy):
+            return _ChebConvFn._backward(ctx, dy)
+
+    @staticmethod
+    def _backward(ctx, dy):
+        t, wp = ctx.saved_tensors
+        graph, (alpha, beta), (K, cin, cp) = ctx.graph, ctx.coef, ctx.dims
+        dy = dy.contiguous()
+        cout = dy.shape[1]
+        dyp = _pad_cols(dy)
+        db = None
+        if ctx.has_bias and ctx.needs_input_grad[1]:
+            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
+            db = ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+        dwp = ops.gemm_tn(dyp, t)
+        dws = tuple(dwp[:cout, k * cp:k * cp + cin] if ctx.needs_input_grad[5 + k] else None for k in range(K))
+        dx = None
+        if ctx.needs_input_grad[0]:
+            if dyp.shape[1] != cout:       # ragged output width: pad the weight rows to match
+                wrow = torch.zeros((dyp.shape[1], wp.shape[1]), dtype=wp.dtype, device=wp.device)
+                wrow[:cout] = wp
+            else:
+                wrow = wp
+            g = ops.gemm_nn(dyp, wrow)     # blocks G_k = dY . W_k
+            blk = lambda k: g[:, k * cp:(k + 1) * cp] if k < K else None
+            # Clenshaw: B_k = G_k + 2 L^ B_{k+1} - B_{k+2} (B_K = B_{K+1} = 0), dX = G_0 + L^ B_1 - B_2; B_k overwrites G_k
+            for k in range(K - 2, 0, -1):
+                ops.spmm_axpby(graph, blk(k + 1), out=blk(k), z=blk(k), z2=blk(k + 2), a=2 * alpha, b=2 * beta, c=1.0, d=-1.0)
+            if K > 1:
+                ops.spmm_axpby(graph, blk(1), out=blk(0), z=blk(0), z2=blk(2), a=alpha, b=beta, c=1.0, d=-1.0)
+            dx = g[:, :cin]
+        return (dx, db, None, None, None) + dws
+
+
+class ChebConv(nn.Module):
+    def __init__(self, in_channels: int, out_channels: int, K: int, normalization: str = "sym", bias: bool = True):
+        super().__init__()
+        if not isinstance(K, int) or K < 1:
+            raise ValueError("ChebConv: K must be an integer >= 1, got %r" % (K,))
+        if normalization != "sym":
+            raise ValueError("ChebConv: only normalization='sym' is implemented on the HIP path, got %r" % (normalization,))
+        self.in_channels, self.out_channels, self.K, self.normalization = in_channels, out_channels, K, normalization
+        self.lins = nn.ModuleList([_Lin(in_channels, out_channels) for _ in range(K)])
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        a = math.sqrt(6.0 / (self.in_channels + self.out_channels))     # PyG 'glorot'
+        with torch.no_grad():
+            for lin in self.lins:
+                lin.weight.uniform_(-a, a)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_weight=None, batch=None, lambda_max=None) -> torch.Tensor:
+        """``edge_index`` must be symmetric (both directions of every edge present)."""
+        if edge_weight is not None or batch is not None:
+            raise ValueError("ChebConv: edge_weight and batch are not implemented on the HIP path")
+        if lambda_max is None:
+            lambda_max = 2.0
+        if isinstance(lambda_max, torch.Tensor) or not isinstance(lambda_max, (int, float)):
+            raise ValueError("ChebConv: lambda_max must be a float (a tensor-valued lambda_max is not implemented)")
+        if not lambda_max > 0:
+            raise ValueError("ChebConv: lambda_max must be positive")
+        if x.dim() != 2 or x.shape[1] != self.in_channels:
+            raise ValueError("ChebConv: expected x of shape [N, %d]" % self.in_channels)
+        if not x.is_cuda:
+            raise ops.DdmpError("ChebConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        alpha, beta = -2.0 / lambda_max, 2.0 / lambda_max - 1.0
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="sym") if self.K > 1 else None      # K = 1 needs no graph
+            return _ChebConvFn.apply(x.to(torch.float32), self.bias, graph, alpha, beta, *[lin.weight for lin in self.lins])
+
+    def extra_repr(self):
+        return "%d, %d, K=%d, normalization=%s" % (self.in_channels, self.out_channels, self.K, self.normalization)

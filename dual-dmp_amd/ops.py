@@ -272,7 +272,7 @@ class Workspace:
 # ---------------------------------------------------------------------------------------- graph
 class Graph:
     """CSR of A + I with D^-1/2 on the device (``ddmp_graph``).  Built once per edge_index
-    (the reference's GCNConv re-normalises on every call, cached=False)."""
+    (the reference's GCNConv re-normalises on every call, cached=False).  ``norm="sym"``: CSR of A, no self loops (ChebConv)."""
 
     def __init__(self, handle, n_rows, n_cols, nnz):
         self._h = handle
@@ -287,15 +287,24 @@ class Graph:
         return self._h
 
     @classmethod
-    def from_edge_index(cls, edge_index: torch.Tensor, num_nodes: int) -> "Graph":
+    def from_edge_index(cls, edge_index: torch.Tensor, num_nodes: int, norm: str = "gcn") -> "Graph":
+        """``norm``: "gcn" = D^-1/2 (A + I) D^-1/2 (GCNConv) | "sym" = D^-1/2 A D^-1/2 without self loops (ChebConv's S:
+        explicit self loops dropped, none added, dinv = 0 and an empty row for a node without edges)."""
         if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
             raise DdmpError("edge_index must be a [2, nnz] int64 tensor")
+        if norm not in ("gcn", "sym"):
+            raise DdmpError("graph normalisation must be 'gcn' or 'sym', got %r" % (norm,))
         ei = edge_index.contiguous()
         h = ctypes.c_void_p()
-        st = _lib.lib().ddmp_graph_create(int(num_nodes), int(ei.shape[1]), _p(ei), 1 if ei.is_cuda else 0,
-                                          ctypes.byref(h))
-        check(st, "ddmp_graph_create")
-        return cls(h, int(num_nodes), int(num_nodes), int(ei.shape[1]) + int(num_nodes))
+        create = _lib.lib().ddmp_graph_create if norm == "gcn" else _lib.lib().ddmp_graph_create_sym
+        st = create(int(num_nodes), int(ei.shape[1]), _p(ei), 1 if ei.is_cuda else 0, ctypes.byref(h))
+        check(st, "ddmp_graph_create" if norm == "gcn" else "ddmp_graph_create_sym")
+        g = cls(h, int(num_nodes), int(num_nodes), int(ei.shape[1]) + int(num_nodes))
+        if norm == "sym":                                       # entries = the edges that are not self loops
+            nnz = ctypes.c_int64()
+            check(_lib.lib().ddmp_graph_info(h, None, None, ctypes.byref(nnz), None), "ddmp_graph_info")
+            g.nnz = int(nnz.value)
+        return g
 
     @classmethod
     def from_csr_host(cls, rowptr: np.ndarray, col: np.ndarray, dinv: np.ndarray, n_cols: int, rows=None) -> "Graph":
@@ -322,12 +331,17 @@ class Graph:
 _graph_cache = {}
 
 
-def graph_for(edge_index: torch.Tensor, num_nodes: int) -> Graph:
+def graph_for(edge_index: torch.Tensor, num_nodes: int, norm: str = "gcn") -> Graph:
     """Graph of a static mesh, cached on the IDENTITY of the edge_index tensor (weak reference + in-place
-    version counter).  A data_ptr key would be wrong: a freed tensor's address is reused by other meshes.
+    version counter) and the normalisation.  A data_ptr key would be wrong: a freed tensor's address is reused by other meshes.
     A caller that builds a fresh edge_index tensor on every call (as ``data.edge_index.to(device)`` does when
-    the dataset lives on the host) gets a correct but rebuilt graph each time -- keep the tensor."""
-    key = id(edge_index)
+    the dataset lives on the host) gets a correct but rebuilt graph each time -- keep the tensor.
+
+    ``norm``: "gcn" (GCNConv: self loops added) | "sym" (ChebConv: S = D^-1/2 A D^-1/2, no self loops).  A GCNConv and a
+    ChebConv on the same edge_index tensor each get their own graph.  "sym" supports SYMMETRIC edge lists only (both
+    directions of every edge present, as every graph of this project is): S is then symmetric, the degree is the in-degree,
+    and the same graph serves the backward pass."""
+    key = (id(edge_index), norm)
     hit = _graph_cache.get(key)
     if hit is not None:
         ref, version, n, g = hit
@@ -335,22 +349,24 @@ def graph_for(edge_index: torch.Tensor, num_nodes: int) -> Graph:
             return g
     for k in [k for k, v in _graph_cache.items() if v[0]() is None]:
         del _graph_cache[k]
-    g = Graph.from_edge_index(edge_index, num_nodes)
+    g = Graph.from_edge_index(edge_index, num_nodes, norm)
     _graph_cache[key] = (weakref.ref(edge_index), edge_index._version, int(num_nodes), g)
     return g
 
 
-def csr_build_host(edge_index: np.ndarray, num_nodes: int):
-    """Host CSR (no GPU needed): -> rowptr int32[n+1], col int32[nnz'], dinv f32[n]."""
+def csr_build_host(edge_index: np.ndarray, num_nodes: int, norm: str = "gcn"):
+    """Host CSR (no GPU needed): -> rowptr int32[n+1], col int32[nnz'], dinv f32[n].  ``norm`` as in ``graph_for``."""
+    if norm not in ("gcn", "sym"):
+        raise DdmpError("graph normalisation must be 'gcn' or 'sym', got %r" % (norm,))
     ei = np.ascontiguousarray(edge_index, dtype=np.int64)
     nnz = ei.shape[1]
     rowptr = np.zeros(num_nodes + 1, np.int32)
     col = np.zeros(nnz + num_nodes, np.int32)
     dinv = np.zeros(num_nodes, np.float32)
     cap = ctypes.c_int64(nnz + num_nodes)
-    st = _lib.lib().ddmp_csr_build_host(num_nodes, nnz, ei.ctypes.data, rowptr.ctypes.data, col.ctypes.data,
-                                        dinv.ctypes.data, ctypes.byref(cap))
-    check(st, "ddmp_csr_build_host")
+    build = _lib.lib().ddmp_csr_build_host if norm == "gcn" else _lib.lib().ddmp_csr_build_sym_host
+    st = build(num_nodes, nnz, ei.ctypes.data, rowptr.ctypes.data, col.ctypes.data, dinv.ctypes.data, ctypes.byref(cap))
+    check(st, "ddmp_csr_build_host" if norm == "gcn" else "ddmp_csr_build_sym_host")
     return rowptr, col[:cap.value].copy(), dinv
 
 
@@ -391,6 +407,37 @@ def spmm(g: Graph, x, out=None, bias=None, pro=None, slope=SLOPE):
         st = _lib.lib().ddmp_spmm(g.handle, _p(x), ldx, _p(out), ldy, C, _dt(x), _p(bias), _p(ps), _p(psh), slope,
                                   _stream())
     check(st, "ddmp_spmm")
+    return out
+
+
+def spmm_axpby(g: Graph, x, out=None, z=None, z2=None, a=1.0, b=0.0, c=0.0, d=0.0):
+    """out[i] = a * (dinv_i * sum_j dinv_j x[j]) + b * x[i] + c * z[i] + d * z2[i], float32 (ddmp_spmm_axpby_f32): one step of a
+    three-term recurrence per launch.  ``z`` / ``z2`` optional (their coefficient is then ignored); ``out`` may be ``z`` or ``z2``,
+    never ``x``.  Column blocks of wider buffers are fine (any row stride)."""
+    x, ldx = _mat(_chk(x, torch.float32, "x"), "x")
+    if x.shape[0] < g.n_cols:
+        raise DdmpError("x has %d rows, graph references %d nodes" % (x.shape[0], g.n_cols))
+    C = x.shape[1]
+    if out is None:
+        out = torch.empty((g.n_rows, C), dtype=x.dtype, device=x.device)
+    out, ldy = _mat(_chk(out, torch.float32, "out"), "out")
+    ldz = ldz2 = 0
+    if z is not None:
+        z, ldz = _mat(_chk(z, torch.float32, "z"), "z")
+    if z2 is not None:
+        z2, ldz2 = _mat(_chk(z2, torch.float32, "z2"), "z2")
+    for t, nm in ((out, "out"), (z, "z"), (z2, "z2")):
+        if t is not None and (t.shape[0] < g.n_rows or t.shape[1] != C):
+            raise DdmpError("%s must be [>= %d, %d], got %s" % (nm, g.n_rows, C, tuple(t.shape)))
+    # algorithmic bytes: N x C x 4 per stream actually touched (the gathered rows, the output, x's own rows when b != 0, z, z2)
+    # + int32 col ids, rowptr, dinv
+    streams = 2 + (1 if b != 0 else 0) + (z is not None) + (z2 is not None)
+    tables = 4.0 * g.nnz + 4.0 * (g.n_rows + 1) + 4.0 * g.n_rows
+    with _timed("spmm_axpby", (C, int(round(g.nnz / max(g.n_rows, 1)))), 4.0 * streams * g.n_rows * C + tables, 2.0 * g.nnz * C,
+                survey=8.0 * g.n_rows * C + tables):
+        st = _lib.lib().ddmp_spmm_axpby_f32(g.handle, _p(x), ldx, _p(out), ldy, _p(z), ldz, _p(z2), ldz2, C, float(a), float(b),
+                                            float(c), float(d), _stream())
+    check(st, "ddmp_spmm_axpby_f32")
     return out
 
 

@@ -103,6 +103,29 @@ int ddmp_spmm_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, in
  * statistics only): distinct rows of a chunk copied to LDS once, gathers from LDS -- csrc/spmm_patch.hip; same results either way */
 int ddmp_spmm_patch_selected(const ddmp_graph* g, int C, int dtype, int has_pro, int has_red);
 
+/* ------------------------------------------------------------------ Chebyshev step (torch_geometric ChebConv, normalization="sym")
+ * The second graph flavour: S = D^-1/2 A D^-1/2 WITHOUT self loops -- explicit self loops are dropped and none is added,
+ * multi-edges keep their multiplicity, CSR row i lists the sources of i (ascending), dinv[i] = in-degree(i)^-1/2 and 0 for a node
+ * without edges (PyG's inf -> 0), whose row is empty.  Only symmetric edge lists (both directions present, as every graph of
+ * this project is) give the S that ChebConv means: the same handle then serves the backward pass.  The handle is an ordinary
+ * ddmp_graph: every ddmp_spmm* entry point takes it.
+ */
+int ddmp_csr_build_sym_host(int64_t n_nodes, int64_t nnz, const int64_t* edge_index_host,
+                            int32_t* rowptr_host /*[n+1]*/, int32_t* col_host /*[nnz_out]*/,
+                            float* dinv_host /*[n]*/, int64_t* nnz_out /*in: capacity (nnz suffices), out: used*/);
+int ddmp_graph_create_sym(int64_t n_nodes, int64_t nnz, const int64_t* edge_index, int edge_index_on_device,
+                          ddmp_graph** out);
+/* One step of a three-term recurrence per launch -- the gather with an affine epilogue, float32:
+ *     Y[i,:] = a * (dinv_i * sum_{e in row i} dinv_{col e} * X[col e,:]) + b * X[i,:] + c * Z[i,:] + d * Z2[i,:]
+ * (T_k = 2 L^ T_{k-1} - T_{k-2} with L^ = alpha S + beta I: a = 2 alpha, b = 2 beta, c = -1, Z = T_{k-2}; the Clenshaw backward
+ * uses both addends).  Z, Z2 nullable (their coefficient is then ignored); b == 0 reads no X[i,:].  Y may alias Z or Z2 (an
+ * output row reads only its own row of them); Y must not alias X (DDMP_EINVAL).  X needs n_cols >= n_rows rows.  A row without
+ * entries gives b X + c Z + d Z2.  No atomics, the gather's fixed summation order.  Widths as ddmp_spmm_f32: the vector
+ * kernels need C % 4 == 0, leading dimensions % 4 == 0 and 16-byte aligned pointers, anything else takes the scalar kernel. */
+int ddmp_spmm_axpby_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, const float* Z /*nullable*/,
+                        int64_t ldz, const float* Z2 /*nullable*/, int64_t ldz2, int C, float a, float b, float c, float d,
+                        ddmp_stream stream);
+
 /* ------------------------------------------------------------------ dense steps (MFMA; float32 operands and results, the
  * arithmetic is ddmp_set_gemm_mode's: by default SPLIT-precision 16-bit MFMA products with f32 accumulation -- f32-class
  * accuracy, not bit-exact f32; mode 0 = f32-input MFMA, the strict one)

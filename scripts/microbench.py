@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|all] [--rows N] [--iters K]
+cheb (not part of all): one Chebyshev step T_k = a S T_{k-1} + c T_{k-2} on the norm="sym" face and vertex graphs of a torus with
+--rows faces in RCB order -- the fused kernel (ops.spmm_axpby, 3 streams of N x C) against the composition it replaces (ops.spmm
+into a temporary + one torch elementwise pass, 5 streams), alternating in the same loop, one HIP-event pair per launch, median
+of --iters (at least 20) repetitions, rotating buffer sets so that no launch finds its operands in the 256 MB MALL.
 hd (not part of all): surface-distance grid build and queries on torus(1000, 500) (1M faces), native and randomly
 permuted vertex order, with and without the counting sort of the queries; CPU brute-force rate from a subset."""
 import argparse, os, sys
@@ -167,3 +171,43 @@ if a.what == "hd":
             e = q - u - t[:, None] * d; (e * e).sum(1)
     dt = (time.perf_counter() - t0) / 16
     print("hd cpu brute force (numpy f64, 1 thread-ish): %.3f s per query -> %.0f s per direction at V=%d" % (dt, dt * len(tv), len(tv)))
+
+if a.what == "cheb":
+    nv_ = int(round((n / 4.0) ** 0.5)); nu_ = n // (2 * nv_)
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    m = Mesh(vs=v, faces=f)
+    e = torch.tensor(m.edges.T, dtype=torch.long); ei = torch.cat([e, e[[1, 0]]], 1).to(dev)
+    fi = torch.from_numpy(m.f_edges).to(dev)
+    reps = max(a.iters, 20)
+    ca, cc = -1.0, 1.0                                           # lambda_max = 2: L^ = -S; one addend, b = 0
+    for gname, idx, nn_ in (("face", fi, len(f)), ("vert", ei, len(v))):
+        g = ops.graph_for(idx, nn_, norm="sym")
+        for C in [int(c) for c in a.widths.split(",")]:
+            R = 2 if nn_ * C * 4 >= (1 << 29) else 4
+            Xs, Zs, Ys = ([torch.randn(nn_, C, device=dev) for _ in range(R)] for _ in range(3))
+            tmp = torch.empty(nn_, C, device=dev)
+
+            def fused(i):
+                ops.spmm_axpby(g, Xs[i], out=Ys[i], z=Zs[i], a=ca, c=cc)
+
+            def composed(i):
+                ops.spmm(g, Xs[i], out=tmp)
+                torch.add(Zs[i], tmp, alpha=ca, out=Ys[i])       # c = 1: ONE elementwise pass (reads tmp, Z, writes Y)
+
+            composed(0); ref = Ys[0].clone(); fused(0)
+            err = float((Ys[0] - ref).double().norm() / ref.double().norm())
+            t = {"fused": [], "composed": []}
+            for r in range(3 + reps):                            # 3 warm-up rounds, then alternating
+                for name, fn in (("fused", fused), ("composed", composed)):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(); fn(r % R); e1.record(); torch.cuda.synchronize()
+                    if r >= 3:
+                        t[name].append(e0.elapsed_time(e1) * 1e3)
+            q = {k: np.percentile(np.array(v_), [0, 25, 50, 75, 100]) for k, v_ in t.items()}
+            b3 = 3.0 * nn_ * C * 4 + 4.0 * g.nnz + 8.0 * nn_
+            print("cheb step %s N=%d C=%3d (%d buffer sets, %d reps): fused %6.0f us [min %.0f q1 %.0f q3 %.0f max %.0f]  composed %6.0f us "
+                  "[min %.0f q1 %.0f q3 %.0f max %.0f]  fused/composed %.3f  fused: %.2f TB/s on the 3-stream count = %.1f%% of 8 TB/s  "
+                  "rel-L2 fused vs composed %.1e" % (gname, nn_, C, R, reps, q["fused"][2], q["fused"][0], q["fused"][1], q["fused"][3],
+                  q["fused"][4], q["composed"][2], q["composed"][0], q["composed"][1], q["composed"][3], q["composed"][4],
+                  q["fused"][2] / q["composed"][2], b3 / q["fused"][2] / 1e6, b3 / q["fused"][2] / 1e6 / 8.0 * 100.0, err), flush=True)
+            del Xs, Zs, Ys, tmp
