@@ -207,6 +207,20 @@ struct ddmp_graph {
     int n_split;        // extra record slots = sum over the split chunks of (parts - 1)
     int32_t* heavy;     // device [n_heavy]: the heavy chunks, ascending
     int n_heavy;
+    // Valued graph (ddmp_graph_create_valued): the structure is COALESCED (one entry per (target, source) pair) and
+    // fixed, the values are set on the device per weight version (ddmp_graph_set_values).  `ew` / `dinv` / `dinv_r` above then hold
+    // a_e * s_col, s and s (normalising) or a_e, 1, 1 (not normalising); every gather a valued graph reaches reads the entry's factor
+    // from `ew` (`ew_t` for the transposed operator), never dinv[col].  0 / nullptr for every other graph.
+    int valued;         // 0 | DDMP_GV_VALUED | flags
+    int64_t nnz_in;     // input edges
+    int32_t* ee_ptr;    // device [nnz + 1]: entry -> its input edges, in input order (empty: the entry is a `fill` self loop)
+    int32_t* ee_idx;    // device [ee_ptr[nnz]]
+    int32_t* eid;       // device [nnz_in]: input edge -> entry (-1: dropped or overridden self loop)
+    int32_t* mirror;    // device [nnz]: entry (i, j) -> entry (j, i)
+    float* a;           // device [nnz]: the coalesced weights a_e
+    float* ew_t;        // device [nnz]: a_mirror(e) * s_col, the transposed operator's factors (== ew: symmetric values by contract)
+    float* ge;          // device [nnz]: the entries' gradient between the two kernels of ddmp_graph_weight_grad
+    int* vstatus;       // device [1]: DDMP_GV_E* bits of the last ddmp_graph_set_values
 };
 namespace ddmp {
 constexpr int kChunkRows = 64;

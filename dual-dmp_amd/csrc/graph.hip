@@ -351,8 +351,263 @@ extern "C" int ddmp_graph_create_sym(int64_t n, int64_t nnz, const int64_t* edge
     return graph_create(n, nnz, edge_index, on_device, out, false);
 }
 
+// ---------------------------------------------------------------------------------------- valued graphs
+// Structure: coalesced CSR by target + the three maps.  Rows are sorted by (source, input position) so that an entry's input
+// edges are listed in input order: the device sums them in that order, deterministically.
+static int csr_build_valued(int64_t n, int64_t nnz, const int64_t* ei, int flags, int32_t* rowptr, int32_t* col, int32_t* ee_ptr,
+                            int32_t* ee_idx, int32_t* eid, int32_t* mirror, int64_t* n_entries) {
+    ARG_TRY(n > 0 && nnz >= 0 && rowptr && col && ee_ptr && ee_idx && eid && mirror && n_entries);
+    ARG_TRY(nnz == 0 || ei);
+    ARG_TRY(n < (int64_t)INT32_MAX && nnz + n < (int64_t)INT32_MAX);
+    ARG_TRY(!(flags & ~(DDMP_GV_LOOPS | DDMP_GV_IMPROVED | DDMP_GV_NORMALIZE | DDMP_GV_DROP_LOOPS | DDMP_GV_REQUIRE_SYM)));
+    ARG_TRY(!((flags & DDMP_GV_LOOPS) && (flags & DDMP_GV_DROP_LOOPS)));
+    const bool loops = flags & DDMP_GV_LOOPS, drop = flags & DDMP_GV_DROP_LOOPS;
+    const int64_t* src = ei;
+    const int64_t* dst = ei + nnz;
+    const int64_t cap = *n_entries;
+    std::vector<int32_t> cnt, last_loop;
+    std::vector<std::pair<int32_t, int32_t>> ent;                // per row: (source, input edge | -1 = the added loop)
+    try {
+        cnt.assign((size_t)n + 1, 0);
+        if (loops) last_loop.assign((size_t)n, -1);
+    } catch (const std::bad_alloc&) { return DDMP_ENOMEM; }
+    for (int64_t k = 0; k < nnz; ++k) {
+        const int64_t s = src[k], d = dst[k];
+        if (s < 0 || s >= n || d < 0 || d >= n) return DDMP_ERANGE;
+        eid[k] = -1;
+        if (s == d && (loops || drop)) {
+            if (loops) last_loop[(size_t)d] = (int32_t)k;        // add_remaining_self_loops: the last explicit loop's weight stays
+            continue;
+        }
+        cnt[(size_t)d + 1]++;
+    }
+    if (loops) for (int64_t i = 0; i < n; ++i) cnt[(size_t)i + 1]++;
+    for (int64_t i = 0; i < n; ++i) cnt[(size_t)i + 1] += cnt[(size_t)i];
+    try { ent.resize((size_t)cnt[(size_t)n]); } catch (const std::bad_alloc&) { return DDMP_ENOMEM; }
+    {
+        std::vector<int32_t> cur(cnt.begin(), cnt.end() - 1);
+        for (int64_t k = 0; k < nnz; ++k) {
+            const int64_t s = src[k], d = dst[k];
+            if (s == d && (loops || drop)) continue;
+            ent[(size_t)cur[(size_t)d]++] = {(int32_t)s, (int32_t)k};
+        }
+        if (loops) for (int64_t i = 0; i < n; ++i) ent[(size_t)cur[(size_t)i]++] = {(int32_t)i, last_loop[(size_t)i]};
+    }
+    int64_t ne = 0, nee = 0;
+    rowptr[0] = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        auto b = ent.begin() + cnt[(size_t)i], e = ent.begin() + cnt[(size_t)i + 1];
+        std::stable_sort(b, e, [](const std::pair<int32_t, int32_t>& x, const std::pair<int32_t, int32_t>& y) { return x.first < y.first; });
+        for (auto it = b; it != e; ++it) {
+            if (it == b || it->first != (it - 1)->first) {
+                if (ne >= cap) return DDMP_EWORKSPACE;
+                col[ne] = it->first;
+                ee_ptr[ne] = (int32_t)nee;
+                ++ne;
+            }
+            if (it->second >= 0) {
+                ee_idx[nee++] = it->second;
+                eid[it->second] = (int32_t)(ne - 1);
+            }
+        }
+        rowptr[i + 1] = (int32_t)ne;
+    }
+    if (ne >= cap + 1) return DDMP_EWORKSPACE;
+    ee_ptr[ne] = (int32_t)nee;
+    for (int64_t i = 0; i < n; ++i)
+        for (int32_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+            const int32_t j = col[e];
+            const int32_t* b = col + rowptr[j];
+            const int32_t* t = col + rowptr[j + 1];
+            const int32_t* p = std::lower_bound(b, t, (int32_t)i);
+            if (p == t || *p != (int32_t)i) return DDMP_EINVAL;   // the edge structure is not symmetric
+            mirror[e] = (int32_t)(p - col);
+        }
+    *n_entries = ne;
+    return DDMP_OK;
+}
+
+extern "C" int ddmp_csr_build_valued_host(int64_t n, int64_t nnz, const int64_t* ei, int flags, int32_t* rowptr, int32_t* col,
+                                          int32_t* ee_ptr, int32_t* ee_idx, int32_t* eid, int32_t* mirror, int64_t* n_entries) {
+    return csr_build_valued(n, nnz, ei, flags, rowptr, col, ee_ptr, ee_idx, eid, mirror, n_entries);
+}
+
+namespace {
+// one thread per row: the entries' coalesced weights (input order), the row's weighted degree (CSR order), s = deg^-1/2
+__global__ __launch_bounds__(256) void gv_rows_kernel(const int* __restrict__ rowptr, const int* __restrict__ ee_ptr,
+                                                      const int* __restrict__ ee_idx, const float* __restrict__ w, float* __restrict__ a,
+                                                      float* __restrict__ s, int n, float fill, int normalize, int* __restrict__ status) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float deg = 0.f;
+    int bad = 0;
+    for (int e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+        const int t0 = ee_ptr[e], t1 = ee_ptr[e + 1];
+        float v = t0 == t1 ? fill : 0.f;
+        for (int t = t0; t < t1; ++t) v += w ? w[ee_idx[t]] : 1.f;
+        a[e] = v;
+        if (!(fabsf(v) <= 3.4028234664e38f)) bad |= DDMP_GV_ENONFINITE;
+        deg += v;
+    }
+    if (!(fabsf(deg) <= 3.4028234664e38f)) bad |= DDMP_GV_ENONFINITE;
+    if (normalize && deg < 0.f) bad |= DDMP_GV_ENEGDEG;
+    s[i] = normalize ? (deg > 0.f ? (float)(1.0 / sqrt((double)deg)) : 0.f) : 1.f;
+    if (bad) atomicOr(status, bad);
+}
+// one thread per entry: the gather's factors for A and A^T
+__global__ __launch_bounds__(256) void gv_entries_kernel(const int* __restrict__ col, const int* __restrict__ mirror,
+                                                         const float* __restrict__ a, const float* __restrict__ s, float* __restrict__ ew,
+                                                         float* __restrict__ ew_t, int ne, int normalize, int require_sym,
+                                                         int* __restrict__ status) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= ne) return;
+    const float ae = a[e], am = a[mirror[e]];
+    const float sj = normalize ? s[col[e]] : 1.f;
+    ew[e] = normalize ? ae * sj : ae;
+    if (ew_t != ew) ew_t[e] = normalize ? am * sj : am;
+    if (require_sym && ae != am) atomicOr(status, DDMP_GV_ENOTSYM);
+}
+// one thread per row: r_i + c_i, then the entries' gradient
+__global__ __launch_bounds__(256) void gv_grad_rows_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                           const int* __restrict__ mirror, const float* __restrict__ ew,
+                                                           const float* __restrict__ ew_t, const float* __restrict__ s,
+                                                           const float* __restrict__ G, float* __restrict__ ge, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int e0 = rowptr[i], e1 = rowptr[i + 1];
+    float rc = 0.f;
+    for (int e = e0; e < e1; ++e) rc += ew[e] * G[e] + ew_t[e] * G[mirror[e]];
+    const float si = s[i];
+    const float k = 0.5f * si * si * si * rc;
+    for (int e = e0; e < e1; ++e) ge[e] = si * s[col[e]] * G[e] - k;
+}
+__global__ __launch_bounds__(256) void gv_grad_edges_kernel(const int* __restrict__ eid, const float* __restrict__ ge,
+                                                            float* __restrict__ dw, int64_t nnz) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nnz) return;
+    const int e = eid[k];
+    dw[k] = e >= 0 ? ge[e] : 0.f;
+}
+}  // namespace
+
+extern "C" int ddmp_graph_set_values(ddmp_graph* g, const float* w, ddmp_stream stream) {
+    ARG_TRY(g && g->valued);
+    hipStream_t st = (hipStream_t)stream;
+    const int normalize = (g->valued & DDMP_GV_NORMALIZE) ? 1 : 0;
+    const float fill = (g->valued & DDMP_GV_IMPROVED) ? 2.f : 1.f;
+    HIP_TRY(hipMemsetAsync(g->vstatus, 0, sizeof(int), st));
+    const int n = (int)g->n_rows, ne = (int)g->nnz;
+    hipLaunchKernelGGL(gv_rows_kernel, dim3((unsigned)ddmp::cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->ee_ptr, g->ee_idx, w, g->a,
+                       g->dinv, n, fill, normalize, g->vstatus);
+    LAUNCH_TRY();
+    if (ne > 0) {
+        hipLaunchKernelGGL(gv_entries_kernel, dim3((unsigned)ddmp::cdiv(ne, 256)), dim3(256), 0, st, g->col, g->mirror, g->a, g->dinv,
+                           g->ew, g->ew_t, ne, normalize, (g->valued & DDMP_GV_REQUIRE_SYM) ? 1 : 0, g->vstatus);
+        LAUNCH_TRY();
+    }
+    return DDMP_OK;
+}
+
+extern "C" int ddmp_graph_values_status(const ddmp_graph* g, int* status_host, ddmp_stream stream) {
+    ARG_TRY(g && g->valued && status_host);
+    HIP_TRY(hipMemcpyAsync(status_host, g->vstatus, sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    return DDMP_OK;
+}
+
+extern "C" int ddmp_graph_export_values(const ddmp_graph* g, float* ew, float* ew_t, float* a, float* s, ddmp_stream stream) {
+    ARG_TRY(g && g->valued);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t eb = sizeof(float) * (size_t)g->nnz;
+    if (ew && eb) HIP_TRY(hipMemcpyAsync(ew, g->ew, eb, hipMemcpyDeviceToDevice, st));
+    if (ew_t && eb) HIP_TRY(hipMemcpyAsync(ew_t, g->ew_t, eb, hipMemcpyDeviceToDevice, st));
+    if (a && eb) HIP_TRY(hipMemcpyAsync(a, g->a, eb, hipMemcpyDeviceToDevice, st));
+    if (s) HIP_TRY(hipMemcpyAsync(s, g->dinv, sizeof(float) * (size_t)g->n_rows, hipMemcpyDeviceToDevice, st));
+    return DDMP_OK;
+}
+
+extern "C" int ddmp_graph_weight_grad(const ddmp_graph* g, const float* G, float* dw, ddmp_stream stream) {
+    ARG_TRY(g && g->valued && G && dw);
+    hipStream_t st = (hipStream_t)stream;
+    const float* ge = G;                                         // not normalising: g_e = G_e
+    if (g->valued & DDMP_GV_NORMALIZE) {
+        hipLaunchKernelGGL(gv_grad_rows_kernel, dim3((unsigned)ddmp::cdiv(g->n_rows, 256)), dim3(256), 0, st, g->rowptr, g->col, g->mirror,
+                           g->ew, g->ew_t, g->dinv, G, g->ge, (int)g->n_rows);
+        LAUNCH_TRY();
+        ge = g->ge;
+    }
+    if (g->nnz_in > 0) {
+        hipLaunchKernelGGL(gv_grad_edges_kernel, dim3((unsigned)ddmp::cdiv(g->nnz_in, 256)), dim3(256), 0, st, g->eid, ge, dw, g->nnz_in);
+        LAUNCH_TRY();
+    }
+    return DDMP_OK;
+}
+
+extern "C" int ddmp_graph_create_valued(int64_t n, int64_t nnz, const int64_t* edge_index, int on_device, int flags, ddmp_graph** out) {
+    ARG_TRY(out && n > 0 && nnz >= 0 && (nnz == 0 || edge_index));
+    std::vector<int64_t> host_ei;
+    std::vector<int32_t> rowptr, col, ee_ptr, ee_idx, eid, mirror;
+    std::vector<float> dinv;
+    const size_t cap = (size_t)(nnz + n);
+    try {
+        rowptr.resize((size_t)n + 1);
+        col.resize(cap);
+        ee_ptr.resize(cap + 1);
+        mirror.resize(cap);
+        ee_idx.resize((size_t)std::max<int64_t>(nnz, 1));
+        eid.resize((size_t)std::max<int64_t>(nnz, 1));
+        dinv.assign((size_t)n, 0.f);
+        if (on_device && nnz > 0) host_ei.resize((size_t)(2 * nnz));
+    } catch (const std::bad_alloc&) {
+        return DDMP_ENOMEM;
+    }
+    const int64_t* ei = edge_index;
+    if (on_device && nnz > 0) {
+        HIP_TRY(hipMemcpy(host_ei.data(), edge_index, sizeof(int64_t) * (size_t)(2 * nnz), hipMemcpyDeviceToHost));
+        ei = host_ei.data();
+    }
+    int64_t ne = (int64_t)cap;
+    int st = csr_build_valued(n, nnz, ei, flags, rowptr.data(), col.data(), ee_ptr.data(), ee_idx.data(), eid.data(), mirror.data(), &ne);
+    if (st != DDMP_OK) return st;
+    ddmp_graph* g = nullptr;
+    st = upload_graph(n, n, rowptr.data(), col.data(), dinv.data(), &g);
+    if (st != DDMP_OK) return st;
+    g->valued = DDMP_GV_VALUED | flags;
+    g->nnz_in = nnz;
+    hipError_t e;
+    const size_t ne1 = (size_t)std::max<int64_t>(ne, 1), nz1 = (size_t)std::max<int64_t>(nnz, 1);
+    auto up = [&](int32_t** dst, const int32_t* src_h, size_t cnt) {
+        if ((e = hipMalloc((void**)dst, sizeof(int32_t) * cnt)) != hipSuccess) return false;
+        return (e = hipMemcpy(*dst, src_h, sizeof(int32_t) * cnt, hipMemcpyHostToDevice)) == hipSuccess;
+    };
+    if (!up(&g->ee_ptr, ee_ptr.data(), (size_t)ne + 1) || !up(&g->ee_idx, ee_idx.data(), nz1) || !up(&g->eid, eid.data(), nz1) ||
+        !up(&g->mirror, mirror.data(), ne1))
+        goto fail;
+    if ((e = hipMalloc((void**)&g->a, sizeof(float) * ne1)) != hipSuccess) goto fail;
+    if ((e = hipMalloc((void**)&g->ge, sizeof(float) * ne1)) != hipSuccess) goto fail;
+    if ((e = hipMalloc((void**)&g->vstatus, sizeof(int))) != hipSuccess) goto fail;
+    if (flags & DDMP_GV_REQUIRE_SYM) g->ew_t = g->ew;            // symmetric values by contract: one array serves both operators
+    else if ((e = hipMalloc((void**)&g->ew_t, sizeof(float) * ne1)) != hipSuccess) goto fail;
+    st = ddmp_graph_set_values(g, nullptr, nullptr);             // the values of all-ones weights
+    if (st == DDMP_OK && (e = hipDeviceSynchronize()) != hipSuccess) goto fail;
+    if (st != DDMP_OK) { ddmp_graph_destroy(g); return st; }
+    *out = g;
+    return DDMP_OK;
+fail:
+    ddmp_graph_destroy(g);
+    return (int)e;
+}
+
 extern "C" int ddmp_graph_destroy(ddmp_graph* g) {
     if (!g) return DDMP_OK;
+    if (g->ee_ptr) (void)hipFree(g->ee_ptr);
+    if (g->ee_idx) (void)hipFree(g->ee_idx);
+    if (g->eid) (void)hipFree(g->eid);
+    if (g->mirror) (void)hipFree(g->mirror);
+    if (g->a) (void)hipFree(g->a);
+    if (g->ge) (void)hipFree(g->ge);
+    if (g->vstatus) (void)hipFree(g->vstatus);
+    if (g->ew_t && g->ew_t != g->ew) (void)hipFree(g->ew_t);
     if (g->rowptr) (void)hipFree(g->rowptr);
     if (g->col) (void)hipFree(g->col);
     if (g->dinv) (void)hipFree(g->dinv);

@@ -55,7 +55,9 @@ __device__ __forceinline__ void axpby_rows(const Axpby& ax, const float* X, int6
     if (ax.Z2) z2 = *reinterpret_cast<const float4*>(ax.Z2 + (int64_t)row * ax.ldz2 + off);
 }
 
-template <int LANES, int CHUNKS, bool PRO, bool AXP = false>
+// EW (all kernels of this file): `dinv` is the graph's PER-ENTRY factor array (ddmp_graph::ew) and is indexed by the entry, not by
+// its column -- valued graphs; separate instantiations, the unvalued ones are unchanged.
+template <int LANES, int CHUNKS, bool PRO, bool AXP = false, bool EW = false>
 __global__ __launch_bounds__(256) void spmm_vec_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ dinv, const float* __restrict__ dinv_r,
     const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int n_rows,
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(256) void spmm_vec_kernel(
         for (int t = tid; t < ne; t += 256) {
             const int c = col[e0 + t];
             s_col[t] = c;
-            s_w[t] = dinv[c];
+            s_w[t] = EW ? dinv[e0 + t] : dinv[c];
         }
     }
     __syncthreads();
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(256) void spmm_vec_kernel(
                     wj[k] = s_w[ek];
                 } else {
                     cj[k] = col[e0 + ek];
-                    wj[k] = dinv[cj[k]];
+                    wj[k] = EW ? dinv[e0 + ek] : dinv[cj[k]];
                 }
                 if (e + k >= ee) wj[k] = 0.f;
             }
@@ -167,7 +169,7 @@ __global__ __launch_bounds__(256) void spmm_vec_kernel(
 }
 
 // any width: one thread per (row, channel)
-template <bool PRO, bool AXP = false>
+template <bool PRO, bool AXP = false, bool EW = false>
 __global__ __launch_bounds__(256) void spmm_scalar_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ dinv, const float* __restrict__ dinv_r,
     const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int n_rows, int C,
@@ -187,7 +189,7 @@ __global__ __launch_bounds__(256) void spmm_scalar_kernel(
             const int j = col[e];
             float t = X[(int64_t)j * ldx + c];
             if (PRO) t = lrelu(fmaf(t, pscale[c], pshift[c]), slope);
-            acc = fmaf(dinv[j], t, acc);
+            acc = fmaf(EW ? dinv[e] : dinv[j], t, acc);
         }
         if (AXP) ax.Y[(int64_t)row * ldy + c] = axpby1(ax, acc * dinv_r[row], ox, oz, oz2);
         else Y[(int64_t)row * ldy + c] = fmaf(acc, dinv_r[row], bias ? bias[c] : 0.f);
@@ -229,7 +231,7 @@ struct BnBwdGather {
     const float *c1, *c0;
 };
 
-template <int LANES, int U, int NR, bool PRO, int SL, bool RED = false, bool BWD = false, bool AXP = false>
+template <int LANES, int U, int NR, bool PRO, int SL, bool RED = false, bool BWD = false, bool AXP = false, bool EW = false>
 __global__ __launch_bounds__(256) void spmm_slab_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ dinv, const float* __restrict__ dinv_r,
     const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int n_rows, int C,
@@ -259,7 +261,7 @@ __global__ __launch_bounds__(256) void spmm_slab_kernel(
         for (int t = tid; t < ne; t += 256) {
             const int c = col[e0 + t];
             s_col[t] = c;
-            s_w[t] = dinv[c];
+            s_w[t] = EW ? dinv[e0 + t] : dinv[c];
         }
     }
     __syncthreads();
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(256) void spmm_slab_kernel(
                             wj[q][k] = s_w[ek];
                         } else {
                             cj[q][k] = col[e0 + ek];
-                            wj[q][k] = dinv[cj[q][k]];
+                            wj[q][k] = EW ? dinv[e0 + ek] : dinv[cj[q][k]];
                         }
                         if (es[q] + k >= ee[q]) wj[q][k] = 0.f;
                     }
@@ -409,10 +411,15 @@ __global__ __launch_bounds__(256) void spmm_slab_kernel(
 #include "spmm_lean.inc"
 
 // chunk_list / n_list: only these chunks (the LDS-patch kernel's heavy list), one workgroup each
-template <bool PRO, int RED, bool BWD, bool AXP = false>
+template <bool PRO, int RED, bool BWD, bool AXP = false, bool EWU = false>
 int launch_lean(const LeanPlan& lp, const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, int C,
                 const float* bias, const float* ps, const float* psh, float slope, hipStream_t st, BnRed red = BnRed(),
                 BnBwdGather bwd = BnBwdGather(), const int* chunk_list = nullptr, int n_list = 0, Axpby ax = Axpby()) {
+    if constexpr (!PRO && RED == 0 && !BWD && !EWU) {           // valued graphs: the hub-chunk path reads `ew` too (plain + affine forms)
+        if (g->valued) return launch_lean<PRO, RED, BWD, AXP, true>(lp, g, X, ldx, Y, ldy, C, bias, ps, psh, slope, st, red, bwd, chunk_list, n_list, ax);
+    } else if (!EWU && g->valued) {
+        return DDMP_EINVAL;
+    }
     const int n = (int)g->n_rows;
     if (chunk_list) {
         if (n_list <= 0) return DDMP_OK;
@@ -423,7 +430,7 @@ int launch_lean(const LeanPlan& lp, const ddmp_graph* g, const float* X, int64_t
         const int want = std::min(n_sl, std::max(1, 2048 / n_list));
         const int per = (n_sl + want - 1) / want;
         const int groups_l = (n_sl + per - 1) / per;
-        hipLaunchKernelGGL((spmm_lean_kernel<PRO, RED, BWD, AXP>), dim3(n_list, groups_l), dim3(256), 0, st, g->rowptr, g->col, g->ew, g->dinv, g->dinv_r, X,
+        hipLaunchKernelGGL((spmm_lean_kernel<PRO, RED, BWD, AXP, EWU>), dim3(n_list, groups_l), dim3(256), 0, st, g->rowptr, g->col, g->ew, g->dinv, g->dinv_r, X,
                            ldx, Y, ldy, n, C, bias, ps, psh, slope, 0, n_list, chunk_list, red, bwd, ax);
         LAUNCH_TRY();
         return DDMP_OK;
@@ -438,7 +445,7 @@ int launch_lean(const LeanPlan& lp, const ddmp_graph* g, const float* X, int64_t
         const int per = (n_slabs + want - 1) / want;
         groups = (n_slabs + per - 1) / per;
     }
-    hipLaunchKernelGGL((spmm_lean_kernel<PRO, RED, BWD, AXP>), dim3(cpx * kXcd, groups), dim3(256), 0, st, g->rowptr, g->col, g->ew, g->dinv, g->dinv_r, X, ldx,
+    hipLaunchKernelGGL((spmm_lean_kernel<PRO, RED, BWD, AXP, EWU>), dim3(cpx * kXcd, groups), dim3(256), 0, st, g->rowptr, g->col, g->ew, g->dinv, g->dinv_r, X, ldx,
                        Y, ldy, n, C, bias, ps, psh, slope, cpx, lp.n_chunks, (const int*)nullptr, red, bwd, ax);
     LAUNCH_TRY();
     return DDMP_OK;
@@ -456,7 +463,11 @@ int launch_slab(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int6
         if (lp.kind && ps) return launch_lean<true, 0, false>(lp, g, X, ldx, Y, ldy, C, bias, ps, psh, slope, st);
         if (lp.kind) return launch_lean<false, 0, false>(lp, g, X, ldx, Y, ldy, C, bias, ps, psh, slope, st);
     }
-    if (ps)
+    if (g->valued && ps) return DDMP_EINVAL;
+    if (g->valued)
+        hipLaunchKernelGGL((spmm_slab_kernel<LANES, U, NR, false, SL, false, false, false, true>), grid, block, 0, st, g->rowptr, g->col,
+                           g->ew, g->dinv_r, X, ldx, Y, ldy, n, C, bias, ps, psh, slope, cpx, n_chunks);
+    else if (ps)
         hipLaunchKernelGGL((spmm_slab_kernel<LANES, U, NR, true, SL>), grid, block, 0, st, g->rowptr, g->col, g->dinv, g->dinv_r, X,
                            ldx, Y, ldy, n, C, bias, ps, psh, slope, cpx, n_chunks);
     else
@@ -473,6 +484,17 @@ int launch_vec(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64
     const int n_chunks = (int)cdiv(n, kRB);
     const int cpx = (int)cdiv(n_chunks, kXcd);
     dim3 grid(cpx * kXcd), block(256);
+    if (g->valued) {                                             // (C = 8 | 16 only: every C % 32 == 0 is the slab route's)
+        if constexpr (LANES <= 4) {
+            if (ps) return DDMP_EINVAL;
+            hipLaunchKernelGGL((spmm_vec_kernel<LANES, CHUNKS, false, false, true>), grid, block, 0, st, g->rowptr, g->col,
+                               g->ew, g->dinv_r, X, ldx, Y, ldy, n, bias, ps, psh, slope, cpx, n_chunks);
+            LAUNCH_TRY();
+            return DDMP_OK;
+        } else {
+            return DDMP_EINVAL;
+        }
+    }
     if (ps)
         hipLaunchKernelGGL((spmm_vec_kernel<LANES, CHUNKS, true>), grid, block, 0, st, g->rowptr, g->col,
                            g->dinv, g->dinv_r, X, ldx, Y, ldy, n, bias, ps, psh, slope, cpx, n_chunks);
@@ -491,6 +513,7 @@ extern "C" int ddmp_spmm_f32(const ddmp_graph* g, const float* X, int64_t ldx, f
     ARG_TRY(g && X && Y && C > 0 && ldx >= C && ldy >= C);
     ARG_TRY((pro_scale == nullptr) == (pro_shift == nullptr));
     ARG_TRY(X != Y);
+    ARG_TRY(!(g->valued && pro_scale));                          // valued graphs: the plain gather (+ bias) and the affine form
     hipStream_t st = (hipStream_t)stream;
     const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) &&
                      ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y)) % 16 == 0) &&
@@ -528,7 +551,10 @@ extern "C" int ddmp_spmm_f32(const ddmp_graph* g, const float* X, int64_t ldx, f
     }
     const int64_t total = g->n_rows * (int64_t)C;
     const int grid = (int)std::min<int64_t>(cdiv(total, 256), 256 * 16);
-    if (pro_scale)
+    if (g->valued)
+        hipLaunchKernelGGL((spmm_scalar_kernel<false, false, true>), dim3(grid), dim3(256), 0, st, g->rowptr, g->col, g->ew, g->dinv_r,
+                           X, ldx, Y, ldy, (int)g->n_rows, C, bias, pro_scale, pro_shift, slope);
+    else if (pro_scale)
         hipLaunchKernelGGL((spmm_scalar_kernel<true>), dim3(grid), dim3(256), 0, st, g->rowptr, g->col, g->dinv, g->dinv_r,
                            X, ldx, Y, ldy, (int)g->n_rows, C, bias, pro_scale, pro_shift, slope);
     else
@@ -563,14 +589,27 @@ extern "C" int ddmp_spmm_axpby_f32(const ddmp_graph* g, const float* X, int64_t 
         if (lp.kind)
             return launch_lean<false, 0, false, true>(lp, g, X, ldx, Y, ldy, C, nullptr, nullptr, nullptr, 0.f, st, BnRed(), BnBwdGather(),
                                                       nullptr, 0, ax);
-        hipLaunchKernelGGL((spmm_slab_kernel<8, 4, 1, false, 1, false, false, true>), dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr,
-                           g->col, g->dinv, g->dinv_r, X, ldx, Y, ldy, n, C, (const float*)nullptr, (const float*)nullptr,
-                           (const float*)nullptr, 0.f, cpx, n_chunks, BnRed(), BnBwdGather(), ax);
+        if (g->valued)
+            hipLaunchKernelGGL((spmm_slab_kernel<8, 4, 1, false, 1, false, false, true, true>), dim3(cpx * kXcd), dim3(256), 0, st,
+                               g->rowptr, g->col, g->ew, g->dinv_r, X, ldx, Y, ldy, n, C, (const float*)nullptr, (const float*)nullptr,
+                               (const float*)nullptr, 0.f, cpx, n_chunks, BnRed(), BnBwdGather(), ax);
+        else
+            hipLaunchKernelGGL((spmm_slab_kernel<8, 4, 1, false, 1, false, false, true>), dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr,
+                               g->col, g->dinv, g->dinv_r, X, ldx, Y, ldy, n, C, (const float*)nullptr, (const float*)nullptr,
+                               (const float*)nullptr, 0.f, cpx, n_chunks, BnRed(), BnBwdGather(), ax);
         LAUNCH_TRY();
         return DDMP_OK;
     }
     if (vec && (C == 8 || C == 16)) {
-        if (C == 8)
+        if (g->valued && C == 8)
+            hipLaunchKernelGGL((spmm_vec_kernel<2, 1, false, true, true>), dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->ew,
+                               g->dinv_r, X, ldx, Y, ldy, n, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f,
+                               cpx, n_chunks, ax);
+        else if (g->valued)
+            hipLaunchKernelGGL((spmm_vec_kernel<4, 1, false, true, true>), dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->ew,
+                               g->dinv_r, X, ldx, Y, ldy, n, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f,
+                               cpx, n_chunks, ax);
+        else if (C == 8)
             hipLaunchKernelGGL((spmm_vec_kernel<2, 1, false, true>), dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->dinv,
                                g->dinv_r, X, ldx, Y, ldy, n, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f,
                                cpx, n_chunks, ax);
@@ -583,8 +622,12 @@ extern "C" int ddmp_spmm_axpby_f32(const ddmp_graph* g, const float* X, int64_t 
     }
     const int64_t total = g->n_rows * (int64_t)C;
     const int grid = (int)std::min<int64_t>(cdiv(total, 256), 256 * 16);
-    hipLaunchKernelGGL((spmm_scalar_kernel<false, true>), dim3(grid), dim3(256), 0, st, g->rowptr, g->col, g->dinv, g->dinv_r, X,
-                       ldx, Y, ldy, n, C, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f, ax);
+    if (g->valued)
+        hipLaunchKernelGGL((spmm_scalar_kernel<false, true, true>), dim3(grid), dim3(256), 0, st, g->rowptr, g->col, g->ew, g->dinv_r, X,
+                           ldx, Y, ldy, n, C, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f, ax);
+    else
+        hipLaunchKernelGGL((spmm_scalar_kernel<false, true>), dim3(grid), dim3(256), 0, st, g->rowptr, g->col, g->dinv, g->dinv_r, X,
+                           ldx, Y, ldy, n, C, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f, ax);
     LAUNCH_TRY();
     return DDMP_OK;
 }
@@ -605,6 +648,7 @@ extern "C" int ddmp_spmm_bnred_f32(const ddmp_graph* g, const float* X, int64_t 
     ddmp::FinalizeScope fin_scope(sums2, stream, C);
     ARG_TRY(g && X && Y && Yp && scale && shift && mean && rstd && sums2 && ws && C > 0 && ldx >= C && ldy >= C && ldyp >= C);
     ARG_TRY(X != Y);
+    ARG_TRY(!g->valued);                                         // (no fused form reads a valued graph's factors)
     if (ws_bytes < ddmp_spmm_bnred_workspace_bytes(g->n_rows, C)) return DDMP_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
@@ -662,6 +706,7 @@ extern "C" int ddmp_spmm_stats_f32(const ddmp_graph* g, const float* X, int64_t 
     ddmp::FinalizeScope fin_scope(sums2, stream, C);
     ARG_TRY(g && X && Y && sums2 && ws && C > 0 && ldx >= C && ldy >= C && X != Y);
     ARG_TRY((pro_scale == nullptr) == (pro_shift == nullptr));
+    ARG_TRY(!g->valued);
     if (ws_bytes < ddmp_spmm_bnred_workspace_bytes(g->n_rows, C)) return DDMP_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
@@ -702,6 +747,7 @@ extern "C" int ddmp_spmm_bnbwd_f32(const ddmp_graph* g, const float* dZ, int64_t
                                    const float* c0, float slope, ddmp_stream stream) {
     ARG_TRY(g && dZ && Yb && out && a && b && c1 && c0 && C > 0 && lddz >= C && ldyb >= C && ld_out >= C);
     ARG_TRY(dZ != out && Yb != out);
+    ARG_TRY(!g->valued);
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (!ddmp_spmm_bnbwd_supported(C) || lddz % 4 || ldyb % 4 || ld_out % 4 || !al16(dZ) || !al16(Yb) || !al16(out) ||
         !al16(a) || !al16(b) || !al16(c1) || !al16(c0))
@@ -724,4 +770,21 @@ extern "C" int ddmp_spmm_bnbwd_f32(const ddmp_graph* g, const float* dZ, int64_t
                        a, b, slope, cpx, n_chunks, BnRed(), bwd);
     LAUNCH_TRY();
     return DDMP_OK;
+}
+
+// The transposed operator of a valued graph: the same structure (symmetric by contract) on the mirrored values `ew_t`.
+extern "C" int ddmp_spmm_t_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, int C, const float* bias,
+                               ddmp_stream stream) {
+    ARG_TRY(g && X && Y && C > 0 && ldx >= C && ldy >= C && X != Y);
+    ARG_TRY(g->valued && g->ew_t);
+    ddmp_graph view = *g;                                        // (a shallow view: owns nothing)
+    view.ew = g->ew_t;
+    return ddmp_spmm_f32(&view, X, ldx, Y, ldy, C, bias, nullptr, nullptr, 0.f, stream);
+}
+
+// 1: a gather of this graph and shape that is not the LDS-patch kernel's runs spmm_lean_kernel; 0: spmm_slab_kernel (DDMP_SPMM_LEAN=0,
+// leading dimensions that are not multiples of 4, or offsets beyond the lean gather's 32 bits).  For tests that name a route.
+extern "C" int ddmp_spmm_lean_selected(const ddmp_graph* g, int64_t ldx, int64_t ldy, int C) {
+    if (!g || C <= 0 || C % 32) return 0;
+    return lean_plan(g, ldx, ldy, C).kind;
 }

@@ -407,6 +407,7 @@ extern "C" int ddmp_spmm_bf16(const ddmp_graph* g, const uint16_t* X, int64_t ld
                               const float* bias, const float* pro_scale, const float* pro_shift, float slope,
                               ddmp_stream stream) {
     ARG_TRY(g && X && Y && X != Y && shape_ok(X, ldx, Y, ldy, C));
+    ARG_TRY(!g->valued);                                         // valued graphs: float32 features only
     ARG_TRY((pro_scale == nullptr) == (pro_shift == nullptr));
     ARG_TRY(coef_ok(bias) && coef_ok(pro_scale) && coef_ok(pro_shift));
     hipStream_t st = (hipStream_t)stream;
@@ -436,6 +437,7 @@ extern "C" int ddmp_spmm_bnred_bf16(const ddmp_graph* g, const uint16_t* X, int6
                                     size_t ws_bytes, ddmp_stream stream) {
     ddmp::FinalizeScope fin_scope(sums2, stream, C);
     ARG_TRY(g && X && Y && Yp && scale && shift && mean && rstd && sums2 && ws && X != Y && shape_ok(X, ldx, Y, ldy, C));
+    ARG_TRY(!g->valued);                                         // valued graphs: float32 features only
     ARG_TRY(ldyp >= C && ldyp % 8 == 0 && b16_aligned(Yp) && b16_aligned(ws));
     ARG_TRY(coef_ok(scale) && coef_ok(shift) && coef_ok(mean) && coef_ok(rstd));
     if (ws_bytes < ddmp_spmm_bnred_bf16_workspace_bytes(g->n_rows, C)) return DDMP_EWORKSPACE;
@@ -463,6 +465,7 @@ extern "C" int ddmp_spmm_stats_bf16(const ddmp_graph* g, const uint16_t* X, int6
     // = ddmp_spmm_bf16 + ddmp_bn_stats_bf16 of the stored output, the statistics from the gather's epilogue around `ref`
     ddmp::FinalizeScope fin_scope(sums2, stream, C);
     ARG_TRY(g && X && Y && sums2 && ws && X != Y && shape_ok(X, ldx, Y, ldy, C));
+    ARG_TRY(!g->valued);                                         // valued graphs: float32 features only
     ARG_TRY((pro_scale == nullptr) == (pro_shift == nullptr));
     ARG_TRY(coef_ok(bias) && coef_ok(pro_scale) && coef_ok(pro_shift) && coef_ok(ref) && b16_aligned(ws));
     if (ws_bytes < ddmp_spmm_bnred_bf16_workspace_bytes(g->n_rows, C)) return DDMP_EWORKSPACE;
@@ -496,6 +499,7 @@ extern "C" int ddmp_spmm_bnbwd_bf16(const ddmp_graph* g, const uint16_t* dZ, int
                                     int64_t ldyb, uint16_t* out, int64_t ld_out, int C, const float* a, const float* b,
                                     const float* c1, const float* c0, float slope, ddmp_stream stream) {
     ARG_TRY(g && dZ && Yb && out && a && b && c1 && c0 && dZ != out && Yb != out && shape_ok(dZ, lddz, out, ld_out, C));
+    ARG_TRY(!g->valued);                                         // valued graphs: float32 features only
     ARG_TRY(ldyb >= C && ldyb % 8 == 0 && b16_aligned(Yb) && coef_ok(a) && coef_ok(b) && coef_ok(c1) && coef_ok(c0));
     BnBwdGatherB bwd{Yb, ldyb, c1, c0};
     {   // LDS-patch form where it applies (round 6); its heavy chunks: the slab kernel over the list

@@ -29,7 +29,9 @@
 // AXP (ddmp_spmm_axpby_f32): the affine epilogue a * (gather) + b * X[row] + c * Z[row] + d * Z2[row] -- see Axpby in spmm.hip; the
 // row's own operands are requested where RED = 1 requests its Yp row: before the neighbour loop.
 constexpr int kLeanSlots = kRB * 16;
-template <bool PRO, int RED, bool BWD, bool AXP = false>
+// EWU: the unstaged (hub-chunk) path reads the entry's factor from `ew` like the staged one -- valued graphs (DESIGN.md 4.7), whose
+// factor is not dinv[col]; a separate instantiation: the unvalued kernels are unchanged.
+template <bool PRO, int RED, bool BWD, bool AXP = false, bool EWU = false>
 __global__ __launch_bounds__(256) void spmm_lean_kernel(
     const int* __restrict__ rowptr, const int* __restrict__ col, const float* __restrict__ ew, const float* __restrict__ dinv,
     const float* __restrict__ dinv_r, const float* __restrict__ X, int64_t ldx, float* __restrict__ Y, int64_t ldy, int n_rows, int C,
@@ -178,9 +180,10 @@ __global__ __launch_bounds__(256) void spmm_lean_kernel(
                 } else {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const int c = col[rbase + min(4 * q + k, nn - 1)];
+                        const int e = rbase + min(4 * q + k, nn - 1);
+                        const int c = col[e];
                         o[k] = (unsigned)c * ld16;
-                        w[k] = 4 * q + k < nn ? dinv[c] : 0.f;
+                        w[k] = 4 * q + k < nn ? (EWU ? ew[e] : dinv[c]) : 0.f;
                     }
                 }
                 float4 v[4], vy[BWD ? 4 : 1];

@@ -286,10 +286,22 @@ class _ModularNet(nn.Module):
             cache[(name, str(self.device))] = hit
         return hit[2]
 
-    def _trunk(self, x, edge_index):
+    def _trunk(self, x, edge_index, edge_weight=None):
         for i in range(1, 13):
-            x = self.l_relu(getattr(self, "bn%d" % i)(getattr(self, "conv%d" % i)(x, edge_index)))
+            conv = getattr(self, "conv%d" % i)
+            y = conv(x, edge_index) if edge_weight is None else conv(x, edge_index, edge_weight)
+            x = self.l_relu(getattr(self, "bn%d" % i)(y))
         return x
+
+    def _weight(self, data, name):
+        """The dataset's per-edge weights (``edge_weight`` on the vertex graph, ``face_weight`` on the face graph) when it has
+        such an attribute; absent (every dataset of the reference): None, the unweighted operator."""
+        t = getattr(data, name, None)
+        if t is None:
+            return None
+        if t.requires_grad and t.device != self.device:          # learnable weights kept on another device: a differentiable
+            return t.to(self.device)                             # copy per forward (``_dev`` caches a DETACHED copy)
+        return self._dev(data, name)
 
 
 class PosNetModular(_ModularNet):
@@ -297,7 +309,7 @@ class PosNetModular(_ModularNet):
 
     def forward(self, data):
         z1, x_pos, edge_index = self._dev(data, "z1"), self._dev(data, "x_pos"), self._dev(data, "edge_index")
-        dx = self._trunk(z1, edge_index)
+        dx = self._trunk(z1, edge_index, self._weight(data, "edge_weight"))
         dx = self.linear2(self.l_relu(self.linear1(dx)))
         return x_pos + dx
 
@@ -307,7 +319,7 @@ class NormalNetModular(_ModularNet):
 
     def forward(self, data):
         z2, edge_index = self._dev(data, "z2"), self._dev(data, "face_index")
-        dx = self._trunk(z2, edge_index)
+        dx = self._trunk(z2, edge_index, self._weight(data, "face_weight"))
         dx = torch.tanh(self.linear2(self.l_relu(self.linear1(dx))))
         dx_norm = torch.reciprocal(torch.norm(dx, dim=1, keepdim=True).expand(-1, 3) + 1.0e-12)
         return torch.mul(dx, dx_norm)

@@ -15,7 +15,26 @@ Glorot-uniform and ``bias`` [out] zeros, ``forward(x, edge_index, edge_weight=No
 lambda_max=None)`` with ``lambda_max`` a float (default 2.0),
 ``Y = sum_k T_k W_k^T + b``, ``T_0 = X``, ``T_1 = L^ X``, ``T_k = 2 L^ T_{k-1} - T_{k-2}``,
 ``L^ = -(2 / lambda_max) D^-1/2 A D^-1/2 + (2 / lambda_max - 1) I`` (no self loops; symmetric
-``edge_index`` only).  ``edge_weight``, ``batch``, a tensor ``lambda_max`` and other normalisations raise.
+``edge_index`` only).  ``batch``, a tensor ``lambda_max`` and other normalisations raise.
+
+``edge_weight`` (both operators; restated from the published PyG 2.2.0 source from memory -- PyG cannot be installed here, so
+this could not be checked against it; the pin is the dense float64 restatement ``tests/gcnw_ref.py``):
+
+* ``GCNConv(in, out, improved=False, cached=False, add_self_loops=True, normalize=True, bias=True)``,
+  ``forward(x, edge_index, edge_weight=None)``.  ``gcn_norm``: ``fill = 2 if improved else 1``; with ``add_self_loops`` explicit
+  self loops leave the edge list and every node gets one loop of weight ``fill`` -- except that a node with explicit loops keeps
+  the weight of its LAST explicit loop in input order (``add_remaining_self_loops``); ``deg_i`` = sum of ``w_e`` over the entries
+  with target i (loop included), ``s_i = deg_i^-1/2`` (inf -> 0), entry value ``s_i w_e s_j``; duplicate edges each contribute.
+  ``normalize=False``: no loops are added and the entry value is ``w_e`` (1 without ``edge_weight``), whatever
+  ``add_self_loops`` says.  ``cached`` is accepted and has no effect: the graph is always cached by tensor identity.
+  Differentiable w.r.t. ``edge_weight`` (an SDDMM over the CSR + the normalisation's chain rule, ``ops.sddmm`` /
+  ``ops.graph_weight_grad``).  The edge STRUCTURE must be symmetric; the weights need not be.
+* ``ChebConv.forward(..., edge_weight=w)``: self loops removed, ``S = D^-1/2 A_w D^-1/2``, the recurrence above on the valued S.
+  SYMMETRIC weights only (after coalescing ``w_ij == w_ji`` bit for bit, else ``ValueError``: PyG takes the degree over sources
+  here and over targets in ``gcn_norm``; the two agree only for symmetric weights).  No gradient w.r.t. ``edge_weight``.
+* Refused with ``ValueError`` before any gather: non-finite weights, a negative weighted degree, a length other than
+  ``edge_index.shape[1]``, a dtype other than float32 / float64 (float64 is rounded to float32 once), a weight tensor that is not
+  on the GPU, bf16 features.  ``edge_weight=None`` with default options is the unvalued graph and code path, bit for bit.
 """
 from __future__ import annotations
 
@@ -93,6 +112,84 @@ class _GCNConvFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
+class _GCNConvWFn(torch.autograd.Function):
+    """GCNConv on a VALUED graph (edge_weight and / or non-default options): Y = A (X W^T) + b with A = the graph's current
+    values, which need not be symmetric -- the backward gathers with A^T (``transpose=True``: same structure, mirrored values).
+    The edge_weight gradient is dL/dA per entry (``ops.sddmm`` of the gather's output gradient and the operand the gather
+    consumed) pushed through the normalisation (``ops.graph_weight_grad``); it runs only when edge_weight requires grad.
+    The gather's operand is SAVED, not recomputed: aggregate-first it is the padded X (saved anyway when x is not already
+    padded: N x C_in x 4 bytes more), aggregate-last it is H = X W^T, kept between forward and backward only when the
+    edge_weight gradient is wanted (N x C_out x 4 bytes) instead of a second forward GEMM in the backward."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, edge_weight, graph):
+        cin, cout = weight.shape[1], weight.shape[0]
+        xp = _pad_cols(x.detach().to(torch.float32))
+        wp = _pad_cols(weight.detach())
+        b = None if bias is None else bias.detach().contiguous()
+        agg_first = xp.shape[1] < cout
+        need_ew = edge_weight is not None and edge_weight.requires_grad
+        if agg_first:
+            p = ops.spmm(graph, xp)
+            y = ops.gemm_nt(p, wp, bias=b)
+            ctx.save_for_backward(p, wp, xp if need_ew else None, graph.values_src)
+        else:
+            h = ops.gemm_nt(xp, wp)
+            y = ops.spmm(graph, h, bias=b if cout % 4 == 0 else None)
+            if cout % 4 != 0 and b is not None:
+                y += b
+            ctx.save_for_backward(xp, wp, h if need_ew else None, graph.values_src)
+        ctx.graph, ctx.agg_first, ctx.cin, ctx.has_bias = graph, agg_first, cin, bias is not None
+        # the values this call ran on: another weight version may have been set on the same structure before the backward (the
+        # weights are saved through autograd, so an in-place change of them in between is an error, not a wrong restore)
+        ctx.values_key = graph.values_key
+        ctx.ew_dtype = None if edge_weight is None else edge_weight.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        with ops.on_device(dy):
+            return _GCNConvWFn._backward(ctx, dy)
+
+    @staticmethod
+    def _backward(ctx, dy):
+        saved, wp, operand, wsrc = ctx.saved_tensors
+        graph, cin = ctx.graph, ctx.cin
+        ops.restore_values(graph, ctx.values_key, wsrc)
+        dy = dy.contiguous()
+        cout = dy.shape[1]
+        dyp = _pad_cols(dy)
+        if dyp.shape[1] != cout:           # ragged output width: pad the weight rows to match
+            wrow = torch.zeros((dyp.shape[1], wp.shape[1]), dtype=wp.dtype, device=wp.device)
+            wrow[:cout] = wp
+        else:
+            wrow = wp
+        need_x, need_ew = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        db = None
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
+            db = ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+        dew = None
+        if ctx.agg_first:
+            dw = ops.gemm_tn(dyp, saved)
+            dp = ops.gemm_nn(dyp, wrow) if (need_x or need_ew) else None
+            dx = ops.spmm(graph, dp, transpose=True) if need_x else None
+            if need_ew:
+                dew = ops.graph_weight_grad(graph, ops.sddmm(graph, dp, operand))
+        else:
+            dh = ops.spmm(graph, dyp, transpose=True)
+            dw = ops.gemm_tn(dh, saved)
+            dx = ops.gemm_nn(dh, wrow) if need_x else None
+            if need_ew:
+                dew = ops.graph_weight_grad(graph, ops.sddmm(graph, dy, operand))
+        dw = dw[:cout, :cin]
+        if dx is not None:
+            dx = dx[:, :cin]
+        if dew is not None:
+            dew = dew.to(ctx.ew_dtype)
+        return dx, dw, db, dew, None
+
+
 class _Lin(nn.Module):
     """Holder so that the weight is addressed as ``conv.lin.weight`` like PyG's ``Linear``."""
 
@@ -102,27 +199,47 @@ class _Lin(nn.Module):
 
 
 class GCNConv(nn.Module):
-    def __init__(self, in_channels: int, out_channels: int):
+    def __init__(self, in_channels: int, out_channels: int, improved: bool = False, cached: bool = False,
+                 add_self_loops: bool = True, normalize: bool = True, bias: bool = True):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
+        self.improved, self.cached, self.add_self_loops, self.normalize = bool(improved), bool(cached), bool(add_self_loops), bool(normalize)
         self.lin = _Lin(in_channels, out_channels)
-        self.bias = nn.Parameter(torch.zeros(out_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(out_channels))
+        else:
+            self.register_parameter("bias", None)
         self.reset_parameters()
 
     def reset_parameters(self):
         a = math.sqrt(6.0 / (self.in_channels + self.out_channels))     # PyG 'glorot'
         with torch.no_grad():
             self.lin.weight.uniform_(-a, a)
-            self.bias.zero_()
+            if self.bias is not None:
+                self.bias.zero_()
 
-    def forward(self, x: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_weight=None) -> torch.Tensor:
         if x.dim() != 2 or x.shape[1] != self.in_channels:
             raise ValueError("GCNConv: expected x of shape [N, %d]" % self.in_channels)
+        if edge_weight is not None:
+            ops.check_edge_weight(edge_weight, edge_index.shape[1])
+            if x.dtype == torch.bfloat16:
+                raise ValueError("GCNConv: bf16 features with edge_weight are not supported on the HIP path")
         if not x.is_cuda:
             raise ops.DdmpError("GCNConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        default = not self.improved and self.add_self_loops and self.normalize
         with ops.on_device(x):
-            graph = ops.graph_for(edge_index, x.shape[0])
-            return _GCNConvFn.apply(x, self.lin.weight, self.bias, graph)
+            if edge_weight is None and default and self.bias is not None:
+                graph = ops.graph_for(edge_index, x.shape[0])
+                return _GCNConvFn.apply(x, self.lin.weight, self.bias, graph)
+            if edge_weight is None and default:                  # bias=False alone: still the unvalued graph and gathers
+                graph = ops.graph_for(edge_index, x.shape[0])
+                zero = self.__dict__.get("_zero_bias")
+                if zero is None or zero.device != x.device:
+                    zero = self.__dict__["_zero_bias"] = torch.zeros(self.out_channels, dtype=torch.float32, device=x.device)
+                return _GCNConvFn.apply(x, self.lin.weight, zero, graph)
+            graph = ops.graph_for(edge_index, x.shape[0], "gcn", edge_weight, self.improved, self.add_self_loops, self.normalize)
+            return _GCNConvWFn.apply(x, self.lin.weight, self.bias, edge_weight, graph)
 
     def extra_repr(self):
         return "%d, %d" % (self.in_channels, self.out_channels)
@@ -153,7 +270,10 @@ class _ChebConvFn(torch.autograd.Function):
             else:
                 ops.spmm_axpby(graph, blk(t, k - 1), out=blk(t, k), z=blk(t, k - 2), a=2 * alpha, b=2 * beta, c=-1.0)
         y = ops.gemm_nt(t, wp, bias=None if bias is None else bias.detach().contiguous())
-        ctx.save_for_backward(t, wp)
+        # a valued graph (edge_weight) holds the values of the LAST weight version set on its structure: record this call's
+        valued = graph is not None and getattr(graph, "valued", 0)
+        ctx.save_for_backward(t, wp, graph.values_src if valued else None)
+        ctx.values_key = graph.values_key if valued else None
         ctx.graph, ctx.coef, ctx.dims, ctx.has_bias = graph, (alpha, beta), (K, cin, cp), bias is not None
         return y
 
@@ -164,8 +284,10 @@ class _ChebConvFn(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, dy):
-        t, wp = ctx.saved_tensors
+        t, wp, wsrc = ctx.saved_tensors
         graph, (alpha, beta), (K, cin, cp) = ctx.graph, ctx.coef, ctx.dims
+        if ctx.values_key is not None:
+            ops.restore_values(graph, ctx.values_key, wsrc)
         dy = dy.contiguous()
         cout = dy.shape[1]
         dyp = _pad_cols(dy)
@@ -218,8 +340,13 @@ class ChebConv(nn.Module):
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_weight=None, batch=None, lambda_max=None) -> torch.Tensor:
         """``edge_index`` must be symmetric (both directions of every edge present)."""
-        if edge_weight is not None or batch is not None:
-            raise ValueError("ChebConv: edge_weight and batch are not implemented on the HIP path")
+        if batch is not None:
+            raise ValueError("ChebConv: batch is not implemented on the HIP path")
+        if edge_weight is not None:
+            ops.check_edge_weight(edge_weight, edge_index.shape[1])
+            if edge_weight.requires_grad:
+                raise ValueError("ChebConv: the gradient with respect to edge_weight is not implemented on the HIP path "
+                                 "(detach the weights; GCNConv has it)")
         if lambda_max is None:
             lambda_max = 2.0
         if isinstance(lambda_max, torch.Tensor) or not isinstance(lambda_max, (int, float)):
@@ -232,7 +359,9 @@ class ChebConv(nn.Module):
             raise ops.DdmpError("ChebConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
         alpha, beta = -2.0 / lambda_max, 2.0 / lambda_max - 1.0
         with ops.on_device(x):
-            graph = ops.graph_for(edge_index, x.shape[0], norm="sym") if self.K > 1 else None      # K = 1 needs no graph
+            graph = None                                         # K = 1 needs no graph
+            if self.K > 1 or edge_weight is not None:            # (the weights are validated even then)
+                graph = ops.graph_for(edge_index, x.shape[0], norm="sym", edge_weight=edge_weight)
             return _ChebConvFn.apply(x.to(torch.float32), self.bias, graph, alpha, beta, *[lin.weight for lin in self.lins])
 
     def extra_repr(self):

@@ -277,6 +277,12 @@ class Graph:
     def __init__(self, handle, n_rows, n_cols, nnz):
         self._h = handle
         self.n_rows, self.n_cols, self.nnz = n_rows, n_cols, nnz
+        self.valued = 0                                         # GV_* flags of a valued graph (from_edge_index(valued=...))
+        self.nnz_in = 0                                         # its input edges
+        self.values_key = None                                  # token of the weight version its values were last set from
+        self.values_src = None                                  # that version's weight tensor (None: all ones) -- what a backward
+        #                                                         pass saves to restore the values it ran on
+        self.n_set_values = self.n_status_reads = 0             # diagnostics: refreshes / reads of the validation word
         self._fin = weakref.finalize(self, _lib.lib().ddmp_graph_destroy, handle)
         a, b, c, d = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
         check(_lib.lib().ddmp_graph_info(handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)), "ddmp_graph_info")
@@ -287,11 +293,28 @@ class Graph:
         return self._h
 
     @classmethod
-    def from_edge_index(cls, edge_index: torch.Tensor, num_nodes: int, norm: str = "gcn") -> "Graph":
+    def from_edge_index(cls, edge_index: torch.Tensor, num_nodes: int, norm: str = "gcn", valued=None) -> "Graph":
         """``norm``: "gcn" = D^-1/2 (A + I) D^-1/2 (GCNConv) | "sym" = D^-1/2 A D^-1/2 without self loops (ChebConv's S:
-        explicit self loops dropped, none added, dinv = 0 and an empty row for a node without edges)."""
+        explicit self loops dropped, none added, dinv = 0 and an empty row for a node without edges).
+
+        ``valued`` = GV_* flags (``norm`` is then ignored): a VALUED graph -- coalesced structure built once, values set on the
+        device per weight version by ``set_values`` (all-ones weights until then).  The edge structure must be symmetric."""
         if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64:
             raise DdmpError("edge_index must be a [2, nnz] int64 tensor")
+        if valued is not None:
+            ei = edge_index.contiguous()
+            h = ctypes.c_void_p()
+            st = _lib.lib().ddmp_graph_create_valued(int(num_nodes), int(ei.shape[1]), _p(ei), 1 if ei.is_cuda else 0, int(valued),
+                                                     ctypes.byref(h))
+            if st == -1:
+                raise ValueError("a valued graph needs a symmetric edge STRUCTURE (both directions of every edge present in "
+                                 "edge_index) and valid flags: ddmp_graph_create_valued refused the edge list")
+            check(st, "ddmp_graph_create_valued")
+            g = cls(h, int(num_nodes), int(num_nodes), 0)
+            nnz = ctypes.c_int64()
+            check(_lib.lib().ddmp_graph_info(h, None, None, ctypes.byref(nnz), None), "ddmp_graph_info")
+            g.nnz, g.valued, g.nnz_in = int(nnz.value), int(valued) | GV_VALUED, int(ei.shape[1])
+            return g
         if norm not in ("gcn", "sym"):
             raise DdmpError("graph normalisation must be 'gcn' or 'sym', got %r" % (norm,))
         ei = edge_index.contiguous()
@@ -305,6 +328,44 @@ class Graph:
             check(_lib.lib().ddmp_graph_info(h, None, None, ctypes.byref(nnz), None), "ddmp_graph_info")
             g.nnz = int(nnz.value)
         return g
+
+    def set_values(self, w=None, key=None, validate=True, checked=False):
+        """Values of one weight version (``ddmp_graph_set_values``: device kernels, no host round trip of the values).  ``w``: CUDA
+        float32 / float64 [nnz_in] (float64 is rounded to float32 once) or None = all ones.  ``validate``: read the device's
+        validation word ONCE and raise ValueError for non-finite weights, a negative weighted degree, or (GV_REQUIRE_SYM)
+        values that are not symmetric.  ``key``: the caller's token of this weight version (``values_key`` afterwards).
+        ``checked``: the caller has run ``check_edge_weight`` on ``w``."""
+        if not self.valued:
+            raise DdmpError("set_values needs a valued graph (Graph.from_edge_index(..., valued=flags))")
+        src = None if w is None else w.detach()                 # (shares storage and version counter with the caller's tensor)
+        if w is not None:
+            if not checked:
+                check_edge_weight(w, self.nnz_in)
+            w = _chk(w.detach().to(torch.float32).contiguous(), torch.float32, "edge_weight")
+        self.n_set_values += 1
+        with _timed("set_values", (int(round(self.nnz / max(self.n_rows, 1))),), 4.0 * self.nnz_in + 24.0 * self.nnz + 12.0 * self.n_rows):
+            check(_lib.lib().ddmp_graph_set_values(self.handle, _p(w), _stream()), "ddmp_graph_set_values")
+        self.values_key, self.values_src = key, src
+        if validate:
+            self.n_status_reads += 1
+            st = ctypes.c_int()
+            check(_lib.lib().ddmp_graph_values_status(self.handle, ctypes.byref(st), _stream()), "ddmp_graph_values_status")
+            if st.value:
+                self.values_key = self.values_src = None
+                what = [m for b, m in ((GV_ENONFINITE, "edge_weight has non-finite values"),
+                                       (GV_ENEGDEG, "a node's weighted degree is negative (PyG's gcn_norm would give NaN)"),
+                                       (GV_ENOTSYM, "edge_weight is not symmetric (w_ij != w_ji after coalescing): ChebConv takes "
+                                                    "symmetric weights only -- symmetrise them, e.g. (w + w[reverse]) / 2")) if st.value & b]
+                raise ValueError("; ".join(what))
+        return self
+
+    def values(self):
+        """-> (ew, ew_t, a [entries], s [n]) device copies of a valued graph's arrays (tests, diagnostics)."""
+        dev = torch.device("cuda", torch.cuda.current_device())
+        ew, ew_t, a = (torch.empty(self.nnz, dtype=torch.float32, device=dev) for _ in range(3))
+        s_ = torch.empty(self.n_rows, dtype=torch.float32, device=dev)
+        check(_lib.lib().ddmp_graph_export_values(self.handle, _p(ew), _p(ew_t), _p(a), _p(s_), _stream()), "ddmp_graph_export_values")
+        return ew, ew_t, a, s_
 
     @classmethod
     def from_csr_host(cls, rowptr: np.ndarray, col: np.ndarray, dinv: np.ndarray, n_cols: int, rows=None) -> "Graph":
@@ -329,9 +390,38 @@ class Graph:
 
 
 _graph_cache = {}
+_values_token = [0]
+
+# flags of a valued graph (DDMP_GV_* of include/ddmp_hip.h) and the validation bits of set_values
+GV_LOOPS, GV_IMPROVED, GV_NORMALIZE, GV_DROP_LOOPS, GV_REQUIRE_SYM, GV_VALUED = 1, 2, 4, 8, 16, 256
+GV_ENONFINITE, GV_ENEGDEG, GV_ENOTSYM = 1, 2, 4
 
 
-def graph_for(edge_index: torch.Tensor, num_nodes: int, norm: str = "gcn") -> Graph:
+def check_edge_weight(w, nnz, need_cuda=True):
+    """The refusals that depend on shape, dtype and device only -- ValueError before any launch."""
+    if not isinstance(w, torch.Tensor):
+        raise ValueError("edge_weight must be a tensor, got %s" % type(w).__name__)
+    if w.dim() != 1 or w.shape[0] != int(nnz):
+        raise ValueError("edge_weight must have one value per edge: expected shape [%d], got %s" % (int(nnz), tuple(w.shape)))
+    if w.dtype not in (torch.float32, torch.float64):
+        raise ValueError("edge_weight must be float32 or float64, got %s" % w.dtype)
+    if need_cuda and not w.is_cuda:
+        raise ValueError("edge_weight must be a CUDA (ROCm) tensor: the HIP path has no CPU fallback")
+    return w
+
+
+def valued_flags(norm="gcn", improved=False, add_self_loops=True, normalize=True):
+    """GV_* flags of PyG's options.  "gcn": gcn_norm(improved, add_self_loops) when normalising, the raw weights otherwise
+    (no loops added, whatever add_self_loops says); "sym": ChebConv's S -- loops dropped, symmetric values required."""
+    if norm == "sym":
+        return GV_DROP_LOOPS | GV_NORMALIZE | GV_REQUIRE_SYM
+    if not normalize:
+        return 0
+    return GV_NORMALIZE | ((GV_LOOPS | (GV_IMPROVED if improved else 0)) if add_self_loops else 0)
+
+
+def graph_for(edge_index: torch.Tensor, num_nodes: int, norm: str = "gcn", edge_weight=None, improved=False,
+              add_self_loops=True, normalize=True) -> Graph:
     """Graph of a static mesh, cached on the IDENTITY of the edge_index tensor (weak reference + in-place
     version counter) and the normalisation.  A data_ptr key would be wrong: a freed tensor's address is reused by other meshes.
     A caller that builds a fresh edge_index tensor on every call (as ``data.edge_index.to(device)`` does when
@@ -340,18 +430,60 @@ def graph_for(edge_index: torch.Tensor, num_nodes: int, norm: str = "gcn") -> Gr
     ``norm``: "gcn" (GCNConv: self loops added) | "sym" (ChebConv: S = D^-1/2 A D^-1/2, no self loops).  A GCNConv and a
     ChebConv on the same edge_index tensor each get their own graph.  "sym" supports SYMMETRIC edge lists only (both
     directions of every edge present, as every graph of this project is): S is then symmetric, the degree is the in-degree,
-    and the same graph serves the backward pass."""
-    key = (id(edge_index), norm)
+    and the same graph serves the backward pass.
+
+    ``edge_weight`` (CUDA float32 / float64 [nnz]) or a non-default ``improved`` / ``add_self_loops`` / ``normalize``: a VALUED
+    graph.  Its structure is cached like any graph's (identity + version of edge_index, and the options); its values are
+    refreshed by ONE ``set_values`` when the identity or ``_version`` of ``edge_weight`` differs from the one last set -- a learned
+    weight changes every step and costs that, not a rebuild.  With ``edge_weight=None`` and default options this is today's
+    unvalued graph, handle and kernels.
+
+    One handle serves every weight version on a structure, so its values are those of the LAST version set: an autograd function
+    that gathers in its backward records ``values_key`` / ``values_src`` in forward and restores them (``restore_values``)."""
+    if norm not in ("gcn", "sym"):
+        raise DdmpError("graph normalisation must be 'gcn' or 'sym', got %r" % (norm,))
+    flags = None
+    if edge_weight is not None or improved or not add_self_loops or not normalize:
+        if edge_weight is not None:
+            check_edge_weight(edge_weight, edge_index.shape[1])
+        flags = valued_flags(norm, improved, add_self_loops, normalize)
+    key = (id(edge_index), norm) if flags is None else (id(edge_index), norm, flags)
     hit = _graph_cache.get(key)
+    g = None
     if hit is not None:
-        ref, version, n, g = hit
+        ref, version, n, g_ = hit
         if ref() is edge_index and version == edge_index._version and n == int(num_nodes):
-            return g
-    for k in [k for k, v in _graph_cache.items() if v[0]() is None]:
-        del _graph_cache[k]
-    g = Graph.from_edge_index(edge_index, num_nodes, norm)
-    _graph_cache[key] = (weakref.ref(edge_index), edge_index._version, int(num_nodes), g)
+            g = g_
+    if g is None:
+        for k in [k for k, v in _graph_cache.items() if v[0]() is None]:
+            del _graph_cache[k]
+        g = Graph.from_edge_index(edge_index, num_nodes, norm, valued=flags)
+        _graph_cache[key] = (weakref.ref(edge_index), edge_index._version, int(num_nodes), g)
+        if flags is not None:
+            g._wref, g.values_key = None, ("ones",)
+    if flags is not None:
+        if edge_weight is None:
+            if g.values_key != ("ones",):
+                g.set_values(None, key=("ones",), validate=False)
+                g._wref = None
+        else:
+            cur = getattr(g, "_wref", None)
+            if not (cur is not None and cur[0]() is edge_weight and cur[1] == edge_weight._version
+                    and g.values_key == cur[2]):
+                _values_token[0] += 1
+                tok = ("w", _values_token[0])
+                g._wref = None
+                g.set_values(edge_weight, key=tok, checked=True)
+                g._wref = (weakref.ref(edge_weight), edge_weight._version, tok)
     return g
+
+
+def restore_values(g: Graph, key, w):
+    """Backward-pass guard of the valued operators: if another weight version was set on ``g`` since the forward that recorded
+    ``key``, set that forward's values again (``w``: its saved weights, None = all ones).  Validated then; no status read."""
+    if g is not None and g.valued and g.values_key != key:
+        g.set_values(w, key=key, validate=False, checked=True)
+        g._wref = None
 
 
 def csr_build_host(edge_index: np.ndarray, num_nodes: int, norm: str = "gcn"):
@@ -368,6 +500,54 @@ def csr_build_host(edge_index: np.ndarray, num_nodes: int, norm: str = "gcn"):
     st = build(num_nodes, nnz, ei.ctypes.data, rowptr.ctypes.data, col.ctypes.data, dinv.ctypes.data, ctypes.byref(cap))
     check(st, "ddmp_csr_build_host" if norm == "gcn" else "ddmp_csr_build_sym_host")
     return rowptr, col[:cap.value].copy(), dinv
+
+
+def csr_build_valued_host(edge_index: np.ndarray, num_nodes: int, flags: int):
+    """Host structure of a valued graph (no GPU needed; ``ddmp_csr_build_valued_host``): -> dict of rowptr [n+1], col, mirror
+    [entries], ee_ptr [entries+1], ee_idx, eid [nnz] (int32).  ValueError when the edge structure is not symmetric."""
+    ei = np.ascontiguousarray(edge_index, dtype=np.int64)
+    nnz, n = ei.shape[1], int(num_nodes)
+    cap = nnz + n
+    rowptr, col, mirror = np.zeros(n + 1, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    ee_ptr, ee_idx, eid = np.zeros(cap + 1, np.int32), np.zeros(max(nnz, 1), np.int32), np.zeros(max(nnz, 1), np.int32)
+    used = ctypes.c_int64(cap)
+    st = _lib.lib().ddmp_csr_build_valued_host(n, nnz, ei.ctypes.data, int(flags), rowptr.ctypes.data, col.ctypes.data,
+                                               ee_ptr.ctypes.data, ee_idx.ctypes.data, eid.ctypes.data, mirror.ctypes.data,
+                                               ctypes.byref(used))
+    if st == -1:
+        raise ValueError("ddmp_csr_build_valued_host: the edge structure is not symmetric (or the flags are invalid)")
+    check(st, "ddmp_csr_build_valued_host")
+    ne = used.value
+    return dict(rowptr=rowptr, col=col[:ne].copy(), mirror=mirror[:ne].copy(), ee_ptr=ee_ptr[:ne + 1].copy(),
+                ee_idx=ee_idx[:int(ee_ptr[ne])].copy(), eid=eid[:nnz].copy())
+
+
+def valued_values_host(tables, w, flags: int):
+    """Host restatement of ``ddmp_graph_set_values`` in float32, the device's summation orders: -> a, s, ew, ew_t (numpy
+    float32).  An entry's edges are summed in input order, a row's entries in CSR order, s = float32(1 / sqrt(float64(deg)))."""
+    rowptr, col, mirror, ee_ptr, ee_idx = (tables[k] for k in ("rowptr", "col", "mirror", "ee_ptr", "ee_idx"))
+    ne, n = len(col), len(rowptr) - 1
+    w = None if w is None else np.asarray(w, dtype=np.float32)
+    fill = np.float32(2.0 if flags & GV_IMPROVED else 1.0)
+    a = np.zeros(ne, np.float32)
+    for e in range(ne):
+        t0, t1 = int(ee_ptr[e]), int(ee_ptr[e + 1])
+        v = fill if t0 == t1 else np.float32(0.0)
+        for t in range(t0, t1):
+            v = np.float32(v + (np.float32(1.0) if w is None else w[ee_idx[t]]))
+        a[e] = v
+    s = np.ones(n, np.float32)
+    if flags & GV_NORMALIZE:
+        for i in range(n):
+            deg = np.float32(0.0)
+            for e in range(int(rowptr[i]), int(rowptr[i + 1])):
+                deg = np.float32(deg + a[e])
+            s[i] = np.float32(1.0 / np.sqrt(np.float64(deg))) if deg > 0 else np.float32(0.0)
+        ew = (a * s[col]).astype(np.float32)
+        ew_t = (a[mirror] * s[col]).astype(np.float32)
+    else:
+        ew, ew_t = a.copy(), a[mirror].copy()
+    return a, s, ew, ew_t
 
 
 def bfs_order_host(rowptr: np.ndarray, col: np.ndarray) -> np.ndarray:
@@ -390,9 +570,14 @@ def rcb_order_host(points: np.ndarray, leaf: int = 64) -> np.ndarray:
 
 
 # ---------------------------------------------------------------------------------------- kernels
-def spmm(g: Graph, x, out=None, bias=None, pro=None, slope=SLOPE):
-    """out[i] = dinv_i * sum_j dinv_j f(x[j]) (+bias); x has g.n_cols rows, out g.n_rows rows."""
+def spmm(g: Graph, x, out=None, bias=None, pro=None, slope=SLOPE, transpose=False):
+    """out[i] = dinv_i * sum_j dinv_j f(x[j]) (+bias); x has g.n_cols rows, out g.n_rows rows.  A valued graph: out = A x (+bias)
+    with its current values, float32 features, no prologue; ``transpose=True``: out = A^T x (same structure, mirrored values)."""
     x, ldx = _mat(x, "x")
+    if g.valued and (x.dtype != torch.float32 or pro is not None):
+        raise ValueError("a valued graph gathers float32 features without a prologue (bf16 features with edge_weight are not supported)")
+    if transpose and not g.valued:
+        raise DdmpError("transpose=True needs a valued graph (an unvalued graph's operator is symmetric)")
     if x.shape[0] < g.n_cols:
         raise DdmpError("x has %d rows, graph references %d nodes" % (x.shape[0], g.n_cols))
     C = x.shape[1]
@@ -404,9 +589,49 @@ def spmm(g: Graph, x, out=None, bias=None, pro=None, slope=SLOPE):
     # algorithmic bytes: every feature row read once + written once, int32 col ids, rowptr, dinv
     alg = 2.0 * g.n_rows * C * es + 4.0 * g.nnz + 4.0 * (g.n_rows + 1) + 4.0 * g.n_rows
     with _timed("spmm", (C, int(round(g.nnz / max(g.n_rows, 1)))), alg, 2.0 * g.nnz * C):      # key: width, CSR entries per row
-        st = _lib.lib().ddmp_spmm(g.handle, _p(x), ldx, _p(out), ldy, C, _dt(x), _p(bias), _p(ps), _p(psh), slope,
-                                  _stream())
+        if transpose:
+            st = _lib.lib().ddmp_spmm_t_f32(g.handle, _p(x), ldx, _p(out), ldy, C, _p(bias), _stream())
+        else:
+            st = _lib.lib().ddmp_spmm(g.handle, _p(x), ldx, _p(out), ldy, C, _dt(x), _p(bias), _p(ps), _p(psh), slope,
+                                      _stream())
     check(st, "ddmp_spmm")
+    return out
+
+
+def sddmm(g: Graph, dy, h, out=None):
+    """out[e] = sum_c dy[row e, c] * h[col e, c] for every CSR entry of ``g`` (``ddmp_sddmm_f32``): dL/dA per entry of Y = A H.
+    float32, fixed summation order (bitwise reproducible).  dy: [>= n_rows, C], h: [>= n_cols, C]; out: float32 [g.nnz]."""
+    dy, lddy = _mat(_chk(dy, torch.float32, "dy"), "dy")
+    h, ldh = _mat(_chk(h, torch.float32, "h"), "h")
+    C = dy.shape[1]
+    if h.shape[1] != C or dy.shape[0] < g.n_rows or h.shape[0] < g.n_cols:
+        raise DdmpError("sddmm: dy must be [>= %d, C] and h [>= %d, C], got %s and %s" % (g.n_rows, g.n_cols, tuple(dy.shape), tuple(h.shape)))
+    if out is None:
+        out = torch.empty(g.nnz, dtype=torch.float32, device=dy.device)
+    _chk(out, torch.float32, "out")
+    if out.numel() < g.nnz or not out.is_contiguous():
+        raise DdmpError("sddmm: out must be a contiguous float32 [%d]" % g.nnz)
+    # algorithmic bytes: the gathered rows and the rows' own dy once each, one float per entry out, int32 col ids, rowptr
+    alg = 4.0 * (g.n_cols + g.n_rows) * C + 8.0 * g.nnz + 4.0 * (g.n_rows + 1)
+    with _timed("sddmm", (C, int(round(g.nnz / max(g.n_rows, 1)))), alg, 2.0 * g.nnz * C):
+        st = _lib.lib().ddmp_sddmm_f32(g.handle, _p(dy), lddy, _p(h), ldh, C, _p(out), _stream())
+    check(st, "ddmp_sddmm_f32")
+    return out
+
+
+def graph_weight_grad(g: Graph, G, out=None):
+    """dL/d(edge_weight) [nnz_in] of a valued graph from G = dL/dA per entry (``sddmm``), through its normalisation
+    (``ddmp_graph_weight_grad``; formulas in include/ddmp_hip.h and DESIGN.md 4.7)."""
+    if not g.valued:
+        raise DdmpError("graph_weight_grad needs a valued graph")
+    _chk(G, torch.float32, "G")
+    if G.numel() < g.nnz or not G.is_contiguous():
+        raise DdmpError("graph_weight_grad: G must be a contiguous float32 [%d]" % g.nnz)
+    if out is None:
+        out = torch.empty(g.nnz_in, dtype=torch.float32, device=G.device)
+    _chk(out, torch.float32, "out")
+    with _timed("graph_weight_grad", (int(round(g.nnz / max(g.n_rows, 1))),), 28.0 * g.nnz + 8.0 * g.nnz_in + 8.0 * g.n_rows):
+        check(_lib.lib().ddmp_graph_weight_grad(g.handle, _p(G), _p(out), _stream()), "ddmp_graph_weight_grad")
     return out
 
 

@@ -102,6 +102,9 @@ int ddmp_spmm_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, in
  * gather; has_red: 0 | 1 the fused BatchNorm-backward reduction | 2 the fused statistics; dtype DDMP_BF16: plain, prologue and
  * statistics only): distinct rows of a chunk copied to LDS once, gathers from LDS -- csrc/spmm_patch.hip; same results either way */
 int ddmp_spmm_patch_selected(const ddmp_graph* g, int C, int dtype, int has_pro, int has_red);
+/* 1: where the LDS-patch form does not run, a C % 32 == 0 gather of this graph and these leading dimensions runs the lean gather;
+ * 0: the slab kernel (DDMP_SPMM_LEAN=0, or offsets beyond the lean gather's 32 bits).  For tests that name a route. */
+int ddmp_spmm_lean_selected(const ddmp_graph* g, int64_t ldx, int64_t ldy, int C);
 
 /* ------------------------------------------------------------------ Chebyshev step (torch_geometric ChebConv, normalization="sym")
  * The second graph flavour: S = D^-1/2 A D^-1/2 WITHOUT self loops -- explicit self loops are dropped and none is added,
@@ -125,6 +128,57 @@ int ddmp_graph_create_sym(int64_t n_nodes, int64_t nnz, const int64_t* edge_inde
 int ddmp_spmm_axpby_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, const float* Z /*nullable*/,
                         int64_t ldz, const float* Z2 /*nullable*/, int64_t ldz2, int C, float a, float b, float c, float d,
                         ddmp_stream stream);
+
+/* ------------------------------------------------------------------ valued graphs (edge_weight of GCNConv / ChebConv)
+ * A third graph flavour whose STRUCTURE is built once per edge_index and whose VALUES are set on the device per weight version.
+ * The structure is coalesced: one CSR entry per (target, source) pair, columns ascending, duplicates merged; three maps stay on
+ * the device: entry -> its input edges in input order, input edge -> entry, entry (i, j) -> entry (j, i) ("mirror").  The edge
+ * structure must be symmetric: an entry without mirror is DDMP_EINVAL.  flags:
+ *   DDMP_GV_LOOPS      PyG add_remaining_self_loops: explicit self loops leave the edge list, every node gets ONE loop entry whose
+ *                      value is the weight of its LAST explicit loop in input order, or `fill` (1; 2 with DDMP_GV_IMPROVED)
+ *   DDMP_GV_NORMALIZE  entry value s_i a_e s_j, s_i = (sum of a_e over row i)^-1/2 (0 where the sum is 0); without it: a_e
+ *   DDMP_GV_DROP_LOOPS explicit self loops are dropped and none is added (ChebConv's S)
+ *   DDMP_GV_REQUIRE_SYM  the coalesced values must be symmetric bit for bit (ChebConv); reported by ddmp_graph_values_status
+ * Until ddmp_graph_set_values has run, a valued graph holds the values of all-ones weights. */
+#define DDMP_GV_LOOPS 1
+#define DDMP_GV_IMPROVED 2
+#define DDMP_GV_NORMALIZE 4
+#define DDMP_GV_DROP_LOOPS 8
+#define DDMP_GV_REQUIRE_SYM 16
+#define DDMP_GV_VALUED 256        /* (internal marker of the handle) */
+/* ddmp_graph_values_status bits */
+#define DDMP_GV_ENONFINITE 1      /* a weight (or a coalesced sum) is NaN or infinite */
+#define DDMP_GV_ENEGDEG 2         /* a node's weighted degree is negative (PyG would produce NaN) */
+#define DDMP_GV_ENOTSYM 4         /* DDMP_GV_REQUIRE_SYM and a_ij != a_ji */
+/* Host structure builder (no GPU): capacity of col / ee_ptr / mirror = *n_entries on entry (nnz + n_nodes always suffices; ee_ptr
+ * needs one more), ee_idx and eid hold nnz.  eid[k] = -1 for an input edge that has no entry (a dropped or overridden loop). */
+int ddmp_csr_build_valued_host(int64_t n_nodes, int64_t nnz, const int64_t* edge_index_host, int flags,
+                               int32_t* rowptr_host /*[n+1]*/, int32_t* col_host, int32_t* ee_ptr_host, int32_t* ee_idx_host,
+                               int32_t* eid_host, int32_t* mirror_host, int64_t* n_entries /*in: capacity, out: used*/);
+int ddmp_graph_create_valued(int64_t n_nodes, int64_t nnz, const int64_t* edge_index, int edge_index_on_device, int flags,
+                             ddmp_graph** out);
+/* Values of one weight version, on the device, no host round trip: a_e = sum of the entry's input weights in input order
+ * (float32; `fill` for a loop entry without explicit loop), deg_i = sum of a_e in CSR order, s_i = (float)(1 / sqrt((double)deg_i)),
+ * factors a_e s_j and a_mirror(e) s_j.  w: device float32 [nnz], NULL = all ones.  Asynchronous on `stream`. */
+int ddmp_graph_set_values(ddmp_graph* g, const float* w /*nullable*/, ddmp_stream stream);
+/* The validation bits of the last ddmp_graph_set_values (synchronises `stream`). */
+int ddmp_graph_values_status(const ddmp_graph* g, int* status_host, ddmp_stream stream);
+/* Copies of the value arrays into caller-owned device buffers (each nullable): ew, ew_t, a [entries], s [n] (ones when not
+ * normalising). */
+int ddmp_graph_export_values(const ddmp_graph* g, float* ew, float* ew_t, float* a, float* s, ddmp_stream stream);
+/* The gather with the TRANSPOSED values on the same structure: Y = A^T X + bias where ddmp_spmm_f32 gives A X + bias. */
+int ddmp_spmm_t_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, int C, const float* bias /*nullable*/,
+                    ddmp_stream stream);
+/* Per-entry gradient (SDDMM over the CSR): G[e] = sum_c dY[row(e), c] * H[col(e), c], float32 products and accumulation, fixed
+ * summation order (bitwise reproducible, no atomics).  Any ddmp_graph; G has one float per CSR entry. */
+int ddmp_sddmm_f32(const ddmp_graph* g, const float* dY, int64_t lddy, const float* H, int64_t ldh, int C, float* G,
+                   ddmp_stream stream);
+/* dL/dw of the input edges from G = dL/dA per entry (ddmp_sddmm_f32) through the normalisation of a valued graph:
+ * g_e = s_i s_j G_e - 1/2 s_i^3 (r_i + c_i), r_i = sum_{e in row i} a_e s_j G_e, c_i = sum_{e in row i} a_m(e) s_j G_m(e)
+ * (g_e = G_e when not normalising); dw[k] = g_eid[k], 0 for an edge without entry.  dw: device float32 [nnz].
+ * NOT reentrant per handle: the entries' gradient passes through scratch the handle owns, as the values themselves do --
+ * ddmp_graph_set_values, ddmp_graph_weight_grad and the gathers of ONE valued graph must be ordered on one stream (or by events). */
+int ddmp_graph_weight_grad(const ddmp_graph* g, const float* G, float* dw, ddmp_stream stream);
 
 /* ------------------------------------------------------------------ dense steps (MFMA; float32 operands and results, the
  * arithmetic is ddmp_set_gemm_mode's: by default SPLIT-precision 16-bit MFMA products with f32 accumulation -- f32-class

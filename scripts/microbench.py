@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|all] [--rows N] [--iters K]
+spmm --weighted (instead of the forms above): the gather on a VALUED graph (edge_weight) against the unvalued graph
+of the same mesh, and its transpose, alternating in one loop like cheb.
+sddmm (not part of all): the per-entry gradient ops.sddmm on the valued face and vertex graphs against (a) ops.spmm on the same
+graph and width and (b) the torch composition that materialises [entries, C]; also the host structure build, set_values and
+graph_weight_grad.
 cheb (not part of all): one Chebyshev step T_k = a S T_{k-1} + c T_{k-2} on the norm="sym" face and vertex graphs of a torus with
 --rows faces in RCB order -- the fused kernel (ops.spmm_axpby, 3 streams of N x C) against the composition it replaces (ops.spmm
 into a temporary + one torch elementwise pass, 5 streams), alternating in the same loop, one HIP-event pair per launch, median
@@ -23,6 +28,7 @@ ap.add_argument("--flip", type=int, default=0, help="rounds of random edge flips
 ap.add_argument("--widths", default="512,256,128,64,32")
 ap.add_argument("--rotate", type=int, default=1, help="spmm: cycle through this many (input, output) buffer sets so that narrow "
                 "widths are not served from the 256 MB MALL (a 1M x 32 float tensor is 128 MB)")
+ap.add_argument("--weighted", action="store_true", help="spmm: valued graph against the unvalued graph of the same mesh")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 n = a.rows
@@ -53,7 +59,7 @@ if a.what in ("gemm", "all"):
             us = timeit(fn)
             print("gemm_%-7s K=%3d M=%3d  %8.0f us  %6.1f TF-eq" % (name, K, M, us, fl / us / 1e6))
 
-if a.what in ("spmm", "all"):
+if a.what in ("spmm", "all") and not a.weighted:
     nu = int(round((n / 2.0) ** 0.5)) if a.what == "spmm_v" else None
     # face graph of a torus with n faces (deg 3+1) and vertex graph with n/2 verts (deg 6+1)
     nv_ = int(round((n / 4.0) ** 0.5)); nu_ = n // (2 * nv_)
@@ -211,3 +217,80 @@ if a.what == "cheb":
                   q["fused"][4], q["composed"][2], q["composed"][0], q["composed"][1], q["composed"][3], q["composed"][4],
                   q["fused"][2] / q["composed"][2], b3 / q["fused"][2] / 1e6, b3 / q["fused"][2] / 1e6 / 8.0 * 100.0, err), flush=True)
             del Xs, Zs, Ys, tmp
+
+
+def alternate(fns, reps, R):
+    """fns: {name: fn(buffer set)}: 3 warm-up rounds, then `reps` rounds of every fn in rotating order, one HIP-event pair per launch ->
+    {name: percentiles [min, q1, median, q3, max] in us}."""
+    t = {k: [] for k in fns}
+    names = list(fns)
+    for r in range(3 + reps):
+        # (the forms of a round read the same buffer set: whoever runs second finds part of it in the 256 MB MALL -- the starting
+        # form rotates so that no form is always first)
+        for name in names[r % len(names):] + names[:r % len(names)]:
+            fn = fns[name]
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(r % R); e1.record(); torch.cuda.synchronize()
+            if r >= 3:
+                t[name].append(e0.elapsed_time(e1) * 1e3)
+    return {k: np.percentile(np.array(v_), [0, 25, 50, 75, 100]) for k, v_ in t.items()}
+
+
+def fmt(q):
+    return "%6.0f us [min %.0f q1 %.0f q3 %.0f max %.0f]" % (q[2], q[0], q[1], q[3], q[4])
+
+
+if (a.what == "spmm" and a.weighted) or a.what == "sddmm":
+    import time
+    nv_ = int(round((n / 4.0) ** 0.5)); nu_ = n // (2 * nv_)
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    m = Mesh(vs=v, faces=f)
+    e = torch.tensor(m.edges.T, dtype=torch.long); ei = torch.cat([e, e[[1, 0]]], 1).to(dev)
+    fi = torch.from_numpy(m.f_edges).to(dev)
+    reps = max(a.iters, 20)
+    for gname, idx, nn_ in (("face", fi, len(f)), ("vert", ei, len(v))):
+        w = torch.rand(idx.shape[1], device=dev) + 0.25
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        gv = ops.graph_for(idx, nn_, edge_weight=w)
+        torch.cuda.synchronize(); t_build = time.perf_counter() - t0
+        g0 = ops.graph_for(idx, nn_)
+        w2 = [torch.rand(idx.shape[1], device=dev) + 0.25 for _ in range(2)]
+        q = alternate({"set_values": lambda i: gv.set_values(w2[i], validate=False)}, reps, 2)
+        gv.set_values(w)
+        print("valued graph %s N=%d entries=%d: structure build + upload + first values %.2f s (host, once); set_values %s"
+              % (gname, nn_, gv.nnz, t_build, fmt(q["set_values"])), flush=True)
+        for C in [int(c) for c in a.widths.split(",")]:
+            R = 2 if nn_ * C * 4 >= (1 << 29) else 4
+            Xs, Ys = ([torch.randn(nn_, C, device=dev) for _ in range(R)] for _ in range(2))
+            Out = torch.empty(nn_, C, device=dev)
+            alg = 2.0 * nn_ * C * 4 + 4.0 * gv.nnz + 8.0 * nn_
+            if a.what == "spmm":
+                q = alternate({"unvalued": lambda i: ops.spmm(g0, Xs[i], out=Out), "valued": lambda i: ops.spmm(gv, Xs[i], out=Out),
+                               "transpose": lambda i: ops.spmm(gv, Xs[i], out=Out, transpose=True)}, reps, R)
+                print("spmm weighted %s N=%d C=%3d (%d buffer sets, %d reps): unvalued %s  valued %s  transpose %s  valued/unvalued %.3f  "
+                      "valued: %.2f TB/s alg = %.1f%% of 8 TB/s" % (gname, nn_, C, R, reps, fmt(q["unvalued"]), fmt(q["valued"]),
+                      fmt(q["transpose"]), q["valued"][2] / q["unvalued"][2], alg / q["valued"][2] / 1e6, alg / q["valued"][2] / 1e6 / 8.0 * 100.0),
+                      flush=True)
+            else:
+                G = torch.empty(gv.nnz, device=dev)
+                t = ops.csr_build_valued_host(idx.cpu().numpy(), nn_, ops.valued_flags())
+                row = torch.from_numpy(np.repeat(np.arange(nn_), np.diff(t["rowptr"]))).to(dev)
+                col = torch.from_numpy(t["col"]).long().to(dev)
+                fns = {"sddmm": lambda i: ops.sddmm(gv, Ys[i], Xs[i], out=G), "spmm": lambda i: ops.spmm(gv, Xs[i], out=Out)}
+                if gv.nnz * C * 4 * 3 < (20 << 30):
+                    fns["torch"] = lambda i: (Ys[i][row] * Xs[i][col]).sum(1)
+                q = alternate(fns, reps, R)
+                ref = (Ys[0][row].double() * Xs[0][col].double()).sum(1) if C <= 128 else None
+                ops.sddmm(gv, Ys[0], Xs[0], out=G)
+                err = float((G.double() - ref).norm() / ref.norm()) if ref is not None else float("nan")
+                alg_s = 2.0 * nn_ * C * 4 + 8.0 * gv.nnz + 4.0 * nn_
+                print("sddmm %s N=%d C=%3d (%d buffer sets, %d reps): sddmm %s = %.2f TB/s alg (%.1f%% of 8 TB/s; %.0f MB)  spmm %s  "
+                      "sddmm/spmm %.3f  torch composition %s  rel-L2 vs float64 %.1e" % (gname, nn_, C, R, reps, fmt(q["sddmm"]),
+                      alg_s / q["sddmm"][2] / 1e6, alg_s / q["sddmm"][2] / 1e6 / 8.0 * 100.0, alg_s / 1e6, fmt(q["spmm"]),
+                      q["sddmm"][2] / q["spmm"][2], fmt(q["torch"]) if "torch" in q else "(skipped: memory)", err), flush=True)
+                del G, row, col
+            del Xs, Ys, Out
+        if a.what == "sddmm":
+            G = torch.randn(gv.nnz, device=dev); dw = torch.empty(idx.shape[1], device=dev)
+            q = alternate({"wgrad": lambda i: ops.graph_weight_grad(gv, G, out=dw)}, reps, 1)
+            print("graph_weight_grad %s N=%d: %s" % (gname, nn_, fmt(q["wgrad"])), flush=True)
