@@ -256,16 +256,15 @@ __global__ __launch_bounds__(256) void bn_lrelu_apply_b16_kernel(const bf16_t* _
 
 template <class F>
 int run_colreduce(const F& f, int64_t n_rows, int C, int width, double* out, void* ws, size_t ws_bytes,
-                  hipStream_t st) {
+                  hipStream_t st, const FinalizeArgs& fin = FinalizeArgs()) {
     const int nblk = colreduce_blocks(n_rows, C, F::VW);
     if (!ws || ws_bytes < (size_t)nblk * 2 * C * sizeof(double)) return DDMP_EWORKSPACE;
     double* partial = (double*)ws;
     hipLaunchKernelGGL((colreduce_kernel<F>), dim3(nblk), dim3(256), 0, st, f, (int)n_rows, C, partial);
     LAUNCH_TRY();
     // partial rows are [2*C]; reduce the first `width` columns (width = C or 2C)
-    // (width = 2C: the coefficients armed by ddmp_bn_next_* ride on the second stage; C: only the first half is exported)
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)cdiv(C, 32)), dim3(256), 0, st, partial, nblk, C, out,
-                       width == 2 * C ? finalize_take(C) : FinalizeArgs());
+    // (width = 2C: the coefficients the call was asked for ride on the second stage; C: only the first half is exported)
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)cdiv(C, 32)), dim3(256), 0, st, partial, nblk, C, out, fin);
     LAUNCH_TRY();
     return DDMP_OK;
 }
@@ -278,12 +277,16 @@ extern "C" size_t ddmp_colreduce_workspace_bytes(int64_t n_rows, int C) {
     return ((size_t)colreduce_blocks(n_rows, C) * 2 * C + 2 * (size_t)C) * sizeof(double);
 }
 
-extern "C" int ddmp_bn_stats_f32(const float* Y, int64_t ldy, int64_t n_rows, int C, double* sums,
-                                 void* ws, size_t ws_bytes, ddmp_stream stream) {
-    FinalizeScope fin_scope(sums, stream, C);
+int ddmp_bn_stats_f32(const float* Y, int64_t ldy, int64_t n_rows, int C, double* sums, void* ws, size_t ws_bytes,
+                      ddmp_stream stream, CallCtx& ctx) {
     ARG_TRY(Y && sums && n_rows > 0 && n_rows < INT32_MAX && width_ok(C) && ldy >= C && ldy % 4 == 0);
     StatsF<float> f{Y, ldy};
-    return run_colreduce(f, n_rows, C, 2 * C, sums, ws, ws_bytes, (hipStream_t)stream);
+    return run_colreduce(f, n_rows, C, 2 * C, sums, ws, ws_bytes, (hipStream_t)stream, ctx.take_fin(C));
+}
+extern "C" int ddmp_bn_stats_f32(const float* Y, int64_t ldy, int64_t n_rows, int C, double* sums,
+                                 void* ws, size_t ws_bytes, ddmp_stream stream) {
+    CallCtx ctx;
+    return ddmp_bn_stats_f32(Y, ldy, n_rows, C, sums, ws, ws_bytes, stream, ctx);
 }
 
 extern "C" int ddmp_bn_prepare_f32(const double* sums, double n_total, int C, const float* gamma,
@@ -314,15 +317,13 @@ extern "C" int ddmp_bn_lrelu_apply_f32(const float* Y, int64_t ldy, float* Z, in
     return DDMP_OK;
 }
 
-extern "C" int ddmp_bn_bwd_reduce_f32(const float* dZ, int64_t lddz, const float* Y, int64_t ldy,
-                                      int64_t n_rows, int C, const float* scale, const float* shift,
-                                      const float* mean, const float* rstd, float slope, double* sums2,
-                                      void* ws, size_t ws_bytes, ddmp_stream stream) {
-    FinalizeScope fin_scope(sums2, stream, C);
+int ddmp_bn_bwd_reduce_f32(const float* dZ, int64_t lddz, const float* Y, int64_t ldy, int64_t n_rows, int C,
+                           const float* scale, const float* shift, const float* mean, const float* rstd, float slope,
+                           double* sums2, void* ws, size_t ws_bytes, ddmp_stream stream, CallCtx& ctx) {
     ARG_TRY(dZ && Y && scale && shift && mean && rstd && sums2);
     ARG_TRY(n_rows > 0 && n_rows < INT32_MAX && width_ok(C) && ldy >= C && lddz >= C && ldy % 4 == 0 && lddz % 4 == 0);
     BwdReduceF<float> f{dZ, Y, scale, shift, mean, rstd, lddz, ldy, slope};
-    return run_colreduce(f, n_rows, C, 2 * C, sums2, ws, ws_bytes, (hipStream_t)stream);
+    return run_colreduce(f, n_rows, C, 2 * C, sums2, ws, ws_bytes, (hipStream_t)stream, ctx.take_fin(C));
 }
 
 extern "C" int ddmp_bn_bwd_prepare_f32(const double* sums2, double n_total, int C, const float* scale,
@@ -387,24 +388,33 @@ extern "C" int ddmp_f64_to_f32(const double* in, float* out, int64_t n, ddmp_str
 
 // ---------------------------------------------------------------- bfloat16 features (b16_common.h): same passes, 8 columns
 // per lane, float32 arithmetic, float64 sums; C a power of two in [16, 1024]; workspace = ddmp_colreduce_workspace_bytes
-extern "C" int ddmp_bn_stats_bf16(const uint16_t* Y, int64_t ldy, int64_t n_rows, int C, double* sums, void* ws,
-                                  size_t ws_bytes, ddmp_stream stream) {
-    FinalizeScope fin_scope(sums, stream, C);
+int ddmp_bn_stats_bf16(const uint16_t* Y, int64_t ldy, int64_t n_rows, int C, double* sums, void* ws, size_t ws_bytes,
+                       ddmp_stream stream, CallCtx& ctx) {
     ARG_TRY(Y && sums && n_rows > 0 && n_rows < INT32_MAX && width_ok(C) && C >= 16 && ldy >= C && ldy % 8 == 0 && b16_aligned(Y));
     StatsF<bf16_t> f{Y, ldy};
-    return run_colreduce(f, n_rows, C, 2 * C, sums, ws, ws_bytes, (hipStream_t)stream);
+    return run_colreduce(f, n_rows, C, 2 * C, sums, ws, ws_bytes, (hipStream_t)stream, ctx.take_fin(C));
+}
+extern "C" int ddmp_bn_stats_bf16(const uint16_t* Y, int64_t ldy, int64_t n_rows, int C, double* sums, void* ws,
+                                  size_t ws_bytes, ddmp_stream stream) {
+    CallCtx ctx;
+    return ddmp_bn_stats_bf16(Y, ldy, n_rows, C, sums, ws, ws_bytes, stream, ctx);
 }
 
-extern "C" int ddmp_bn_bwd_reduce_bf16(const uint16_t* dZ, int64_t lddz, const uint16_t* Y, int64_t ldy, int64_t n_rows,
-                                       int C, const float* scale, const float* shift, const float* mean,
-                                       const float* rstd, float slope, double* sums2, void* ws, size_t ws_bytes,
-                                       ddmp_stream stream) {
-    FinalizeScope fin_scope(sums2, stream, C);
+int ddmp_bn_bwd_reduce_bf16(const uint16_t* dZ, int64_t lddz, const uint16_t* Y, int64_t ldy, int64_t n_rows, int C,
+                            const float* scale, const float* shift, const float* mean, const float* rstd, float slope,
+                            double* sums2, void* ws, size_t ws_bytes, ddmp_stream stream, CallCtx& ctx) {
     ARG_TRY(dZ && Y && scale && shift && mean && rstd && sums2);
     ARG_TRY(n_rows > 0 && n_rows < INT32_MAX && width_ok(C) && C >= 16 && ldy >= C && lddz >= C && ldy % 8 == 0 && lddz % 8 == 0);
     ARG_TRY(b16_aligned(dZ) && b16_aligned(Y));
     BwdReduceF<bf16_t> f{dZ, Y, scale, shift, mean, rstd, lddz, ldy, slope};
-    return run_colreduce(f, n_rows, C, 2 * C, sums2, ws, ws_bytes, (hipStream_t)stream);
+    return run_colreduce(f, n_rows, C, 2 * C, sums2, ws, ws_bytes, (hipStream_t)stream, ctx.take_fin(C));
+}
+extern "C" int ddmp_bn_bwd_reduce_bf16(const uint16_t* dZ, int64_t lddz, const uint16_t* Y, int64_t ldy, int64_t n_rows,
+                                       int C, const float* scale, const float* shift, const float* mean,
+                                       const float* rstd, float slope, double* sums2, void* ws, size_t ws_bytes,
+                                       ddmp_stream stream) {
+    CallCtx ctx;
+    return ddmp_bn_bwd_reduce_bf16(dZ, lddz, Y, ldy, n_rows, C, scale, shift, mean, rstd, slope, sums2, ws, ws_bytes, stream, ctx);
 }
 
 extern "C" int ddmp_bn_bwd_apply_bf16(const uint16_t* dZ, int64_t lddz, const uint16_t* Y, int64_t ldy, uint16_t* dY,

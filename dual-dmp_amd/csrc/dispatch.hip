@@ -150,73 +150,9 @@ extern "C" int ddmp_build_ablation_flags(void) {
     return f;
 }
 
-// ---------------------------------------------------------------- tail-fused finalisation of column reductions (finalize.h)
-namespace ddmp {
-static thread_local FinalizeArgs g_fin_pending, g_fin_active;
-FinalizeArgs& finalize_pending() { return g_fin_pending; }
-FinalizeArgs& finalize_active() { return g_fin_active; }
-FinalizeArgs finalize_take(int C) {
-    FinalizeArgs f = g_fin_active;
-    if (f.kind == 0 || f.C != C) return FinalizeArgs();
-    g_fin_active = FinalizeArgs();
-    return f;
-}
-FinalizeScope::FinalizeScope(const double* sums_, ddmp_stream stream, int width)
-    : sums(sums_), st((hipStream_t)stream), owns(false) {
-    if (g_fin_pending.kind != 0) {
-        const bool fits = g_fin_pending.C == width && sums_ != nullptr;
-        if (fits) g_fin_active = g_fin_pending;
-        g_fin_pending = FinalizeArgs();                          // consumed or dropped: never left for a later call
-        owns = fits;
-    }
-}
-FinalizeScope::~FinalizeScope() {
-    if (!owns) return;
-    const FinalizeArgs f = g_fin_active;
-    g_fin_active = FinalizeArgs();
-    if (f.kind == 1)
-        (void)ddmp_bn_prepare_f32(sums, f.n_total, f.C, f.in[0], f.in[1], f.eps, f.momentum, f.out[0], f.out[1], f.out[2],
-                                  f.out[3], f.out[4], f.out[5], (ddmp_stream)st);
-    else if (f.kind == 2)
-        (void)ddmp_bn_bwd_prepare_f32(sums, f.n_total, f.C, f.in[0], f.in[1], f.in[2], f.out[0], f.out[1], f.out[2], f.out[3],
-                                      (ddmp_stream)st);
-}
-}  // namespace ddmp
-
-extern "C" int ddmp_bn_next_prepare(double n_total, int C, const float* gamma, const float* beta, float eps, float momentum,
-                                    float* scale, float* shift, float* mean, float* rstd, float* running_mean,
-                                    float* running_var) {
-    ARG_TRY(n_total > 0 && C > 0 && gamma && beta && scale && shift && mean && rstd);
-    ARG_TRY((running_mean == nullptr) == (running_var == nullptr));
-    ddmp::FinalizeArgs f;
-    f.kind = 1; f.C = C; f.n_total = n_total; f.eps = eps; f.momentum = momentum;
-    f.in[0] = gamma; f.in[1] = beta;
-    f.out[0] = scale; f.out[1] = shift; f.out[2] = mean; f.out[3] = rstd; f.out[4] = running_mean; f.out[5] = running_var;
-    ddmp::finalize_pending() = f;
-    return DDMP_OK;
-}
-extern "C" int ddmp_bn_next_bwd_prepare(double n_total, int C, const float* scale, const float* mean, const float* rstd,
-                                        float* dgamma, float* dbeta, float* c1, float* c0) {
-    ARG_TRY(n_total > 0 && C > 0 && scale && mean && rstd && dgamma && dbeta && c1 && c0);
-    ddmp::FinalizeArgs f;
-    f.kind = 2; f.C = C; f.n_total = n_total;
-    f.in[0] = scale; f.in[1] = mean; f.in[2] = rstd;
-    f.out[0] = dgamma; f.out[1] = dbeta; f.out[2] = c1; f.out[3] = c0;
-    ddmp::finalize_pending() = f;
-    return DDMP_OK;
-}
-extern "C" int ddmp_bn_next_cancel(void) {
-    ddmp::finalize_pending() = ddmp::FinalizeArgs();
-    return DDMP_OK;
-}
-// bit 0: BatchNorm coefficients armed (ddmp_bn_next_*), bit 1: GEMM scale slots named (ddmp_gemm_next_scales), bit 2: prepared
-// weight planes announced (ddmp_gemm_next_prepared)
-extern "C" int ddmp_next_pending(void) { return (ddmp::finalize_pending().kind != 0 ? 1 : 0) | ddmp::gemm_next_pending(); }
-extern "C" int ddmp_next_cancel(void) {
-    ddmp::finalize_pending() = ddmp::FinalizeArgs();
-    ddmp::gemm_next_cancel();
-    return DDMP_OK;
-}
+// Part of the exported ABI 3 as a diagnostic of options "still recorded for this host thread".  Options are arguments of their
+// own call (finalize.h: CallCtx) and are recorded nowhere: there is nothing that could be pending.
+extern "C" int ddmp_next_pending(void) { return 0; }
 
 extern "C" int ddmp_f32_to_bf16(const float* in, uint16_t* out, int64_t n, ddmp_stream stream) {
     ARG_TRY(in && out && n > 0);
@@ -240,21 +176,32 @@ extern "C" int ddmp_spmm(const ddmp_graph* g, const void* X, int64_t ldx, void* 
 extern "C" size_t ddmp_spmm_bnred_ws_bytes(int64_t n_rows, int C, int dtype) {
     return dtype == DDMP_BF16 ? ddmp_spmm_bnred_bf16_workspace_bytes(n_rows, C) : ddmp_spmm_bnred_workspace_bytes(n_rows, C);
 }
+int ddmp_spmm_bnred(const ddmp_graph* g, const void* X, int64_t ldx, void* Y, int64_t ldy, int C, int dtype, const void* Yp,
+                    int64_t ldyp, const float* scale, const float* shift, const float* mean, const float* rstd, float slope,
+                    double* sums2, void* ws, size_t wsb, ddmp_stream st, CallCtx& ctx) {
+    ARG_TRY(dt_ok(dtype));
+    return dtype == DDMP_BF16
+               ? ddmp_spmm_bnred_bf16(g, (cb)X, ldx, (uint16_t*)Y, ldy, C, (cb)Yp, ldyp, scale, shift, mean, rstd, slope, sums2, ws, wsb, st, ctx)
+               : ddmp_spmm_bnred_f32(g, (cf)X, ldx, (float*)Y, ldy, C, (cf)Yp, ldyp, scale, shift, mean, rstd, slope, sums2, ws, wsb, st, ctx);
+}
 extern "C" int ddmp_spmm_bnred(const ddmp_graph* g, const void* X, int64_t ldx, void* Y, int64_t ldy, int C, int dtype,
                                const void* Yp, int64_t ldyp, const float* scale, const float* shift, const float* mean,
                                const float* rstd, float slope, double* sums2, void* ws, size_t wsb, ddmp_stream st) {
+    CallCtx ctx;
+    return ddmp_spmm_bnred(g, X, ldx, Y, ldy, C, dtype, Yp, ldyp, scale, shift, mean, rstd, slope, sums2, ws, wsb, st, ctx);
+}
+int ddmp_spmm_stats(const ddmp_graph* g, const void* X, int64_t ldx, void* Y, int64_t ldy, int C, int dtype, const float* bias,
+                    const float* ps, const float* psh, float slope, const float* ref, double* sums2, void* ws, size_t wsb,
+                    ddmp_stream st, CallCtx& ctx) {
     ARG_TRY(dt_ok(dtype));
-    return dtype == DDMP_BF16
-               ? ddmp_spmm_bnred_bf16(g, (cb)X, ldx, (uint16_t*)Y, ldy, C, (cb)Yp, ldyp, scale, shift, mean, rstd, slope, sums2, ws, wsb, st)
-               : ddmp_spmm_bnred_f32(g, (cf)X, ldx, (float*)Y, ldy, C, (cf)Yp, ldyp, scale, shift, mean, rstd, slope, sums2, ws, wsb, st);
+    return dtype == DDMP_BF16 ? ddmp_spmm_stats_bf16(g, (cb)X, ldx, (uint16_t*)Y, ldy, C, bias, ps, psh, slope, ref, sums2, ws, wsb, st, ctx)
+                              : ddmp_spmm_stats_f32(g, (cf)X, ldx, (float*)Y, ldy, C, bias, ps, psh, slope, ref, sums2, ws, wsb, st, ctx);
 }
 extern "C" int ddmp_spmm_stats(const ddmp_graph* g, const void* X, int64_t ldx, void* Y, int64_t ldy, int C, int dtype,
                                const float* bias, const float* ps, const float* psh, float slope, const float* ref,
                                double* sums2, void* ws, size_t wsb, ddmp_stream st) {
-    ddmp::FinalizeScope fin_scope(sums2, st, C);
-    ARG_TRY(dt_ok(dtype));
-    return dtype == DDMP_BF16 ? ddmp_spmm_stats_bf16(g, (cb)X, ldx, (uint16_t*)Y, ldy, C, bias, ps, psh, slope, ref, sums2, ws, wsb, st)
-                              : ddmp_spmm_stats_f32(g, (cf)X, ldx, (float*)Y, ldy, C, bias, ps, psh, slope, ref, sums2, ws, wsb, st);
+    CallCtx ctx;
+    return ddmp_spmm_stats(g, X, ldx, Y, ldy, C, dtype, bias, ps, psh, slope, ref, sums2, ws, wsb, st, ctx);
 }
 extern "C" int ddmp_spmm_bnbwd(const ddmp_graph* g, const void* dZ, int64_t lddz, const void* Yb, int64_t ldyb, void* out,
                                int64_t ld_out, int C, int dtype, const float* a, const float* b, const float* c1,
@@ -266,42 +213,69 @@ extern "C" int ddmp_spmm_bnbwd(const ddmp_graph* g, const void* dZ, int64_t lddz
 extern "C" size_t ddmp_gemm_rows_ws_bytes(int K, int M, int dtype) {
     return dtype == DDMP_BF16 ? ddmp_gemm_rows_bf16_workspace_bytes(K, M) : ddmp_gemm_rows_workspace_bytes(K, M);
 }
+// (the bfloat16 GEMMs take no options: DDMP_OPT_SCALES / DDMP_OPT_PREPARED belong to the float32 split-plane routes)
+int ddmp_gemm_nt(const void* A, int64_t lda, const float* W, int64_t ldw, void* Y, int64_t ldy, int64_t n, int K, int M, int dtype,
+                 const float* bias, const float* ps, const float* psh, float slope, void* ws, size_t wsb, ddmp_stream st,
+                 CallCtx& ctx) {
+    ARG_TRY(dt_ok(dtype));
+    return dtype == DDMP_BF16 ? ddmp_gemm_nt_bf16((cb)A, lda, W, ldw, (uint16_t*)Y, ldy, n, K, M, bias, ps, psh, slope, ws, wsb, st)
+                              : ddmp_gemm_nt_f32((cf)A, lda, W, ldw, (float*)Y, ldy, n, K, M, bias, ps, psh, slope, ws, wsb, st, ctx);
+}
 extern "C" int ddmp_gemm_nt(const void* A, int64_t lda, const float* W, int64_t ldw, void* Y, int64_t ldy, int64_t n, int K,
                             int M, int dtype, const float* bias, const float* ps, const float* psh, float slope, void* ws,
                             size_t wsb, ddmp_stream st) {
+    CallCtx ctx;
+    return ddmp_gemm_nt(A, lda, W, ldw, Y, ldy, n, K, M, dtype, bias, ps, psh, slope, ws, wsb, st, ctx);
+}
+int ddmp_gemm_nn(const void* A, int64_t lda, const float* W, int64_t ldw, void* Y, int64_t ldy, int64_t n, int M, int K, int dtype,
+                 void* ws, size_t wsb, ddmp_stream st, CallCtx& ctx) {
     ARG_TRY(dt_ok(dtype));
-    return dtype == DDMP_BF16 ? ddmp_gemm_nt_bf16((cb)A, lda, W, ldw, (uint16_t*)Y, ldy, n, K, M, bias, ps, psh, slope, ws, wsb, st)
-                              : ddmp_gemm_nt_f32((cf)A, lda, W, ldw, (float*)Y, ldy, n, K, M, bias, ps, psh, slope, ws, wsb, st);
+    return dtype == DDMP_BF16 ? ddmp_gemm_nn_bf16((cb)A, lda, W, ldw, (uint16_t*)Y, ldy, n, M, K, ws, wsb, st)
+                              : ddmp_gemm_nn_f32((cf)A, lda, W, ldw, (float*)Y, ldy, n, M, K, ws, wsb, st, ctx);
 }
 extern "C" int ddmp_gemm_nn(const void* A, int64_t lda, const float* W, int64_t ldw, void* Y, int64_t ldy, int64_t n, int M,
                             int K, int dtype, void* ws, size_t wsb, ddmp_stream st) {
-    ARG_TRY(dt_ok(dtype));
-    return dtype == DDMP_BF16 ? ddmp_gemm_nn_bf16((cb)A, lda, W, ldw, (uint16_t*)Y, ldy, n, M, K, ws, wsb, st)
-                              : ddmp_gemm_nn_f32((cf)A, lda, W, ldw, (float*)Y, ldy, n, M, K, ws, wsb, st);
+    CallCtx ctx;
+    return ddmp_gemm_nn(A, lda, W, ldw, Y, ldy, n, M, K, dtype, ws, wsb, st, ctx);
 }
 extern "C" size_t ddmp_gemm_tn_ws_bytes(int64_t n_rows, int M, int K, int dtype) {
     return dtype == DDMP_BF16 ? ddmp_gemm_tn_bf16_workspace_bytes(n_rows, M, K) : ddmp_gemm_tn_workspace_bytes(n_rows, M, K);
 }
+int ddmp_gemm_tn(const void* G, int64_t ldg, const void* Z, int64_t ldz, float* dW, int64_t lddw, int64_t n, int M, int K, int dtype,
+                 const float* ps, const float* psh, float slope, void* ws, size_t wsb, ddmp_stream st, CallCtx& ctx) {
+    ARG_TRY(dt_ok(dtype));
+    return dtype == DDMP_BF16 ? ddmp_gemm_tn_bf16((cb)G, ldg, (cb)Z, ldz, dW, lddw, n, M, K, ps, psh, slope, ws, wsb, st)
+                              : ddmp_gemm_tn_f32((cf)G, ldg, (cf)Z, ldz, dW, lddw, n, M, K, ps, psh, slope, ws, wsb, st, ctx);
+}
 extern "C" int ddmp_gemm_tn(const void* G, int64_t ldg, const void* Z, int64_t ldz, float* dW, int64_t lddw, int64_t n, int M,
                             int K, int dtype, const float* ps, const float* psh, float slope, void* ws, size_t wsb,
                             ddmp_stream st) {
+    CallCtx ctx;
+    return ddmp_gemm_tn(G, ldg, Z, ldz, dW, lddw, n, M, K, dtype, ps, psh, slope, ws, wsb, st, ctx);
+}
+int ddmp_bn_stats(const void* Y, int64_t ldy, int64_t n, int C, int dtype, double* sums, void* ws, size_t wsb, ddmp_stream st,
+                  CallCtx& ctx) {
     ARG_TRY(dt_ok(dtype));
-    return dtype == DDMP_BF16 ? ddmp_gemm_tn_bf16((cb)G, ldg, (cb)Z, ldz, dW, lddw, n, M, K, ps, psh, slope, ws, wsb, st)
-                              : ddmp_gemm_tn_f32((cf)G, ldg, (cf)Z, ldz, dW, lddw, n, M, K, ps, psh, slope, ws, wsb, st);
+    return dtype == DDMP_BF16 ? ddmp_bn_stats_bf16((cb)Y, ldy, n, C, sums, ws, wsb, st, ctx)
+                              : ddmp_bn_stats_f32((cf)Y, ldy, n, C, sums, ws, wsb, st, ctx);
 }
 extern "C" int ddmp_bn_stats(const void* Y, int64_t ldy, int64_t n, int C, int dtype, double* sums, void* ws, size_t wsb,
                              ddmp_stream st) {
-    ddmp::FinalizeScope fin_scope(sums, st, C);
+    CallCtx ctx;
+    return ddmp_bn_stats(Y, ldy, n, C, dtype, sums, ws, wsb, st, ctx);
+}
+int ddmp_bn_bwd_reduce(const void* dZ, int64_t lddz, const void* Y, int64_t ldy, int64_t n, int C, int dtype, const float* scale,
+                       const float* shift, const float* mean, const float* rstd, float slope, double* sums2, void* ws, size_t wsb,
+                       ddmp_stream st, CallCtx& ctx) {
     ARG_TRY(dt_ok(dtype));
-    return dtype == DDMP_BF16 ? ddmp_bn_stats_bf16((cb)Y, ldy, n, C, sums, ws, wsb, st) : ddmp_bn_stats_f32((cf)Y, ldy, n, C, sums, ws, wsb, st);
+    return dtype == DDMP_BF16 ? ddmp_bn_bwd_reduce_bf16((cb)dZ, lddz, (cb)Y, ldy, n, C, scale, shift, mean, rstd, slope, sums2, ws, wsb, st, ctx)
+                              : ddmp_bn_bwd_reduce_f32((cf)dZ, lddz, (cf)Y, ldy, n, C, scale, shift, mean, rstd, slope, sums2, ws, wsb, st, ctx);
 }
 extern "C" int ddmp_bn_bwd_reduce(const void* dZ, int64_t lddz, const void* Y, int64_t ldy, int64_t n, int C, int dtype,
                                   const float* scale, const float* shift, const float* mean, const float* rstd, float slope,
                                   double* sums2, void* ws, size_t wsb, ddmp_stream st) {
-    ddmp::FinalizeScope fin_scope(sums2, st, C);
-    ARG_TRY(dt_ok(dtype));
-    return dtype == DDMP_BF16 ? ddmp_bn_bwd_reduce_bf16((cb)dZ, lddz, (cb)Y, ldy, n, C, scale, shift, mean, rstd, slope, sums2, ws, wsb, st)
-                              : ddmp_bn_bwd_reduce_f32((cf)dZ, lddz, (cf)Y, ldy, n, C, scale, shift, mean, rstd, slope, sums2, ws, wsb, st);
+    CallCtx ctx;
+    return ddmp_bn_bwd_reduce(dZ, lddz, Y, ldy, n, C, dtype, scale, shift, mean, rstd, slope, sums2, ws, wsb, st, ctx);
 }
 extern "C" int ddmp_bn_bwd_apply(const void* dZ, int64_t lddz, const void* Y, int64_t ldy, void* dY, int64_t lddy, int64_t n,
                                  int C, int dtype, const float* scale, const float* shift, const float* c1, const float* c0,

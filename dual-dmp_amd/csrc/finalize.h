@@ -1,13 +1,13 @@
-// Tail-fused finalisation of the column reductions (round 3).
+// Tail-fused finalisation of the column reductions, and the per-call context that carries it.
 //
 // Every BatchNorm of the path turns a float64 [2C] result of a column reduction into float32 per-column coefficients:
 // forward (sum y, sum y^2) -> scale / shift / mean / rstd (+ running statistics); backward (sum g, sum g*yhat) -> dgamma,
-// dbeta, c1, c0.  That used to be a kernel of its own behind the reduction's second stage -- 48 launches of ~3 us per
-// iteration, 11 % of the launches of a 13k-face mesh.  ddmp_bn_next_prepare / ddmp_bn_next_bwd_prepare (include/ddmp_hip.h)
-// arm the NEXT reducing entry point of this host thread: its second-stage kernel (one thread holds both sums of a column)
-// writes the coefficients too, with the arithmetic of bn_prepare_kernel / bn_bwd_prepare_kernel (same device function:
-// bitwise the same values).  A reducing entry that takes a route without a second stage falls back to the stand-alone
-// kernel by itself (FinalizeScope), so "armed => the coefficients exist when the call returns" holds on every route.
+// dbeta, c1, c0.  As a kernel of its own behind the reduction's second stage that is 48 launches of ~3 us per iteration, 11 %
+// of the launches of a 13k-face mesh.  A reducing call that is given DDMP_OPT_BN_FWD / DDMP_OPT_BN_BWD (include/ddmp_hip.h,
+// ddmp_opts) has its second-stage kernel (one thread holds both sums of a column) write the coefficients too, with the
+// arithmetic of bn_prepare_kernel / bn_bwd_prepare_kernel (same device function: bitwise the same values).  On a route
+// without a second stage the _o entry point runs the stand-alone kernel behind the call (opts.hip), so "requested => the
+// coefficients exist when the call returns DDMP_OK" holds on every route.
 #pragma once
 #include "ddmp_common.h"
 
@@ -52,28 +52,21 @@ __device__ __forceinline__ void finalize_column(const FinalizeArgs& f, int c, do
     }
 }
 
-// host side (dispatch.hip): what ddmp_bn_next_* armed on this thread / what the running reducing entry has to apply
-FinalizeArgs& finalize_pending();
-FinalizeArgs& finalize_active();
-// second-stage helpers: the coefficients to write for a reduction over C columns (kind 0 if none / another width), marking
-// them as taken
-FinalizeArgs finalize_take(int C);
-
-// At the top of every extern "C" entry that produces a float64 [2C] column reduction.  Nested entries (a fused form falling
-// back to GEMM + ddmp_bn_stats) share the outermost scope's request.
-// `width` = the columns of THIS call's reduction: a pending request for another width (armed for a call that was never made:
-// an error or an exception in the caller in between) is DROPPED here, never run against sums of another size; so is a
-// request whose call has no sums buffer (argument error).
-struct FinalizeScope {
-    const double* sums;
-    hipStream_t st;
-    bool owns;
-    FinalizeScope(const double* sums_, ddmp_stream stream, int width);
-    ~FinalizeScope();                                            // request still open: stand-alone prepare kernel
+// One call's options (ddmp_opts, validated by the _o entry point: opts.hip), passed by reference from that entry point down
+// to the launch helper that consumes them.  An exported entry point without options runs on an empty one.
+struct CallCtx {
+    FinalizeArgs fin;                                            // kind 0: no BatchNorm coefficients requested
+    bool fin_done = false;                                       // a second-stage kernel of this call has written them
+    float* slot_a = nullptr;                                     // DDMP_OPT_SCALES: f16 split mode (gemm_f16s.inc), the
+    float* slot_b = nullptr;                                     // operands' persistent scale slots
+    int prime = 0;
+    bool prepared = false;                                       // DDMP_OPT_PREPARED
+    // second stage of a reduction over C columns: the coefficients it writes as well (kind 0: none), marked as written
+    FinalizeArgs take_fin(int C) {
+        if (fin.kind == 0 || fin_done || fin.C != C) return FinalizeArgs();
+        fin_done = true;
+        return fin;
+    }
 };
-// everything armed on this host thread for "the next call" (ddmp_next_pending / ddmp_next_cancel of the C ABI); the GEMM
-// side's share lives in gemm.hip
-int gemm_next_pending();
-void gemm_next_cancel();
 
 }  // namespace ddmp

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void fpartials_stage1_kernel(const PT* __restr
     }
 }
 
-// one thread per column: both sums (+ the coefficients armed by ddmp_bn_next_*: finalize.h)
+// one thread per column: both sums (+ the coefficients the call was asked for: finalize.h)
 // shift_ref (nullable): the partials are sums of (y - ref[c]) and (y - ref[c])^2 over shift_n rows; undone here
 __global__ void fpartials_stage2_kernel(const double* __restrict__ mid, int S, int C, double* __restrict__ sums,
                                         ddmp::FinalizeArgs fin, const float* __restrict__ shift_ref, double shift_n) {
@@ -137,18 +137,18 @@ __global__ __launch_bounds__(1024) void fpartials_single_kernel(const PT* __rest
 
 inline size_t fpartials_mid_bytes(int C) { return (size_t)kFpMaxS * 2 * (size_t)C * sizeof(double); }
 
-// `mid` = scratch of fpartials_mid_bytes(C)
+// `mid` = scratch of fpartials_mid_bytes(C); `fin`: the coefficients to write with the sums (ctx.take_fin(C))
 template <typename PT>
 inline void fpartials_reduce(const PT* part, int groups, int ld, int C, double* mid, double* sums, hipStream_t st,
-                             const float* shift_ref = nullptr, double shift_n = 0.0) {
+                             const ddmp::FinalizeArgs& fin, const float* shift_ref = nullptr, double shift_n = 0.0) {
     if (groups <= kFpSingleGroups) {
         hipLaunchKernelGGL((fpartials_single_kernel<PT>), dim3((unsigned)((C + 31) / 32)), dim3(1024), 0, st, part, groups, ld, C,
-                           sums, ddmp::finalize_take(C), shift_ref, shift_n);
+                           sums, fin, shift_ref, shift_n);
         return;
     }
     const int S = (int)std::max<int64_t>(1, std::min<int64_t>(kFpMaxS, groups / 64));
     hipLaunchKernelGGL((fpartials_stage1_kernel<PT>), dim3((unsigned)((C + 31) / 32), (unsigned)S), dim3(256), 0, st, part, groups,
                        ld, C, S, mid);
     hipLaunchKernelGGL(fpartials_stage2_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, st, mid, S, C, sums,
-                       ddmp::finalize_take(C), shift_ref, shift_n);
+                       fin, shift_ref, shift_n);
 }

@@ -425,8 +425,8 @@ static bool ws_enabled() { return true; }
 // ---------------------------------------------------------------- weights prepared once per iteration (round 3)
 // Every GEMM call used to split its weight matrix into 16-bit planes itself: absolute maximum (memset + kernel) + split
 // kernel, ~90 launches of 4-10 us per training iteration.  ddmp_gemm_prepare_weights does all matrices of a net in TWO
-// launches into caller-owned plane buffers; a GEMM call whose workspace IS such a buffer and that was announced with
-// ddmp_gemm_next_prepared() skips its own split -- if and only if the recorded layout is exactly the one its route wants
+// launches into caller-owned plane buffers; a GEMM call whose workspace IS such a buffer and that is given
+// DDMP_OPT_PREPARED skips its own split -- if and only if the recorded layout is exactly the one its route wants
 // (same matrix, shape, orientation, plane format); otherwise it splits as before.  Same device code, same values.
 enum { kWPanelF16 = 1, kWPanelB16 = 2, kWTiled = 3, kWPlain = 4 };
 struct WPrepDesc {
@@ -445,10 +445,10 @@ static inline bool wprep_same(const WPrepDesc& a, const WPrepDesc& b) {
            a.KD == b.KD && a.transpose == b.transpose && a.P == b.P;
 }
 static thread_local std::vector<WPrepDesc> g_w_registry;         // what the last ddmp_gemm_prepare_weights calls wrote
-static thread_local bool g_w_next_prepared = false, g_w_call_prepared = false;
-// at a split site: does `planes` already hold exactly this layout (and did the caller say so)?
-static bool w_prepared(const float* W, int64_t ldw, void* planes, int kind, int nterm, int MD, int KD, int transpose, int P) {
-    if (!g_w_call_prepared) return false;
+// at a split site: does `planes` already hold exactly this layout (and did the caller say so: `prepared`)?
+static bool w_prepared(bool prepared, const float* W, int64_t ldw, void* planes, int kind, int nterm, int MD, int KD, int transpose,
+                       int P) {
+    if (!prepared) return false;
     const WPrepDesc want{W, planes, ldw, kind, nterm, MD, KD, transpose, P};
     for (const WPrepDesc& e : g_w_registry)
         if (wprep_same(e, want)) return true;
@@ -500,14 +500,14 @@ __global__ __launch_bounds__(256) void wprep_split_kernel(WPrepBatch b, const fl
 template <bool PRO>
 static void launch_ws(int mode, const float* A, int64_t lda, const float* W, int64_t ldw, int transpose, void* planes,
                       float* Y, int64_t ldy, int n_rows, int KD, int MD, const float* bias, const float* ps,
-                      const float* psh, float slope, hipStream_t st) {
+                      const float* psh, float slope, hipStream_t st, bool prepared) {
     const int n_row_tiles = (int)ddmp::cdiv(n_rows, kBM);
     const int TN = MD > 64 ? 2 : 1;
     {
         const int BN = 64 * TN;
         const int64_t total = ddmp::cdiv(MD, BN) * BN * (int64_t)KD;
         const int sgrid = (int)std::min<int64_t>(ddmp::cdiv(total, 256), 1024);
-        if (w_prepared(W, ldw, planes, kWTiled, mode == 6 ? 3 : 2, MD, KD, transpose, BN)) {
+        if (w_prepared(prepared, W, ldw, planes, kWTiled, mode == 6 ? 3 : 2, MD, KD, transpose, BN)) {
         } else if (mode == 6)
             hipLaunchKernelGGL((split_w_tiled_kernel<3>), dim3(sgrid), dim3(256), 0, st, W, ldw, MD, KD, transpose, BN, (__bf16*)planes);
         else
@@ -578,27 +578,6 @@ static inline bool rr_route_ok(int64_t n_rows, int KD, int64_t lda, int64_t lda2
     return rr_enabled() && KD >= 64 && KD <= 512 && n_rows >= kRRMinRows &&
            n_rows * lda * 4 < ((int64_t)1 << 32) && n_rows * lda2 * 4 < ((int64_t)1 << 32);      // (32-bit lane offsets)
 }
-// f16 split mode (gemm_f16s.inc): 0 | 13; operand scale slots of the NEXT ddmp_gemm_* call on this host thread
-struct ScaleCtx {
-    float* a = nullptr;
-    float* b = nullptr;
-    int prime = 0;
-};
-static thread_local ScaleCtx g_scale_ctx;
-namespace ddmp {
-int gemm_next_pending() { return ((g_scale_ctx.a || g_scale_ctx.b || g_scale_ctx.prime) ? 2 : 0) | (g_w_next_prepared ? 4 : 0); }
-void gemm_next_cancel() {
-    g_scale_ctx = ScaleCtx();
-    g_w_next_prepared = false;
-}
-}  // namespace ddmp
-static ScaleCtx take_scale_ctx() {                               // (top of every GEMM entry point)
-    ScaleCtx c = g_scale_ctx;
-    g_scale_ctx = ScaleCtx();
-    g_w_call_prepared = g_w_next_prepared;
-    g_w_next_prepared = false;
-    return c;
-}
 // slot[0] = max |f(A)|, exactly (pre-pass)
 template <int PM>
 static void f16s_measure(const float* A, int64_t lda, const float* A2, int64_t lda2, int64_t n_rows, int C,
@@ -615,8 +594,8 @@ template <int PM>
 static void launch_panel(int mode, const float* A, int64_t lda, const float* A2, int64_t lda2, const float* W,
                          int64_t ldw, int transpose, void* planes, float* Y, int64_t ldy, int n_rows, int KD, int MD,
                          const float* bias, const float* ps, const float* psh, const float* pc1, const float* pc0,
-                         float slope, hipStream_t st, double* stats = nullptr, double* sums = nullptr,
-                         ScaleCtx ctx = ScaleCtx(), const float* red_yp = nullptr, int64_t red_ldyp = 0,
+                         float slope, hipStream_t st, double* stats, double* sums, ddmp::CallCtx& ctx,
+                         const float* red_yp = nullptr, int64_t red_ldyp = 0,
                          const float* const* red_bn4 = nullptr /* scale, shift, mean, rstd: stats = the backward reductions */) {
     // wide outputs: 128 x 512 | 256 x 256 blocks (64 x 128 per wave); narrow outputs (MD <= 128): 512-row blocks, 64 x 32 NJ
     const int WC = MD > 256 ? 4 : MD > 128 ? 2 : 1, WR = 8 / WC;
@@ -631,9 +610,9 @@ static void launch_panel(int mode, const float* A, int64_t lda, const float* A2,
         // two f16 planes of W * wscale; the scale and (without caller slots) the A operand's slot sit behind them
         char* tail = (char*)planes + (size_t)2 * MP * KD * 2;
         float* wscale = (float*)tail;
-        float* slot = ctx.a ? ctx.a : (float*)(tail + 16);
-        const bool prime = !ctx.a || ctx.prime;
-        const bool w_ready = w_prepared(W, ldw, planes, kWPanelF16, 2, MD, KD, transpose, MP);
+        float* slot = ctx.slot_a ? ctx.slot_a : (float*)(tail + 16);
+        const bool prime = !ctx.slot_a || ctx.prime;
+        const bool w_ready = w_prepared(ctx.prepared, W, ldw, planes, kWPanelF16, 2, MD, KD, transpose, MP);
         if (!w_ready) {
             (void)hipMemsetAsync(wscale, 0, 4, st);               // = max |W| (the kernels derive the power of two)
             hipLaunchKernelGGL(f16s_wmax_kernel, dim3((unsigned)std::min(transpose ? KD : MD, 128)), dim3(256), 0, st, W, ldw,
@@ -674,7 +653,7 @@ static void launch_panel(int mode, const float* A, int64_t lda, const float* A2,
             }
             if (stats && sums) {
                 const size_t pbytes = ((size_t)tiles * 2 * 2 * MP * sizeof(double) + 255) / 256 * 256;
-                fpartials_reduce(stats, tiles * 2, MP, MD, (double*)((char*)stats + pbytes), sums, st);
+                fpartials_reduce(stats, tiles * 2, MP, MD, (double*)((char*)stats + pbytes), sums, st, ctx.take_fin(MD));
             }
             return;
         }
@@ -693,11 +672,11 @@ static void launch_panel(int mode, const float* A, int64_t lda, const float* A2,
 #undef DDMP_PANEL_H
         if (stats && sums) {
             const size_t pbytes = ((size_t)n_row_tiles * WR * 2 * MP * sizeof(double) + 255) / 256 * 256;
-            fpartials_reduce(stats, n_row_tiles * WR, MP, MD, (double*)((char*)stats + pbytes), sums, st);
+            fpartials_reduce(stats, n_row_tiles * WR, MP, MD, (double*)((char*)stats + pbytes), sums, st, ctx.take_fin(MD));
         }
         return;
     }
-    if (w_prepared(W, ldw, planes, kWPanelB16, mode == 6 ? 3 : 2, MD, KD, transpose, MP)) {
+    if (w_prepared(ctx.prepared, W, ldw, planes, kWPanelB16, mode == 6 ? 3 : 2, MD, KD, transpose, MP)) {
     } else if (mode == 6)
         hipLaunchKernelGGL((split_w_panel_kernel<3, __bf16>), dim3(sgrid), dim3(256), 0, st, W, ldw, MD, KD, transpose, MP, (__bf16*)planes, (const float*)nullptr);
     else
@@ -737,7 +716,7 @@ static void launch_panel(int mode, const float* A, int64_t lda, const float* A2,
 #undef DDMP_PANEL
     if (stats && sums) {
         const size_t pbytes = ((size_t)n_row_tiles * WR * 2 * MP * sizeof(double) + 255) / 256 * 256;
-        fpartials_reduce(stats, n_row_tiles * WR, MP, MD, (double*)((char*)stats + pbytes), sums, st);
+        fpartials_reduce(stats, n_row_tiles * WR, MP, MD, (double*)((char*)stats + pbytes), sums, st, ctx.take_fin(MD));
     }
 }
 
@@ -771,12 +750,6 @@ extern "C" int ddmp_set_gemm_mode(int mode) {
 }
 extern "C" int ddmp_get_gemm_mode(void) { return gemm_f16() ? gemm_f16() : gemm_mode(); }
 
-extern "C" int ddmp_gemm_next_scales(float* slot_a, float* slot_b, int prime) {
-    g_scale_ctx.a = slot_a;
-    g_scale_ctx.b = slot_b;
-    g_scale_ctx.prime = prime;
-    return DDMP_OK;
-}
 extern "C" int ddmp_gemm_scales_roll(float* slots, int n_slots, ddmp_stream stream) {
     ARG_TRY(slots && n_slots > 0);
     hipLaunchKernelGGL(f16s_roll_kernel, dim3((unsigned)cdiv(n_slots, 64)), dim3(64), 0, (hipStream_t)stream, slots, n_slots);
@@ -794,14 +767,14 @@ extern "C" size_t ddmp_gemm_rows_workspace_bytes(int K, int M) {
 
 // bf16 modes with a workspace: W is split ONCE here instead of by every row-tile workgroup
 static bool presplit_w(const float* W, int64_t ldw, int M, int K, int transpose, void* ws, size_t ws_bytes,
-                       hipStream_t st) {
+                       hipStream_t st, bool prepared) {
     const int mode = gemm_mode();
     const int RK = transpose ? M : K;                           // reduction length of the consumer
     if (mode == 0 || !ws || ws_bytes < ddmp_gemm_rows_workspace_bytes(K, M) || RK % 8 != 0 ||
         (reinterpret_cast<uintptr_t>(ws) & 15))
         return false;
     const int grid = (int)std::min<int64_t>(cdiv((int64_t)M * K, 256), 1024);
-    if (w_prepared(W, ldw, ws, kWPlain, mode == 6 ? 3 : 2, M, K, transpose, 0)) return true;
+    if (w_prepared(prepared, W, ldw, ws, kWPlain, mode == 6 ? 3 : 2, M, K, transpose, 0)) return true;
     if (mode == 6)
         hipLaunchKernelGGL((split_w_kernel<3>), dim3(grid), dim3(256), 0, st, W, ldw, M, K, transpose, (__bf16*)ws);
     else
@@ -851,10 +824,6 @@ static WPrepDesc plan_w(int form, int64_t n_rows, const float* W, int64_t ldw, i
     return d;
 }
 
-extern "C" int ddmp_gemm_next_prepared(void) {
-    g_w_next_prepared = true;
-    return DDMP_OK;
-}
 // the owner of a plane buffer is about to free it (or to stop maintaining it): drop what this thread recorded for it, so that
 // a later allocation at the same address is never taken for prepared planes.  planes == NULL: everything.
 extern "C" int ddmp_gemm_forget_planes(const void* planes) {
@@ -889,11 +858,9 @@ extern "C" int ddmp_gemm_prepare_weights(int n, const float* const* W, const int
     return DDMP_OK;
 }
 
-extern "C" int ddmp_gemm_nt_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y,
-                                int64_t ldy, int64_t n_rows, int K, int M, const float* bias,
-                                const float* pro_scale, const float* pro_shift, float slope,
-                                void* workspace, size_t workspace_bytes, ddmp_stream stream) {
-    const ScaleCtx ctx = take_scale_ctx();
+int ddmp_gemm_nt_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y, int64_t ldy, int64_t n_rows, int K,
+                     int M, const float* bias, const float* pro_scale, const float* pro_shift, float slope, void* workspace,
+                     size_t workspace_bytes, ddmp_stream stream, ddmp::CallCtx& ctx) {
     ARG_TRY(A && W && Y && n_rows > 0 && K > 0 && M > 0 && n_rows < INT32_MAX);
     ARG_TRY(K % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && lda >= K && ldw >= K && ldy >= M);
     ARG_TRY(aligned16(A) && aligned16(W));
@@ -911,12 +878,12 @@ extern "C" int ddmp_gemm_nt_f32(const float* A, int64_t lda, const float* W, int
         return DDMP_OK;
     }
     if (gemm_mode() != 0 && !(pro_scale && K > 512) && ws_ok(K, M, Y, ldy, workspace, workspace_bytes)) {
-        if (pro_scale) launch_ws<true>(gemm_mode(), A, lda, W, ldw, 0, workspace, Y, ldy, (int)n_rows, K, M, bias, pro_scale, pro_shift, slope, st);
-        else launch_ws<false>(gemm_mode(), A, lda, W, ldw, 0, workspace, Y, ldy, (int)n_rows, K, M, bias, nullptr, nullptr, slope, st);
+        if (pro_scale) launch_ws<true>(gemm_mode(), A, lda, W, ldw, 0, workspace, Y, ldy, (int)n_rows, K, M, bias, pro_scale, pro_shift, slope, st, ctx.prepared);
+        else launch_ws<false>(gemm_mode(), A, lda, W, ldw, 0, workspace, Y, ldy, (int)n_rows, K, M, bias, nullptr, nullptr, slope, st, ctx.prepared);
         LAUNCH_TRY();
         return DDMP_OK;
     }
-    const bool pre = !(pro_scale && K > 512) && presplit_w(W, ldw, M, K, 0, workspace, workspace_bytes, st);
+    const bool pre = !(pro_scale && K > 512) && presplit_w(W, ldw, M, K, 0, workspace, workspace_bytes, st, ctx.prepared);
     const float* Bop = pre ? (const float*)workspace : W;
 #define DDMP_LAUNCH_NT(KERNEL_, PRO_)                                                                    \
     hipLaunchKernelGGL((KERNEL_), grid, block, 0, st, A, lda, Bop, ldw, Y, ldy, (int)n_rows, K, M, bias, \
@@ -948,12 +915,18 @@ extern "C" int ddmp_gemm_nt_f32(const float* A, int64_t lda, const float* W, int
     LAUNCH_TRY();
     return DDMP_OK;
 }
+extern "C" int ddmp_gemm_nt_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y,
+                                int64_t ldy, int64_t n_rows, int K, int M, const float* bias,
+                                const float* pro_scale, const float* pro_shift, float slope,
+                                void* workspace, size_t workspace_bytes, ddmp_stream stream) {
+    ddmp::CallCtx ctx;
+    return ddmp_gemm_nt_f32(A, lda, W, ldw, Y, ldy, n_rows, K, M, bias, pro_scale, pro_shift, slope, workspace, workspace_bytes,
+                            stream, ctx);
+}
 
-extern "C" int ddmp_gemm_nn_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y,
-                                int64_t ldy, int64_t n_rows, int M, int K, void* workspace,
-                                size_t workspace_bytes, ddmp_stream stream) {
+int ddmp_gemm_nn_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y, int64_t ldy, int64_t n_rows, int M,
+                     int K, void* workspace, size_t workspace_bytes, ddmp_stream stream, ddmp::CallCtx& ctx) {
     // Y[n,K] = A[n,M] . W[M,K] : reduction over M, output width K
-    const ScaleCtx ctx = take_scale_ctx();
     ARG_TRY(A && W && Y && n_rows > 0 && K > 0 && M > 0 && n_rows < INT32_MAX);
     ARG_TRY(M % 4 == 0 && K % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && lda >= M && ldw >= K && ldy >= K);
     ARG_TRY(aligned16(A) && aligned16(W));
@@ -970,11 +943,11 @@ extern "C" int ddmp_gemm_nn_f32(const float* A, int64_t lda, const float* W, int
         return DDMP_OK;
     }
     if (gemm_mode() != 0 && ws_ok(M, K, Y, ldy, workspace, workspace_bytes)) {
-        launch_ws<false>(gemm_mode(), A, lda, W, ldw, 1, workspace, Y, ldy, (int)n_rows, M, K, nullptr, nullptr, nullptr, 0.f, st);
+        launch_ws<false>(gemm_mode(), A, lda, W, ldw, 1, workspace, Y, ldy, (int)n_rows, M, K, nullptr, nullptr, nullptr, 0.f, st, ctx.prepared);
         LAUNCH_TRY();
         return DDMP_OK;
     }
-    const bool pre = presplit_w(W, ldw, M, K, 1, workspace, workspace_bytes, st);
+    const bool pre = presplit_w(W, ldw, M, K, 1, workspace, workspace_bytes, st, ctx.prepared);
 #define DDMP_LAUNCH_NN(KERNEL_)                                                                        \
     hipLaunchKernelGGL((KERNEL_), grid, block, 0, st, A, lda, W, ldw, Y, ldy, (int)n_rows, M, K, nullptr, \
                        nullptr, nullptr, 0.f, n_row_tiles, n_col_tiles)
@@ -1039,11 +1012,9 @@ extern "C" size_t ddmp_gemm_tn_workspace_bytes(int64_t n_rows, int M, int K) {
     return (size_t)std::max(p.n_splits, q.n_splits) * (size_t)M * (size_t)K * sizeof(float) + 64;    // + two scale slots (f16 modes)
 }
 
-extern "C" int ddmp_gemm_tn_f32(const float* G, int64_t ldg, const float* Z, int64_t ldz, float* dW,
-                                int64_t lddw, int64_t n_rows, int M, int K, const float* pro_scale,
-                                const float* pro_shift, float slope, void* workspace,
-                                size_t workspace_bytes, ddmp_stream stream) {
-    const ScaleCtx ctx = take_scale_ctx();
+int ddmp_gemm_tn_f32(const float* G, int64_t ldg, const float* Z, int64_t ldz, float* dW, int64_t lddw, int64_t n_rows, int M,
+                     int K, const float* pro_scale, const float* pro_shift, float slope, void* workspace, size_t workspace_bytes,
+                     ddmp_stream stream, ddmp::CallCtx& ctx) {
     ARG_TRY(G && Z && dW && n_rows > 0 && M > 0 && K > 0 && n_rows < INT32_MAX);
     ARG_TRY(M % 4 == 0 && K % 4 == 0 && ldg % 4 == 0 && ldz % 4 == 0 && ldg >= M && ldz >= K && lddw >= K);
     ARG_TRY(aligned16(G) && aligned16(Z));
@@ -1071,9 +1042,9 @@ extern "C" int ddmp_gemm_tn_f32(const float* G, int64_t ldg, const float* Z, int
         const int mode_ = gemm_mode();
         if (mode_ == 6 && gemm_f16() && tn_wide_ok(p.rows_per_split, ldg, 0, ldz)) {
             float* tail = (float*)((char*)workspace + need - 64);
-            const bool own = !(ctx.a && ctx.b);
-            gslot = own ? tail : ctx.a;
-            zslot = own ? tail + 4 : ctx.b;
+            const bool own = !(ctx.slot_a && ctx.slot_b);
+            gslot = own ? tail : ctx.slot_a;
+            zslot = own ? tail + 4 : ctx.slot_b;
             const bool prime = own || ctx.prime;
             target = prime ? kF16TargetExact : kF16TargetStale;
             if (prime) {
@@ -1137,13 +1108,10 @@ extern "C" int ddmp_gemm_nn_bnred_supported(int M, int K, int64_t n_rows) {
     return (narrow && (gemm_mode() == 6 || gemm_mode() == 3) && panel_enabled() && n_rows >= kPanelMinRows && M % 32 == 0 &&
             M >= 32 && M <= kMaxProK && (K == 128 || K == 64)) ? 2 : 0;
 }
-extern "C" int ddmp_gemm_nn_bnred_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* out, int64_t ld_out,
-                                      int64_t n_rows, int M, int K, const float* Yp, int64_t ldyp, const float* scale,
-                                      const float* shift, const float* mean, const float* rstd, float slope, double* sums2,
-                                      void* workspace, size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes,
-                                      ddmp_stream stream) {
-    ddmp::FinalizeScope fin_scope(sums2, stream, K);
-    const ScaleCtx ctx = take_scale_ctx();
+int ddmp_gemm_nn_bnred_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* out, int64_t ld_out, int64_t n_rows,
+                           int M, int K, const float* Yp, int64_t ldyp, const float* scale, const float* shift, const float* mean,
+                           const float* rstd, float slope, double* sums2, void* workspace, size_t workspace_bytes, void* stats_ws,
+                           size_t stats_ws_bytes, ddmp_stream stream, ddmp::CallCtx& ctx) {
     ARG_TRY(A && W && out && Yp && scale && shift && mean && rstd && sums2 && n_rows > 0 && n_rows < INT32_MAX);
     ARG_TRY(M % 4 == 0 && K % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && lda >= M && ldw >= K && ld_out >= K && ldyp >= K);
     ARG_TRY(aligned16(A) && aligned16(W));
@@ -1156,6 +1124,15 @@ extern "C" int ddmp_gemm_nn_bnred_f32(const float* A, int64_t lda, const float* 
                     nullptr, nullptr, slope, (hipStream_t)stream, (double*)stats_ws, sums2, ctx, Yp, ldyp, bn4);
     LAUNCH_TRY();
     return DDMP_OK;
+}
+extern "C" int ddmp_gemm_nn_bnred_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* out, int64_t ld_out,
+                                      int64_t n_rows, int M, int K, const float* Yp, int64_t ldyp, const float* scale,
+                                      const float* shift, const float* mean, const float* rstd, float slope, double* sums2,
+                                      void* workspace, size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes,
+                                      ddmp_stream stream) {
+    ddmp::CallCtx ctx;
+    return ddmp_gemm_nn_bnred_f32(A, lda, W, ldw, out, ld_out, n_rows, M, K, Yp, ldyp, scale, shift, mean, rstd, slope, sums2,
+                                  workspace, workspace_bytes, stats_ws, stats_ws_bytes, stream, ctx);
 }
 
 extern "C" int ddmp_gemm_bnbwd_supported(int cout, int cin, int64_t n_rows) {
@@ -1176,12 +1153,11 @@ extern "C" int ddmp_gemm_tn_bnbwd_supported(int cout, int cin, int64_t n_rows) {
     return (cout % 4 == 0 && cin % 4 == 0 && (panel || mode_ == 6 || mode_ == 3)) ? 1 : 0;
 }
 
-extern "C" int ddmp_gemm_nn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64_t ldyb, const float* W,
-                                      int64_t ldw, float* out, int64_t ld_out, int64_t n_rows, int M, int K,
-                                      const float* a, const float* b, const float* c1, const float* c0, float slope,
-                                      void* workspace, size_t workspace_bytes, ddmp_stream stream) {
+int ddmp_gemm_nn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64_t ldyb, const float* W, int64_t ldw, float* out,
+                           int64_t ld_out, int64_t n_rows, int M, int K, const float* a, const float* b, const float* c1,
+                           const float* c0, float slope, void* workspace, size_t workspace_bytes, ddmp_stream stream,
+                           ddmp::CallCtx& ctx) {
     // out[n,K] = dY[n,M] . W[M,K],  dY = a * dZ * lrelu'(a * Yb + b) + c1 * Yb + c0  (per column of M)
-    const ScaleCtx ctx = take_scale_ctx();
     ARG_TRY(dZ && Yb && W && out && a && b && c1 && c0 && n_rows > 0 && n_rows < INT32_MAX && M > 0 && K > 0);
     ARG_TRY(lddz % 4 == 0 && ldyb % 4 == 0 && ldw % 4 == 0 && lddz >= M && ldyb >= M && ldw >= K && ld_out >= K);
     ARG_TRY(aligned16(dZ) && aligned16(Yb) && aligned16(W));
@@ -1191,14 +1167,20 @@ extern "C" int ddmp_gemm_nn_bnbwd_f32(const float* dZ, int64_t lddz, const float
     LAUNCH_TRY();
     return DDMP_OK;
 }
+extern "C" int ddmp_gemm_nn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64_t ldyb, const float* W,
+                                      int64_t ldw, float* out, int64_t ld_out, int64_t n_rows, int M, int K,
+                                      const float* a, const float* b, const float* c1, const float* c0, float slope,
+                                      void* workspace, size_t workspace_bytes, ddmp_stream stream) {
+    ddmp::CallCtx ctx;
+    return ddmp_gemm_nn_bnbwd_f32(dZ, lddz, Yb, ldyb, W, ldw, out, ld_out, n_rows, M, K, a, b, c1, c0, slope, workspace,
+                                  workspace_bytes, stream, ctx);
+}
 
-extern "C" int ddmp_gemm_tn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64_t ldyb, const float* Z,
-                                      int64_t ldz, float* dW, int64_t lddw, int64_t n_rows, int M, int K,
-                                      const float* a, const float* b, const float* c1, const float* c0,
-                                      const float* pro_scale, const float* pro_shift, float slope, void* workspace,
-                                      size_t workspace_bytes, ddmp_stream stream) {
+int ddmp_gemm_tn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64_t ldyb, const float* Z, int64_t ldz, float* dW,
+                           int64_t lddw, int64_t n_rows, int M, int K, const float* a, const float* b, const float* c1,
+                           const float* c0, const float* pro_scale, const float* pro_shift, float slope, void* workspace,
+                           size_t workspace_bytes, ddmp_stream stream, ddmp::CallCtx& ctx) {
     // dW[M,K] = dY^T . f(Z),  dY as above (columns of M), f = optional BatchNorm+LeakyReLU prologue on Z (columns of K)
-    const ScaleCtx ctx = take_scale_ctx();
     ARG_TRY(dZ && Yb && Z && dW && a && b && c1 && c0 && n_rows > 0 && n_rows < INT32_MAX && M > 0 && K > 0);
     ARG_TRY(M % 4 == 0 && K % 4 == 0 && lddz >= M && ldyb >= M && ldz >= K && lddw >= K);
     ARG_TRY((pro_scale == nullptr) == (pro_shift == nullptr));
@@ -1247,9 +1229,9 @@ extern "C" int ddmp_gemm_tn_bnbwd_f32(const float* dZ, int64_t lddz, const float
     if (mode_ == 6 && gemm_f16() && lddz % 4 == 0 && ldyb % 4 == 0 && ldz % 4 == 0 && tn_wide_ok(p.rows_per_split, lddz, ldyb, ldz) &&
         aligned16(dZ) && aligned16(Yb) && aligned16(Z)) {
         float* tail = (float*)((char*)workspace + need - 64);
-        const bool own = !(ctx.a && ctx.b);
-        gslot = own ? tail : ctx.a;
-        zslot = own ? tail + 4 : ctx.b;
+        const bool own = !(ctx.slot_a && ctx.slot_b);
+        gslot = own ? tail : ctx.slot_a;
+        zslot = own ? tail + 4 : ctx.slot_b;
         const bool prime = own || ctx.prime;
         target = prime ? kF16TargetExact : kF16TargetStale;
         if (prime) {
@@ -1273,6 +1255,15 @@ extern "C" int ddmp_gemm_tn_bnbwd_f32(const float* dZ, int64_t lddz, const float
     LAUNCH_TRY();
     return DDMP_OK;
 }
+extern "C" int ddmp_gemm_tn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64_t ldyb, const float* Z,
+                                      int64_t ldz, float* dW, int64_t lddw, int64_t n_rows, int M, int K,
+                                      const float* a, const float* b, const float* c1, const float* c0,
+                                      const float* pro_scale, const float* pro_shift, float slope, void* workspace,
+                                      size_t workspace_bytes, ddmp_stream stream) {
+    ddmp::CallCtx ctx;
+    return ddmp_gemm_tn_bnbwd_f32(dZ, lddz, Yb, ldyb, Z, ldz, dW, lddw, n_rows, M, K, a, b, c1, c0, pro_scale, pro_shift, slope,
+                                  workspace, workspace_bytes, stream, ctx);
+}
 
 
 // ---- forward GEMM that also returns the BatchNorm statistics of its output (column sums of Y and Y^2, float64 [2M]):
@@ -1283,13 +1274,10 @@ extern "C" size_t ddmp_gemm_nt_stats_workspace_bytes(int64_t n_rows, int M) {
     return std::max(fused, ddmp_colreduce_workspace_bytes(n_rows, M));
 }
 
-extern "C" int ddmp_gemm_nt_stats_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y, int64_t ldy,
-                                      int64_t n_rows, int K, int M, const float* bias, const float* pro_scale,
-                                      const float* pro_shift, float slope, double* sums2, void* workspace,
-                                      size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes,
-                                      ddmp_stream stream) {
-    ddmp::FinalizeScope fin_scope(sums2, stream, M);
-    const ScaleCtx ctx = take_scale_ctx();
+int ddmp_gemm_nt_stats_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y, int64_t ldy, int64_t n_rows, int K,
+                           int M, const float* bias, const float* pro_scale, const float* pro_shift, float slope, double* sums2,
+                           void* workspace, size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes, ddmp_stream stream,
+                           ddmp::CallCtx& ctx) {
     ARG_TRY(sums2 && stats_ws);
     if (stats_ws_bytes < ddmp_gemm_nt_stats_workspace_bytes(n_rows, M)) return DDMP_EWORKSPACE;
     const bool fused = A && W && Y && n_rows > 0 && n_rows < INT32_MAX && K > 0 && M > 0 && K % 4 == 0 && lda % 4 == 0 &&
@@ -1303,10 +1291,17 @@ extern "C" int ddmp_gemm_nt_stats_f32(const float* A, int64_t lda, const float* 
         LAUNCH_TRY();
         return DDMP_OK;
     }
-    g_scale_ctx = ctx;
-    g_w_next_prepared = g_w_call_prepared;
     int rc = ddmp_gemm_nt_f32(A, lda, W, ldw, Y, ldy, n_rows, K, M, bias, pro_scale, pro_shift, slope, workspace,
-                              workspace_bytes, stream);
+                              workspace_bytes, stream, ctx);
     if (rc != DDMP_OK) return rc;
-    return ddmp_bn_stats_f32(Y, ldy, n_rows, M, sums2, stats_ws, stats_ws_bytes, stream);
+    return ddmp_bn_stats_f32(Y, ldy, n_rows, M, sums2, stats_ws, stats_ws_bytes, stream, ctx);
+}
+extern "C" int ddmp_gemm_nt_stats_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y, int64_t ldy,
+                                      int64_t n_rows, int K, int M, const float* bias, const float* pro_scale,
+                                      const float* pro_shift, float slope, double* sums2, void* workspace,
+                                      size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes,
+                                      ddmp_stream stream) {
+    ddmp::CallCtx ctx;
+    return ddmp_gemm_nt_stats_f32(A, lda, W, ldw, Y, ldy, n_rows, K, M, bias, pro_scale, pro_shift, slope, sums2, workspace,
+                                  workspace_bytes, stats_ws, stats_ws_bytes, stream, ctx);
 }

@@ -796,7 +796,7 @@ template <bool BWD>
 int launch_rr_b16(const bf16_t* A, int64_t lda, const bf16_t* A2, int64_t lda2, const float* W, int64_t ldw, int transpose,
                   bf16_t* Y, int64_t ldy, int64_t n_rows, int KD, int MD, const float* bias, const float* ps, const float* psh,
                   const float* pc1, const float* pc0, float slope, void* ws, size_t ws_bytes, void* stats_ws,
-                  size_t stats_ws_bytes, double* sums, hipStream_t st) {
+                  size_t stats_ws_bytes, double* sums, hipStream_t st, const FinalizeArgs& fin = FinalizeArgs()) {
     const int MPW = MD > kRBCols ? 512 : 256;
     const size_t need = (size_t)KD * MPW * sizeof(uint16_t);
     if (!ws || ws_bytes < need || !b16_aligned(ws)) return DDMP_EWORKSPACE;
@@ -822,7 +822,7 @@ int launch_rr_b16(const bf16_t* A, int64_t lda, const bf16_t* A2, int64_t lda2, 
     LAUNCH_TRY();
     if (sums) {
         const size_t pbytes = ((size_t)tiles * 2 * 2 * MPW * sizeof(double) + 255) / 256 * 256;
-        fpartials_reduce(stats, tiles * 2, MPW, MD, (double*)((char*)stats + pbytes), sums, st);
+        fpartials_reduce(stats, tiles * 2, MPW, MD, (double*)((char*)stats + pbytes), sums, st, fin);
         LAUNCH_TRY();
     }
     return DDMP_OK;
@@ -912,17 +912,25 @@ extern "C" int ddmp_gemm_fused_bf16_supported(int cout, int cin, int64_t n_rows)
     return r;
 }
 
-extern "C" int ddmp_gemm_nt_stats_bf16(const uint16_t* A, int64_t lda, const float* W, int64_t ldw, uint16_t* Y, int64_t ldy,
-                                       int64_t n_rows, int K, int M, const float* bias, const float* pro_scale,
-                                       const float* pro_shift, float slope, double* sums2, void* workspace,
-                                       size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes, ddmp_stream stream) {
-    ddmp::FinalizeScope fin_scope(sums2, stream, M);
+int ddmp_gemm_nt_stats_bf16(const uint16_t* A, int64_t lda, const float* W, int64_t ldw, uint16_t* Y, int64_t ldy, int64_t n_rows,
+                            int K, int M, const float* bias, const float* pro_scale, const float* pro_shift, float slope,
+                            double* sums2, void* workspace, size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes,
+                            ddmp_stream stream, ddmp::CallCtx& ctx) {
     ARG_TRY(A && W && Y && sums2 && n_rows > 0 && n_rows < INT32_MAX && K > 0 && M > 0 && ldw >= K);
     ARG_TRY(lda >= K && ldy >= M && lda % 8 == 0 && ldy % 8 == 0 && b16_aligned(A) && b16_aligned(Y));
     ARG_TRY((pro_scale == nullptr) == (pro_shift == nullptr));
     if (!rr_b16_ok(n_rows, K, M, lda, 0)) return DDMP_EINVAL;
     return launch_rr_b16<false>(A, lda, nullptr, 0, W, ldw, 0, Y, ldy, n_rows, K, M, bias, pro_scale, pro_shift, nullptr, nullptr,
-                                slope, workspace, workspace_bytes, stats_ws, stats_ws_bytes, sums2, (hipStream_t)stream);
+                                slope, workspace, workspace_bytes, stats_ws, stats_ws_bytes, sums2, (hipStream_t)stream,
+                                ctx.take_fin(M));
+}
+extern "C" int ddmp_gemm_nt_stats_bf16(const uint16_t* A, int64_t lda, const float* W, int64_t ldw, uint16_t* Y, int64_t ldy,
+                                       int64_t n_rows, int K, int M, const float* bias, const float* pro_scale,
+                                       const float* pro_shift, float slope, double* sums2, void* workspace,
+                                       size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes, ddmp_stream stream) {
+    ddmp::CallCtx ctx;
+    return ddmp_gemm_nt_stats_bf16(A, lda, W, ldw, Y, ldy, n_rows, K, M, bias, pro_scale, pro_shift, slope, sums2, workspace,
+                                   workspace_bytes, stats_ws, stats_ws_bytes, stream, ctx);
 }
 
 // out[n, K] = bf16(dY) . W[M, K] with dY = BatchNorm+LeakyReLU backward of (dZ, Yb) rebuilt on the operand load

@@ -17,7 +17,7 @@
 //         drops NaN -- a NaN operand is not seen here; trainer.check_scales tests the parameter and gradient arenas
 //         for finiteness instead, which a NaN activation or gradient cannot miss)
 // Without caller slots the library measures [0] exactly in a pre-pass over the operand (one more read of it; target
-// 2^15).  A training loop passes persistent slots (ddmp_gemm_next_scales) and rolls [1] into [0] once per iteration
+// 2^15).  A training loop passes persistent slots (DDMP_OPT_SCALES) and rolls [1] into [0] once per iteration
 // (ddmp_gemm_scales_roll): the scale then lags one iteration behind the data, target 2^10 leaves a factor 64 of
 // head-room, growth beyond that is clamped AND flagged.  SELF-HEALING: every GEMM launch that runs on a stale scale is
 // followed by a second launch of the same kernel in `heal` mode.  That launch returns at once while the flag is clear;

@@ -641,11 +641,9 @@ extern "C" size_t ddmp_spmm_bnred_workspace_bytes(int64_t n_rows, int C) {
     return std::max(fused, ddmp_colreduce_workspace_bytes(n_rows, C));
 }
 
-extern "C" int ddmp_spmm_bnred_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, int C,
-                                   const float* Yp, int64_t ldyp, const float* scale, const float* shift,
-                                   const float* mean, const float* rstd, float slope, double* sums2, void* ws,
-                                   size_t ws_bytes, ddmp_stream stream) {
-    ddmp::FinalizeScope fin_scope(sums2, stream, C);
+int ddmp_spmm_bnred_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, int C, const float* Yp,
+                        int64_t ldyp, const float* scale, const float* shift, const float* mean, const float* rstd, float slope,
+                        double* sums2, void* ws, size_t ws_bytes, ddmp_stream stream, ddmp::CallCtx& ctx) {
     ARG_TRY(g && X && Y && Yp && scale && shift && mean && rstd && sums2 && ws && C > 0 && ldx >= C && ldy >= C && ldyp >= C);
     ARG_TRY(X != Y);
     ARG_TRY(!g->valued);                                         // (no fused form reads a valued graph's factors)
@@ -658,7 +656,7 @@ extern "C" int ddmp_spmm_bnred_f32(const ddmp_graph* g, const float* X, int64_t 
         int rc = ddmp_spmm_f32(g, X, ldx, Y, ldy, C, nullptr, nullptr, nullptr, slope, stream);
         if (rc != DDMP_OK) return rc;
         return ddmp_bn_bwd_reduce_f32(Y, ldy, Yp, ldyp, g->n_rows, C, scale, shift, mean, rstd, slope, sums2, ws, ws_bytes,
-                                      stream);
+                                      stream, ctx);
     }
     const int n = (int)g->n_rows;
     const int n_chunks = (int)cdiv(n, kRB);
@@ -673,7 +671,7 @@ extern "C" int ddmp_spmm_bnred_f32(const ddmp_graph* g, const float* X, int64_t 
                                               g->heavy, g->n_heavy);
         if (rc == DDMP_OK) {
             const size_t pb2 = ((size_t)n_chunks * 4 * 2 * (size_t)C * sizeof(float) + 255) / 256 * 256;
-            fpartials_reduce((const float*)ws, n_chunks + g->n_split, C, C, (double*)((char*)ws + pb2), sums2, st);   // (+ the split chunks' second records)
+            fpartials_reduce((const float*)ws, n_chunks + g->n_split, C, C, (double*)((char*)ws + pb2), sums2, st, ctx.take_fin(C));   // (+ the split chunks' second records)
             LAUNCH_TRY();
             return DDMP_OK;
         }
@@ -691,7 +689,7 @@ extern "C" int ddmp_spmm_bnred_f32(const ddmp_graph* g, const float* X, int64_t 
         LAUNCH_TRY();
     }
     const size_t pbytes = ((size_t)n_chunks * 4 * 2 * (size_t)C * sizeof(float) + 255) / 256 * 256;
-    fpartials_reduce((const float*)ws, red_groups, C, C, (double*)((char*)ws + pbytes), sums2, st);
+    fpartials_reduce((const float*)ws, red_groups, C, C, (double*)((char*)ws + pbytes), sums2, st, ctx.take_fin(C));
     LAUNCH_TRY();
     return DDMP_OK;
 }
@@ -700,10 +698,9 @@ extern "C" int ddmp_spmm_bnred_f32(const ddmp_graph* g, const float* X, int64_t 
 // (= ddmp_bn_stats_f32(Y)), from the lean kernel's epilogue around the per-column reference `ref` (spmm_lean.inc, RED = 2).
 extern "C" int ddmp_spmm_stats_supported(int C) { return (C % 32 == 0 && C >= 32 && C <= 1024) ? 1 : 0; }
 
-extern "C" int ddmp_spmm_stats_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, int C,
-                                   const float* bias, const float* pro_scale, const float* pro_shift, float slope,
-                                   const float* ref, double* sums2, void* ws, size_t ws_bytes, ddmp_stream stream) {
-    ddmp::FinalizeScope fin_scope(sums2, stream, C);
+int ddmp_spmm_stats_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, int C, const float* bias,
+                        const float* pro_scale, const float* pro_shift, float slope, const float* ref, double* sums2, void* ws,
+                        size_t ws_bytes, ddmp_stream stream, ddmp::CallCtx& ctx) {
     ARG_TRY(g && X && Y && sums2 && ws && C > 0 && ldx >= C && ldy >= C && X != Y);
     ARG_TRY((pro_scale == nullptr) == (pro_shift == nullptr));
     ARG_TRY(!g->valued);
@@ -716,7 +713,7 @@ extern "C" int ddmp_spmm_stats_f32(const ddmp_graph* g, const float* X, int64_t 
     if (!fused) {
         int rc = ddmp_spmm_f32(g, X, ldx, Y, ldy, C, bias, pro_scale, pro_shift, slope, stream);
         if (rc != DDMP_OK) return rc;
-        return ddmp_bn_stats_f32(Y, ldy, g->n_rows, C, sums2, ws, ws_bytes, stream);
+        return ddmp_bn_stats_f32(Y, ldy, g->n_rows, C, sums2, ws, ws_bytes, stream, ctx);
     }
     BnRed red{nullptr, 0, nullptr, nullptr, ref, nullptr, (float*)ws};
     // LDS-patch kernel where selected (one record per chunk, like the lean gather; its heavy chunks: the lean gather's list)
@@ -733,10 +730,16 @@ extern "C" int ddmp_spmm_stats_f32(const ddmp_graph* g, const float* X, int64_t 
     if (rc != DDMP_OK) return rc;
     const size_t pbytes = ((size_t)lp.n_chunks * 4 * 2 * (size_t)C * sizeof(float) + 255) / 256 * 256;
     // (a split chunk of the LDS-patch kernel has a second record behind the chunks': the records' area is sized for four per chunk)
-    fpartials_reduce((const float*)ws, lp.n_chunks + (patched ? g->n_split : 0), C, C, (double*)((char*)ws + pbytes), sums2, st, ref,
-                     (double)g->n_rows);
+    fpartials_reduce((const float*)ws, lp.n_chunks + (patched ? g->n_split : 0), C, C, (double*)((char*)ws + pbytes), sums2, st,
+                     ctx.take_fin(C), ref, (double)g->n_rows);
     LAUNCH_TRY();
     return DDMP_OK;
+}
+extern "C" int ddmp_spmm_stats_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, int C,
+                                   const float* bias, const float* pro_scale, const float* pro_shift, float slope,
+                                   const float* ref, double* sums2, void* ws, size_t ws_bytes, ddmp_stream stream) {
+    ddmp::CallCtx ctx;
+    return ddmp_spmm_stats_f32(g, X, ldx, Y, ldy, C, bias, pro_scale, pro_shift, slope, ref, sums2, ws, ws_bytes, stream, ctx);
 }
 
 // out = A_hat . dY with dY = BatchNorm+LeakyReLU backward of (dZ, Yb) rebuilt on the gather (see BnBwdGather)

@@ -431,11 +431,9 @@ extern "C" size_t ddmp_spmm_bnred_bf16_workspace_bytes(int64_t n_rows, int C) {
     return (size_t)ddmp::cdiv(n_rows, kRB) * 4 * 2 * (size_t)C * sizeof(float) + 256 + fpartials_mid_bytes(C);
 }
 
-extern "C" int ddmp_spmm_bnred_bf16(const ddmp_graph* g, const uint16_t* X, int64_t ldx, uint16_t* Y, int64_t ldy, int C,
-                                    const uint16_t* Yp, int64_t ldyp, const float* scale, const float* shift,
-                                    const float* mean, const float* rstd, float slope, double* sums2, void* ws,
-                                    size_t ws_bytes, ddmp_stream stream) {
-    ddmp::FinalizeScope fin_scope(sums2, stream, C);
+int ddmp_spmm_bnred_bf16(const ddmp_graph* g, const uint16_t* X, int64_t ldx, uint16_t* Y, int64_t ldy, int C, const uint16_t* Yp,
+                         int64_t ldyp, const float* scale, const float* shift, const float* mean, const float* rstd, float slope,
+                         double* sums2, void* ws, size_t ws_bytes, ddmp_stream stream, ddmp::CallCtx& ctx) {
     ARG_TRY(g && X && Y && Yp && scale && shift && mean && rstd && sums2 && ws && X != Y && shape_ok(X, ldx, Y, ldy, C));
     ARG_TRY(!g->valued);                                         // valued graphs: float32 features only
     ARG_TRY(ldyp >= C && ldyp % 8 == 0 && b16_aligned(Yp) && b16_aligned(ws));
@@ -454,16 +452,16 @@ extern "C" int ddmp_spmm_bnred_bf16(const ddmp_graph* g, const uint16_t* X, int6
         rc = dispatch_b16<false, 1, false>(g, X, ldx, Y, ldy, C, nullptr, nullptr, nullptr, slope, st, red);
     if (rc != DDMP_OK) return rc;
     const size_t pbytes = ((size_t)n_chunks * 4 * 2 * (size_t)C * sizeof(float) + 255) / 256 * 256;
-    fpartials_reduce((const float*)ws, n_chunks + (patched ? g->n_split : 0), C, C, (double*)((char*)ws + pbytes), sums2, st);    // (one record per chunk, both kernels; + the LDS-patch kernel's split chunks)
+    fpartials_reduce((const float*)ws, n_chunks + (patched ? g->n_split : 0), C, C, (double*)((char*)ws + pbytes), sums2, st,
+                     ctx.take_fin(C));                           // (one record per chunk, both kernels; + the LDS-patch kernel's split chunks)
     LAUNCH_TRY();
     return DDMP_OK;
 }
 
-extern "C" int ddmp_spmm_stats_bf16(const ddmp_graph* g, const uint16_t* X, int64_t ldx, uint16_t* Y, int64_t ldy, int C,
-                                    const float* bias, const float* pro_scale, const float* pro_shift, float slope,
-                                    const float* ref, double* sums2, void* ws, size_t ws_bytes, ddmp_stream stream) {
+int ddmp_spmm_stats_bf16(const ddmp_graph* g, const uint16_t* X, int64_t ldx, uint16_t* Y, int64_t ldy, int C, const float* bias,
+                         const float* pro_scale, const float* pro_shift, float slope, const float* ref, double* sums2, void* ws,
+                         size_t ws_bytes, ddmp_stream stream, ddmp::CallCtx& ctx) {
     // = ddmp_spmm_bf16 + ddmp_bn_stats_bf16 of the stored output, the statistics from the gather's epilogue around `ref`
-    ddmp::FinalizeScope fin_scope(sums2, stream, C);
     ARG_TRY(g && X && Y && sums2 && ws && X != Y && shape_ok(X, ldx, Y, ldy, C));
     ARG_TRY(!g->valued);                                         // valued graphs: float32 features only
     ARG_TRY((pro_scale == nullptr) == (pro_shift == nullptr));
@@ -473,7 +471,7 @@ extern "C" int ddmp_spmm_stats_bf16(const ddmp_graph* g, const uint16_t* X, int6
     if (!ref || C % 16 != 0 || C > 1024) {
         int rc = ddmp_spmm_bf16(g, X, ldx, Y, ldy, C, bias, pro_scale, pro_shift, slope, stream);
         if (rc != DDMP_OK) return rc;
-        return ddmp_bn_stats_bf16(Y, ldy, g->n_rows, C, sums2, ws, ws_bytes, stream);
+        return ddmp_bn_stats_bf16(Y, ldy, g->n_rows, C, sums2, ws, ws_bytes, stream, ctx);
     }
     const int n_chunks = (int)cdiv(g->n_rows, kRB);
     BnRedB red{nullptr, 0, nullptr, nullptr, ref, nullptr, (float*)ws};
@@ -489,8 +487,8 @@ extern "C" int ddmp_spmm_stats_bf16(const ddmp_graph* g, const uint16_t* X, int6
                                                        list, g->n_heavy);
     if (rc != DDMP_OK) return rc;
     const size_t pbytes = ((size_t)n_chunks * 4 * 2 * (size_t)C * sizeof(float) + 255) / 256 * 256;
-    fpartials_reduce((const float*)ws, n_chunks + (patched ? g->n_split : 0), C, C, (double*)((char*)ws + pbytes), sums2, st, ref,
-                     (double)g->n_rows);    // (one record per chunk; + the LDS-patch kernel's split chunks)
+    fpartials_reduce((const float*)ws, n_chunks + (patched ? g->n_split : 0), C, C, (double*)((char*)ws + pbytes), sums2, st,
+                     ctx.take_fin(C), ref, (double)g->n_rows);   // (one record per chunk; + the LDS-patch kernel's split chunks)
     LAUNCH_TRY();
     return DDMP_OK;
 }

@@ -135,8 +135,8 @@ def unfused(name: str) -> bool:
 
 
 def next_pending() -> int:
-    """Diagnostic: bit mask of per-call options (1 BatchNorm coefficients, 2 GEMM scale slots, 4 prepared weight planes) still
-    recorded for this host thread -- 0 between calls: an ``_o`` entry point sets its options and clears them around its own call."""
+    """Diagnostic of the C ABI for per-call options "still recorded for this host thread".  Always 0: the options of an ``_o``
+    entry point are arguments of that call and are recorded nowhere."""
     return int(_lib.lib().ddmp_next_pending())
 
 

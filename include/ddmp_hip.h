@@ -38,9 +38,9 @@ extern "C" {
 #define DDMP_ENOMEM (-3)      /* host allocation failed */
 #define DDMP_EWORKSPACE (-4)  /* caller workspace too small */
 
-#define DDMP_ABI_VERSION 3      /* 3 (round 5): per-call options (ddmp_opts, the *_o entry points) replace the armed state;
-                                   2 (round 4): rules for the "armed for the next call" state + ddmp_next_pending / ddmp_next_cancel /
-                                   ddmp_gemm_forget_planes; additions only otherwise (the *_bf16 and dtype-tagged entry points) */
+#define DDMP_ABI_VERSION 3      /* 3: per-call options (ddmp_opts, the *_o entry points);
+                                   2: ddmp_next_pending, ddmp_gemm_forget_planes; additions only otherwise (the *_bf16 and
+                                   dtype-tagged entry points) */
 
 typedef struct ddmp_graph ddmp_graph;
 typedef void* ddmp_stream;    /* hipStream_t */
@@ -240,9 +240,8 @@ int ddmp_bn_bwd_prepare_f32(const double* sums2, double n_total, int C, const fl
                             const float* rstd, float* dgamma, float* dbeta, float* c1, float* c0,
                             ddmp_stream stream);
 /* Tail-fused coefficients (round 3) and the other per-call options are arguments of the *_o entry points at the end of this header
- * (ABI 3); the ABI-2 calls that armed them "for the next call of this host thread" left the ABI in round 6 (they are the hidden
- * implementation of the _o scopes: csrc/ddmp_internal.h).  Diagnostic: the bit mask of options still recorded for this host thread
- * -- BatchNorm coefficients (bit 0), GEMM scale slots (bit 1), prepared weight planes (bit 2); 0 between calls. */
+ * (ABI 3).  ddmp_next_pending is the ABI's diagnostic for options "still recorded for this host thread": options travel with their
+ * own call as arguments and are recorded nowhere, so it returns 0, always. */
 int ddmp_next_pending(void);
 /* dY (gradient w.r.t. the conv output) and its column sums (= gradient of the conv bias; dbias_sums NULL: dY only -- behind
  * a BatchNorm those sums are zero in exact arithmetic) */
@@ -383,9 +382,9 @@ int ddmp_gemm_nt_stats_f32(const float* A, int64_t lda, const float* W, int64_t 
  * ddmp_gemm_rows_workspace_bytes(K[i], M[i]) bytes, 16-byte aligned), in the layout the product over n_rows rows will want:
  * W[i] is [M[i], K[i]] float32 with leading dimension ldw[i]; form[i] 0 = forward (ddmp_gemm_nt*: Y[n,M] = f(A[n,K]) . W^T,
  * has_pro[i] = with a prologue), 1 = dgrad (ddmp_gemm_nn*: Y[n,K] = A[n,M] . W).  scratch: 8 n floats.
- * A GEMM call then passes planes[i] as its `workspace` and is announced by ddmp_gemm_next_prepared() (this host thread, the
- * NEXT ddmp_gemm_* call): it skips its own split if the buffer was prepared for exactly this matrix, shape and route, and
- * splits as before otherwise.  The caller re-prepares whenever the weights change. */
+ * A GEMM call then passes planes[i] as its `workspace` and says so with DDMP_OPT_PREPARED (the *_o entry points below): it
+ * skips its own split if the buffer was prepared for exactly this matrix, shape and route, and splits as before otherwise.
+ * The caller re-prepares whenever the weights change. */
 int ddmp_gemm_prepare_weights(int n, const float* const* W, const int64_t* ldw, const int* M, const int* K, const int* form,
                               const int* has_pro /*nullable*/, void* const* planes, const size_t* planes_bytes,
                               int64_t n_rows, float* scratch, ddmp_stream stream);
@@ -589,11 +588,12 @@ int ddmp_head_bwd(const void* Y, int64_t ldy, int64_t n_rows, int dtype, const f
                   void* workspace, size_t workspace_bytes, ddmp_stream stream);
 
 
-/* ------------------------------------------------------------------ ABI 3: per-call options instead of "armed" state
- * Everything the ddmp_*_next_* calls used to attach to "the next call of this host thread" is an explicit, nullable last
- * argument of the call itself: `name_o(<the arguments of name>, const ddmp_opts* opts)`.  The options apply to THAT call and
- * to nothing else (whatever it returns); opts == NULL is the plain call.  The arming calls above stay for one more round as
- * deprecated wrappers (they fill the same per-thread record the _o forms set and clear around their call).
+/* ------------------------------------------------------------------ ABI 3: per-call options
+ * What a call can be asked for beyond its own arguments is an explicit, nullable last argument of the call itself:
+ * `name_o(<the arguments of name>, const ddmp_opts* opts)`.  The options apply to THAT call and to nothing else (whatever it
+ * returns); opts == NULL is the plain call.  A malformed block is DDMP_EINVAL before any device work; so are BatchNorm
+ * coefficients asked of a call that has no float64 column reduction, or whose reduction is not bn_C columns wide.  A call that
+ * fails writes no coefficients.
  *   DDMP_OPT_BN_FWD   the call's float64 [2C] reduction (sum y, sum y^2) also yields what ddmp_bn_prepare_f32 would write:
  *                     bn_in = {gamma, beta}, bn_out = {scale, shift, mean, rstd, running_mean | NULL, running_var | NULL}
  *   DDMP_OPT_BN_BWD   ... (sum g, sum g yhat) also yields what ddmp_bn_bwd_prepare_f32 would write:

@@ -27,9 +27,9 @@ def test_c_abi_exports_every_declared_symbol():
 
 
 def test_per_call_options_reach_their_own_call_only():
-    """ABI 3: the *_o entry points take what ABI 2 armed "for the next call" as an explicit ddmp_opts argument (the arming calls
-    themselves are gone from the ABI since round 6).  The options apply to that call alone -- whatever it returns -- and a
-    malformed block is an argument error.  No device work involved (every call fails its argument checks)."""
+    """ABI 3: the *_o entry points take their options as an explicit ddmp_opts argument (no call arms anything "for the next
+    call").  The options apply to that call alone -- whatever it returns -- and a malformed block is an argument error.  No
+    device work involved (every call fails its argument checks)."""
     from dual_dmp_amd import _lib, ops
     lib = _lib.lib()
     buf = (ctypes.c_float * 64)()
@@ -47,11 +47,16 @@ def test_per_call_options_reach_their_own_call_only():
     t = T()
     o, keep = ops._mk_opts(ops.BnFwd(100.0, t, t, [t, t, t, t]), (t, None, True), True)
     assert keep[0].flags == ops.OPT_BN_FWD | ops.OPT_SCALES | ops.OPT_PREPARED and keep[0].struct_size == ctypes.sizeof(ops._Opts)
-    # the wrapped call fails its argument checks: the options are gone afterwards
+    # the wrapped call fails its argument checks: nothing of its options is left behind
     assert lib.ddmp_gemm_nt_stats_f32_o(None, 0, None, 0, None, 0, 0, 0, 0, None, None, None, 0.01, None, None, 0, None, 0, None, o) == -1
     assert lib.ddmp_next_pending() == 0
     assert lib.ddmp_gemm_nn_o(None, 0, None, 0, None, 0, 0, 0, 0, 0, None, 0, None, o) == -1
     assert lib.ddmp_next_pending() == 0
+    # BatchNorm coefficients of another width (32) than the call's reduction (64), or asked of a call without a reduction:
+    # argument errors of the options themselves, before the wrapped call looks at anything
+    bn_only, keep_bn = ops._mk_opts(ops.BnFwd(100.0, t, t, [t, t, t, t]))
+    assert lib.ddmp_bn_stats_o(p, 64, 100, 64, 0, p, p, 0, None, bn_only) == -1
+    assert lib.ddmp_gemm_nt_o(None, 0, None, 0, None, 0, 0, 0, 0, 0, None, None, None, 0.01, None, 0, None, bn_only) == -1
     # a block of another size / with unknown flags / with both BatchNorm directions: argument error before the call
     keep[0].struct_size = 8
     assert lib.ddmp_bn_stats_o(None, 0, 0, 32, 0, None, None, 0, None, o) == -1

@@ -732,6 +732,12 @@ def test_tail_fused_coefficients_are_bitwise_those_of_the_prepare_kernels(dev, g
             assert torch.equal(a, b)
     c10 = bwd(True, lambda kw: ops.bn_bwd_reduce(dz, y, bn4, **kw))[3]
     assert ops.next_pending() == 0                            # nothing outlives the call it was passed to
+    # coefficients of another width than the call's reduction: an argument error before any launch, nothing written
+    h = C // 2
+    out4 = torch.full((4, h), 7.0, device=dev)
+    with pytest.raises(ops.DdmpError):
+        ops.bn_stats(y, bn=ops.BnFwd(n, gamma[:h].contiguous(), beta[:h].contiguous(), out4))
+    assert torch.equal(out4, torch.full((4, h), 7.0, device=dev))
     # dY without its (analytically zero) column sums
     dy0, dy1 = torch.empty_like(y), torch.empty_like(y)
     ops.bn_bwd_apply(dz, y, bn4, c10, dy0, torch.empty(2 * C, dtype=torch.float64, device=dev))
