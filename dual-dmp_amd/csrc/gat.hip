@@ -1,0 +1,576 @@
+// Graph attention (GATConv): scores, fused edge-softmax + gather, and the two backward launches.
+//
+//   z_e = leaky_relu(s_src[col e, h] + s_dst[row e, h]),  alpha_e = a_e exp(z_e - max) / sum_row a_e exp(z_e - max),
+//   Y[i,h,:] = sum_{e in row i} alpha_e Hf[col e, h, :]
+//
+// over the COALESCED CSR of a valued graph left at all-ones values: a_e is the multiplicity of the entry, so the a_e exp(..) terms
+// are the softmax over the multiset of edges.  Work layout of sddmm.hip / spmm_lean.inc:
+//   * a workgroup (4 waves) owns a chunk of 64 consecutive rows, blockIdx -> chunk XCD-aware; 8 lanes x float4 per row, 8 rows per
+//     wave step, two steps per chunk;
+//   * a row is walked in HEAD PASSES, so that a lane's head is fixed while it gathers and a float4 never straddles a head.  With
+//     W = C / 4 float4 per head: W in {1, 2, 4} -> W lanes per head and 8 / W heads per pass (the 8 lanes cover one 128-byte slab
+//     of the row, eight / four / two heads inside it); any other W -> the 8 lanes walk one head's W float4, 8 at a time;
+//   * the per-(row, head) reductions (max, denominator, delta, ds_dst, ds_src, the dot products) are strided over the head's lanes
+//     and combined by a fixed xor tree; a row's entries are gathered 8 at a time with the batch compiled per entry count (the
+//     loads of a batch are unconditional and in flight together; a shorter row re-reads its last entry with factor 0);
+//   * a row longer than one batch accumulates through its own output row (same lane, same address, program order): the
+//     1200-entry hub row is exact like any other.
+// No atomics, no LDS, no barrier; every sum has a fixed order: bitwise reproducible.  Every row * stride product is int64.
+// Widths that are not a multiple of 4 (or unaligned operands) take scalar kernels: one thread per row.
+#include "ddmp_common.h"
+
+#include <type_traits>
+
+namespace {
+
+using namespace ddmp;
+
+constexpr int kRB = 64;            // rows per workgroup
+constexpr int kEB = 8;             // entries per batch
+constexpr int kDR = 256;           // rows per partial of the attention-vector gradient
+
+__device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : slope * x; }
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float dot4(float4 a, float4 b, float acc) {
+    return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, fmaf(a.x, b.x, acc))));
+}
+__device__ __forceinline__ void fma4(float4& acc, float s, float4 x) {
+    acc.x = fmaf(s, x.x, acc.x);
+    acc.y = fmaf(s, x.y, acc.y);
+    acc.z = fmaf(s, x.z, acc.z);
+    acc.w = fmaf(s, x.w, acc.w);
+}
+// fixed xor tree over the lw (1, 2, 4, 8; kernel-uniform) lanes of a head
+__device__ __forceinline__ float red_sum(float t, int lw) {
+    if (lw > 1) t += __shfl_xor(t, 1, 64);
+    if (lw > 2) t += __shfl_xor(t, 2, 64);
+    if (lw > 4) t += __shfl_xor(t, 4, 64);
+    return t;
+}
+__device__ __forceinline__ float red_max(float t, int lw) {
+    if (lw > 1) t = fmaxf(t, __shfl_xor(t, 1, 64));
+    if (lw > 2) t = fmaxf(t, __shfl_xor(t, 2, 64));
+    if (lw > 4) t = fmaxf(t, __shfl_xor(t, 4, 64));
+    return t;
+}
+inline int lanes_per_head(int C) {
+    const int W = C / 4;
+    return (W == 1 || W == 2 || W == 4) ? W : 8;
+}
+
+// This workgroup's chunk, the lane's 8-lane row group and its place in a head pass (lw lanes per head, hp heads per pass).
+#define GAT_CHUNK_PROLOGUE                                                                         \
+    const int chunk = (blockIdx.x & (kXcd - 1)) * chunks_per_xcd + (blockIdx.x >> 3);              \
+    if (chunk >= n_chunks) return;                                                                 \
+    const int r0 = chunk * kRB;                                                                    \
+    const int nr = min(kRB, n_rows - r0);                                                          \
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;                                    \
+    const int grp = lane >> 3, sl = lane & 7;                                                      \
+    const int hp = 8 / lw, sub = sl / lw, q0 = sl & (lw - 1);
+
+// ------------------------------------------------------------------------------------------------ scores
+__global__ __launch_bounds__(256) void gat_scores_kernel(const float* __restrict__ Hf, int64_t ldh, int n_rows, int heads, int C,
+                                                         const float* __restrict__ att_src, const float* __restrict__ att_dst,
+                                                         float* __restrict__ s_src, float* __restrict__ s_dst, int lw,
+                                                         int chunks_per_xcd, int n_chunks) {
+    GAT_CHUNK_PROLOGUE
+    const int W = C >> 2;
+#pragma unroll 1
+    for (int qq = 0; qq < 2; ++qq) {
+        const int lr = wave * 8 + grp + qq * 32;
+        if (lr >= nr) continue;
+        const int row = r0 + lr;
+        const float* hrow = Hf + (int64_t)row * ldh;
+#pragma unroll 1
+        for (int hg = 0; hg < heads; hg += hp) {
+            const int h = hg + sub;
+            const bool hv = h < heads;
+            const int hh = hv ? h : heads - 1;
+            float as = 0.f, ad = 0.f;
+            for (int q = q0; q < W; q += lw) {
+                const float4 x = ld4(hrow + hh * C + q * 4);
+                as = dot4(x, ld4(att_src + hh * C + q * 4), as);
+                ad = dot4(x, ld4(att_dst + hh * C + q * 4), ad);
+            }
+            as = red_sum(as, lw);
+            ad = red_sum(ad, lw);
+            if (hv && q0 == 0) {
+                s_src[(int64_t)row * heads + h] = as;
+                s_dst[(int64_t)row * heads + h] = ad;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void gat_scores_scalar_kernel(const float* __restrict__ Hf, int64_t ldh, int n_rows, int heads,
+                                                                int C, const float* __restrict__ att_src,
+                                                                const float* __restrict__ att_dst, float* __restrict__ s_src,
+                                                                float* __restrict__ s_dst) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= n_rows) return;
+    const float* hrow = Hf + (int64_t)row * ldh;
+    for (int h = 0; h < heads; ++h) {
+        float as = 0.f, ad = 0.f;
+        for (int c = 0; c < C; ++c) {
+            const float x = hrow[h * C + c];
+            as = fmaf(x, att_src[h * C + c], as);
+            ad = fmaf(x, att_dst[h * C + c], ad);
+        }
+        s_src[(int64_t)row * heads + h] = as;
+        s_dst[(int64_t)row * heads + h] = ad;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ the gather of one head pass
+// out[row, hh, :] = init(q) + sum_{e in row} f_e X[col e, hh, :],  f_e = fac[(kMirror ? mirror[e] : e), hh].  The lanes of the
+// pass that hold no valid head (hv false) run head hh = heads - 1 again and store nothing.
+template <bool kMirror, class Init>
+__device__ __forceinline__ void gather_pass(const int* __restrict__ col, const int* __restrict__ mirror, const float* fac,
+                                            const float* __restrict__ X, int64_t ldx, float* orow, int rbase, int nn, int heads,
+                                            int C, int hh, bool hv, int q0, int lw, Init init) {
+    const int W = C >> 2;
+    if (nn == 0) {
+        for (int q = q0; q < W; q += lw)
+            if (hv) *reinterpret_cast<float4*>(orow + hh * C + q * 4) = init(q);
+        return;
+    }
+#pragma unroll 1
+    for (int b0 = 0; b0 < nn; b0 += kEB) {
+        // entry slots of this batch: the longest row's count among the wave's rows (wave-uniform, from ballots)
+        int ne_w = 0;
+#pragma unroll
+        for (int k = 0; k < kEB; ++k) ne_w += __any(b0 + k < nn) ? 1 : 0;
+        auto batch = [&](auto ne_tag) {
+            constexpr int NE = decltype(ne_tag)::value;
+            const float* xp[NE];
+            float f[NE];
+#pragma unroll
+            for (int k = 0; k < NE; ++k) {
+                const int e = rbase + min(b0 + k, nn - 1);
+                xp[k] = X + (int64_t)col[e] * ldx + hh * C;
+                const int64_t fe = kMirror ? mirror[e] : e;
+                const float v = fac[fe * heads + hh];
+                f[k] = b0 + k < nn ? v : 0.f;
+            }
+            for (int q = q0; q < W; q += lw) {
+                float* op = orow + hh * C + q * 4;
+                float4 acc = b0 == 0 ? init(q) : ld4(op);
+                float4 x[NE];
+#pragma unroll
+                for (int k = 0; k < NE; ++k) x[k] = ld4(xp[k] + q * 4);
+#pragma unroll
+                for (int k = 0; k < NE; ++k) fma4(acc, f[k], x[k]);
+                if (hv) *reinterpret_cast<float4*>(op) = acc;
+            }
+        };
+        switch (ne_w) {
+            case 1: batch(std::integral_constant<int, 1>()); break;
+            case 2: batch(std::integral_constant<int, 2>()); break;
+            case 3: batch(std::integral_constant<int, 3>()); break;
+            case 4: batch(std::integral_constant<int, 4>()); break;
+            case 5: batch(std::integral_constant<int, 5>()); break;
+            case 6: batch(std::integral_constant<int, 6>()); break;
+            case 7: batch(std::integral_constant<int, 7>()); break;
+            default: batch(std::integral_constant<int, 8>()); break;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ forward
+__global__ __launch_bounds__(256) void gat_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                      const float* __restrict__ mult, const float* __restrict__ Hf, int64_t ldh,
+                                                      const float* __restrict__ s_src, const float* __restrict__ s_dst, float slope,
+                                                      const float* __restrict__ bias, float* alpha, float* Y, int64_t ldy, int n_rows,
+                                                      int heads, int C, int lw, int chunks_per_xcd, int n_chunks) {
+    GAT_CHUNK_PROLOGUE
+#pragma unroll 1
+    for (int qq = 0; qq < 2; ++qq) {
+        const int lr = wave * 8 + grp + qq * 32;
+        if (lr >= nr) continue;
+        const int row = r0 + lr;
+        const int rbase = rowptr[row];
+        const int nn = rowptr[row + 1] - rbase;
+        float* yrow = Y + (int64_t)row * ldy;
+#pragma unroll 1
+        for (int hg = 0; hg < heads; hg += hp) {
+            const int h = hg + sub;
+            const bool hv = h < heads;
+            const int hh = hv ? h : heads - 1;
+            const float sd = s_dst[(int64_t)row * heads + hh];
+            // softmax of the row's entries for head hh: the head's lw lanes take the entries lw apart
+            float m = -INFINITY;
+            for (int e = q0; e < nn; e += lw) m = fmaxf(m, leaky(s_src[(int64_t)col[rbase + e] * heads + hh] + sd, slope));
+            m = red_max(m, lw);
+            float den = 0.f;
+            for (int e = q0; e < nn; e += lw)
+                den += mult[rbase + e] * expf(leaky(s_src[(int64_t)col[rbase + e] * heads + hh] + sd, slope) - m);
+            den = red_sum(den, lw);
+            const float inv = 1.f / den;                          // (nn > 0: den >= the largest entry's multiplicity >= 1)
+            for (int e = q0; e < nn; e += lw) {
+                const float z = leaky(s_src[(int64_t)col[rbase + e] * heads + hh] + sd, slope);
+                if (hv) alpha[(int64_t)(rbase + e) * heads + h] = mult[rbase + e] * expf(z - m) * inv;
+            }
+            // the gather reads the factors its sibling lanes wrote: same wave, same CU's L1 -- a workgroup-scope fence
+            __threadfence_block();
+            gather_pass<false>(col, nullptr, alpha, Hf, ldh, yrow, rbase, nn, heads, C, hh, hv, q0, lw, [&](int q) {
+                return bias ? ld4(bias + hh * C + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            });
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void gat_fwd_scalar_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                             const float* __restrict__ mult, const float* __restrict__ Hf,
+                                                             int64_t ldh, const float* __restrict__ s_src,
+                                                             const float* __restrict__ s_dst, float slope,
+                                                             const float* __restrict__ bias, float* alpha, float* __restrict__ Y,
+                                                             int64_t ldy, int n_rows, int heads, int C) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= n_rows) return;
+    const int e0 = rowptr[row], e1 = rowptr[row + 1];
+    float* yrow = Y + (int64_t)row * ldy;
+    for (int h = 0; h < heads; ++h) {
+        const float sd = s_dst[(int64_t)row * heads + h];
+        float m = -INFINITY;
+        for (int e = e0; e < e1; ++e) m = fmaxf(m, leaky(s_src[(int64_t)col[e] * heads + h] + sd, slope));
+        float den = 0.f;
+        for (int e = e0; e < e1; ++e) den += mult[e] * expf(leaky(s_src[(int64_t)col[e] * heads + h] + sd, slope) - m);
+        const float inv = 1.f / den;
+        for (int e = e0; e < e1; ++e)
+            alpha[(int64_t)e * heads + h] = mult[e] * expf(leaky(s_src[(int64_t)col[e] * heads + h] + sd, slope) - m) * inv;
+        for (int c = 0; c < C; ++c) {
+            float acc = bias ? bias[h * C + c] : 0.f;
+            for (int e = e0; e < e1; ++e) acc = fmaf(alpha[(int64_t)e * heads + h], Hf[(int64_t)col[e] * ldh + h * C + c], acc);
+            yrow[h * C + c] = acc;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ backward, edge side
+__global__ __launch_bounds__(256) void gat_bwd_edge_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                           const float* __restrict__ dOut, int64_t lddo,
+                                                           const float* __restrict__ Hf, int64_t ldh,
+                                                           const float* __restrict__ s_src, const float* __restrict__ s_dst,
+                                                           float slope, const float* __restrict__ alpha, float* ds,
+                                                           float* __restrict__ ds_dst, int n_rows, int heads, int C, int lw,
+                                                           int chunks_per_xcd, int n_chunks) {
+    GAT_CHUNK_PROLOGUE
+    const int W = C >> 2;
+#pragma unroll 1
+    for (int qq = 0; qq < 2; ++qq) {
+        const int lr = wave * 8 + grp + qq * 32;
+        if (lr >= nr) continue;
+        const int row = r0 + lr;
+        const int rbase = rowptr[row];
+        const int nn = rowptr[row + 1] - rbase;
+        const float* grow = dOut + (int64_t)row * lddo;
+#pragma unroll 1
+        for (int hg = 0; hg < heads; hg += hp) {
+            const int h = hg + sub;
+            const bool hv = h < heads;
+            const int hh = hv ? h : heads - 1;
+            // dalpha_e for every entry (parked in ds) and delta = sum_e alpha_e dalpha_e, entries in ascending order
+            float delta = 0.f;
+#pragma unroll 1
+            for (int b0 = 0; b0 < nn; b0 += kEB) {
+                int ne_w = 0;
+#pragma unroll
+                for (int k = 0; k < kEB; ++k) ne_w += __any(b0 + k < nn) ? 1 : 0;
+                auto batch = [&](auto ne_tag) {
+                    constexpr int NE = decltype(ne_tag)::value;
+                    const float* xp[NE];
+                    float acc[NE];
+#pragma unroll
+                    for (int k = 0; k < NE; ++k) {
+                        const int e = rbase + min(b0 + k, nn - 1);
+                        xp[k] = Hf + (int64_t)col[e] * ldh + hh * C;
+                        acc[k] = 0.f;
+                    }
+                    for (int q = q0; q < W; q += lw) {
+                        const float4 y = ld4(grow + hh * C + q * 4);
+                        float4 x[NE];
+#pragma unroll
+                        for (int k = 0; k < NE; ++k) x[k] = ld4(xp[k] + q * 4);
+#pragma unroll
+                        for (int k = 0; k < NE; ++k) acc[k] = dot4(y, x[k], acc[k]);
+                    }
+#pragma unroll
+                    for (int k = 0; k < NE; ++k) {
+                        const float t = red_sum(acc[k], lw);
+                        const bool ok = b0 + k < nn;
+                        const int64_t e = rbase + min(b0 + k, nn - 1);
+                        const float al = alpha[e * heads + hh];
+                        delta = fmaf(ok ? al : 0.f, t, delta);
+                        // lane (entry mod lw) of the head parks it: the lane that takes this entry in the sweep below
+                        if (ok && hv && q0 == (k & (lw - 1))) ds[e * heads + h] = t;
+                    }
+                };
+                switch (ne_w) {
+                    case 1: batch(std::integral_constant<int, 1>()); break;
+                    case 2: batch(std::integral_constant<int, 2>()); break;
+                    case 3: batch(std::integral_constant<int, 3>()); break;
+                    case 4: batch(std::integral_constant<int, 4>()); break;
+                    case 5: batch(std::integral_constant<int, 5>()); break;
+                    case 6: batch(std::integral_constant<int, 6>()); break;
+                    case 7: batch(std::integral_constant<int, 7>()); break;
+                    default: batch(std::integral_constant<int, 8>()); break;
+                }
+            }
+            // ds_e = alpha_e (dalpha_e - delta) leaky'(z_e), and its row sum
+            const float sd = s_dst[(int64_t)row * heads + hh];
+            float part = 0.f;
+            for (int e = q0; hv && e < nn; e += lw) {
+                const int64_t ee = rbase + e;
+                const float z0 = s_src[(int64_t)col[ee] * heads + h] + sd;
+                const float v = alpha[ee * heads + h] * (ds[ee * heads + h] - delta) * (z0 > 0.f ? 1.f : slope);
+                ds[ee * heads + h] = v;
+                part += v;
+            }
+            part = red_sum(part, lw);
+            if (hv && q0 == 0) ds_dst[(int64_t)row * heads + h] = part;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void gat_bwd_edge_scalar_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                                  const float* __restrict__ dOut, int64_t lddo,
+                                                                  const float* __restrict__ Hf, int64_t ldh,
+                                                                  const float* __restrict__ s_src, const float* __restrict__ s_dst,
+                                                                  float slope, const float* __restrict__ alpha, float* ds,
+                                                                  float* __restrict__ ds_dst, int n_rows, int heads, int C) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= n_rows) return;
+    const int e0 = rowptr[row], e1 = rowptr[row + 1];
+    const float* grow = dOut + (int64_t)row * lddo;
+    for (int h = 0; h < heads; ++h) {
+        float delta = 0.f;
+        for (int e = e0; e < e1; ++e) {
+            const float* x = Hf + (int64_t)col[e] * ldh + h * C;
+            float t = 0.f;
+            for (int c = 0; c < C; ++c) t = fmaf(grow[h * C + c], x[c], t);
+            ds[(int64_t)e * heads + h] = t;
+            delta = fmaf(alpha[(int64_t)e * heads + h], t, delta);
+        }
+        const float sd = s_dst[(int64_t)row * heads + h];
+        float part = 0.f;
+        for (int e = e0; e < e1; ++e) {
+            const float z0 = s_src[(int64_t)col[e] * heads + h] + sd;
+            const float v = alpha[(int64_t)e * heads + h] * (ds[(int64_t)e * heads + h] - delta) * (z0 > 0.f ? 1.f : slope);
+            ds[(int64_t)e * heads + h] = v;
+            part += v;
+        }
+        ds_dst[(int64_t)row * heads + h] = part;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ backward, node side
+__global__ __launch_bounds__(256) void gat_bwd_node_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                           const int* __restrict__ mirror, const float* __restrict__ dOut,
+                                                           int64_t lddo, const float* __restrict__ alpha, const float* __restrict__ ds,
+                                                           const float* __restrict__ ds_dst, const float* __restrict__ att_src,
+                                                           const float* __restrict__ att_dst, float* dHf, int64_t lddh,
+                                                           float* __restrict__ ds_src, int n_rows, int heads, int C, int lw,
+                                                           int chunks_per_xcd, int n_chunks) {
+    GAT_CHUNK_PROLOGUE
+#pragma unroll 1
+    for (int qq = 0; qq < 2; ++qq) {
+        const int lr = wave * 8 + grp + qq * 32;
+        if (lr >= nr) continue;
+        const int row = r0 + lr;
+        const int rbase = rowptr[row];
+        const int nn = rowptr[row + 1] - rbase;
+        float* orow = dHf + (int64_t)row * lddh;
+#pragma unroll 1
+        for (int hg = 0; hg < heads; hg += hp) {
+            const int h = hg + sub;
+            const bool hv = h < heads;
+            const int hh = hv ? h : heads - 1;
+            float p = 0.f;
+            for (int e = q0; e < nn; e += lw) p += ds[(int64_t)mirror[rbase + e] * heads + hh];
+            p = red_sum(p, lw);
+            const float dd = ds_dst[(int64_t)row * heads + hh];
+            if (hv && q0 == 0) ds_src[(int64_t)row * heads + h] = p;
+            gather_pass<true>(col, mirror, alpha, dOut, lddo, orow, rbase, nn, heads, C, hh, hv, q0, lw, [&](int q) {
+                const float4 a = ld4(att_src + hh * C + q * 4), b = ld4(att_dst + hh * C + q * 4);
+                return make_float4(fmaf(p, a.x, dd * b.x), fmaf(p, a.y, dd * b.y), fmaf(p, a.z, dd * b.z), fmaf(p, a.w, dd * b.w));
+            });
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void gat_bwd_node_scalar_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                                  const int* __restrict__ mirror, const float* __restrict__ dOut,
+                                                                  int64_t lddo, const float* __restrict__ alpha,
+                                                                  const float* __restrict__ ds, const float* __restrict__ ds_dst,
+                                                                  const float* __restrict__ att_src, const float* __restrict__ att_dst,
+                                                                  float* __restrict__ dHf, int64_t lddh, float* __restrict__ ds_src,
+                                                                  int n_rows, int heads, int C) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= n_rows) return;
+    const int e0 = rowptr[row], e1 = rowptr[row + 1];
+    float* orow = dHf + (int64_t)row * lddh;
+    for (int h = 0; h < heads; ++h) {
+        float p = 0.f;
+        for (int e = e0; e < e1; ++e) p += ds[(int64_t)mirror[e] * heads + h];
+        const float dd = ds_dst[(int64_t)row * heads + h];
+        ds_src[(int64_t)row * heads + h] = p;
+        for (int c = 0; c < C; ++c) {
+            float acc = fmaf(p, att_src[h * C + c], dd * att_dst[h * C + c]);
+            for (int e = e0; e < e1; ++e)
+                acc = fmaf(alpha[(int64_t)mirror[e] * heads + h], dOut[(int64_t)col[e] * lddo + h * C + c], acc);
+            orow[h * C + c] = acc;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ attention-vector gradient
+// stage 1: partial[chunk][0 | 1][col] = sum over the chunk's kDR rows (ascending) of ds_{src | dst}[r, col / C] Hf[r, col]
+__global__ __launch_bounds__(256) void gat_datt_partial_kernel(const float* __restrict__ Hf, int64_t ldh, int64_t n_rows, int heads,
+                                                               int C, const float* __restrict__ ds_src,
+                                                               const float* __restrict__ ds_dst, float* __restrict__ partial) {
+    const int HC = heads * C;
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    if (c >= HC) return;
+    const int h = c / C;
+    const int64_t ra = (int64_t)blockIdx.x * kDR, rb = ra + kDR < n_rows ? ra + kDR : n_rows;
+    float ps = 0.f, pd = 0.f;
+    for (int64_t r = ra; r < rb; ++r) {
+        const float x = Hf[r * ldh + c];
+        ps = fmaf(ds_src[r * heads + h], x, ps);
+        pd = fmaf(ds_dst[r * heads + h], x, pd);
+    }
+    partial[((int64_t)blockIdx.x * 2 + 0) * HC + c] = ps;
+    partial[((int64_t)blockIdx.x * 2 + 1) * HC + c] = pd;
+}
+
+// stage 2: 64 columns per workgroup; four lanes per column take the partials 4 apart (float64), combined in a fixed order
+__global__ __launch_bounds__(256) void gat_datt_final_kernel(const float* __restrict__ partial, int n_chunks, int HC,
+                                                             float* __restrict__ datt_src, float* __restrict__ datt_dst) {
+    __shared__ double sm[2][4][64];
+    const int cl = threadIdx.x & 63, part = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    double a = 0.0, b = 0.0;
+    if (c < HC)
+        for (int ch = part; ch < n_chunks; ch += 4) {
+            a += (double)partial[((int64_t)ch * 2 + 0) * HC + c];
+            b += (double)partial[((int64_t)ch * 2 + 1) * HC + c];
+        }
+    sm[0][part][cl] = a;
+    sm[1][part][cl] = b;
+    __syncthreads();
+    if (part == 0 && c < HC) {
+        datt_src[c] = (float)(((sm[0][0][cl] + sm[0][1][cl]) + sm[0][2][cl]) + sm[0][3][cl]);
+        datt_dst[c] = (float)(((sm[1][0][cl] + sm[1][1][cl]) + sm[1][2][cl]) + sm[1][3][cl]);
+    }
+}
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool gat_graph_ok(const ddmp_graph* g) {
+    return g && (g->valued & DDMP_GV_VALUED) && g->a && g->mirror && g->n_cols == g->n_rows && g->n_rows < (int64_t)INT32_MAX;
+}
+inline bool gat_dims_ok(int heads, int C) { return heads > 0 && C > 0 && (int64_t)heads * C < (1 << 24); }
+
+}  // namespace
+
+extern "C" int ddmp_gat_scores_f32(const float* Hf, int64_t ldh, int64_t n_rows, int heads, int C, const float* att_src,
+                                   const float* att_dst, float* s_src, float* s_dst, ddmp_stream stream) {
+    ARG_TRY(Hf && att_src && att_dst && s_src && s_dst && n_rows >= 0 && n_rows < (int64_t)INT32_MAX && gat_dims_ok(heads, C) &&
+            ldh >= (int64_t)heads * C);
+    if (n_rows == 0) return DDMP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int n = (int)n_rows;
+    if (C % 4 == 0 && ldh % 4 == 0 && al16(Hf) && al16(att_src) && al16(att_dst)) {
+        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
+        hipLaunchKernelGGL(gat_scores_kernel, dim3(cpx * kXcd), dim3(256), 0, st, Hf, ldh, n, heads, C, att_src, att_dst, s_src, s_dst,
+                           lanes_per_head(C), cpx, n_chunks);
+    } else {
+        hipLaunchKernelGGL(gat_scores_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, Hf, ldh, n, heads, C, att_src,
+                           att_dst, s_src, s_dst);
+    }
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
+
+extern "C" int ddmp_gat_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ldh, int heads, int C, const float* s_src,
+                                const float* s_dst, float slope, const float* bias, float* alpha, float* Y, int64_t ldy,
+                                ddmp_stream stream) {
+    ARG_TRY(gat_graph_ok(g) && Hf && s_src && s_dst && alpha && Y && gat_dims_ok(heads, C) && ldh >= (int64_t)heads * C &&
+            ldy >= (int64_t)heads * C && Y != Hf);
+    if (g->n_rows == 0) return DDMP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int n = (int)g->n_rows;
+    if (C % 4 == 0 && ldh % 4 == 0 && ldy % 4 == 0 && al16(Hf) && al16(Y) && (!bias || al16(bias))) {
+        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
+        hipLaunchKernelGGL(gat_fwd_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh, s_src, s_dst, slope,
+                           bias, alpha, Y, ldy, n, heads, C, lanes_per_head(C), cpx, n_chunks);
+    } else {
+        hipLaunchKernelGGL(gat_fwd_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh,
+                           s_src, s_dst, slope, bias, alpha, Y, ldy, n, heads, C);
+    }
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
+
+extern "C" int ddmp_gat_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Hf, int64_t ldh, int heads,
+                                     int C, const float* s_src, const float* s_dst, float slope, const float* alpha, float* ds,
+                                     float* ds_dst, ddmp_stream stream) {
+    ARG_TRY(gat_graph_ok(g) && dOut && Hf && s_src && s_dst && alpha && ds && ds_dst && gat_dims_ok(heads, C) &&
+            lddo >= (int64_t)heads * C && ldh >= (int64_t)heads * C && ds != alpha);
+    if (g->n_rows == 0) return DDMP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int n = (int)g->n_rows;
+    if (C % 4 == 0 && lddo % 4 == 0 && ldh % 4 == 0 && al16(dOut) && al16(Hf)) {
+        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
+        hipLaunchKernelGGL(gat_bwd_edge_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, dOut, lddo, Hf, ldh, s_src,
+                           s_dst, slope, alpha, ds, ds_dst, n, heads, C, lanes_per_head(C), cpx, n_chunks);
+    } else {
+        hipLaunchKernelGGL(gat_bwd_edge_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, dOut, lddo,
+                           Hf, ldh, s_src, s_dst, slope, alpha, ds, ds_dst, n, heads, C);
+    }
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
+
+extern "C" int ddmp_gat_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, int heads, int C, const float* alpha,
+                                     const float* ds, const float* ds_dst, const float* att_src, const float* att_dst, float* dHf,
+                                     int64_t lddh, float* ds_src, ddmp_stream stream) {
+    ARG_TRY(gat_graph_ok(g) && dOut && alpha && ds && ds_dst && att_src && att_dst && dHf && ds_src && gat_dims_ok(heads, C) &&
+            lddo >= (int64_t)heads * C && lddh >= (int64_t)heads * C && dHf != dOut);
+    if (g->n_rows == 0) return DDMP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int n = (int)g->n_rows;
+    if (C % 4 == 0 && lddo % 4 == 0 && lddh % 4 == 0 && al16(dOut) && al16(dHf) && al16(att_src) && al16(att_dst)) {
+        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
+        hipLaunchKernelGGL(gat_bwd_node_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo, alpha,
+                           ds, ds_dst, att_src, att_dst, dHf, lddh, ds_src, n, heads, C, lanes_per_head(C), cpx, n_chunks);
+    } else {
+        hipLaunchKernelGGL(gat_bwd_node_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, g->mirror,
+                           dOut, lddo, alpha, ds, ds_dst, att_src, att_dst, dHf, lddh, ds_src, n, heads, C);
+    }
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
+
+extern "C" size_t ddmp_gat_datt_workspace_bytes(int64_t n_rows, int heads, int C) {
+    if (n_rows <= 0 || heads <= 0 || C <= 0) return 0;
+    return (size_t)cdiv(n_rows, kDR) * 2 * (size_t)heads * (size_t)C * sizeof(float);
+}
+
+extern "C" int ddmp_gat_datt_f32(const float* Hf, int64_t ldh, int64_t n_rows, int heads, int C, const float* ds_src,
+                                 const float* ds_dst, float* datt_src, float* datt_dst, void* workspace, size_t workspace_bytes,
+                                 ddmp_stream stream) {
+    ARG_TRY(Hf && ds_src && ds_dst && datt_src && datt_dst && n_rows > 0 && n_rows < (int64_t)INT32_MAX && gat_dims_ok(heads, C) &&
+            ldh >= (int64_t)heads * C);
+    if (!workspace || workspace_bytes < ddmp_gat_datt_workspace_bytes(n_rows, heads, C)) return DDMP_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int HC = heads * C;
+    const int n_chunks = (int)cdiv(n_rows, kDR);
+    float* partial = static_cast<float*>(workspace);
+    hipLaunchKernelGGL(gat_datt_partial_kernel, dim3(n_chunks, (unsigned)cdiv(HC, 256)), dim3(256), 0, st, Hf, ldh, n_rows, heads, C,
+                       ds_src, ds_dst, partial);
+    LAUNCH_TRY();
+    hipLaunchKernelGGL(gat_datt_final_kernel, dim3((unsigned)cdiv(HC, 64)), dim3(256), 0, st, partial, n_chunks, HC, datt_src,
+                       datt_dst);
+    LAUNCH_TRY();
+    return DDMP_OK;
+}

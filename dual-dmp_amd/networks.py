@@ -16,8 +16,10 @@ Two interchangeable forms, both taking the reference's ``Dataset`` object (field
     ``nn.LeakyReLU``) + two ``nn.Linear`` -- with our drop-in :class:`nn_ops.GCNConv` standing where
     ``torch_geometric.nn.GCNConv`` stands in ``util/networks.py:4``.  ``conv="cheb", K=3`` builds the twelve
     convolutions from :class:`nn_ops.ChebConv` instead (spectral layers of order K; parameters
-    ``convN.lins.k.weight``).  The fused engine, the trainer, the CLI, the partitioned path and bf16
-    features are GCN-only: ``fused=True`` with ``conv="cheb"`` raises.
+    ``convN.lins.k.weight``); ``conv="gat", heads=4`` builds them from :class:`nn_ops.GATConv` (graph attention with
+    ``out_channels = width // heads`` per head, concatenated; parameters ``convN.lin_src.weight``, ``convN.att_src`` ...;
+    every width must be divisible by ``heads``).  The fused engine, the trainer, the CLI, the partitioned path and bf16
+    features are GCN-only: ``fused=True`` with ``conv="cheb"`` or ``conv="gat"`` raises.
 
 The reference's unused ``torch.randn(V,3)*1e-5`` draw (``util/networks.py:50``) is dropped: it only
 advances the RNG.  ``z1``/``z2`` carry ``requires_grad=True`` in the reference but are never
@@ -33,7 +35,7 @@ import torch.nn as nn
 
 from . import ops
 from .engine import ArenaLayout, GcnEngine, NORM_WIDTHS, POS_WIDTHS
-from .nn_ops import ChebConv, GCNConv
+from .nn_ops import ChebConv, GATConv, GCNConv
 
 
 class _EngineFn(torch.autograd.Function):
@@ -258,14 +260,22 @@ class NormalNetFused(_FusedNet):
 class _ModularNet(nn.Module):
     _widths = None
 
-    def __init__(self, device, conv="gcn", K=3):
+    def __init__(self, device, conv="gcn", K=3, heads=1):
         super().__init__()
         self.device = torch.device(device)
         h = self._widths
-        if conv not in ("gcn", "cheb"):
-            raise ValueError("conv must be 'gcn' or 'cheb', got %r" % (conv,))
+        if conv not in ("gcn", "cheb", "gat"):
+            raise ValueError("conv must be 'gcn', 'cheb' or 'gat', got %r" % (conv,))
+        if conv == "gat":
+            bad = [w for w in h[1:13] if not isinstance(heads, int) or heads < 1 or w % heads]
+            if bad:
+                raise ValueError("conv='gat': every layer width must be divisible by heads=%r, %r is not" % (heads, bad[0]))
         for i in range(12):
-            setattr(self, "conv%d" % (i + 1), GCNConv(h[i], h[i + 1]) if conv == "gcn" else ChebConv(h[i], h[i + 1], K))
+            if conv == "gat":
+                layer = GATConv(h[i], h[i + 1] // heads, heads=heads)
+            else:
+                layer = GCNConv(h[i], h[i + 1]) if conv == "gcn" else ChebConv(h[i], h[i + 1], K)
+            setattr(self, "conv%d" % (i + 1), layer)
         self.linear1 = nn.Linear(h[12], h[13])
         self.linear2 = nn.Linear(h[13], h[14])
         for i in range(12):
@@ -325,20 +335,20 @@ class NormalNetModular(_ModularNet):
         return torch.mul(dx, dx_norm)
 
 
-def _make_net(fused_cls, modular_cls, device, fused, conv, K, kw):
-    if conv not in ("gcn", "cheb"):
-        raise ValueError("conv must be 'gcn' or 'cheb', got %r" % (conv,))
+def _make_net(fused_cls, modular_cls, device, fused, conv, K, heads, kw):
+    if conv not in ("gcn", "cheb", "gat"):
+        raise ValueError("conv must be 'gcn', 'cheb' or 'gat', got %r" % (conv,))
     if fused:
         if conv != "gcn":
             raise ValueError("conv=%r needs fused=False: the fused engine (and with it the trainer, the CLI, the partitioned "
                              "path and bf16 features) is GCN-only" % (conv,))
         return fused_cls(device, **kw)
-    return modular_cls(device, conv=conv, K=K)
+    return modular_cls(device, conv=conv, K=K, heads=heads)
 
 
-def PosNet(device, fused=True, conv="gcn", K=3, **kw):
-    return _make_net(PosNetFused, PosNetModular, device, fused, conv, K, kw)
+def PosNet(device, fused=True, conv="gcn", K=3, heads=1, **kw):
+    return _make_net(PosNetFused, PosNetModular, device, fused, conv, K, heads, kw)
 
 
-def NormalNet(device, fused=True, conv="gcn", K=3, **kw):
-    return _make_net(NormalNetFused, NormalNetModular, device, fused, conv, K, kw)
+def NormalNet(device, fused=True, conv="gcn", K=3, heads=1, **kw):
+    return _make_net(NormalNetFused, NormalNetModular, device, fused, conv, K, heads, kw)

@@ -1,4 +1,4 @@
-"""Drop-in ``GCNConv`` and ``ChebConv`` on the HIP kernels.
+"""Drop-in ``GCNConv``, ``ChebConv`` and ``GATConv`` on the HIP kernels.
 
 Same constructor / call signature, parameter names and initialisation as
 ``torch_geometric.nn.GCNConv`` 2.2.0 with the defaults the reference uses
@@ -35,6 +35,27 @@ this could not be checked against it; the pin is the dense float64 restatement `
 * Refused with ``ValueError`` before any gather: non-finite weights, a negative weighted degree, a length other than
   ``edge_index.shape[1]``, a dtype other than float32 / float64 (float64 is rounded to float32 once), a weight tensor that is not
   on the GPU, bf16 features.  ``edge_weight=None`` with default options is the unvalued graph and code path, bit for bit.
+
+``GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True, edge_dim=None,
+fill_value="mean", bias=True)``, ``forward(x, edge_index, edge_attr=None, size=None, return_attention_weights=None)`` restates
+``torch_geometric.nn.GATConv`` 2.2.0 (like ``edge_weight`` above: written from the published source from memory -- PyG cannot be
+installed here, so this could not be checked against it; the pin is the float64 restatement ``tests/gat_ref.py``):
+
+* parameters ``lin_src.weight`` [heads * out, in] Glorot-uniform (``a = sqrt(6 / (in + heads * out))``); ``lin_dst`` IS ``lin_src``
+  (``in_channels`` is an int), so ``state_dict()`` carries both keys and ``parameters()`` yields the weight once; ``att_src`` /
+  ``att_dst`` [1, heads, out] Glorot (``a = sqrt(6 / (heads + out))``); ``bias`` zeros, [heads * out] when ``concat``, else [out].
+* ``Hf = x lin_src.weight^T`` viewed [N, heads, C]; ``s_src[j,h] = sum_c Hf[j,h,c] att_src[h,c]``, ``s_dst`` likewise; with
+  ``add_self_loops`` explicit self loops are removed and every node gets exactly one loop; for an edge j -> i
+  ``z = leaky_relu(s_src[j,h] + s_dst[i,h], negative_slope)``; ``alpha`` = softmax of z over ALL edges with target i, per head
+  (duplicate edges each take part); ``out[i,h,:] = sum alpha Hf[j,h,:]``; ``concat``: [N, heads * C], else the mean over heads;
+  the bias is added last.  A node without incoming entries (``add_self_loops=False`` only) gets a zero aggregate plus bias.
+* one launch for scores, one for edge softmax + gather (``ops.gat_fwd``), two for the backward of the graph part
+  (``ops.gat_bwd_edge`` / ``ops.gat_bwd_node``), a two-stage reduction for the attention vectors; the dense part goes through
+  the GEMMs.  The graph is ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=...)``: the coalesced structure whose
+  per-entry multiplicity weighs the softmax terms -- exact for duplicate edges.  Symmetric edge STRUCTURE only.
+* differentiable w.r.t. x, ``lin_src.weight``, ``att_src``, ``att_dst`` and ``bias``; float32, bitwise reproducible.
+* refused with ``ValueError`` before any launch: ``dropout != 0`` in training mode, ``edge_dim`` / ``edge_attr``, tuple
+  ``in_channels`` or a tuple ``x`` (bipartite), ``size``, ``return_attention_weights``, bf16 features.
 """
 from __future__ import annotations
 
@@ -366,3 +387,123 @@ class ChebConv(nn.Module):
 
     def extra_repr(self):
         return "%d, %d, K=%d, normalization=%s" % (self.in_channels, self.out_channels, self.K, self.normalization)
+
+
+class _GATConvFn(torch.autograd.Function):
+    """Hf = X W^T (GEMM), the scores, then ONE launch for edge softmax + gather (``ops.gat_fwd``).  Saved: the padded x and weight,
+    Hf, the scores and alpha [entries, heads].  Backward: the edge-side launch (ds per entry, ds_dst per node), the node-side launch
+    (dHf completely, ds_src), the attention-vector reduction, then the two GEMMs of the linear map.  ``concat=False``: the mean
+    over heads and its broadcast backward are torch ops around the kernels."""
+
+    @staticmethod
+    def forward(ctx, x, weight, att_src, att_dst, bias, graph, heads, concat, slope):
+        cin, hc = weight.shape[1], weight.shape[0]
+        C = hc // heads
+        xp = _pad_cols(x.detach().to(torch.float32))
+        wp = _pad_cols(weight.detach())
+        asrc = att_src.detach().reshape(heads, C).contiguous()
+        adst = att_dst.detach().reshape(heads, C).contiguous()
+        hf = ops.gemm_nt(xp, wp)
+        s_src, s_dst = ops.gat_scores(hf, asrc, adst, heads)
+        b = None if bias is None else bias.detach().contiguous()
+        y, alpha = ops.gat_fwd(graph, hf, s_src, s_dst, heads, slope, bias=b if concat else None)
+        if not concat:
+            y = y.view(-1, heads, C).mean(1)
+            if b is not None:
+                y = y + b
+        ctx.save_for_backward(xp, wp, hf, s_src, s_dst, alpha, asrc, adst)
+        ctx.graph, ctx.dims, ctx.has_bias = graph, (cin, heads, C, concat, slope), bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        with ops.on_device(dy):
+            return _GATConvFn._backward(ctx, dy)
+
+    @staticmethod
+    def _backward(ctx, dy):
+        xp, wp, hf, s_src, s_dst, alpha, asrc, adst = ctx.saved_tensors
+        graph, (cin, heads, C, concat, slope) = ctx.graph, ctx.dims
+        hc = heads * C
+        dy = dy.contiguous().to(torch.float32)
+        db = None
+        if ctx.has_bias and ctx.needs_input_grad[4]:
+            cout = dy.shape[1]
+            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
+            db = ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+        dout = dy if concat else (dy / heads).unsqueeze(1).expand(-1, heads, C).reshape(-1, hc)
+        ds, ds_dst = ops.gat_bwd_edge(graph, dout, hf, s_src, s_dst, alpha, heads, slope)
+        dhf, ds_src = ops.gat_bwd_node(graph, dout, alpha, ds, ds_dst, asrc, adst, heads)
+        datt_src = datt_dst = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            datt_src, datt_dst = ops.gat_datt(hf, ds_src, ds_dst, heads)
+            datt_src, datt_dst = datt_src.view(1, heads, C), datt_dst.view(1, heads, C)
+        dhp = _pad_cols(dhf)
+        if dhp.shape[1] != hc:             # ragged total width: pad the weight rows to match
+            wrow = torch.zeros((dhp.shape[1], wp.shape[1]), dtype=wp.dtype, device=wp.device)
+            wrow[:hc] = wp
+        else:
+            wrow = wp
+        dw = ops.gemm_tn(dhp, xp)[:hc, :cin] if ctx.needs_input_grad[1] else None
+        dx = ops.gemm_nn(dhp, wrow)[:, :cin] if ctx.needs_input_grad[0] else None
+        return dx, dw, datt_src, datt_dst, db, None, None, None, None
+
+
+class GATConv(nn.Module):
+    def __init__(self, in_channels, out_channels: int, heads: int = 1, concat: bool = True, negative_slope: float = 0.2,
+                 dropout: float = 0.0, add_self_loops: bool = True, edge_dim=None, fill_value="mean", bias: bool = True):
+        super().__init__()
+        if isinstance(in_channels, (tuple, list)):
+            raise ValueError("GATConv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
+        if edge_dim is not None:
+            raise ValueError("GATConv: edge_dim (edge features) is not implemented on the HIP path")
+        if not isinstance(heads, int) or heads < 1:
+            raise ValueError("GATConv: heads must be an integer >= 1, got %r" % (heads,))
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.concat, self.negative_slope, self.dropout = bool(concat), float(negative_slope), float(dropout)
+        self.add_self_loops, self.edge_dim, self.fill_value = bool(add_self_loops), None, fill_value
+        self.lin_src = _Lin(in_channels, heads * out_channels)
+        self.lin_dst = self.lin_src                              # PyG: one Linear under both names when in_channels is an int
+        self.att_src = nn.Parameter(torch.empty(1, heads, out_channels))
+        self.att_dst = nn.Parameter(torch.empty(1, heads, out_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(heads * out_channels if concat else out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        a = math.sqrt(6.0 / (self.in_channels + self.heads * self.out_channels))     # PyG 'glorot': fan of the last two dims
+        b = math.sqrt(6.0 / (self.heads + self.out_channels))
+        with torch.no_grad():
+            self.lin_src.weight.uniform_(-a, a)
+            self.att_src.uniform_(-b, b)
+            self.att_dst.uniform_(-b, b)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def forward(self, x, edge_index, edge_attr=None, size=None, return_attention_weights=None) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
+        if isinstance(x, (tuple, list)):
+            raise ValueError("GATConv: a tuple x (bipartite graphs) is not implemented on the HIP path")
+        if edge_attr is not None:
+            raise ValueError("GATConv: edge_attr is not implemented on the HIP path")
+        if size is not None:
+            raise ValueError("GATConv: size is not implemented on the HIP path")
+        if return_attention_weights is not None:
+            raise ValueError("GATConv: return_attention_weights is not implemented on the HIP path")
+        if self.dropout != 0.0 and self.training:
+            raise ValueError("GATConv: attention dropout in training mode is not implemented on the HIP path (dropout=%g)" % self.dropout)
+        if x.dtype == torch.bfloat16:
+            raise ValueError("GATConv: bf16 features are not supported on the HIP path")
+        if x.dim() != 2 or x.shape[1] != self.in_channels:
+            raise ValueError("GATConv: expected x of shape [N, %d]" % self.in_channels)
+        if not x.is_cuda:
+            raise ops.DdmpError("GATConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=self.add_self_loops)
+            return _GATConvFn.apply(x, self.lin_src.weight, self.att_src, self.att_dst, self.bias, graph, self.heads, self.concat,
+                                    self.negative_slope)
+
+    def extra_repr(self):
+        return "%d, %d, heads=%d" % (self.in_channels, self.out_channels, self.heads)

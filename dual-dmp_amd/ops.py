@@ -427,7 +427,8 @@ def graph_for(edge_index: torch.Tensor, num_nodes: int, norm: str = "gcn", edge_
     A caller that builds a fresh edge_index tensor on every call (as ``data.edge_index.to(device)`` does when
     the dataset lives on the host) gets a correct but rebuilt graph each time -- keep the tensor.
 
-    ``norm``: "gcn" (GCNConv: self loops added) | "sym" (ChebConv: S = D^-1/2 A D^-1/2, no self loops).  A GCNConv and a
+    ``norm``: "gcn" (GCNConv: self loops added) | "sym" (ChebConv: S = D^-1/2 A D^-1/2, no self loops) | "gat" (GATConv: the
+    coalesced structure with multiplicities, ``_gat_graph_for``).  A GCNConv and a
     ChebConv on the same edge_index tensor each get their own graph.  "sym" supports SYMMETRIC edge lists only (both
     directions of every edge present, as every graph of this project is): S is then symmetric, the degree is the in-degree,
     and the same graph serves the backward pass.
@@ -440,6 +441,8 @@ def graph_for(edge_index: torch.Tensor, num_nodes: int, norm: str = "gcn", edge_
 
     One handle serves every weight version on a structure, so its values are those of the LAST version set: an autograd function
     that gathers in its backward records ``values_key`` / ``values_src`` in forward and restores them (``restore_values``)."""
+    if norm == "gat":
+        return _gat_graph_for(edge_index, num_nodes, edge_weight, improved, add_self_loops, normalize)
     if norm not in ("gcn", "sym"):
         raise DdmpError("graph normalisation must be 'gcn' or 'sym', got %r" % (norm,))
     flags = None
@@ -475,6 +478,28 @@ def graph_for(edge_index: torch.Tensor, num_nodes: int, norm: str = "gcn", edge_
                 g._wref = None
                 g.set_values(edge_weight, key=tok, checked=True)
                 g._wref = (weakref.ref(edge_weight), edge_weight._version, tok)
+    return g
+
+
+def _gat_graph_for(edge_index, num_nodes, edge_weight, improved, add_self_loops, normalize) -> Graph:
+    """``graph_for(..., norm="gat")``: the structure GATConv attends over -- a valued graph with flags GV_LOOPS alone (0 for
+    ``add_self_loops=False``: explicit loops stay ordinary entries) that KEEPS its all-ones values: ``a`` is then the multiplicity
+    of each coalesced entry, which the edge softmax weighs its terms by.  Cached on the identity + version of ``edge_index``
+    under a key of its own: a GCNConv on the same tensor never gets this handle, and ``set_values`` never runs on it."""
+    if edge_weight is not None or improved or not normalize:
+        raise ValueError("graph_for(norm='gat') takes add_self_loops only: the attention graph has no edge weights")
+    flags = GV_LOOPS if add_self_loops else 0
+    key = (id(edge_index), "gat", flags)
+    hit = _graph_cache.get(key)
+    if hit is not None:
+        ref, version, n, g = hit
+        if ref() is edge_index and version == edge_index._version and n == int(num_nodes):
+            return g
+    for k in [k for k, v in _graph_cache.items() if v[0]() is None]:
+        del _graph_cache[k]
+    g = Graph.from_edge_index(edge_index, num_nodes, valued=flags)
+    g._wref, g.values_key = None, ("ones",)
+    _graph_cache[key] = (weakref.ref(edge_index), edge_index._version, int(num_nodes), g)
     return g
 
 
@@ -633,6 +658,130 @@ def graph_weight_grad(g: Graph, G, out=None):
     with _timed("graph_weight_grad", (int(round(g.nnz / max(g.n_rows, 1))),), 28.0 * g.nnz + 8.0 * g.nnz_in + 8.0 * g.n_rows):
         check(_lib.lib().ddmp_graph_weight_grad(g.handle, _p(G), _p(out), _stream()), "ddmp_graph_weight_grad")
     return out
+
+
+# ---------------------------------------------------------------------------------------- graph attention (DESIGN.md 4.8)
+def _gat_graph(g: Graph):
+    if not g.valued or g.values_key != ("ones",):
+        raise DdmpError("the attention kernels need the graph of graph_for(edge_index, n, norm='gat'): a valued graph left at its "
+                        "all-ones values (its entries' multiplicities)")
+    return g
+
+
+def _gat_hf(t, heads, name, rows=None):
+    """[n, heads * C] float32 matrix -> (tensor, ld, C)."""
+    t, ld = _mat(_chk(t, torch.float32, name), name)
+    if heads < 1 or t.shape[1] % heads:
+        raise DdmpError("%s: width %d is not heads (%d) x C" % (name, t.shape[1], heads))
+    if rows is not None and t.shape[0] < rows:
+        raise DdmpError("%s has %d rows, the graph has %d" % (name, t.shape[0], rows))
+    return t, ld, t.shape[1] // heads
+
+
+def _gat_arr(t, shape, name):
+    """contiguous float32 array of exactly ``shape``."""
+    _chk(t, torch.float32, name)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise DdmpError("%s must be a contiguous float32 %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    return t
+
+
+def _gat_key(g, heads, C):
+    return (heads, C, int(round(g.nnz / max(g.n_rows, 1))))
+
+
+def gat_scores(hf, att_src, att_dst, heads):
+    """-> (s_src, s_dst) [n, heads]: s[i, h] = sum_c hf[i, h * C + c] * att[h, c] (``ddmp_gat_scores_f32``; att: [heads, C])."""
+    hf, ldh, C = _gat_hf(hf, heads, "hf")
+    n = hf.shape[0]
+    att_src, att_dst = _gat_arr(att_src, (heads, C), "att_src"), _gat_arr(att_dst, (heads, C), "att_dst")
+    s_src, s_dst = (torch.empty((n, heads), dtype=torch.float32, device=hf.device) for _ in range(2))
+    # algorithmic bytes: hf read once, the two score arrays written, the attention vectors
+    with _timed("gat_scores", (heads, C), 4.0 * n * heads * C + 8.0 * n * heads + 8.0 * heads * C, 4.0 * n * heads * C):
+        st = _lib.lib().ddmp_gat_scores_f32(_p(hf), ldh, n, heads, C, _p(att_src), _p(att_dst), _p(s_src), _p(s_dst), _stream())
+    check(st, "ddmp_gat_scores_f32")
+    return s_src, s_dst
+
+
+def gat_fwd(g: Graph, hf, s_src, s_dst, heads, slope, bias=None, out=None):
+    """Edge softmax + gather in one launch (``ddmp_gat_fwd_f32``) -> (y [n, heads * C], alpha [g.nnz, heads]).
+    ``bias``: float32 [heads * C] added in the epilogue, or None."""
+    _gat_graph(g)
+    hf, ldh, C = _gat_hf(hf, heads, "hf", g.n_rows)
+    n = g.n_rows
+    s_src, s_dst = _gat_arr(s_src, (hf.shape[0], heads), "s_src"), _gat_arr(s_dst, (hf.shape[0], heads), "s_dst")
+    if bias is not None:
+        bias = _gat_arr(bias, (heads * C,), "bias")
+    if out is None:
+        out = torch.empty((n, heads * C), dtype=torch.float32, device=hf.device)
+    out, ldy, _ = _gat_hf(out, heads, "out", n)
+    if out.shape[1] != hf.shape[1]:
+        raise DdmpError("gat_fwd: out must be [%d, %d]" % (n, hf.shape[1]))
+    alpha = torch.empty((g.nnz, heads), dtype=torch.float32, device=hf.device)
+    # algorithmic bytes: every feature row read once + written once, alpha written, both scores read, col + multiplicity, rowptr
+    alg = 8.0 * n * heads * C + 4.0 * g.nnz * heads + 8.0 * n * heads + 8.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("gat_fwd", _gat_key(g, heads, C), alg, 2.0 * g.nnz * heads * C, survey=8.0 * n * heads * C + 4.0 * g.nnz + 4.0 * (n + 1)):
+        st = _lib.lib().ddmp_gat_fwd_f32(g.handle, _p(hf), ldh, heads, C, _p(s_src), _p(s_dst), float(slope), _p(bias), _p(alpha),
+                                         _p(out), ldy, _stream())
+    check(st, "ddmp_gat_fwd_f32")
+    return out, alpha
+
+
+def gat_bwd_edge(g: Graph, dout, hf, s_src, s_dst, alpha, heads, slope):
+    """Edge side of the backward (``ddmp_gat_bwd_edge_f32``) -> (ds [g.nnz, heads], ds_dst [n, heads])."""
+    _gat_graph(g)
+    n = g.n_rows
+    dout, lddo, C = _gat_hf(dout, heads, "dout", n)
+    hf, ldh, C2 = _gat_hf(hf, heads, "hf", n)
+    if C2 != C:
+        raise DdmpError("gat_bwd_edge: dout and hf differ in width")
+    s_src, s_dst = _gat_arr(s_src, (hf.shape[0], heads), "s_src"), _gat_arr(s_dst, (hf.shape[0], heads), "s_dst")
+    alpha = _gat_arr(alpha, (g.nnz, heads), "alpha")
+    ds = torch.empty((g.nnz, heads), dtype=torch.float32, device=hf.device)
+    ds_dst = torch.empty((n, heads), dtype=torch.float32, device=hf.device)
+    # algorithmic bytes: dout and hf read once each, alpha read, ds written, the scores read, ds_dst written, col, rowptr
+    alg = 8.0 * n * heads * C + 8.0 * g.nnz * heads + 12.0 * n * heads + 4.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("gat_bwd_edge", _gat_key(g, heads, C), alg, 2.0 * g.nnz * heads * C):
+        st = _lib.lib().ddmp_gat_bwd_edge_f32(g.handle, _p(dout), lddo, _p(hf), ldh, heads, C, _p(s_src), _p(s_dst), float(slope),
+                                              _p(alpha), _p(ds), _p(ds_dst), _stream())
+    check(st, "ddmp_gat_bwd_edge_f32")
+    return ds, ds_dst
+
+
+def gat_bwd_node(g: Graph, dout, alpha, ds, ds_dst, att_src, att_dst, heads):
+    """Node side of the backward (``ddmp_gat_bwd_node_f32``) -> (dhf [n, heads * C] written completely, ds_src [n, heads])."""
+    _gat_graph(g)
+    n = g.n_rows
+    dout, lddo, C = _gat_hf(dout, heads, "dout", n)
+    alpha, ds = _gat_arr(alpha, (g.nnz, heads), "alpha"), _gat_arr(ds, (g.nnz, heads), "ds")
+    ds_dst = _gat_arr(ds_dst, (n, heads), "ds_dst")
+    att_src, att_dst = _gat_arr(att_src, (heads, C), "att_src"), _gat_arr(att_dst, (heads, C), "att_dst")
+    dhf = torch.empty((n, heads * C), dtype=torch.float32, device=dout.device)
+    ds_src = torch.empty((n, heads), dtype=torch.float32, device=dout.device)
+    # algorithmic bytes: dout read once, dhf written, alpha and ds read through the mirror map, col + mirror, ds_dst / ds_src, rowptr
+    alg = 8.0 * n * heads * C + 8.0 * g.nnz * heads + 8.0 * n * heads + 8.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("gat_bwd_node", _gat_key(g, heads, C), alg, 2.0 * g.nnz * heads * C):
+        st = _lib.lib().ddmp_gat_bwd_node_f32(g.handle, _p(dout), lddo, heads, C, _p(alpha), _p(ds), _p(ds_dst), _p(att_src),
+                                              _p(att_dst), _p(dhf), dhf.stride(0), _p(ds_src), _stream())
+    check(st, "ddmp_gat_bwd_node_f32")
+    return dhf, ds_src
+
+
+def gat_datt(hf, ds_src, ds_dst, heads):
+    """-> (datt_src, datt_dst) [heads, C]: datt[h, c] = sum_i ds[i, h] * hf[i, h * C + c] (``ddmp_gat_datt_f32``: two-stage
+    column reduction, per-chunk partials in the workspace, fixed order)."""
+    hf, ldh, C = _gat_hf(hf, heads, "hf")
+    n = hf.shape[0]
+    ds_src, ds_dst = _gat_arr(ds_src, (n, heads), "ds_src"), _gat_arr(ds_dst, (n, heads), "ds_dst")
+    L = _lib.lib()
+    need = L.ddmp_gat_datt_workspace_bytes(n, heads, C)
+    ws = Workspace.get(need, hf.device)
+    datt_src, datt_dst = (torch.empty((heads, C), dtype=torch.float32, device=hf.device) for _ in range(2))
+    with _timed("gat_datt", (heads, C), 4.0 * n * heads * C + 8.0 * n * heads + 2.0 * need, 4.0 * n * heads * C):
+        st = L.ddmp_gat_datt_f32(_p(hf), ldh, n, heads, C, _p(ds_src), _p(ds_dst), _p(datt_src), _p(datt_dst), _p(ws), ws.numel(),
+                                 _stream())
+    check(st, "ddmp_gat_datt_f32")
+    return datt_src, datt_dst
 
 
 def spmm_axpby(g: Graph, x, out=None, z=None, z2=None, a=1.0, b=0.0, c=0.0, d=0.0):

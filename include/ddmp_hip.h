@@ -180,6 +180,40 @@ int ddmp_sddmm_f32(const ddmp_graph* g, const float* dY, int64_t lddy, const flo
  * ddmp_graph_set_values, ddmp_graph_weight_grad and the gathers of ONE valued graph must be ordered on one stream (or by events). */
 int ddmp_graph_weight_grad(const ddmp_graph* g, const float* G, float* dw, ddmp_stream stream);
 
+/* ------------------------------------------------------------------ graph attention (torch_geometric GATConv)
+ * float32.  Hf is the projected feature matrix [n, heads * C] (head-major columns: Hf[i, h * C + c]), any leading dimension.
+ * The graph is a VALUED graph (ddmp_graph_create_valued with DDMP_GV_LOOPS or 0) left at its all-ones values: its a_e is the
+ * multiplicity of the coalesced entry, and a softmax over a multiset of edges equals the softmax with a_e exp(z_e) terms.
+ * Per-entry arrays (alpha, ds) are entry-major [entries, heads]; per-node arrays (s_src, s_dst, ds_src, ds_dst) are contiguous
+ * [n, heads].  No atomics, fixed summation orders: two calls give the same bits.  The vector kernels need C % 4 == 0, leading
+ * dimensions % 4 == 0 and 16-byte aligned matrices; anything else takes scalar kernels.  An unvalued graph is DDMP_EINVAL.
+ *
+ * scores:    s_src[i,h] = sum_c Hf[i,h,c] att_src[h,c], s_dst likewise (att_*: [heads, C] contiguous). */
+int ddmp_gat_scores_f32(const float* Hf, int64_t ldh, int64_t n_rows, int heads, int C, const float* att_src, const float* att_dst,
+                        float* s_src, float* s_dst, ddmp_stream stream);
+/* forward:   z_e = leaky_relu(s_src[col e, h] + s_dst[row e, h], slope), alpha_e = a_e exp(z_e - max_row z) / sum_row a_e exp(..)
+ *            (written to alpha, saved for the backward), Y[i,h,:] = sum_{e in row i} alpha_e Hf[col e, h, :] (+ bias[h * C + c],
+ *            nullable).  One launch.  A row without entries gets the bias alone.  exp arguments are <= 0. */
+int ddmp_gat_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ldh, int heads, int C, const float* s_src, const float* s_dst,
+                     float slope, const float* bias /*nullable*/, float* alpha, float* Y, int64_t ldy, ddmp_stream stream);
+/* backward, edge side:  dalpha_e = dOut[row e, h, :] . Hf[col e, h, :], delta = sum_row alpha_e dalpha_e,
+ *            ds_e = alpha_e (dalpha_e - delta) leaky'(z_e) (z_e recomputed from the scores) -> ds [entries, heads];
+ *            ds_dst[i,h] = sum_{e in row i} ds_e. */
+int ddmp_gat_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Hf, int64_t ldh, int heads, int C,
+                          const float* s_src, const float* s_dst, float slope, const float* alpha, float* ds, float* ds_dst,
+                          ddmp_stream stream);
+/* backward, node side:  ds_src[j,h] = sum_{e' in row j} ds[mirror e', h] and
+ *            dHf[j,h,:] = sum_{e' in row j} alpha[mirror e', h] dOut[col e', h, :] + ds_src[j,h] att_src[h,:] + ds_dst[j,h] att_dst[h,:]
+ *            (the structure is symmetric: row j's own entries enumerate the targets j feeds).  Writes dHf completely. */
+int ddmp_gat_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, int heads, int C, const float* alpha, const float* ds,
+                          const float* ds_dst, const float* att_src, const float* att_dst, float* dHf, int64_t lddh, float* ds_src,
+                          ddmp_stream stream);
+/* attention-vector gradient:  datt_src[h,c] = sum_i ds_src[i,h] Hf[i,h,c], datt_dst likewise with ds_dst; two stages, per-chunk
+ * partials in the caller's workspace. */
+size_t ddmp_gat_datt_workspace_bytes(int64_t n_rows, int heads, int C);
+int ddmp_gat_datt_f32(const float* Hf, int64_t ldh, int64_t n_rows, int heads, int C, const float* ds_src, const float* ds_dst,
+                      float* datt_src, float* datt_dst, void* workspace, size_t workspace_bytes, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ dense steps (MFMA; float32 operands and results, the
  * arithmetic is ddmp_set_gemm_mode's: by default SPLIT-precision 16-bit MFMA products with f32 accumulation -- f32-class
  * accuracy, not bit-exact f32; mode 0 = f32-input MFMA, the strict one)

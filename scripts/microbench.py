@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|all] [--rows N] [--iters K]
+gat (not part of all): the graph-attention launches (ops.gat_scores, gat_fwd, gat_bwd_edge, gat_bwd_node, gat_datt)
+on the vertex graph of a torus with --rows vertices in RCB order, against the valued ops.spmm at the same total width on the same
+graph, alternating in one loop; the figures and the algorithmic byte counts go to --out (profiles/gat_microbench.txt).
 spmm --weighted (instead of the forms above): the gather on a VALUED graph (edge_weight) against the unvalued graph
 of the same mesh, and its transpose, alternating in one loop like cheb.
 sddmm (not part of all): the per-entry gradient ops.sddmm on the valued face and vertex graphs against (a) ops.spmm on the same
@@ -29,6 +32,7 @@ ap.add_argument("--widths", default="512,256,128,64,32")
 ap.add_argument("--rotate", type=int, default=1, help="spmm: cycle through this many (input, output) buffer sets so that narrow "
                 "widths are not served from the 256 MB MALL (a 1M x 32 float tensor is 128 MB)")
 ap.add_argument("--weighted", action="store_true", help="spmm: valued graph against the unvalued graph of the same mesh")
+ap.add_argument("--out", default=None, help="gat: the file the figures are written to (default profiles/gat_microbench.txt)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 n = a.rows
@@ -294,3 +298,54 @@ if (a.what == "spmm" and a.weighted) or a.what == "sddmm":
             G = torch.randn(gv.nnz, device=dev); dw = torch.empty(idx.shape[1], device=dev)
             q = alternate({"wgrad": lambda i: ops.graph_weight_grad(gv, G, out=dw)}, reps, 1)
             print("graph_weight_grad %s N=%d: %s" % (gname, nn_, fmt(q["wgrad"])), flush=True)
+
+
+if a.what == "gat":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    g = ops.graph_for(ei, nn_, norm="gat")
+    reps = max(a.iters, 20)
+    lines = ["graph attention on the vertex graph of torus(%d, %d) in RCB order: N=%d, entries=%d (loops included), float32; "
+             "median of %d launches [min q1 q3 max], one HIP-event pair per launch, forms alternating in one loop, rotating buffer "
+             "sets; bytes = the algorithmic counts of ops.py (MB)" % (nu_, nv_, nn_, g.nnz, reps)]
+    print(lines[0], flush=True)
+    for heads, C in ((4, 128), (8, 32), (1, 64), (8, 4)):
+        hc = heads * C
+        R = 2 if nn_ * hc * 4 >= (1 << 29) else 4
+        Hs, Ds = ([torch.randn(nn_, hc, device=dev) for _ in range(R)] for _ in range(2))
+        att_s, att_d = torch.randn(heads, C, device=dev) * 0.1, torch.randn(heads, C, device=dev) * 0.1
+        Out = torch.empty(nn_, hc, device=dev)
+        st = []
+        for i in range(R):                                       # the saved state of a forward per buffer set
+            s_src, s_dst = ops.gat_scores(Hs[i], att_s, att_d, heads)
+            y, alpha = ops.gat_fwd(g, Hs[i], s_src, s_dst, heads, 0.2)
+            ds, ds_dst = ops.gat_bwd_edge(g, Ds[i], Hs[i], s_src, s_dst, alpha, heads, 0.2)
+            dhf, ds_src = ops.gat_bwd_node(g, Ds[i], alpha, ds, ds_dst, att_s, att_d, heads)
+            st.append((s_src, s_dst, alpha, ds, ds_dst, ds_src))
+            del y, dhf
+        q = alternate({
+            "spmm": lambda i: ops.spmm(g, Hs[i], out=Out),
+            "scores": lambda i: ops.gat_scores(Hs[i], att_s, att_d, heads),
+            "fwd": lambda i: ops.gat_fwd(g, Hs[i], st[i][0], st[i][1], heads, 0.2, out=Out),
+            "bwd_edge": lambda i: ops.gat_bwd_edge(g, Ds[i], Hs[i], st[i][0], st[i][1], st[i][2], heads, 0.2),
+            "bwd_node": lambda i: ops.gat_bwd_node(g, Ds[i], st[i][2], st[i][3], st[i][4], att_s, att_d, heads),
+            "datt": lambda i: ops.gat_datt(Hs[i], st[i][5], st[i][4], heads)}, reps, R)
+        feat, ent, node = 4.0 * nn_ * hc, 4.0 * g.nnz, 4.0 * nn_
+        alg = {"spmm": 2 * feat + ent + 2 * node, "scores": feat + 2 * node * heads,
+               "fwd": 2 * feat + ent * heads + 2 * node * heads + 2 * ent + node,
+               "bwd_edge": 2 * feat + 2 * ent * heads + 3 * node * heads + ent + node,
+               "bwd_node": 2 * feat + 2 * ent * heads + 2 * node * heads + 2 * ent + node, "datt": feat + 2 * node * heads}
+        lines.append("heads=%d C=%d (width %d, %d buffer sets):" % (heads, C, hc, R))
+        for k in ("spmm", "scores", "fwd", "bwd_edge", "bwd_node", "datt"):
+            lines.append("  %-9s %s  %7.0f MB  %.2f TB/s alg  x%.2f of the valued spmm" % (
+                k, fmt(q[k]), alg[k] / 1e6, alg[k] / q[k][2] / 1e6, q[k][2] / q["spmm"][2]))
+        print("\n".join(lines[-7:]), flush=True)
+        del Hs, Ds, Out, st
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gat_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
