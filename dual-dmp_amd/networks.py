@@ -18,8 +18,10 @@ Two interchangeable forms, both taking the reference's ``Dataset`` object (field
     convolutions from :class:`nn_ops.ChebConv` instead (spectral layers of order K; parameters
     ``convN.lins.k.weight``); ``conv="gat", heads=4`` builds them from :class:`nn_ops.GATConv` (graph attention with
     ``out_channels = width // heads`` per head, concatenated; parameters ``convN.lin_src.weight``, ``convN.att_src`` ...;
-    every width must be divisible by ``heads``).  The fused engine, the trainer, the CLI, the partitioned path and bf16
-    features are GCN-only: ``fused=True`` with ``conv="cheb"`` or ``conv="gat"`` raises.
+    every width must be divisible by ``heads``); ``conv="feast", heads=4`` builds them from :class:`nn_ops.FeaStConv`
+    (feature-steered convolution: ``heads`` weight matrices per layer mixed by a translation-invariant softmax, any ``heads``;
+    parameters ``convN.lin.weight``, ``convN.u.weight``, ``convN.c``, ``convN.bias``).  The fused engine, the trainer, the CLI,
+    the partitioned path and bf16 features are GCN-only: ``fused=True`` with any other ``conv`` raises.
 
 The reference's unused ``torch.randn(V,3)*1e-5`` draw (``util/networks.py:50``) is dropped: it only
 advances the RNG.  ``z1``/``z2`` carry ``requires_grad=True`` in the reference but are never
@@ -35,7 +37,7 @@ import torch.nn as nn
 
 from . import ops
 from .engine import ArenaLayout, GcnEngine, NORM_WIDTHS, POS_WIDTHS
-from .nn_ops import ChebConv, GATConv, GCNConv
+from .nn_ops import ChebConv, FeaStConv, GATConv, GCNConv
 
 
 class _EngineFn(torch.autograd.Function):
@@ -257,6 +259,9 @@ class NormalNetFused(_FusedNet):
 
 
 # -------------------------------------------------------------------------------- operator-level form
+_CONVS = ("gcn", "cheb", "gat", "feast")
+
+
 class _ModularNet(nn.Module):
     _widths = None
 
@@ -264,8 +269,8 @@ class _ModularNet(nn.Module):
         super().__init__()
         self.device = torch.device(device)
         h = self._widths
-        if conv not in ("gcn", "cheb", "gat"):
-            raise ValueError("conv must be 'gcn', 'cheb' or 'gat', got %r" % (conv,))
+        if conv not in _CONVS:
+            raise ValueError("conv must be 'gcn', 'cheb', 'gat' or 'feast', got %r" % (conv,))
         if conv == "gat":
             bad = [w for w in h[1:13] if not isinstance(heads, int) or heads < 1 or w % heads]
             if bad:
@@ -273,6 +278,8 @@ class _ModularNet(nn.Module):
         for i in range(12):
             if conv == "gat":
                 layer = GATConv(h[i], h[i + 1] // heads, heads=heads)
+            elif conv == "feast":
+                layer = FeaStConv(h[i], h[i + 1], heads=heads)
             else:
                 layer = GCNConv(h[i], h[i + 1]) if conv == "gcn" else ChebConv(h[i], h[i + 1], K)
             setattr(self, "conv%d" % (i + 1), layer)
@@ -336,8 +343,8 @@ class NormalNetModular(_ModularNet):
 
 
 def _make_net(fused_cls, modular_cls, device, fused, conv, K, heads, kw):
-    if conv not in ("gcn", "cheb", "gat"):
-        raise ValueError("conv must be 'gcn', 'cheb' or 'gat', got %r" % (conv,))
+    if conv not in _CONVS:
+        raise ValueError("conv must be 'gcn', 'cheb', 'gat' or 'feast', got %r" % (conv,))
     if fused:
         if conv != "gcn":
             raise ValueError("conv=%r needs fused=False: the fused engine (and with it the trainer, the CLI, the partitioned "

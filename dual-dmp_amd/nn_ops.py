@@ -1,4 +1,4 @@
-"""Drop-in ``GCNConv``, ``ChebConv`` and ``GATConv`` on the HIP kernels.
+"""Drop-in ``GCNConv``, ``ChebConv``, ``GATConv`` and ``FeaStConv`` on the HIP kernels.
 
 Same constructor / call signature, parameter names and initialisation as
 ``torch_geometric.nn.GCNConv`` 2.2.0 with the defaults the reference uses
@@ -56,6 +56,28 @@ installed here, so this could not be checked against it; the pin is the float64 
 * differentiable w.r.t. x, ``lin_src.weight``, ``att_src``, ``att_dst`` and ``bias``; float32, bitwise reproducible.
 * refused with ``ValueError`` before any launch: ``dropout != 0`` in training mode, ``edge_dim`` / ``edge_attr``, tuple
   ``in_channels`` or a tuple ``x`` (bipartite), ``size``, ``return_attention_weights``, bf16 features.
+
+``FeaStConv(in_channels, out_channels, heads=1, add_self_loops=True, bias=True)``, ``forward(x, edge_index)`` restates
+``torch_geometric.nn.FeaStConv`` 2.2.0 (Verma et al., FeaStNet, CVPR 2018; like GATConv above: written from the published source
+from memory -- PyG cannot be installed here, so this could not be checked against it; the pin is the float64 restatement
+``tests/feast_ref.py``):
+
+* parameters ``lin.weight`` [heads * out, in] and ``u.weight`` [heads, in], both uniform(-1/sqrt(in), 1/sqrt(in)) and without
+  bias; ``c`` [heads] and ``bias`` [out] normal(0, 0.1).  The initialisations are from memory too; the arithmetic is what the
+  tests pin.
+* ``Hf = x lin.weight^T`` viewed [N, heads, out], ``P = x u.weight^T`` [N, heads]; with ``add_self_loops`` explicit self loops are
+  removed and every node gets exactly one loop; for an edge j -> i ``q[h]`` = softmax over the HEADS of ``P[j,h] - P[i,h] + c[h]``
+  (translation invariant in x); ``out[i,:] = (1 / deg_i) sum_{j -> i} sum_h q[h] Hf[j,h,:] + bias`` with ``deg_i`` the number of
+  edges with target i (duplicates each count, the added loop counts).  A node without incoming edges (``add_self_loops=False``
+  only) gets the bias.  With ``heads=1`` this is the plain mean of ``x lin.weight^T`` over the neighbourhood.
+* one GEMM against the packed ``[lin.weight; u.weight]`` for ``[Hf | P]``, one launch for head softmax + gather
+  (``ops.feast_fwd``), two for the backward of the graph part (``ops.feast_bwd_edge`` / ``ops.feast_bwd_node``), a two-stage
+  reduction for ``c`` (``ops.feast_dc``), one wgrad GEMM for ``[dW; dU]`` and one dgrad GEMM for ``dx``.  No [E, heads * out]
+  tensor exists at any point.  The graph is GATConv's: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=...)``, same
+  handle and cache key.  Symmetric edge STRUCTURE only.
+* differentiable w.r.t. x, ``lin.weight``, ``u.weight``, ``c`` and ``bias``; float32, bitwise reproducible.
+* refused with ``ValueError`` before any launch: tuple ``in_channels`` or a tuple ``x`` (bipartite), an ``aggr`` other than
+  ``"mean"``, bf16 features, ``heads < 1``, an ``x`` that is not [N, in].
 """
 from __future__ import annotations
 
@@ -504,6 +526,110 @@ class GATConv(nn.Module):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=self.add_self_loops)
             return _GATConvFn.apply(x, self.lin_src.weight, self.att_src, self.att_dst, self.bias, graph, self.heads, self.concat,
                                     self.negative_slope)
+
+    def extra_repr(self):
+        return "%d, %d, heads=%d" % (self.in_channels, self.out_channels, self.heads)
+
+
+class _FeaStConvFn(torch.autograd.Function):
+    """ONE GEMM against the packed weight [lin.weight; u.weight] (rows padded to a multiple of 4) gives the row buffer [Hf | P],
+    then ONE launch for head softmax + gather (``ops.feast_fwd``).  Saved: the padded x, the packed weight, the [Hf | P] buffer and
+    beta [entries, heads].  Backward: the edge-side launch (dz per entry, its row sums rs), the node-side launch that writes
+    [dHf | dP] into one row buffer, the offset reduction dc = colsum(rs), then ONE wgrad GEMM ([dW; dU]) and ONE dgrad GEMM (dx)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, u, c, bias, graph, heads):
+        cin, hc = weight.shape[1], weight.shape[0]
+        wt = hc + heads
+        wtp = (wt + 3) // 4 * 4
+        xp = _pad_cols(x.detach().to(torch.float32))
+        wp = torch.zeros((wtp, xp.shape[1]), dtype=torch.float32, device=x.device)
+        wp[:hc, :cin] = weight.detach()
+        wp[hc:wt, :cin] = u.detach()
+        buf = ops.gemm_nt(xp, wp)                                # [N, wtp]: Hf | P | zero padding
+        b = None if bias is None else bias.detach().contiguous()
+        y, beta = ops.feast_fwd(graph, buf[:, :hc], buf[:, hc:wt], c.detach().contiguous(), heads, bias=b)
+        ctx.save_for_backward(xp, wp, buf, beta)
+        ctx.graph, ctx.dims, ctx.has_bias = graph, (cin, heads, hc), bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        with ops.on_device(dy):
+            return _FeaStConvFn._backward(ctx, dy)
+
+    @staticmethod
+    def _backward(ctx, dy):
+        xp, wp, buf, beta = ctx.saved_tensors
+        graph, (cin, heads, hc) = ctx.graph, ctx.dims
+        wt, wtp = hc + heads, wp.shape[0]
+        dy = dy.contiguous().to(torch.float32)
+        db = None
+        if ctx.has_bias and ctx.needs_input_grad[4]:
+            cout = dy.shape[1]
+            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
+            db = ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+        dz, rs = ops.feast_bwd_edge(graph, dy, buf[:, :hc], beta, heads)
+        g = torch.empty((dy.shape[0], wtp), dtype=torch.float32, device=dy.device)
+        if wtp != wt:
+            g[:, wt:] = 0
+        ops.feast_bwd_node(graph, dy, beta, dz, rs, heads, out=g)          # g = [dHf | dP | 0]
+        dc = ops.feast_dc(rs, heads) if ctx.needs_input_grad[3] else None
+        dw = du = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dwp = ops.gemm_tn(g, xp)                             # [dW; dU]
+            dw, du = dwp[:hc, :cin], dwp[hc:wt, :cin]
+        dx = ops.gemm_nn(g, wp)[:, :cin] if ctx.needs_input_grad[0] else None
+        return dx, dw, du, dc, db, None, None
+
+
+class FeaStConv(nn.Module):
+    """``torch_geometric.nn.FeaStConv`` 2.2.0 on the HIP kernels (module docstring)."""
+
+    def __init__(self, in_channels, out_channels: int, heads: int = 1, add_self_loops: bool = True, bias: bool = True, **kwargs):
+        super().__init__()
+        if isinstance(in_channels, (tuple, list)):
+            raise ValueError("FeaStConv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
+        aggr = kwargs.pop("aggr", "mean")
+        if aggr != "mean":
+            raise ValueError("FeaStConv: only aggr='mean' is implemented on the HIP path, got %r" % (aggr,))
+        if kwargs:
+            raise TypeError("FeaStConv: unexpected keyword arguments %s" % sorted(kwargs))
+        if not isinstance(heads, int) or isinstance(heads, bool) or heads < 1:
+            raise ValueError("FeaStConv: heads must be an integer >= 1, got %r" % (heads,))
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.add_self_loops = bool(add_self_loops)
+        self.lin = _Lin(in_channels, heads * out_channels)
+        self.u = _Lin(in_channels, heads)
+        self.c = nn.Parameter(torch.empty(heads))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        a = 1.0 / math.sqrt(self.in_channels)                    # (from memory of the published source, like the arithmetic)
+        with torch.no_grad():
+            self.lin.weight.uniform_(-a, a)
+            self.u.weight.uniform_(-a, a)
+            self.c.normal_(0.0, 0.1)
+            if self.bias is not None:
+                self.bias.normal_(0.0, 0.1)
+
+    def forward(self, x, edge_index) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
+        if isinstance(x, (tuple, list)):
+            raise ValueError("FeaStConv: a tuple x (bipartite graphs) is not implemented on the HIP path")
+        if x.dtype == torch.bfloat16:
+            raise ValueError("FeaStConv: bf16 features are not supported on the HIP path")
+        if x.dim() != 2 or x.shape[1] != self.in_channels:
+            raise ValueError("FeaStConv: expected x of shape [N, %d]" % self.in_channels)
+        if not x.is_cuda:
+            raise ops.DdmpError("FeaStConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=self.add_self_loops)
+            return _FeaStConvFn.apply(x, self.lin.weight, self.u.weight, self.c, self.bias, graph, self.heads)
 
     def extra_repr(self):
         return "%d, %d, heads=%d" % (self.in_channels, self.out_channels, self.heads)

@@ -784,6 +784,110 @@ def gat_datt(hf, ds_src, ds_dst, heads):
     return datt_src, datt_dst
 
 
+# ---------------------------------------------------------------------------------------- feature-steered convolution (DESIGN.md 4.9)
+def _feast_p(t, heads, name, rows):
+    """[n, heads] float32 matrix (a column block of a wider row buffer is fine) -> (tensor, ld)."""
+    t, ld = _mat(_chk(t, torch.float32, name), name)
+    if t.shape[1] != heads or t.shape[0] < rows:
+        raise DdmpError("%s must be [>= %d, %d], got %s" % (name, rows, heads, tuple(t.shape)))
+    return t, ld
+
+
+def feast_fwd(g: Graph, hf, p, c, heads, bias=None, out=None):
+    """Head softmax + gather in one launch (``ddmp_feast_fwd_f32``) -> (y [n, C], beta [g.nnz, heads]).  ``hf``: [n, heads * C],
+    ``p``: [n, heads] (both may be column blocks of one row buffer), ``c``: [heads], ``bias``: float32 [C] or None."""
+    _gat_graph(g)
+    n = g.n_rows
+    hf, ldh, C = _gat_hf(hf, heads, "hf", n)
+    p, ldp = _feast_p(p, heads, "p", n)
+    c = _gat_arr(c, (heads,), "c")
+    if bias is not None:
+        bias = _gat_arr(bias, (C,), "bias")
+    if out is None:
+        out = torch.empty((n, C), dtype=torch.float32, device=hf.device)
+    out, ldy = _mat(_chk(out, torch.float32, "out"), "out")
+    if out.shape[0] < n or out.shape[1] != C:
+        raise DdmpError("feast_fwd: out must be [%d, %d]" % (n, C))
+    beta = torch.empty((g.nnz, heads), dtype=torch.float32, device=hf.device)
+    # algorithmic bytes: every gathered row (heads * C wide) read once, the output row (C wide) written once, beta written, p read
+    # once, col + multiplicity, rowptr
+    alg = 4.0 * n * (heads + 1) * C + 4.0 * g.nnz * heads + 4.0 * n * heads + 8.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("feast_fwd", _gat_key(g, heads, C), alg, 2.0 * g.nnz * heads * C,
+                survey=4.0 * n * (heads + 1) * C + 4.0 * g.nnz + 4.0 * (n + 1)):
+        st = _lib.lib().ddmp_feast_fwd_f32(g.handle, _p(hf), ldh, _p(p), ldp, heads, C, _p(c), _p(bias), _p(beta), _p(out), ldy,
+                                           _stream())
+    check(st, "ddmp_feast_fwd_f32")
+    return out, beta
+
+
+def feast_bwd_edge(g: Graph, dout, hf, beta, heads):
+    """Edge side of the backward (``ddmp_feast_bwd_edge_f32``) -> (dz [g.nnz, heads], rs [n, heads]).  ``dout``: [n, C]."""
+    _gat_graph(g)
+    n = g.n_rows
+    hf, ldh, C = _gat_hf(hf, heads, "hf", n)
+    dout, lddo = _mat(_chk(dout, torch.float32, "dout"), "dout")
+    if dout.shape[0] < n or dout.shape[1] != C:
+        raise DdmpError("feast_bwd_edge: dout must be [>= %d, %d], got %s" % (n, C, tuple(dout.shape)))
+    beta = _gat_arr(beta, (g.nnz, heads), "beta")
+    dz = torch.empty((g.nnz, heads), dtype=torch.float32, device=hf.device)
+    rs = torch.empty((n, heads), dtype=torch.float32, device=hf.device)
+    # algorithmic bytes: hf and dout read once each, beta read, dz written, rs written, col, rowptr
+    alg = 4.0 * n * (heads + 1) * C + 8.0 * g.nnz * heads + 4.0 * n * heads + 4.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("feast_bwd_edge", _gat_key(g, heads, C), alg, 2.0 * g.nnz * heads * C):
+        st = _lib.lib().ddmp_feast_bwd_edge_f32(g.handle, _p(dout), lddo, _p(hf), ldh, heads, C, _p(beta), _p(dz), _p(rs), _stream())
+    check(st, "ddmp_feast_bwd_edge_f32")
+    return dz, rs
+
+
+def feast_bwd_node(g: Graph, dout, beta, dz, rs, heads, out=None):
+    """Node side of the backward (``ddmp_feast_bwd_node_f32``) -> (dhf [n, heads * C] written completely, dp [n, heads]).
+    ``out``: a float32 [n, >= heads * C + heads] row buffer that receives [dhf | dp] in its leading columns (the two results are
+    then views of it); None: two tensors of their own."""
+    _gat_graph(g)
+    n = g.n_rows
+    dout, lddo = _mat(_chk(dout, torch.float32, "dout"), "dout")
+    C = dout.shape[1]
+    if dout.shape[0] < n or C < 1:
+        raise DdmpError("feast_bwd_node: dout must be [>= %d, C], got %s" % (n, tuple(dout.shape)))
+    beta, dz = _gat_arr(beta, (g.nnz, heads), "beta"), _gat_arr(dz, (g.nnz, heads), "dz")
+    rs = _gat_arr(rs, (n, heads), "rs")
+    hc = heads * C
+    if out is None:
+        dhf = torch.empty((n, hc), dtype=torch.float32, device=dout.device)
+        dp = torch.empty((n, heads), dtype=torch.float32, device=dout.device)
+    else:
+        out, _ = _mat(_chk(out, torch.float32, "out"), "out")
+        if out.shape[0] != n or out.shape[1] < hc + heads:
+            raise DdmpError("feast_bwd_node: out must be [%d, >= %d], got %s" % (n, hc + heads, tuple(out.shape)))
+        dhf, dp = out[:, :hc], out[:, hc:hc + heads]
+    (dhf, lddh), (dp, lddp) = _mat(dhf, "dhf"), _mat(dp, "dp")
+    # algorithmic bytes: dout read once, dhf written, beta and dz read through the mirror map, col + mirror, rs read, dp written, rowptr
+    alg = 4.0 * n * (heads + 1) * C + 8.0 * g.nnz * heads + 8.0 * n * heads + 8.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("feast_bwd_node", _gat_key(g, heads, C), alg, 2.0 * g.nnz * heads * C):
+        st = _lib.lib().ddmp_feast_bwd_node_f32(g.handle, _p(dout), lddo, heads, C, _p(beta), _p(dz), _p(rs), _p(dhf), lddh, _p(dp),
+                                                lddp, _stream())
+    check(st, "ddmp_feast_bwd_node_f32")
+    return dhf, dp
+
+
+def feast_dc(rs, heads):
+    """-> dc [heads]: dc[h] = sum_i rs[i, h] (``ddmp_feast_dc_f32``: two-stage column reduction, per-chunk partials in the
+    workspace, fixed order).  ``colsum`` takes power-of-two widths from 8 on a 4-aligned leading dimension; the head counts in use
+    (1, 2, 3, 4, 8) almost never qualify, so every head count takes this one path."""
+    _chk(rs, torch.float32, "rs")
+    if rs.dim() != 2 or rs.shape[1] != heads or not rs.is_contiguous() or rs.shape[0] < 1:
+        raise DdmpError("rs must be a contiguous float32 [n >= 1, %d], got %s" % (heads, tuple(rs.shape)))
+    n = rs.shape[0]
+    L = _lib.lib()
+    need = L.ddmp_feast_dc_workspace_bytes(n, heads)
+    ws = Workspace.get(need, rs.device)
+    dc = torch.empty(heads, dtype=torch.float32, device=rs.device)
+    with _timed("feast_dc", (heads,), 4.0 * n * heads + 2.0 * need, 1.0 * n * heads):
+        st = L.ddmp_feast_dc_f32(_p(rs), n, heads, _p(dc), _p(ws), ws.numel(), _stream())
+    check(st, "ddmp_feast_dc_f32")
+    return dc
+
+
 def spmm_axpby(g: Graph, x, out=None, z=None, z2=None, a=1.0, b=0.0, c=0.0, d=0.0):
     """out[i] = a * (dinv_i * sum_j dinv_j x[j]) + b * x[i] + c * z[i] + d * z2[i], float32 (ddmp_spmm_axpby_f32): one step of a
     three-term recurrence per launch.  ``z`` / ``z2`` optional (their coefficient is then ignored); ``out`` may be ``z`` or ``z2``,

@@ -214,6 +214,37 @@ size_t ddmp_gat_datt_workspace_bytes(int64_t n_rows, int heads, int C);
 int ddmp_gat_datt_f32(const float* Hf, int64_t ldh, int64_t n_rows, int heads, int C, const float* ds_src, const float* ds_dst,
                       float* datt_src, float* datt_dst, void* workspace, size_t workspace_bytes, ddmp_stream stream);
 
+/* ------------------------------------------------------------------ feature-steered convolution (torch_geometric FeaStConv;
+ * DESIGN.md 4.9).  float32.  Hf is the projected feature matrix [n, heads * C] (head-major columns), P = X u^T the steering
+ * projection [n, heads], each with its own pointer and leading dimension (they may be column blocks of one row buffer); c is
+ * [heads].  The graph is the attention graph above: a VALUED graph left at its all-ones values, a_e = the entry's multiplicity.
+ * Per-entry arrays (beta, dz) are entry-major [entries, heads]; rs is contiguous [n, heads].  No atomics, fixed summation orders:
+ * two calls give the same bits.  The vector kernels need C % 4 == 0, leading dimensions of the [.., C]-wide matrices % 4 == 0 and
+ * 16-byte aligned matrices; anything else takes scalar kernels.  heads <= 256.  An unvalued graph is DDMP_EINVAL.
+ *
+ * forward:   q_e[h] = softmax over the HEADS h of (P[col e, h] - P[row e, h] + c[h]) (exp arguments <= 0),
+ *            beta_e[h] = a_e q_e[h] / deg_i with deg_i = sum_{e in row i} a_e (written to beta, saved for the backward;
+ *            sum_h beta_e[h] = a_e / deg_i =: m_e, so q_e = beta_e / m_e needs no degree table),
+ *            Y[i,:] = sum_{e in row i} sum_h beta_e[h] Hf[col e, h, :] (+ bias[C], nullable).  Y is [n, C].  One launch.  A row
+ *            without entries gets the bias alone. */
+int ddmp_feast_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ldh, const float* P, int64_t ldp, int heads, int C,
+                       const float* c, const float* bias /*nullable*/, float* beta, float* Y, int64_t ldy, ddmp_stream stream);
+/* backward, edge side:  g_e[h] = dOut[row e, :] . Hf[col e, h, :], delta_e = sum_h beta_e[h] g_e[h] / m_e,
+ *            dz_e[h] = beta_e[h] (g_e[h] - delta_e) -> dz [entries, heads]; rs[i,h] = sum_{e in row i} dz_e[h].  dOut is [n, C].
+ *            With heads == 1, dz and rs are exactly zero. */
+int ddmp_feast_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Hf, int64_t ldh, int heads, int C,
+                            const float* beta, float* dz, float* rs, ddmp_stream stream);
+/* backward, node side:  dHf[j,h,:] = sum_{e' in row j} beta[mirror e', h] dOut[col e', :]  (written completely) and
+ *            dP[j,h] = sum_{e' in row j} dz[mirror e', h] - rs[j,h]  (the structure is symmetric: row j's own entries enumerate
+ *            the targets j feeds).  dHf [n, heads * C] and dP [n, heads] each have their own leading dimension. */
+int ddmp_feast_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, int heads, int C, const float* beta,
+                            const float* dz, const float* rs, float* dHf, int64_t lddh, float* dP, int64_t lddp,
+                            ddmp_stream stream);
+/* offset gradient:  dc[h] = sum_i rs[i,h]; two stages, per-chunk partials in the caller's workspace, fixed order. */
+size_t ddmp_feast_dc_workspace_bytes(int64_t n_rows, int heads);
+int ddmp_feast_dc_f32(const float* rs, int64_t n_rows, int heads, float* dc, void* workspace, size_t workspace_bytes,
+                      ddmp_stream stream);
+
 /* ------------------------------------------------------------------ dense steps (MFMA; float32 operands and results, the
  * arithmetic is ddmp_set_gemm_mode's: by default SPLIT-precision 16-bit MFMA products with f32 accumulation -- f32-class
  * accuracy, not bit-exact f32; mode 0 = f32-input MFMA, the strict one)

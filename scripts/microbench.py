@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|feast|all] [--rows N] [--iters K]
+feast (not part of all): the feature-steered launches (ops.feast_fwd, feast_bwd_edge, feast_bwd_node, feast_dc) on
+the same graph as gat, against the valued ops.spmm at the gathered width heads * C, alternating in one loop; the figures and the
+algorithmic byte counts go to --out (profiles/feast_microbench.txt).
 gat (not part of all): the graph-attention launches (ops.gat_scores, gat_fwd, gat_bwd_edge, gat_bwd_node, gat_datt)
 on the vertex graph of a torus with --rows vertices in RCB order, against the valued ops.spmm at the same total width on the same
 graph, alternating in one loop; the figures and the algorithmic byte counts go to --out (profiles/gat_microbench.txt).
@@ -32,7 +35,7 @@ ap.add_argument("--widths", default="512,256,128,64,32")
 ap.add_argument("--rotate", type=int, default=1, help="spmm: cycle through this many (input, output) buffer sets so that narrow "
                 "widths are not served from the 256 MB MALL (a 1M x 32 float tensor is 128 MB)")
 ap.add_argument("--weighted", action="store_true", help="spmm: valued graph against the unvalued graph of the same mesh")
-ap.add_argument("--out", default=None, help="gat: the file the figures are written to (default profiles/gat_microbench.txt)")
+ap.add_argument("--out", default=None, help="gat / feast: the file the figures are written to (default profiles/<what>_microbench.txt)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 n = a.rows
@@ -347,5 +350,58 @@ if a.what == "gat":
         print("\n".join(lines[-7:]), flush=True)
         del Hs, Ds, Out, st
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gat_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.what == "feast":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    g = ops.graph_for(ei, nn_, norm="gat")
+    reps = max(a.iters, 20)
+    lines = ["feature-steered convolution on the vertex graph of torus(%d, %d) in RCB order: N=%d, entries=%d (loops included), "
+             "float32; median of %d launches [min q1 q3 max], one HIP-event pair per launch, forms alternating in one loop, rotating "
+             "buffer sets; the valued spmm gathers rows of the same width heads * C; bytes = the algorithmic counts of ops.py (MB)"
+             % (nu_, nv_, nn_, g.nnz, reps)]
+    print(lines[0], flush=True)
+    for heads, C in ((4, 128), (8, 32), (1, 64), (8, 4)):
+        hc = heads * C
+        wtp = (hc + heads + 3) // 4 * 4                          # the operator's row buffers: [Hf | P | padding], [dHf | dP | padding]
+        R = 2 if nn_ * hc * 4 >= (1 << 29) else 4
+        Bs = [torch.randn(nn_, wtp, device=dev) for _ in range(R)]
+        Hs, Ps = [b[:, :hc] for b in Bs], [b[:, hc:hc + heads] for b in Bs]
+        Ds = [torch.randn(nn_, C, device=dev) for _ in range(R)]
+        cvec = torch.randn(heads, device=dev) * 0.5
+        Out, Wide, G = torch.empty(nn_, C, device=dev), torch.empty(nn_, hc, device=dev), torch.empty(nn_, wtp, device=dev)
+        st = []
+        for i in range(R):                                       # the saved state of a forward per buffer set
+            y, beta = ops.feast_fwd(g, Hs[i], Ps[i], cvec, heads)
+            dz, rs = ops.feast_bwd_edge(g, Ds[i], Hs[i], beta, heads)
+            st.append((beta, dz, rs))
+            del y
+        q = alternate({
+            "spmm": lambda i: ops.spmm(g, Hs[i], out=Wide),
+            "fwd": lambda i: ops.feast_fwd(g, Hs[i], Ps[i], cvec, heads, out=Out),
+            "bwd_edge": lambda i: ops.feast_bwd_edge(g, Ds[i], Hs[i], st[i][0], heads),
+            "bwd_node": lambda i: ops.feast_bwd_node(g, Ds[i], st[i][0], st[i][1], st[i][2], heads, out=G),
+            "dc": lambda i: ops.feast_dc(st[i][2], heads)}, reps, R)
+        wide, narrow, ent, node = 4.0 * nn_ * hc, 4.0 * nn_ * C, 4.0 * g.nnz, 4.0 * nn_
+        alg = {"spmm": 2 * wide + ent + 2 * node,
+               "fwd": wide + narrow + ent * heads + node * heads + 2 * ent + node,
+               "bwd_edge": wide + narrow + 2 * ent * heads + node * heads + ent + node,
+               "bwd_node": wide + narrow + 2 * ent * heads + 2 * node * heads + 2 * ent + node,
+               "dc": node * heads}
+        lines.append("heads=%d C=%d (gathered width %d, %d buffer sets):" % (heads, C, hc, R))
+        for k in ("spmm", "fwd", "bwd_edge", "bwd_node", "dc"):
+            lines.append("  %-9s %s  %7.0f MB  %.2f TB/s alg  x%.2f of the valued spmm" % (
+                k, fmt(q[k]), alg[k] / 1e6, alg[k] / q[k][2] / 1e6, q[k][2] / q["spmm"][2]))
+        print("\n".join(lines[-6:]), flush=True)
+        del Bs, Hs, Ps, Ds, Out, Wide, G, st
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "feast_microbench.txt")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
