@@ -1,0 +1,269 @@
+// Max aggregation with its winner (EdgeConv): the fused arg-max gather and its one-launch backward.
+//
+//   Y[i,c]   = A[i,c] + max_{e in row i} B[col e, c],   arg[i,c] = col e of the winning entry   (a row without entries: 0 and -1)
+//   dA[j,:]  = dG[j,:] (0 for a row without entries)
+//   dB[j,c]  = sum_{e' in row j} (arg[col e', c] == j ? dG[col e', c] : 0)
+//
+// over the COALESCED CSR of a valued graph (the graph of gat.hip / feast.hip; its values are not read: a duplicate edge cannot
+// change a maximum).  The backward relies on the SYMMETRIC structure: row j's own entries enumerate the rows j feeds, and arg
+// holds node ids, so no mirror map is read.  Ties go to the first entry in CSR order (the smallest source id): the running
+// maximum starts at the row's first entry and is replaced on a strict > only.
+// Work layout of gat.hip / feast.hip: a workgroup (4 waves) owns a chunk of 64 consecutive rows, blockIdx -> chunk XCD-aware;
+// 8 lanes x float4 per row, 8 rows per wave step, two steps per chunk; the 8 lanes walk the C / 4 float4 of the row 8 at a time.
+// Entries are gathered 8 at a time with the batch compiled per entry count (unconditional loads, all in flight together; a
+// shorter row re-reads its last entry, which can neither win a strict > nor -- masked -- add to a sum).  The running maximum and
+// its id (forward) and the sum (backward) stay in registers over ALL entries of the row: the 1200-entry hub row is exact like any
+// other.  No atomics, no LDS, no barrier, fixed orders: bitwise reproducible.  Every row * stride product is int64.  Widths that
+// are not a multiple of 4 (or unaligned operands) take scalar kernels: one thread per row.
+#include "ddmp_common.h"
+
+#include <type_traits>
+
+namespace {
+
+using namespace ddmp;
+
+constexpr int kRB = 64;            // rows per workgroup
+constexpr int kEB = 8;             // entries per batch
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ int4 ld4i(const int* p) { return *reinterpret_cast<const int4*>(p); }
+__device__ __forceinline__ void take(float& m, int& id, float v, int j) {
+    const bool w = v > m;
+    m = w ? v : m;
+    id = w ? j : id;
+}
+
+// This workgroup's chunk and the lane's 8-lane row group.
+#define GMAX_CHUNK_PROLOGUE                                                                        \
+    const int chunk = (blockIdx.x & (kXcd - 1)) * chunks_per_xcd + (blockIdx.x >> 3);              \
+    if (chunk >= n_chunks) return;                                                                 \
+    const int r0 = chunk * kRB;                                                                    \
+    const int nr = min(kRB, n_rows - r0);                                                          \
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;                                    \
+    const int grp = lane >> 3, sl = lane & 7;
+
+// Run `batch` with the entry count of this batch as a compile-time constant: the longest row's count among the wave's active
+// rows (wave-uniform, from ballots).
+#define GMAX_BATCH_SWITCH(b0, nn, batch)                                                           \
+    {                                                                                              \
+        int ne_w = 0;                                                                              \
+        _Pragma("unroll") for (int k = 0; k < kEB; ++k) ne_w += __any((b0) + k < (nn)) ? 1 : 0;     \
+        switch (ne_w) {                                                                            \
+            case 1: batch(std::integral_constant<int, 1>()); break;                                \
+            case 2: batch(std::integral_constant<int, 2>()); break;                                \
+            case 3: batch(std::integral_constant<int, 3>()); break;                                \
+            case 4: batch(std::integral_constant<int, 4>()); break;                                \
+            case 5: batch(std::integral_constant<int, 5>()); break;                                \
+            case 6: batch(std::integral_constant<int, 6>()); break;                                \
+            case 7: batch(std::integral_constant<int, 7>()); break;                                \
+            default: batch(std::integral_constant<int, 8>()); break;                               \
+        }                                                                                          \
+    }
+
+// ------------------------------------------------------------------------------------------------ forward
+__global__ __launch_bounds__(256) void gather_max_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                         const float* __restrict__ B, int64_t ldb, const float* __restrict__ A,
+                                                         int64_t lda, float* __restrict__ Y, int64_t ldy, int* __restrict__ arg,
+                                                         int64_t ldg, int n_rows, int C, int chunks_per_xcd, int n_chunks) {
+    GMAX_CHUNK_PROLOGUE
+    const int W = C >> 2;
+#pragma unroll 1
+    for (int qq = 0; qq < 2; ++qq) {
+        const int lr = wave * 8 + grp + qq * 32;
+        if (lr >= nr) continue;
+        const int row = r0 + lr;
+        const int rbase = rowptr[row];
+        const int nn = rowptr[row + 1] - rbase;
+        float* yrow = Y + (int64_t)row * ldy;
+        int* grow = arg ? arg + (int64_t)row * ldg : nullptr;
+        if (nn == 0) {                                            // a row without entries: 0, not A (the edge function never ran)
+            for (int q = sl; q < W; q += 8) {
+                *reinterpret_cast<float4*>(yrow + q * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (grow) *reinterpret_cast<int4*>(grow + q * 4) = make_int4(-1, -1, -1, -1);
+            }
+            continue;
+        }
+        const int j0 = col[rbase];
+        for (int q = sl; q < W; q += 8) {
+            float4 m = ld4(B + (int64_t)j0 * ldb + q * 4);
+            int4 id = make_int4(j0, j0, j0, j0);
+#pragma unroll 1
+            for (int b0 = 0; b0 < nn; b0 += kEB) {
+                auto batch = [&](auto ne_tag) {
+                    constexpr int NE = decltype(ne_tag)::value;
+                    int j[NE];
+                    float4 x[NE];
+#pragma unroll
+                    for (int k = 0; k < NE; ++k) j[k] = col[rbase + min(b0 + k, nn - 1)];
+#pragma unroll
+                    for (int k = 0; k < NE; ++k) x[k] = ld4(B + (int64_t)j[k] * ldb + q * 4);
+#pragma unroll
+                    for (int k = 0; k < NE; ++k) {
+                        take(m.x, id.x, x[k].x, j[k]);
+                        take(m.y, id.y, x[k].y, j[k]);
+                        take(m.z, id.z, x[k].z, j[k]);
+                        take(m.w, id.w, x[k].w, j[k]);
+                    }
+                };
+                GMAX_BATCH_SWITCH(b0, nn, batch)
+            }
+            if (A) {
+                const float4 a = ld4(A + (int64_t)row * lda + q * 4);
+                m.x = a.x + m.x, m.y = a.y + m.y, m.z = a.z + m.z, m.w = a.w + m.w;
+            }
+            *reinterpret_cast<float4*>(yrow + q * 4) = m;
+            if (grow) *reinterpret_cast<int4*>(grow + q * 4) = id;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void gather_max_scalar_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                                const float* __restrict__ B, int64_t ldb,
+                                                                const float* __restrict__ A, int64_t lda, float* __restrict__ Y,
+                                                                int64_t ldy, int* __restrict__ arg, int64_t ldg, int n_rows,
+                                                                int C) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= n_rows) return;
+    const int e0 = rowptr[row], e1 = rowptr[row + 1];
+    float* yrow = Y + (int64_t)row * ldy;
+    int* grow = arg ? arg + (int64_t)row * ldg : nullptr;
+    for (int c = 0; c < C; ++c) {
+        float m = 0.f;
+        int id = -1;
+        if (e1 > e0) {
+            id = col[e0];
+            m = B[(int64_t)id * ldb + c];
+            for (int e = e0 + 1; e < e1; ++e) {
+                const int j = col[e];
+                take(m, id, B[(int64_t)j * ldb + c], j);
+            }
+            if (A) m = A[(int64_t)row * lda + c] + m;
+        }
+        yrow[c] = m;
+        if (grow) grow[c] = id;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ backward
+__global__ __launch_bounds__(256) void gather_max_bwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                             const float* __restrict__ dG, int64_t lddg,
+                                                             const int* __restrict__ arg, int64_t ldg, float* __restrict__ dA,
+                                                             int64_t ldda, float* __restrict__ dB, int64_t lddb, int n_rows, int C,
+                                                             int chunks_per_xcd, int n_chunks) {
+    GMAX_CHUNK_PROLOGUE
+    const int W = C >> 2;
+#pragma unroll 1
+    for (int qq = 0; qq < 2; ++qq) {
+        const int lr = wave * 8 + grp + qq * 32;
+        if (lr >= nr) continue;
+        const int row = r0 + lr;
+        const int rbase = rowptr[row];
+        const int nn = rowptr[row + 1] - rbase;
+        float* arow = dA + (int64_t)row * ldda;
+        float* brow = dB + (int64_t)row * lddb;
+        if (nn == 0) {
+            for (int q = sl; q < W; q += 8) {
+                *reinterpret_cast<float4*>(arow + q * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+                *reinterpret_cast<float4*>(brow + q * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            continue;
+        }
+        for (int q = sl; q < W; q += 8) {
+            *reinterpret_cast<float4*>(arow + q * 4) = ld4(dG + (int64_t)row * lddg + q * 4);
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 1
+            for (int b0 = 0; b0 < nn; b0 += kEB) {
+                auto batch = [&](auto ne_tag) {
+                    constexpr int NE = decltype(ne_tag)::value;
+                    int64_t j[NE];
+                    int4 w[NE];
+                    float4 x[NE];
+#pragma unroll
+                    for (int k = 0; k < NE; ++k) j[k] = col[rbase + min(b0 + k, nn - 1)];
+#pragma unroll
+                    for (int k = 0; k < NE; ++k) {
+                        w[k] = ld4i(arg + j[k] * ldg + q * 4);
+                        x[k] = ld4(dG + j[k] * lddg + q * 4);
+                    }
+#pragma unroll
+                    for (int k = 0; k < NE; ++k) {
+                        const int me = b0 + k < nn ? row : -2;            // (a re-read last entry adds nothing; arg >= -1)
+                        acc.x += w[k].x == me ? x[k].x : 0.f;
+                        acc.y += w[k].y == me ? x[k].y : 0.f;
+                        acc.z += w[k].z == me ? x[k].z : 0.f;
+                        acc.w += w[k].w == me ? x[k].w : 0.f;
+                    }
+                };
+                GMAX_BATCH_SWITCH(b0, nn, batch)
+            }
+            *reinterpret_cast<float4*>(brow + q * 4) = acc;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void gather_max_bwd_scalar_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                                    const float* __restrict__ dG, int64_t lddg,
+                                                                    const int* __restrict__ arg, int64_t ldg,
+                                                                    float* __restrict__ dA, int64_t ldda, float* __restrict__ dB,
+                                                                    int64_t lddb, int n_rows, int C) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= n_rows) return;
+    const int e0 = rowptr[row], e1 = rowptr[row + 1];
+    for (int c = 0; c < C; ++c) {
+        float acc = 0.f;
+        for (int e = e0; e < e1; ++e) {
+            const int64_t j = col[e];
+            acc += arg[j * ldg + c] == row ? dG[j * lddg + c] : 0.f;
+        }
+        dA[(int64_t)row * ldda + c] = e1 > e0 ? dG[(int64_t)row * lddg + c] : 0.f;
+        dB[(int64_t)row * lddb + c] = acc;
+    }
+}
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool gmax_graph_ok(const ddmp_graph* g) {
+    return g && (g->valued & DDMP_GV_VALUED) && g->n_cols == g->n_rows && g->n_rows < (int64_t)INT32_MAX;
+}
+
+}  // namespace
+
+extern "C" int ddmp_gather_max_f32(const ddmp_graph* g, const float* B, int64_t ldb, const float* A, int64_t lda, int C, float* Y,
+                                   int64_t ldy, int32_t* arg, int64_t ldarg, ddmp_stream stream) {
+    ARG_TRY(gmax_graph_ok(g) && B && Y && C >= 1 && ldb >= C && ldy >= C && (!A || lda >= C) && (!arg || ldarg >= C) && Y != B &&
+            Y != A);
+    if (g->n_rows == 0) return DDMP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int n = (int)g->n_rows;
+    if (C % 4 == 0 && ldb % 4 == 0 && ldy % 4 == 0 && al16(B) && al16(Y) && (!A || (lda % 4 == 0 && al16(A))) &&
+        (!arg || (ldarg % 4 == 0 && al16(arg)))) {
+        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
+        hipLaunchKernelGGL(gather_max_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, B, ldb, A, lda, Y, ldy, arg,
+                           ldarg, n, C, cpx, n_chunks);
+    } else {
+        hipLaunchKernelGGL(gather_max_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, B, ldb, A,
+                           lda, Y, ldy, arg, ldarg, n, C);
+    }
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
+
+extern "C" int ddmp_gather_max_bwd_f32(const ddmp_graph* g, const float* dG, int64_t lddg, const int32_t* arg, int64_t ldarg, int C,
+                                       float* dA, int64_t ldda, float* dB, int64_t lddb, ddmp_stream stream) {
+    ARG_TRY(gmax_graph_ok(g) && dG && arg && dA && dB && C >= 1 && lddg >= C && ldarg >= C && ldda >= C && lddb >= C && dA != dG &&
+            dB != dG && dA != dB);
+    if (g->n_rows == 0) return DDMP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int n = (int)g->n_rows;
+    if (C % 4 == 0 && lddg % 4 == 0 && ldarg % 4 == 0 && ldda % 4 == 0 && lddb % 4 == 0 && al16(dG) && al16(arg) && al16(dA) &&
+        al16(dB)) {
+        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
+        hipLaunchKernelGGL(gather_max_bwd_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, dG, lddg, arg, ldarg, dA,
+                           ldda, dB, lddb, n, C, cpx, n_chunks);
+    } else {
+        hipLaunchKernelGGL(gather_max_bwd_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, dG, lddg,
+                           arg, ldarg, dA, ldda, dB, lddb, n, C);
+    }
+    LAUNCH_TRY();
+    return DDMP_OK;
+}

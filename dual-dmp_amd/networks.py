@@ -20,7 +20,9 @@ Two interchangeable forms, both taking the reference's ``Dataset`` object (field
     ``out_channels = width // heads`` per head, concatenated; parameters ``convN.lin_src.weight``, ``convN.att_src`` ...;
     every width must be divisible by ``heads``); ``conv="feast", heads=4`` builds them from :class:`nn_ops.FeaStConv`
     (feature-steered convolution: ``heads`` weight matrices per layer mixed by a translation-invariant softmax, any ``heads``;
-    parameters ``convN.lin.weight``, ``convN.u.weight``, ``convN.c``, ``convN.bias``).  The fused engine, the trainer, the CLI,
+    parameters ``convN.lin.weight``, ``convN.u.weight``, ``convN.c``, ``convN.bias``); ``conv="edge"`` builds them from
+    :class:`nn_ops.EdgeConv` over ``nn.Linear(2 * in, out)`` (static EdgeConv: the maximum over the neighbourhood of a linear
+    edge function; parameters ``convN.nn.weight``, ``convN.nn.bias``).  The fused engine, the trainer, the CLI,
     the partitioned path and bf16 features are GCN-only: ``fused=True`` with any other ``conv`` raises.
 
 The reference's unused ``torch.randn(V,3)*1e-5`` draw (``util/networks.py:50``) is dropped: it only
@@ -37,7 +39,7 @@ import torch.nn as nn
 
 from . import ops
 from .engine import ArenaLayout, GcnEngine, NORM_WIDTHS, POS_WIDTHS
-from .nn_ops import ChebConv, FeaStConv, GATConv, GCNConv
+from .nn_ops import ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv
 
 
 class _EngineFn(torch.autograd.Function):
@@ -259,7 +261,7 @@ class NormalNetFused(_FusedNet):
 
 
 # -------------------------------------------------------------------------------- operator-level form
-_CONVS = ("gcn", "cheb", "gat", "feast")
+_CONVS = ("gcn", "cheb", "gat", "feast", "edge")
 
 
 class _ModularNet(nn.Module):
@@ -270,7 +272,7 @@ class _ModularNet(nn.Module):
         self.device = torch.device(device)
         h = self._widths
         if conv not in _CONVS:
-            raise ValueError("conv must be 'gcn', 'cheb', 'gat' or 'feast', got %r" % (conv,))
+            raise ValueError("conv must be 'gcn', 'cheb', 'gat', 'feast' or 'edge', got %r" % (conv,))
         if conv == "gat":
             bad = [w for w in h[1:13] if not isinstance(heads, int) or heads < 1 or w % heads]
             if bad:
@@ -280,6 +282,8 @@ class _ModularNet(nn.Module):
                 layer = GATConv(h[i], h[i + 1] // heads, heads=heads)
             elif conv == "feast":
                 layer = FeaStConv(h[i], h[i + 1], heads=heads)
+            elif conv == "edge":
+                layer = EdgeConv(nn.Linear(2 * h[i], h[i + 1]))
             else:
                 layer = GCNConv(h[i], h[i + 1]) if conv == "gcn" else ChebConv(h[i], h[i + 1], K)
             setattr(self, "conv%d" % (i + 1), layer)
@@ -344,7 +348,7 @@ class NormalNetModular(_ModularNet):
 
 def _make_net(fused_cls, modular_cls, device, fused, conv, K, heads, kw):
     if conv not in _CONVS:
-        raise ValueError("conv must be 'gcn', 'cheb', 'gat' or 'feast', got %r" % (conv,))
+        raise ValueError("conv must be 'gcn', 'cheb', 'gat', 'feast' or 'edge', got %r" % (conv,))
     if fused:
         if conv != "gcn":
             raise ValueError("conv=%r needs fused=False: the fused engine (and with it the trainer, the CLI, the partitioned "

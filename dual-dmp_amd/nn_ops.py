@@ -1,4 +1,4 @@
-"""Drop-in ``GCNConv``, ``ChebConv``, ``GATConv`` and ``FeaStConv`` on the HIP kernels.
+"""Drop-in ``GCNConv``, ``ChebConv``, ``GATConv``, ``FeaStConv`` and ``EdgeConv`` on the HIP kernels.
 
 Same constructor / call signature, parameter names and initialisation as
 ``torch_geometric.nn.GCNConv`` 2.2.0 with the defaults the reference uses
@@ -78,6 +78,30 @@ from memory -- PyG cannot be installed here, so this could not be checked agains
 * differentiable w.r.t. x, ``lin.weight``, ``u.weight``, ``c`` and ``bias``; float32, bitwise reproducible.
 * refused with ``ValueError`` before any launch: tuple ``in_channels`` or a tuple ``x`` (bipartite), an ``aggr`` other than
   ``"mean"``, bf16 features, ``heads < 1``, an ``x`` that is not [N, in].
+
+``EdgeConv(nn, aggr="max")``, ``forward(x, edge_index)`` restates ``torch_geometric.nn.EdgeConv`` 2.2.0 (Wang et al., Dynamic
+Graph CNN, 2019; like the operators above: written from the published source from memory -- PyG cannot be installed here, so this
+could not be checked against it; the pin is the float64 restatement ``tests/edgeconv_ref.py``):
+
+* ``out[i] = max over the edges j -> i of nn(cat[x_i, x_j - x_i])``, a node without incoming edges gets 0.  No self loops are
+  added; an explicit loop is an ordinary edge (it contributes ``nn(cat[x_i, 0])``); a duplicate edge changes nothing.
+* accepted ``nn``: a ``torch.nn.Linear(2 * in, out)`` with or without bias, or a ``torch.nn.Sequential`` whose first module is
+  such a ``Linear`` and whose other modules are all ``ReLU``, ``LeakyReLU(negative_slope >= 0)`` or ``Identity``.  Those are
+  elementwise, non-decreasing in floating point and map 0 to 0, so ``max_j act(z_j) == act(max_j z_j)`` bit for bit and an empty
+  neighbourhood stays 0: they run as ordinary torch modules after the fused core.  (A ``Sigmoid`` fails the second condition, a
+  ``BatchNorm`` the first.)  The module is kept as given under ``self.nn``: ``state_dict()`` has PyG's keys (``nn.weight``,
+  ``nn.bias`` or ``nn.0.weight`` ...) and ``parameters()`` are the user's own tensors.
+* with ``W = [Wa | Wb]``: ``W [x_i ; x_j - x_i] + b = (Wa - Wb) x_i + b + Wb x_j = A[i] + B[j]``, so
+  ``out[i] = A[i] + max_j B[j]``: one GEMM against the packed ``[Wa - Wb ; Wb]`` for the row buffer ``[A | B]``, one launch for the
+  per-column maximum and its winner (``ops.gather_max``; the winner is kept only when a gradient is wanted), one launch for the
+  backward of the graph part (``ops.gather_max_bwd`` -> ``[dA | dB]``), one wgrad GEMM (``dWa = dM``, ``dWb = dN - dM``) and one
+  dgrad GEMM.  No [E, .] tensor exists at any point.  The graph is GATConv's without loops:
+  ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric edge STRUCTURE only.
+* differentiable w.r.t. x and the ``Linear``'s weight and bias; float32, bitwise reproducible.  Deviation: with exact ties PyG's
+  winner is unspecified, ours is the smallest source id -- either one is a valid subgradient.
+* refused with ``ValueError`` before any launch: any other ``nn`` (an arbitrary MLP; a ``Linear`` whose ``in_features`` is odd),
+  ``aggr != "max"``, a tuple ``x`` (bipartite), bf16 features, an ``x`` that is not [N, in].  Not implemented:
+  ``DynamicEdgeConv`` / kNN graphs.
 """
 from __future__ import annotations
 
@@ -633,3 +657,130 @@ class FeaStConv(nn.Module):
 
     def extra_repr(self):
         return "%d, %d, heads=%d" % (self.in_channels, self.out_channels, self.heads)
+
+
+class _EdgeConvFn(torch.autograd.Function):
+    """ONE GEMM against the packed weight [Wa - Wb ; Wb] (each block's rows padded to a multiple of 4) with the bias [b ; 0] gives
+    the row buffer [A | B], then ONE launch gathers the per-column maximum of B and who won (``ops.gather_max``).  Saved: the
+    padded x, the packed weight and arg [N, out] -- not the row buffer.  Backward: one launch writes [dA | dB]
+    (``ops.gather_max_bwd``), ONE wgrad GEMM gives [dM ; dN] (dWa = dM, dWb = dN - dM), ONE dgrad GEMM gives dx; db = colsum(dA).
+    ``want_arg``: whether a backward can follow (grad mode cannot be read inside ``forward``: ``_edge_conv`` passes it in)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, graph, want_arg):
+        cout, cin = weight.shape[0], weight.shape[1] // 2
+        cp = (cout + 3) // 4 * 4
+        xp = _pad_cols(x.detach().to(torch.float32))
+        w = weight.detach()
+        wp = torch.zeros((2 * cp, xp.shape[1]), dtype=torch.float32, device=x.device)
+        wp[:cout, :cin] = w[:, :cin] - w[:, cin:]
+        wp[cp:cp + cout, :cin] = w[:, cin:]
+        bp = None
+        if bias is not None:
+            bp = torch.zeros(2 * cp, dtype=torch.float32, device=x.device)
+            bp[:cout] = bias.detach()
+        buf = ops.gemm_nt(xp, wp, bias=bp)                       # [N, 2 cp]: A | padding | B | padding
+        want = bool(want_arg) and any(ctx.needs_input_grad[:3])
+        y, arg = ops.gather_max(graph, buf[:, cp:cp + cout], a=buf[:, :cout], want_arg=want)
+        ctx.save_for_backward(xp, wp, arg)
+        ctx.graph, ctx.dims, ctx.has_bias = graph, (cin, cout, cp), bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        with ops.on_device(dy):
+            return _EdgeConvFn._backward(ctx, dy)
+
+    @staticmethod
+    def _backward(ctx, dy):
+        xp, wp, arg = ctx.saved_tensors
+        graph, (cin, cout, cp) = ctx.graph, ctx.dims
+        dy = dy.contiguous().to(torch.float32)
+        g = torch.empty((dy.shape[0], 2 * cp), dtype=torch.float32, device=dy.device)
+        if cp != cout:
+            g[:, cout:cp] = 0
+            g[:, cp + cout:] = 0
+        da, _ = ops.gather_max_bwd(graph, dy, arg, out=g)        # g = [dA | 0 | dB | 0]
+        db = None
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
+            db = ops.colsum(da).to(torch.float32) if pow2 else da.sum(0)
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dwp = ops.gemm_tn(g, xp)                             # [dM ; dN]
+            dm, dn = dwp[:cout, :cin], dwp[cp:cp + cout, :cin]
+            dw = torch.cat([dm, dn - dm], 1)
+        dx = ops.gemm_nn(g, wp)[:, :cin] if ctx.needs_input_grad[0] else None
+        return dx, dw, db, None, None
+
+
+def _edge_conv(x, weight, bias, graph):
+    want = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias))
+    return _EdgeConvFn.apply(x, weight, bias, graph, want)
+
+
+_EDGE_NN_MSG = ("EdgeConv: on the HIP path nn must be a torch.nn.Linear(2 * in, out), or a torch.nn.Sequential of one followed by ReLU, "
+                "LeakyReLU(negative_slope >= 0) or Identity modules only (elementwise, non-decreasing, 0 -> 0: they commute with the "
+                "maximum); got %s")
+
+
+def _edge_nn(module):
+    """-> (the ``Linear`` of an accepted edge function, the elementwise modules behind it), or ``ValueError``."""
+    lin, rest = module, []
+    if isinstance(module, nn.Sequential) and len(module) > 0:
+        lin, rest = module[0], list(module)[1:]
+    if type(lin) is not nn.Linear or lin.weight.dtype != torch.float32:
+        raise ValueError(_EDGE_NN_MSG % (module,))
+    if lin.in_features % 2:
+        raise ValueError("EdgeConv: the Linear takes cat[x_i, x_j - x_i], so its in_features must be even, got %d" % lin.in_features)
+    for m in rest:
+        if not (type(m) in (nn.ReLU, nn.Identity) or (type(m) is nn.LeakyReLU and m.negative_slope >= 0)):
+            raise ValueError(_EDGE_NN_MSG % (module,))
+    return lin, rest
+
+
+class EdgeConv(nn.Module):
+    """``torch_geometric.nn.EdgeConv`` 2.2.0 on the HIP kernels (module docstring)."""
+
+    def __init__(self, nn, aggr: str = "max", **kwargs):
+        super().__init__()
+        if aggr != "max":
+            raise ValueError("EdgeConv: only aggr='max' is implemented on the HIP path, got %r" % (aggr,))
+        if kwargs:
+            raise TypeError("EdgeConv: unexpected keyword arguments %s" % sorted(kwargs))
+        lin, _ = _edge_nn(nn)
+        self.aggr = aggr
+        self.in_channels, self.out_channels = lin.in_features // 2, lin.out_features
+        self.nn = nn                                             # kept as given: PyG's state_dict keys, the user's own parameters
+
+    def reset_parameters(self):
+        for m in self.nn.modules():
+            if m is not self.nn and hasattr(m, "reset_parameters"):
+                m.reset_parameters()
+        if hasattr(self.nn, "reset_parameters"):
+            self.nn.reset_parameters()
+
+    def forward(self, x, edge_index) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
+        if isinstance(x, (tuple, list)):
+            raise ValueError("EdgeConv: a tuple x (bipartite graphs) is not implemented on the HIP path")
+        if x.dtype == torch.bfloat16:
+            raise ValueError("EdgeConv: bf16 features are not supported on the HIP path")
+        if x.dim() != 2 or x.shape[1] != self.in_channels:
+            raise ValueError("EdgeConv: expected x of shape [N, %d]" % self.in_channels)
+        _edge_nn(self.nn)                                        # (the module is the user's: it may have been edited since)
+        if not x.is_cuda:
+            raise ops.DdmpError("EdgeConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        return self._core(x, edge_index)
+
+    def _core(self, x, edge_index):
+        lin, rest = _edge_nn(self.nn)
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
+            y = _edge_conv(x, lin.weight, lin.bias, graph)
+        for m in rest:
+            y = m(y)
+        return y
+
+    def extra_repr(self):
+        return "aggr=%s" % self.aggr

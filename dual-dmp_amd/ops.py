@@ -888,6 +888,74 @@ def feast_dc(rs, heads):
     return dc
 
 
+# ---------------------------------------------------------------------------------------- max aggregation (DESIGN.md 4.10)
+def _gmax_mat(t, name, rows, C=None):
+    """[>= rows, C] float32 matrix (a column block of a wider row buffer is fine) -> (tensor, ld)."""
+    t, ld = _mat(_chk(t, torch.float32, name), name)
+    if t.shape[0] < rows or t.shape[1] < 1 or (C is not None and t.shape[1] != C):
+        raise DdmpError("%s must be [>= %d, %s], got %s" % (name, rows, "C" if C is None else C, tuple(t.shape)))
+    return t, ld
+
+
+def _gmax_arg(arg, n, C):
+    _chk(arg, torch.int32, "arg")
+    if arg.dim() != 2 or arg.stride(1) != 1 or arg.shape[0] < n or arg.shape[1] != C:
+        raise DdmpError("arg must be an int32 [>= %d, %d] with contiguous rows, got %s" % (n, C, tuple(arg.shape)))
+    return arg, (arg.stride(0) if arg.shape[0] > 1 else max(C, arg.stride(0)))
+
+
+def gather_max(g: Graph, b, a=None, out=None, want_arg=True):
+    """Arg-max gather in one launch (``ddmp_gather_max_f32``) -> (y [n, C], arg int32 [n, C] | None):
+    ``y[i, c] = a[i, c] + max_{e in row i} b[col e, c]``, ``arg[i, c]`` the source node id of the winning entry (ties: the smallest
+    id).  A row without entries gets y = 0 (not ``a``) and arg = -1.  ``b``, ``a``: [n, C] (they may be column blocks of one row
+    buffer; ``a=None`` means 0); ``want_arg=False`` skips the store of ``arg`` (a forward without a backward)."""
+    _gat_graph(g)
+    n = g.n_rows
+    b, ldb = _gmax_mat(b, "b", n)
+    C = b.shape[1]
+    lda = 0
+    if a is not None:
+        a, lda = _gmax_mat(a, "a", n, C)
+    if out is None:
+        out = torch.empty((n, C), dtype=torch.float32, device=b.device)
+    out, ldy = _gmax_mat(out, "out", n, C)
+    arg, ldg = None, 0
+    if want_arg:
+        arg, ldg = _gmax_arg(torch.empty((n, C), dtype=torch.int32, device=b.device), n, C)
+    # algorithmic bytes: every gathered row read once, the rows' own a read, y written, arg written, col, rowptr
+    na = (1 if a is not None else 0) + (1 if want_arg else 0)
+    alg = 4.0 * n * C * (2 + na) + 4.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("gather_max", (C, int(round(g.nnz / max(n, 1)))), alg, 1.0 * g.nnz * C, survey=8.0 * n * C + 4.0 * g.nnz + 4.0 * (n + 1)):
+        st = _lib.lib().ddmp_gather_max_f32(g.handle, _p(b), ldb, _p(a), lda, C, _p(out), ldy, _p(arg), ldg, _stream())
+    check(st, "ddmp_gather_max_f32")
+    return out, arg
+
+
+def gather_max_bwd(g: Graph, dg, arg, out=None):
+    """Backward of ``gather_max`` in one launch (``ddmp_gather_max_bwd_f32``) -> (dA, dB), both [n, C]: ``dA[j] = dg[j]`` (0 for
+    a row without entries), ``dB[j, c] = sum_{e' in row j} (arg[col e', c] == j ? dg[col e', c] : 0)``.  The results are views
+    into ``out``, a float32 [n, 2 * Cp] row buffer with Cp = C rounded up to 4: dA in columns [0, C), dB in [Cp, Cp + C); the
+    padding columns are left untouched.  ``out=None``: a buffer of its own."""
+    _gat_graph(g)
+    n = g.n_rows
+    dg, lddg = _gmax_mat(dg, "dg", n)
+    C = dg.shape[1]
+    arg, ldg = _gmax_arg(arg, n, C)
+    cp = (C + 3) // 4 * 4
+    if out is None:
+        out = torch.empty((n, 2 * cp), dtype=torch.float32, device=dg.device)
+    out, _ = _mat(_chk(out, torch.float32, "out"), "out")
+    if out.shape[0] != n or out.shape[1] != 2 * cp:
+        raise DdmpError("gather_max_bwd: out must be [%d, %d], got %s" % (n, 2 * cp, tuple(out.shape)))
+    (da, ldda), (db, lddb) = _mat(out[:, :C], "dA"), _mat(out[:, cp:cp + C], "dB")
+    # algorithmic bytes: dg and arg read once each, dA and dB written, col, rowptr
+    alg = 16.0 * n * C + 4.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("gather_max_bwd", (C, int(round(g.nnz / max(n, 1)))), alg, 1.0 * g.nnz * C):
+        st = _lib.lib().ddmp_gather_max_bwd_f32(g.handle, _p(dg), lddg, _p(arg), ldg, C, _p(da), ldda, _p(db), lddb, _stream())
+    check(st, "ddmp_gather_max_bwd_f32")
+    return da, db
+
+
 def spmm_axpby(g: Graph, x, out=None, z=None, z2=None, a=1.0, b=0.0, c=0.0, d=0.0):
     """out[i] = a * (dinv_i * sum_j dinv_j x[j]) + b * x[i] + c * z[i] + d * z2[i], float32 (ddmp_spmm_axpby_f32): one step of a
     three-term recurrence per launch.  ``z`` / ``z2`` optional (their coefficient is then ignored); ``out`` may be ``z`` or ``z2``,

@@ -245,6 +245,24 @@ size_t ddmp_feast_dc_workspace_bytes(int64_t n_rows, int heads);
 int ddmp_feast_dc_f32(const float* rs, int64_t n_rows, int heads, float* dc, void* workspace, size_t workspace_bytes,
                       ddmp_stream stream);
 
+/* ------------------------------------------------------------------ max aggregation (torch_geometric EdgeConv with a Linear edge
+ * function).  float32.  The graph is the attention graph above (a VALUED graph; its values are not read: the
+ * structure is coalesced and a duplicate edge cannot change a maximum); an unvalued graph is DDMP_EINVAL.  Every matrix has its own
+ * pointer and leading dimension (A and B, dA and dB are meant to be the column blocks of one row buffer).  No atomics, fixed orders:
+ * two calls give the same bits.  The vector kernels need C % 4 == 0, leading dimensions % 4 == 0 and 16-byte aligned matrices;
+ * anything else takes scalar kernels.
+ *
+ * forward:   Y[i,c] = A[i,c] + max_{e in row i} B[col e, c] (A nullable: 0), arg[i,c] = col e of the winning entry (int32
+ *            [n, C]; nullable: not stored).  Ties go to the first entry in CSR order, i.e. the smallest source id (strict >
+ *            from the row's first entry).  A row without entries gets Y = 0 (not A) and arg = -1.  One launch. */
+int ddmp_gather_max_f32(const ddmp_graph* g, const float* B, int64_t ldb, const float* A /*nullable*/, int64_t lda, int C, float* Y,
+                        int64_t ldy, int32_t* arg /*nullable*/, int64_t ldarg, ddmp_stream stream);
+/* backward:  dA[j,:] = dG[j,:] for a row with entries, 0 for one without;
+ *            dB[j,c] = sum_{e' in row j} (arg[col e', c] == j ? dG[col e', c] : 0) in CSR order (the structure is symmetric: row
+ *            j's own entries enumerate the rows j feeds; arg holds node ids, so no mirror map is read).  dG is [n, C].  One launch. */
+int ddmp_gather_max_bwd_f32(const ddmp_graph* g, const float* dG, int64_t lddg, const int32_t* arg, int64_t ldarg, int C, float* dA,
+                            int64_t ldda, float* dB, int64_t lddb, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ dense steps (MFMA; float32 operands and results, the
  * arithmetic is ddmp_set_gemm_mode's: by default SPLIT-precision 16-bit MFMA products with f32 accumulation -- f32-class
  * accuracy, not bit-exact f32; mode 0 = f32-input MFMA, the strict one)

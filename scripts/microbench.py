@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|feast|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|feast|edge|all] [--rows N] [--iters K]
+edge (not part of all): the two max-aggregation launches (ops.gather_max with and without arg, ops.gather_max_bwd)
+at C = 64, 128, 512 on the same torus without loops, against the valued ops.spmm at the same width, alternating in one loop; the
+figures and the algorithmic byte counts go to --out (profiles/edge_microbench.txt).
 feast (not part of all): the feature-steered launches (ops.feast_fwd, feast_bwd_edge, feast_bwd_node, feast_dc) on
 the same graph as gat, against the valued ops.spmm at the gathered width heads * C, alternating in one loop; the figures and the
 algorithmic byte counts go to --out (profiles/feast_microbench.txt).
@@ -35,7 +38,7 @@ ap.add_argument("--widths", default="512,256,128,64,32")
 ap.add_argument("--rotate", type=int, default=1, help="spmm: cycle through this many (input, output) buffer sets so that narrow "
                 "widths are not served from the 256 MB MALL (a 1M x 32 float tensor is 128 MB)")
 ap.add_argument("--weighted", action="store_true", help="spmm: valued graph against the unvalued graph of the same mesh")
-ap.add_argument("--out", default=None, help="gat / feast: the file the figures are written to (default profiles/<what>_microbench.txt)")
+ap.add_argument("--out", default=None, help="gat / feast / edge: the file the figures are written to (default profiles/<what>_microbench.txt)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 n = a.rows
@@ -403,5 +406,46 @@ if a.what == "feast":
         print("\n".join(lines[-6:]), flush=True)
         del Bs, Hs, Ps, Ds, Out, Wide, G, st
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "feast_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.what == "edge":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    g = ops.graph_for(ei, nn_, norm="gat", add_self_loops=False)
+    reps = max(a.iters, 20)
+    lines = ["max aggregation (EdgeConv) on the vertex graph of torus(%d, %d) in RCB order: N=%d, entries=%d (no loops), float32; "
+             "median of %d launches [min q1 q3 max], one HIP-event pair per launch, forms alternating in one loop, rotating buffer "
+             "sets; A / B and dA / dB are the halves of one [N, 2 C] row buffer; the valued spmm gathers rows of the same width C; "
+             "bytes = the algorithmic counts of ops.py and DESIGN.md 4.10 (MB)" % (nu_, nv_, nn_, g.nnz, reps)]
+    print(lines[0], flush=True)
+    for C in (64, 128, 512):
+        R = 2 if nn_ * C * 4 >= (1 << 29) else 4
+        Bs = [torch.randn(nn_, 2 * C, device=dev) for _ in range(R)]
+        As, Xs = [b[:, :C] for b in Bs], [b[:, C:] for b in Bs]
+        Ds = [torch.randn(nn_, C, device=dev) for _ in range(R)]
+        Out, G = torch.empty(nn_, C, device=dev), torch.empty(nn_, 2 * C, device=dev)
+        args = [ops.gather_max(g, Xs[i], a=As[i])[1] for i in range(R)]          # the saved state of a forward per buffer set
+        q = alternate({
+            "spmm": lambda i: ops.spmm(g, Xs[i], out=Out),
+            "fwd": lambda i: ops.gather_max(g, Xs[i], a=As[i], out=Out),
+            "fwd_noarg": lambda i: ops.gather_max(g, Xs[i], a=As[i], out=Out, want_arg=False),
+            "bwd": lambda i: ops.gather_max_bwd(g, Ds[i], args[i], out=G)}, reps, R)
+        feat, ent, node = 4.0 * nn_ * C, 4.0 * g.nnz, 4.0 * nn_
+        alg = {"spmm": 2 * feat + ent + 2 * node, "fwd": 4 * feat + ent + node, "fwd_noarg": 3 * feat + ent + node,
+               "bwd": 4 * feat + ent + node}
+        lines.append("C=%d (%d buffer sets):" % (C, R))
+        for k in ("spmm", "fwd", "fwd_noarg", "bwd"):
+            lines.append("  %-9s %s  %7.0f MB  %.2f TB/s alg  x%.2f of the valued spmm" % (
+                k, fmt(q[k]), alg[k] / 1e6, alg[k] / q[k][2] / 1e6, q[k][2] / q["spmm"][2]))
+        print("\n".join(lines[-5:]), flush=True)
+        del Bs, As, Xs, Ds, Out, G, args
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edge_microbench.txt")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
