@@ -17,76 +17,12 @@
 // factor 0).  An output float4 is accumulated in registers over ALL entries and heads of its row before it is stored: the
 // 1200-entry hub row is exact like any other.  No atomics, no LDS, no barrier; every sum has a fixed order: bitwise reproducible.
 // Every row * stride product is int64.  Widths that are not a multiple of 4 (or unaligned operands) take scalar kernels: one
-// thread per row.
-#include "ddmp_common.h"
-
-#include <type_traits>
+// thread per row.  The layout's helpers and the three gather loops live in gather_mix.h, shared with gmm.hip.
+#include "gather_mix.h"
 
 namespace {
 
-using namespace ddmp;
-
-constexpr int kRB = 64;            // rows per workgroup
-constexpr int kEB = 8;             // entries per batch
 constexpr int kDR = 1024;          // rows per partial of the offset gradient
-constexpr int kMaxHeads = 256;     // (one thread per head in the offset-gradient reduction)
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float dot4(float4 a, float4 b, float acc) {
-    return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, fmaf(a.x, b.x, acc))));
-}
-__device__ __forceinline__ void fma4(float4& acc, float s, float4 x) {
-    acc.x = fmaf(s, x.x, acc.x);
-    acc.y = fmaf(s, x.y, acc.y);
-    acc.z = fmaf(s, x.z, acc.z);
-    acc.w = fmaf(s, x.w, acc.w);
-}
-// fixed xor tree over the lw (1, 2, 4, 8; kernel-uniform) low lanes of an 8-lane row group
-__device__ __forceinline__ float red_sum(float t, int lw) {
-    if (lw > 1) t += __shfl_xor(t, 1, 64);
-    if (lw > 2) t += __shfl_xor(t, 2, 64);
-    if (lw > 4) t += __shfl_xor(t, 4, 64);
-    return t;
-}
-// fixed xor tree over the 8 / lw lanes of a row group that hold the same columns (different heads)
-__device__ __forceinline__ float red_heads(float t, int lw) {
-    if (lw < 2) t += __shfl_xor(t, 1, 64);
-    if (lw < 4) t += __shfl_xor(t, 2, 64);
-    if (lw < 8) t += __shfl_xor(t, 4, 64);
-    return t;
-}
-inline int lanes_per_head(int C) {
-    const int W = C / 4;
-    return (W == 1 || W == 2 || W == 4) ? W : 8;
-}
-
-// This workgroup's chunk, the lane's 8-lane row group and its place in a head pass (lw lanes per head, hp heads per pass).
-#define FEAST_CHUNK_PROLOGUE                                                                       \
-    const int chunk = (blockIdx.x & (kXcd - 1)) * chunks_per_xcd + (blockIdx.x >> 3);              \
-    if (chunk >= n_chunks) return;                                                                 \
-    const int r0 = chunk * kRB;                                                                    \
-    const int nr = min(kRB, n_rows - r0);                                                          \
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;                                    \
-    const int grp = lane >> 3, sl = lane & 7;                                                      \
-    const int hp = 8 / lw, sub = sl / lw, q0 = sl & (lw - 1);
-
-// Run `batch` with the entry count of this batch as a compile-time constant: the longest row's count among the wave's active
-// rows (wave-uniform, from ballots).
-#define FEAST_BATCH_SWITCH(b0, nn, batch)                                                          \
-    {                                                                                              \
-        int ne_w = 0;                                                                              \
-        _Pragma("unroll") for (int k = 0; k < kEB; ++k) ne_w += __any((b0) + k < (nn)) ? 1 : 0;     \
-        switch (ne_w) {                                                                            \
-            case 1: batch(std::integral_constant<int, 1>()); break;                                \
-            case 2: batch(std::integral_constant<int, 2>()); break;                                \
-            case 3: batch(std::integral_constant<int, 3>()); break;                                \
-            case 4: batch(std::integral_constant<int, 4>()); break;                                \
-            case 5: batch(std::integral_constant<int, 5>()); break;                                \
-            case 6: batch(std::integral_constant<int, 6>()); break;                                \
-            case 7: batch(std::integral_constant<int, 7>()); break;                                \
-            default: batch(std::integral_constant<int, 8>()); break;                               \
-        }                                                                                          \
-    }
 
 // beta_e[:] of one entry: the head softmax (exp arguments <= 0) times scale = a_e / deg_i
 __device__ __forceinline__ void head_softmax(const float* __restrict__ pc, const float* __restrict__ pr, const float* __restrict__ cv,
@@ -133,43 +69,7 @@ __global__ __launch_bounds__(256) void feast_fwd_kernel(const int* __restrict__ 
         // the gather reads the factors its sibling lanes wrote: same wave, same CU's L1 -- a workgroup-scope fence
         __threadfence_block();
         for (int q = q0; q < W; q += lw) {                        // (lw < 8: exactly one trip, all 8 lanes together)
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 1
-            for (int b0 = 0; b0 < nn; b0 += kEB) {
-                auto batch = [&](auto ne_tag) {
-                    constexpr int NE = decltype(ne_tag)::value;
-                    const float* xp[NE];
-                    const float* fp[NE];
-#pragma unroll
-                    for (int k = 0; k < NE; ++k) {
-                        const int64_t e = rbase + min(b0 + k, nn - 1);
-                        xp[k] = Hf + (int64_t)col[e] * ldh + q * 4;
-                        fp[k] = beta + e * heads;
-                    }
-#pragma unroll 1
-                    for (int hg = 0; hg < heads; hg += hp) {
-                        const int h = hg + sub;
-                        const bool hv = h < heads;
-                        const int hh = hv ? h : heads - 1;
-                        float4 x[NE];
-                        float f[NE];
-#pragma unroll
-                        for (int k = 0; k < NE; ++k) {
-                            x[k] = ld4(xp[k] + hh * C);
-                            f[k] = fp[k][hh];
-                        }
-#pragma unroll
-                        for (int k = 0; k < NE; ++k) fma4(acc, (hv && b0 + k < nn) ? f[k] : 0.f, x[k]);
-                    }
-                };
-                FEAST_BATCH_SWITCH(b0, nn, batch)
-            }
-            if (lw < 8) {                                         // the 8 / lw head groups of this slab -> one row
-                acc.x = red_heads(acc.x, lw);
-                acc.y = red_heads(acc.y, lw);
-                acc.z = red_heads(acc.z, lw);
-                acc.w = red_heads(acc.w, lw);
-            }
+            float4 acc = mix_gather_row(col, Hf, ldh, beta, heads, C, lw, hp, sub, rbase, nn, q);
             if (bias) {
                 const float4 b = ld4(bias + q * 4);
                 acc.x += b.x, acc.y += b.y, acc.z += b.z, acc.w += b.w;
@@ -220,7 +120,6 @@ __global__ __launch_bounds__(256) void feast_bwd_edge_kernel(const int* __restri
                                                              const float* __restrict__ beta, float* dz, float* rs, int n_rows,
                                                              int heads, int C, int lw, int chunks_per_xcd, int n_chunks) {
     FEAST_CHUNK_PROLOGUE
-    const int W = C >> 2;
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
         const int lr = wave * 8 + grp + qq * 32;
@@ -235,40 +134,7 @@ __global__ __launch_bounds__(256) void feast_bwd_edge_kernel(const int* __restri
             continue;
         }
         // g_e[h] = dOut[i,:] . Hf[col e, h, :] for every (entry, head), parked in dz
-#pragma unroll 1
-        for (int hg = 0; hg < heads; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < heads;
-            const int hh = hv ? h : heads - 1;
-#pragma unroll 1
-            for (int b0 = 0; b0 < nn; b0 += kEB) {
-                auto batch = [&](auto ne_tag) {
-                    constexpr int NE = decltype(ne_tag)::value;
-                    const float* xp[NE];
-                    float acc[NE];
-#pragma unroll
-                    for (int k = 0; k < NE; ++k) {
-                        const int e = rbase + min(b0 + k, nn - 1);
-                        xp[k] = Hf + (int64_t)col[e] * ldh + hh * C;
-                        acc[k] = 0.f;
-                    }
-                    for (int q = q0; q < W; q += lw) {
-                        const float4 y = ld4(grow + q * 4);
-                        float4 x[NE];
-#pragma unroll
-                        for (int k = 0; k < NE; ++k) x[k] = ld4(xp[k] + q * 4);
-#pragma unroll
-                        for (int k = 0; k < NE; ++k) acc[k] = dot4(y, x[k], acc[k]);
-                    }
-#pragma unroll
-                    for (int k = 0; k < NE; ++k) {
-                        const float t = red_sum(acc[k], lw);
-                        if (b0 + k < nn && hv && q0 == 0) dz[(int64_t)(rbase + b0 + k) * heads + h] = t;
-                    }
-                };
-                FEAST_BATCH_SWITCH(b0, nn, batch)
-            }
-        }
+        mix_edge_dots(col, grow, Hf, ldh, dz, heads, C, lw, hp, sub, q0, rbase, nn);
         // the sweep below reads what the sibling lanes parked: same wave, same CU's L1 -- a workgroup-scope fence
         __threadfence_block();
         // one entry per lane, all heads: dz in place; its row sums by a fixed xor tree per 8 entries, accumulated through rs[i,:]
@@ -349,25 +215,7 @@ __global__ __launch_bounds__(256) void feast_bwd_node_kernel(const int* __restri
             if (hv && q0 == 0) dP[(int64_t)row * lddp + h] = p - rs[(int64_t)row * heads + h];
             // dHf[j,h,:] = sum_{e'} beta[mirror e', h] dOut[col e', :]
             for (int q = q0; q < W; q += lw) {
-                float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 1
-                for (int b0 = 0; b0 < nn; b0 += kEB) {
-                    auto batch = [&](auto ne_tag) {
-                        constexpr int NE = decltype(ne_tag)::value;
-                        float4 x[NE];
-                        float f[NE];
-#pragma unroll
-                        for (int k = 0; k < NE; ++k) {
-                            const int e = rbase + min(b0 + k, nn - 1);
-                            x[k] = ld4(dOut + (int64_t)col[e] * lddo + q * 4);
-                            const float v = beta[(int64_t)mirror[e] * heads + hh];
-                            f[k] = b0 + k < nn ? v : 0.f;
-                        }
-#pragma unroll
-                        for (int k = 0; k < NE; ++k) fma4(acc, f[k], x[k]);
-                    };
-                    FEAST_BATCH_SWITCH(b0, nn, batch)
-                }
+                const float4 acc = mix_node_gather(col, mirror, dOut, lddo, beta, heads, hh, rbase, nn, q);
                 if (hv) *reinterpret_cast<float4*>(orow + hh * C + q * 4) = acc;
             }
         }
@@ -430,12 +278,6 @@ __global__ __launch_bounds__(1024) void feast_dc_final_kernel(const float* __res
     __syncthreads();
     if (part == 0 && h < heads) dc[h] = (float)(((sm[0][h] + sm[1][h]) + sm[2][h]) + sm[3][h]);
 }
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool feast_graph_ok(const ddmp_graph* g) {
-    return g && (g->valued & DDMP_GV_VALUED) && g->a && g->mirror && g->n_cols == g->n_rows && g->n_rows < (int64_t)INT32_MAX;
-}
-inline bool feast_dims_ok(int heads, int C) { return heads > 0 && heads <= kMaxHeads && C > 0 && (int64_t)heads * C < (1 << 24); }
 
 }  // namespace
 

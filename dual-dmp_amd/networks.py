@@ -22,7 +22,12 @@ Two interchangeable forms, both taking the reference's ``Dataset`` object (field
     (feature-steered convolution: ``heads`` weight matrices per layer mixed by a translation-invariant softmax, any ``heads``;
     parameters ``convN.lin.weight``, ``convN.u.weight``, ``convN.c``, ``convN.bias``); ``conv="edge"`` builds them from
     :class:`nn_ops.EdgeConv` over ``nn.Linear(2 * in, out)`` (static EdgeConv: the maximum over the neighbourhood of a linear
-    edge function; parameters ``convN.nn.weight``, ``convN.nn.bias``).  The fused engine, the trainer, the CLI,
+    edge function; parameters ``convN.nn.weight``, ``convN.nn.bias``); ``conv="gmm", K=3`` builds them from
+    :class:`nn_ops.GMMConv` with ``dim=3`` and ``kernel_size=K`` (MoNet: K Gaussians over per-edge pseudo-coordinates weigh K
+    weight matrices; parameters ``convN.g``, ``convN.mu``, ``convN.sigma``, ``convN.root.weight``, ``convN.bias``).  Its
+    pseudo-coordinates are the dataset's ``edge_attr`` (vertex graph) / ``face_attr`` (face graph) when it has them, else
+    ``nn_ops.cartesian_pseudo`` of the smoothed vertex positions / the noisy face centroids, computed once and cached on the
+    dataset.  The fused engine, the trainer, the CLI,
     the partitioned path and bf16 features are GCN-only: ``fused=True`` with any other ``conv`` raises.
 
 The reference's unused ``torch.randn(V,3)*1e-5`` draw (``util/networks.py:50``) is dropped: it only
@@ -39,7 +44,7 @@ import torch.nn as nn
 
 from . import ops
 from .engine import ArenaLayout, GcnEngine, NORM_WIDTHS, POS_WIDTHS
-from .nn_ops import ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv
+from .nn_ops import ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv, GMMConv, cartesian_pseudo
 
 
 class _EngineFn(torch.autograd.Function):
@@ -261,7 +266,8 @@ class NormalNetFused(_FusedNet):
 
 
 # -------------------------------------------------------------------------------- operator-level form
-_CONVS = ("gcn", "cheb", "gat", "feast", "edge")
+_CONVS = ("gcn", "cheb", "gat", "feast", "edge", "gmm")
+_CONV_MSG = "conv must be 'gcn', 'cheb', 'gat', 'feast', 'edge' or 'gmm', got %r"
 
 
 class _ModularNet(nn.Module):
@@ -272,7 +278,7 @@ class _ModularNet(nn.Module):
         self.device = torch.device(device)
         h = self._widths
         if conv not in _CONVS:
-            raise ValueError("conv must be 'gcn', 'cheb', 'gat', 'feast' or 'edge', got %r" % (conv,))
+            raise ValueError(_CONV_MSG % (conv,))
         if conv == "gat":
             bad = [w for w in h[1:13] if not isinstance(heads, int) or heads < 1 or w % heads]
             if bad:
@@ -284,6 +290,8 @@ class _ModularNet(nn.Module):
                 layer = FeaStConv(h[i], h[i + 1], heads=heads)
             elif conv == "edge":
                 layer = EdgeConv(nn.Linear(2 * h[i], h[i + 1]))
+            elif conv == "gmm":
+                layer = GMMConv(h[i], h[i + 1], dim=3, kernel_size=K)
             else:
                 layer = GCNConv(h[i], h[i + 1]) if conv == "gcn" else ChebConv(h[i], h[i + 1], K)
             setattr(self, "conv%d" % (i + 1), layer)
@@ -292,6 +300,7 @@ class _ModularNet(nn.Module):
         for i in range(12):
             setattr(self, "bn%d" % (i + 1), nn.BatchNorm1d(h[i + 1]))
         self.l_relu = nn.LeakyReLU()
+        self.conv_kind = conv
         self.to(self.device)
 
     def _dev(self, data, name):
@@ -307,10 +316,13 @@ class _ModularNet(nn.Module):
             cache[(name, str(self.device))] = hit
         return hit[2]
 
-    def _trunk(self, x, edge_index, edge_weight=None):
+    def _trunk(self, x, edge_index, edge_weight=None, pseudo=None):
         for i in range(1, 13):
             conv = getattr(self, "conv%d" % i)
-            y = conv(x, edge_index) if edge_weight is None else conv(x, edge_index, edge_weight)
+            if pseudo is not None:
+                y = conv(x, edge_index, pseudo)
+            else:
+                y = conv(x, edge_index) if edge_weight is None else conv(x, edge_index, edge_weight)
             x = self.l_relu(getattr(self, "bn%d" % i)(y))
         return x
 
@@ -325,12 +337,30 @@ class _ModularNet(nn.Module):
         return self._dev(data, name)
 
 
+    def _pseudo(self, data, name, pos, edge_index, cols=None):
+        """Pseudo-coordinates of ``conv="gmm"`` (None for every other operator): the dataset's ``name`` attribute when it has
+        one, else ``cartesian_pseudo(pos[:, :cols], edge_index)`` computed once and kept on the dataset like ``_dev``'s copies
+        (keyed on the identity and version of the two tensors it was computed from)."""
+        if self.conv_kind != "gmm":
+            return None
+        if getattr(data, name, None) is not None:
+            return self._weight(data, name)
+        cache = data.__dict__.setdefault("_ddmp_dev", {})
+        key = ("cartesian:" + name, str(self.device))
+        hit = cache.get(key)
+        if hit is None or hit[0] is not pos or hit[1] is not edge_index or hit[2] != (pos._version, edge_index._version):
+            with torch.no_grad():
+                hit = (pos, edge_index, (pos._version, edge_index._version), cartesian_pseudo(pos if cols is None else pos[:, :cols], edge_index).contiguous())
+            cache[key] = hit
+        return hit[3]
+
+
 class PosNetModular(_ModularNet):
     _widths = POS_WIDTHS
 
     def forward(self, data):
         z1, x_pos, edge_index = self._dev(data, "z1"), self._dev(data, "x_pos"), self._dev(data, "edge_index")
-        dx = self._trunk(z1, edge_index, self._weight(data, "edge_weight"))
+        dx = self._trunk(z1, edge_index, self._weight(data, "edge_weight"), self._pseudo(data, "edge_attr", x_pos, edge_index))
         dx = self.linear2(self.l_relu(self.linear1(dx)))
         return x_pos + dx
 
@@ -340,7 +370,7 @@ class NormalNetModular(_ModularNet):
 
     def forward(self, data):
         z2, edge_index = self._dev(data, "z2"), self._dev(data, "face_index")
-        dx = self._trunk(z2, edge_index, self._weight(data, "face_weight"))
+        dx = self._trunk(z2, edge_index, self._weight(data, "face_weight"), self._pseudo(data, "face_attr", z2, edge_index, cols=3))
         dx = torch.tanh(self.linear2(self.l_relu(self.linear1(dx))))
         dx_norm = torch.reciprocal(torch.norm(dx, dim=1, keepdim=True).expand(-1, 3) + 1.0e-12)
         return torch.mul(dx, dx_norm)
@@ -348,7 +378,7 @@ class NormalNetModular(_ModularNet):
 
 def _make_net(fused_cls, modular_cls, device, fused, conv, K, heads, kw):
     if conv not in _CONVS:
-        raise ValueError("conv must be 'gcn', 'cheb', 'gat', 'feast' or 'edge', got %r" % (conv,))
+        raise ValueError(_CONV_MSG % (conv,))
     if fused:
         if conv != "gcn":
             raise ValueError("conv=%r needs fused=False: the fused engine (and with it the trainer, the CLI, the partitioned "

@@ -1,4 +1,4 @@
-"""Drop-in ``GCNConv``, ``ChebConv``, ``GATConv``, ``FeaStConv`` and ``EdgeConv`` on the HIP kernels.
+"""Drop-in ``GCNConv``, ``ChebConv``, ``GATConv``, ``FeaStConv``, ``EdgeConv`` and ``GMMConv`` on the HIP kernels.
 
 Same constructor / call signature, parameter names and initialisation as
 ``torch_geometric.nn.GCNConv`` 2.2.0 with the defaults the reference uses
@@ -102,6 +102,33 @@ could not be checked against it; the pin is the float64 restatement ``tests/edge
 * refused with ``ValueError`` before any launch: any other ``nn`` (an arbitrary MLP; a ``Linear`` whose ``in_features`` is odd),
   ``aggr != "max"``, a tuple ``x`` (bipartite), bf16 features, an ``x`` that is not [N, in].  Not implemented:
   ``DynamicEdgeConv`` / kNN graphs.
+
+``GMMConv(in_channels, out_channels, dim, kernel_size, separate_gaussians=False, aggr="mean", root_weight=True, bias=True)``,
+``forward(x, edge_index, edge_attr, size=None)`` restates ``torch_geometric.nn.GMMConv`` 2.2.0 (Monti et al., MoNet, CVPR 2017;
+like the operators above: written from the published source from memory -- PyG cannot be installed here, so this could not be
+checked against it; the pin is the float64 restatement ``tests/gmm_ref.py``).  It is the one operator here that consumes the
+GEOMETRY of an edge: ``edge_attr`` holds per-edge pseudo-coordinates ([E, dim]; ``cartesian_pseudo`` below restates PyG's
+``Cartesian`` transform).
+
+* parameters ``g`` [in, K * out], ``mu`` / ``sigma`` [K, dim] and ``root.weight`` [out, in] (no bias; absent with
+  ``root_weight=False``), all Glorot-uniform; ``bias`` [out] zeros, or None.  K = ``kernel_size``.
+* ``Hf = x g`` viewed [N, K, out]; for an edge t: j -> i with pseudo-coordinates ``a_t``
+  ``gamma_t[k] = exp(-1/2 sum_d (a_t[d] - mu[k,d])^2 / (1e-15 + sigma[k,d]^2))`` and
+  ``out[i] = (1 / deg_i) sum_{t -> i} sum_k gamma_t[k] Hf[j,k,:] + root(x_i) + bias`` with ``deg_i`` the number of edges with
+  target i (duplicates each count).  No self loops are added, an explicit loop is an ordinary edge, a node without incoming edges
+  gets ``root(x_i) + bias``.
+* one GEMM against the packed ``[g^T ; root.weight]`` for the row buffer ``[Hf | R]``, one launch for the Gaussians + gather + root
+  + bias (``ops.gmm_fwd``), two for the backward of the graph part (``ops.gmm_bwd_edge`` / ``ops.gmm_bwd_node``; the second also
+  copies the output gradient into the root block of the ``[dHf | dR]`` row buffer), the column reduction ``ops.feast_dc`` for
+  ``[dmu | dsigma]``, one wgrad GEMM for ``[dg^T ; droot]`` and one dgrad GEMM for ``dx``.  No [E, K * out] tensor and no
+  ``index_add_`` exist at any point.  The graph is GATConv's without loops: ``ops.graph_for(edge_index, N, norm="gat",
+  add_self_loops=False)``, same handle and cache key; a coalesced entry sums the Gaussians of its input edges in input order, so
+  duplicate edges with different pseudo-coordinates are exact.  Symmetric edge STRUCTURE only.
+* differentiable w.r.t. x, ``g``, ``mu``, ``sigma``, ``root.weight`` and ``bias``, and w.r.t. ``edge_attr`` when it requires grad;
+  float32, bitwise reproducible.
+* refused with ``ValueError`` before any launch: ``separate_gaussians=True``, ``aggr != "mean"``, tuple ``in_channels`` or a tuple
+  ``x`` (bipartite), ``size``, bf16 features, ``edge_attr`` missing, not [E, dim] or not float32 / float64 (float64 is rounded to
+  float32 once), ``kernel_size < 1``, ``dim < 1``, ``2 * kernel_size * dim > 256``.
 """
 from __future__ import annotations
 
@@ -657,6 +684,165 @@ class FeaStConv(nn.Module):
 
     def extra_repr(self):
         return "%d, %d, heads=%d" % (self.in_channels, self.out_channels, self.heads)
+
+
+class _GMMConvFn(torch.autograd.Function):
+    """ONE GEMM against the packed weight [g^T ; root.weight] (rows padded to a multiple of 4) gives the row buffer [Hf | R], then
+    ONE launch for the per-edge Gaussians + gather + root + bias (``ops.gmm_fwd``).  Saved: the padded x, the packed weight, the
+    [Hf | R] buffer, w [entries, K], the float32 pseudo-coordinates (and mu / sigma).  Backward: the edge-side launch (per-row
+    partials of dmu / dsigma, dattr when wanted), the node-side launch that writes [dHf | dOut] into one row buffer, the column sum
+    of the partials, then ONE wgrad GEMM ([dg^T ; droot]) and ONE dgrad GEMM (dx)."""
+
+    @staticmethod
+    def forward(ctx, x, g, mu, sigma, root, bias, attr, graph, K):
+        cin, hc = g.shape
+        C = hc // K
+        wt = hc + (C if root is not None else 0)
+        wtp = (wt + 3) // 4 * 4
+        xp = _pad_cols(x.detach().to(torch.float32))
+        wp = torch.zeros((wtp, xp.shape[1]), dtype=torch.float32, device=x.device)
+        wp[:hc, :cin] = g.detach().t()
+        if root is not None:
+            wp[hc:wt, :cin] = root.detach()
+        buf = ops.gemm_nt(xp, wp)                                # [N, wtp]: Hf | R | zero padding
+        b = None if bias is None else bias.detach().contiguous()
+        a32 = attr.detach().to(torch.float32).contiguous()       # (float64 pseudo-coordinates are rounded once)
+        m, s = mu.detach().contiguous(), sigma.detach().contiguous()
+        y, w = ops.gmm_fwd(graph, buf[:, :hc], a32, m, s, K, root=buf[:, hc:wt] if root is not None else None, bias=b)
+        ctx.save_for_backward(xp, wp, buf, w, a32, m, s)
+        ctx.graph, ctx.dims, ctx.has_bias, ctx.attr_dtype = graph, (cin, K, hc, wt), bias is not None, attr.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        with ops.on_device(dy):
+            return _GMMConvFn._backward(ctx, dy)
+
+    @staticmethod
+    def _backward(ctx, dy):
+        xp, wp, buf, w, a32, m, s = ctx.saved_tensors
+        graph, (cin, K, hc, wt) = ctx.graph, ctx.dims
+        wtp, kd = wp.shape[0], m.numel()
+        dy = dy.contiguous().to(torch.float32)
+        db = None
+        if ctx.has_bias and ctx.needs_input_grad[5]:
+            cout = dy.shape[1]
+            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
+            db = ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+        parts, dattr = ops.gmm_bwd_edge(graph, dy, buf[:, :hc], a32, m, s, K, want_dattr=ctx.needs_input_grad[6])
+        gb = torch.empty((dy.shape[0], wtp), dtype=torch.float32, device=dy.device)
+        if wtp != wt:
+            gb[:, wt:] = 0
+        ops.gmm_bwd_node(graph, dy, w, K, out=gb, root=wt != hc)  # gb = [dHf | dOut | 0]
+        dmu = dsigma = None
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            dms = ops.feast_dc(parts, 2 * kd)                    # [dmu | dsigma]
+            dmu, dsigma = dms[:kd].view_as(m), dms[kd:].view_as(s)
+        dg = droot = None
+        if ctx.needs_input_grad[1] or (wt != hc and ctx.needs_input_grad[4]):
+            dwp = ops.gemm_tn(gb, xp)                            # [dg^T ; droot]
+            dg = dwp[:hc, :cin].t()
+            droot = dwp[hc:wt, :cin] if wt != hc else None
+        dx = ops.gemm_nn(gb, wp)[:, :cin] if ctx.needs_input_grad[0] else None
+        if dattr is not None:
+            dattr = dattr.to(ctx.attr_dtype)
+        return dx, dg, dmu, dsigma, droot, db, dattr, None, None
+
+
+class GMMConv(nn.Module):
+    """``torch_geometric.nn.GMMConv`` 2.2.0 (Monti et al., MoNet, CVPR 2017) on the HIP kernels, with
+    ``separate_gaussians=False`` and mean aggregation: parameters ``g`` [in, K * out], ``mu`` / ``sigma`` [K, dim], ``root.weight``
+    [out, in] (absent with ``root_weight=False``), all Glorot-uniform, and ``bias`` [out] zeros.  With ``Hf = x g`` viewed
+    [N, K, out] and an edge t: j -> i with pseudo-coordinates ``a_t``:
+    ``gamma_t[k] = exp(-1/2 sum_d (a_t[d] - mu[k,d])^2 / (1e-15 + sigma[k,d]^2))``,
+    ``out[i] = (1 / deg_i) sum_{t -> i} sum_k gamma_t[k] Hf[j,k,:] + root(x_i) + bias``; no self loops are added, duplicate edges
+    each count, a node without incoming edges gets ``root(x_i) + bias``.  Written from the published PyG source from memory --
+    PyG cannot be installed here, so this could not be checked against it; the pin is the float64 restatement
+    ``tests/gmm_ref.py``.  Differentiable w.r.t. x, every parameter, and ``edge_attr`` when it requires grad."""
+
+    def __init__(self, in_channels, out_channels: int, dim: int, kernel_size: int, separate_gaussians: bool = False,
+                 aggr: str = "mean", root_weight: bool = True, bias: bool = True, **kwargs):
+        super().__init__()
+        if isinstance(in_channels, (tuple, list)):
+            raise ValueError("GMMConv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
+        if separate_gaussians:
+            raise ValueError("GMMConv: separate_gaussians=True is not implemented on the HIP path")
+        if aggr != "mean":
+            raise ValueError("GMMConv: only aggr='mean' is implemented on the HIP path, got %r" % (aggr,))
+        if kwargs:
+            raise TypeError("GMMConv: unexpected keyword arguments %s" % sorted(kwargs))
+        for name, v in (("kernel_size", kernel_size), ("dim", dim)):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+                raise ValueError("GMMConv: %s must be an integer >= 1, got %r" % (name, v))
+        if 2 * kernel_size * dim > 256:
+            raise ValueError("GMMConv: 2 * kernel_size * dim must be <= 256 on the HIP path (the dmu / dsigma reduction), got %d"
+                             % (2 * kernel_size * dim))
+        self.in_channels, self.out_channels, self.dim, self.kernel_size = in_channels, out_channels, dim, kernel_size
+        self.separate_gaussians, self.aggr = False, aggr
+        self.g = nn.Parameter(torch.empty(in_channels, kernel_size * out_channels))
+        self.mu = nn.Parameter(torch.empty(kernel_size, dim))
+        self.sigma = nn.Parameter(torch.empty(kernel_size, dim))
+        if root_weight:
+            self.root = _Lin(in_channels, out_channels)
+        else:
+            self.register_parameter("root", None)
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        glorot = lambda t: t.uniform_(-math.sqrt(6.0 / (t.shape[-2] + t.shape[-1])), math.sqrt(6.0 / (t.shape[-2] + t.shape[-1])))
+        with torch.no_grad():
+            glorot(self.g)
+            glorot(self.mu)
+            glorot(self.sigma)
+            if self.root is not None:
+                glorot(self.root.weight)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def forward(self, x, edge_index, edge_attr=None, size=None) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present); ``edge_attr``: [E, dim]
+        pseudo-coordinates, float32 or float64 (rounded to float32 once)."""
+        if isinstance(x, (tuple, list)):
+            raise ValueError("GMMConv: a tuple x (bipartite graphs) is not implemented on the HIP path")
+        if size is not None:
+            raise ValueError("GMMConv: size is not implemented on the HIP path")
+        if x.dtype == torch.bfloat16:
+            raise ValueError("GMMConv: bf16 features are not supported on the HIP path")
+        if x.dim() != 2 or x.shape[1] != self.in_channels:
+            raise ValueError("GMMConv: expected x of shape [N, %d]" % self.in_channels)
+        if not isinstance(edge_attr, torch.Tensor):
+            raise ValueError("GMMConv: edge_attr (the pseudo-coordinates, [E, %d]) is required" % self.dim)
+        if edge_attr.dim() != 2 or tuple(edge_attr.shape) != (edge_index.shape[1], self.dim):
+            raise ValueError("GMMConv: edge_attr must be [%d, %d], got %s" % (edge_index.shape[1], self.dim, tuple(edge_attr.shape)))
+        if edge_attr.dtype not in (torch.float32, torch.float64):
+            raise ValueError("GMMConv: edge_attr must be float32 or float64, got %s" % edge_attr.dtype)
+        if not x.is_cuda or not edge_attr.is_cuda:
+            raise ops.DdmpError("GMMConv runs on the HIP path only: x and edge_attr must be CUDA (ROCm) tensors, there is no CPU "
+                                "fallback")
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
+            return _GMMConvFn.apply(x, self.g, self.mu, self.sigma, None if self.root is None else self.root.weight, self.bias,
+                                    edge_attr, graph, self.kernel_size)
+
+    def extra_repr(self):
+        return "%d, %d, dim=%d, kernel_size=%d" % (self.in_channels, self.out_channels, self.dim, self.kernel_size)
+
+
+def cartesian_pseudo(pos: torch.Tensor, edge_index: torch.Tensor, norm: bool = True, max_value=None) -> torch.Tensor:
+    """PyG's ``Cartesian`` transform in plain torch (any device; it runs once per mesh, not on the hot path):
+    ``pos[edge_index[0]] - pos[edge_index[1]]`` per edge; with ``norm`` divided by ``2 * max|.|`` (or by ``2 * max_value``) and
+    shifted by 0.5, i.e. into [0, 1]."""
+    cart = pos[edge_index[0]] - pos[edge_index[1]]
+    if cart.dim() == 1:
+        cart = cart.view(-1, 1)
+    if norm and cart.numel() > 0:
+        m = cart.abs().max() if max_value is None else max_value
+        cart = cart / (2 * m) + 0.5
+    return cart
 
 
 class _EdgeConvFn(torch.autograd.Function):

@@ -888,6 +888,112 @@ def feast_dc(rs, heads):
     return dc
 
 
+# ---------------------------------------------------------------------------------------- Gaussian-mixture convolution
+GMM_MAX_KD = 128            # K * dim: the [n, 2 K dim] partials of the edge-side backward go through feast_dc (<= 256 columns)
+
+
+def _gmm_graph(g: Graph):
+    _gat_graph(g)
+    if g.valued != GV_VALUED:
+        raise DdmpError("the Gaussian-mixture kernels need the graph of graph_for(edge_index, n, norm='gat', add_self_loops=False): "
+                        "every input edge must belong to exactly one entry")
+    return g
+
+
+def _gmm_params(g, attr, mu, sigma, K):
+    """-> (attr, mu, sigma, dim) checked: attr contiguous float32 [g.nnz_in, dim], mu / sigma contiguous float32 [K, dim]."""
+    _chk(attr, torch.float32, "attr")
+    if attr.dim() != 2 or attr.shape[0] != g.nnz_in or attr.shape[1] < 1 or not attr.is_contiguous():
+        raise DdmpError("attr must be a contiguous float32 [%d, dim] (one row per input edge), got %s" % (g.nnz_in, tuple(attr.shape)))
+    dim = attr.shape[1]
+    if K < 1 or K * dim > GMM_MAX_KD:
+        raise DdmpError("K (%d) x dim (%d) must be in [1, %d]" % (K, dim, GMM_MAX_KD))
+    return attr, _gat_arr(mu, (K, dim), "mu"), _gat_arr(sigma, (K, dim), "sigma"), dim
+
+
+def gmm_fwd(g: Graph, hf, attr, mu, sigma, K, root=None, bias=None, out=None):
+    """Per-edge Gaussians + gather in one launch (``ddmp_gmm_fwd_f32``) -> (y [n, C], w [g.nnz, K]).  ``hf``: [n, K * C], ``root``:
+    [n, C] added per row or None (both may be column blocks of one row buffer), ``attr``: [g.nnz_in, dim] pseudo-coordinates of
+    the input edges, ``mu`` / ``sigma``: [K, dim], ``bias``: float32 [C] or None."""
+    _gmm_graph(g)
+    n = g.n_rows
+    hf, ldh, C = _gat_hf(hf, K, "hf", n)
+    attr, mu, sigma, dim = _gmm_params(g, attr, mu, sigma, K)
+    ldr = 0
+    if root is not None:
+        root, ldr = _feast_p(root, C, "root", n)
+    if bias is not None:
+        bias = _gat_arr(bias, (C,), "bias")
+    if out is None:
+        out = torch.empty((n, C), dtype=torch.float32, device=hf.device)
+    out, ldy = _mat(_chk(out, torch.float32, "out"), "out")
+    if out.shape[0] < n or out.shape[1] != C:
+        raise DdmpError("gmm_fwd: out must be [%d, %d]" % (n, C))
+    w = torch.empty((g.nnz, K), dtype=torch.float32, device=hf.device)
+    # algorithmic bytes: every gathered row (K * C wide) read once, the output row (C wide) written once, the root block read, w
+    # written, the attribute rows read once, col + multiplicity + ee_ptr, ee_idx, rowptr
+    alg = (4.0 * n * (K + 1 + (root is not None)) * C + 4.0 * g.nnz * K + 4.0 * g.nnz_in * (dim + 1) + 12.0 * g.nnz + 4.0 * (n + 1))
+    with _timed("gmm_fwd", _gat_key(g, K, C) + (dim,), alg, 2.0 * g.nnz * K * C,
+                survey=4.0 * n * (K + 1) * C + 4.0 * g.nnz + 4.0 * (n + 1)):
+        st = _lib.lib().ddmp_gmm_fwd_f32(g.handle, _p(hf), ldh, _p(attr), dim, _p(mu), _p(sigma), K, C, _p(root), ldr, _p(bias),
+                                         _p(w), _p(out), ldy, _stream())
+    check(st, "ddmp_gmm_fwd_f32")
+    return out, w
+
+
+def gmm_bwd_edge(g: Graph, dout, hf, attr, mu, sigma, K, want_dattr=False):
+    """Edge side of the backward (``ddmp_gmm_bwd_edge_f32``) -> (parts [n, 2 * K * dim], dattr [g.nnz_in, dim] | None).  The column
+    sums of ``parts`` (``feast_dc(parts, 2 * K * dim)``) are [dmu | dsigma], each [K, dim] flattened.  ``dout``: [n, C]."""
+    _gmm_graph(g)
+    n = g.n_rows
+    hf, ldh, C = _gat_hf(hf, K, "hf", n)
+    dout, lddo = _mat(_chk(dout, torch.float32, "dout"), "dout")
+    if dout.shape[0] < n or dout.shape[1] != C:
+        raise DdmpError("gmm_bwd_edge: dout must be [>= %d, %d], got %s" % (n, C, tuple(dout.shape)))
+    attr, mu, sigma, dim = _gmm_params(g, attr, mu, sigma, K)
+    ge = torch.empty((g.nnz, K), dtype=torch.float32, device=hf.device)
+    parts = torch.empty((n, 2 * K * dim), dtype=torch.float32, device=hf.device)
+    dattr = torch.empty((g.nnz_in, dim), dtype=torch.float32, device=hf.device) if want_dattr else None
+    # algorithmic bytes: hf and dout read once each, the dot products written and read back, the attribute rows read (and their
+    # gradient written), the partials written, col + multiplicity + ee_ptr, ee_idx, rowptr
+    alg = (4.0 * n * (K + 1) * C + 8.0 * g.nnz * K + 4.0 * g.nnz_in * (dim * (2 if want_dattr else 1) + 1) + 8.0 * n * K * dim
+           + 12.0 * g.nnz + 4.0 * (n + 1))
+    with _timed("gmm_bwd_edge", _gat_key(g, K, C) + (dim,), alg, 2.0 * g.nnz * K * C):
+        st = _lib.lib().ddmp_gmm_bwd_edge_f32(g.handle, _p(dout), lddo, _p(hf), ldh, _p(attr), dim, _p(mu), _p(sigma), K, C, _p(ge),
+                                              _p(parts), _p(dattr), _stream())
+    check(st, "ddmp_gmm_bwd_edge_f32")
+    return parts, dattr
+
+
+def gmm_bwd_node(g: Graph, dout, w, K, out=None, root=False):
+    """Node side of the backward (``ddmp_gmm_bwd_node_f32``) -> (dhf [n, K * C] written completely, droot [n, C] | None): with
+    ``root`` the launch also copies ``dout`` into the root block's columns.  ``out``: a float32 [n, >= K * C (+ C)] row buffer that
+    receives [dhf | droot] in its leading columns (the results are then views of it; further columns are left untouched); None: a
+    buffer of its own."""
+    _gmm_graph(g)
+    n = g.n_rows
+    dout, lddo = _mat(_chk(dout, torch.float32, "dout"), "dout")
+    C = dout.shape[1]
+    if dout.shape[0] < n or C < 1:
+        raise DdmpError("gmm_bwd_node: dout must be [>= %d, C], got %s" % (n, tuple(dout.shape)))
+    w = _gat_arr(w, (g.nnz, K), "w")
+    hc = K * C
+    wt = hc + (C if root else 0)
+    if out is None:
+        out = torch.empty((n, wt), dtype=torch.float32, device=dout.device)
+    out, _ = _mat(_chk(out, torch.float32, "out"), "out")
+    if out.shape[0] != n or out.shape[1] < wt:
+        raise DdmpError("gmm_bwd_node: out must be [%d, >= %d], got %s" % (n, wt, tuple(out.shape)))
+    dhf, lddh = _mat(out[:, :hc], "dhf")
+    dr, lddr = _mat(out[:, hc:wt], "droot") if root else (None, 0)
+    # algorithmic bytes: dout read once, dhf (and the root block) written, w read through the mirror map, col + mirror, rowptr
+    alg = 4.0 * n * (K + 1 + bool(root)) * C + 4.0 * g.nnz * K + 8.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("gmm_bwd_node", _gat_key(g, K, C), alg, 2.0 * g.nnz * K * C):
+        st = _lib.lib().ddmp_gmm_bwd_node_f32(g.handle, _p(dout), lddo, K, C, _p(w), _p(dhf), lddh, _p(dr), lddr, _stream())
+    check(st, "ddmp_gmm_bwd_node_f32")
+    return dhf, dr
+
+
 # ---------------------------------------------------------------------------------------- max aggregation (DESIGN.md 4.10)
 def _gmax_mat(t, name, rows, C=None):
     """[>= rows, C] float32 matrix (a column block of a wider row buffer is fine) -> (tensor, ld)."""

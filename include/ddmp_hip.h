@@ -245,6 +245,38 @@ size_t ddmp_feast_dc_workspace_bytes(int64_t n_rows, int heads);
 int ddmp_feast_dc_f32(const float* rs, int64_t n_rows, int heads, float* dc, void* workspace, size_t workspace_bytes,
                       ddmp_stream stream);
 
+/* ------------------------------------------------------------------ Gaussian-mixture convolution (torch_geometric GMMConv, mean
+ * aggregation, separate_gaussians=False).  float32.  Hf is the projected feature matrix [n, K * C] (component-major
+ * columns); attr holds the pseudo-coordinates of the INPUT edges, contiguous [input edges, dim], in the order of the edge list the
+ * graph was created from; mu and sigma are contiguous [K, dim].  The graph is the attention graph above created with flags 0 (no
+ * loop handling: every input edge belongs to exactly one entry) and left at its all-ones values; any other graph is DDMP_EINVAL.
+ * Per-entry arrays (w, ge) are entry-major [entries, K].  K * dim <= 128, so the [n, 2 K dim] partials fit ddmp_feast_dc_f32.
+ * No atomics, fixed summation orders: two calls give the same bits.  The vector kernels need C % 4 == 0, leading dimensions % 4 == 0
+ * and 16-byte aligned matrices; anything else takes scalar kernels.
+ *
+ * forward:   gamma_t[k] = exp(-1/2 sum_d (attr[t,d] - mu[k,d])^2 / (1e-15 + sigma[k,d]^2)) per input edge t (exp arguments <= 0),
+ *            w_e[k] = (1 / deg_i) sum_{t in the edges of entry e, input order} gamma_t[k] with deg_i = sum_{e in row i} a_e (written
+ *            to w, saved for the backward),
+ *            Y[i,:] = sum_{e in row i} sum_k w_e[k] Hf[col e, k, :] (+ R[i,:], nullable, own leading dimension) (+ bias[C], nullable).
+ *            Y is [n, C].  One launch.  A row without entries gets R[i,:] + bias. */
+int ddmp_gmm_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ldh, const float* attr, int dim, const float* mu,
+                     const float* sigma, int K, int C, const float* R /*nullable*/, int64_t ldr, const float* bias /*nullable*/,
+                     float* w, float* Y, int64_t ldy, ddmp_stream stream);
+/* backward, edge side:  G_e[k] = dOut[row e, :] . Hf[col e, k, :] -> ge [entries, K] (scratch of the call); with
+ *            c_t[k] = gamma_t[k] G_e[k] / deg_i and inv[k,d] = 1 / (1e-15 + sigma[k,d]^2), per ROW the sums over its entries' edges
+ *            parts[i, k dim + d]         = sum_t c_t[k] (attr[t,d] - mu[k,d]) inv[k,d]                      (the dmu terms)
+ *            parts[i, K dim + k dim + d] = sum_t c_t[k] (attr[t,d] - mu[k,d])^2 sigma[k,d] inv[k,d]^2       (the dsigma terms)
+ *            (an entry's edges in input order, the row's entries by a fixed xor tree per 8 in CSR order; a row without entries
+ *            writes zeros; dmu / dsigma are the column sums: ddmp_feast_dc_f32 with heads = 2 K dim), and, dattr non-null,
+ *            dattr[t,d] = - sum_k c_t[k] (attr[t,d] - mu[k,d]) inv[k,d] for every input edge ([input edges, dim]).  One launch. */
+int ddmp_gmm_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Hf, int64_t ldh, const float* attr,
+                          int dim, const float* mu, const float* sigma, int K, int C, float* ge, float* parts,
+                          float* dattr /*nullable*/, ddmp_stream stream);
+/* backward, node side:  dHf[j,k,:] = sum_{e' in row j} w[mirror e', k] dOut[col e', :] (written completely) and, dR non-null,
+ *            dR[j,:] = dOut[j,:] (the root block's gradient; dHf and dR are meant to be column blocks of one row buffer). */
+int ddmp_gmm_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, int K, int C, const float* w, float* dHf,
+                          int64_t lddh, float* dR /*nullable*/, int64_t lddr, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ max aggregation (torch_geometric EdgeConv with a Linear edge
  * function).  float32.  The graph is the attention graph above (a VALUED graph; its values are not read: the
  * structure is coalesced and a duplicate edge cannot change a maximum); an unvalued graph is DDMP_EINVAL.  Every matrix has its own

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|feast|edge|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|feast|edge|gmm|all] [--rows N] [--iters K]
+gmm (not part of all): the Gaussian-mixture launches (ops.gmm_fwd, gmm_bwd_edge, gmm_bwd_node and the feast_dc column sum of the
+[N, 2 K dim] partials) with dim = 3 on the same torus without loops, each alternating in one loop with the valued
+ops.spmm at the gathered width K * C and with the feast_* launch of the same role at the same (heads, C); the figures and the
+algorithmic byte counts go to --out (profiles/gmm_microbench.txt).
 edge (not part of all): the two max-aggregation launches (ops.gather_max with and without arg, ops.gather_max_bwd)
 at C = 64, 128, 512 on the same torus without loops, against the valued ops.spmm at the same width, alternating in one loop; the
 figures and the algorithmic byte counts go to --out (profiles/edge_microbench.txt).
@@ -38,7 +42,7 @@ ap.add_argument("--widths", default="512,256,128,64,32")
 ap.add_argument("--rotate", type=int, default=1, help="spmm: cycle through this many (input, output) buffer sets so that narrow "
                 "widths are not served from the 256 MB MALL (a 1M x 32 float tensor is 128 MB)")
 ap.add_argument("--weighted", action="store_true", help="spmm: valued graph against the unvalued graph of the same mesh")
-ap.add_argument("--out", default=None, help="gat / feast / edge: the file the figures are written to (default profiles/<what>_microbench.txt)")
+ap.add_argument("--out", default=None, help="gat / feast / edge / gmm: the file the figures are written to (default profiles/<what>_microbench.txt)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 n = a.rows
@@ -447,5 +451,76 @@ if a.what == "edge":
         print("\n".join(lines[-5:]), flush=True)
         del Bs, As, Xs, Ds, Out, G, args
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "edge_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.what == "gmm":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    g = ops.graph_for(ei, nn_, norm="gat", add_self_loops=False)
+    reps = max(a.iters, 20)
+    dim = 3
+    lines = ["Gaussian-mixture convolution (GMMConv, dim = %d) on the vertex graph of torus(%d, %d) in RCB order: N=%d, entries=%d "
+             "(no loops), input edges=%d, float32; median of %d launches [min q1 q3 max], one HIP-event pair per launch, forms "
+             "alternating in one loop, rotating buffer sets; the valued spmm gathers rows of the same width K * C, feast_* are the "
+             "feature-steered launches of the same role at heads = K on the same graph; [Hf | R] and [dHf | dR] are one row buffer "
+             "each; bytes = the algorithmic counts of ops.py (MB)" % (dim, nu_, nv_, nn_, g.nnz, g.nnz_in, reps)]
+    print(lines[0], flush=True)
+    attr = torch.rand(g.nnz_in, dim, device=dev)
+    for K, C in ((4, 128), (8, 32), (1, 64), (8, 4)):
+        hc, kd = K * C, K * dim
+        wt = hc + C                                              # the operator's row buffers: [Hf | R], [dHf | dR]
+        R = 2 if nn_ * hc * 4 >= (1 << 29) else 4
+        Bs = [torch.randn(nn_, wt, device=dev) for _ in range(R)]
+        Hs, Rs = [b[:, :hc] for b in Bs], [b[:, hc:] for b in Bs]
+        Ps = [torch.randn(nn_, K, device=dev) for _ in range(R)]
+        Ds = [torch.randn(nn_, C, device=dev) for _ in range(R)]
+        mu, sigma = torch.rand(K, dim, device=dev), 0.3 + 0.7 * torch.rand(K, dim, device=dev)
+        cvec, bias = torch.randn(K, device=dev) * 0.5, torch.randn(C, device=dev)
+        Out, Wide, G = torch.empty(nn_, C, device=dev), torch.empty(nn_, hc, device=dev), torch.empty(nn_, wt, device=dev)
+        Gf = torch.empty(nn_, (hc + K + 3) // 4 * 4, device=dev)   # feast's [dHf | dP | padding]
+        st = []
+        for i in range(R):                                       # the saved state of a forward per buffer set
+            y, w = ops.gmm_fwd(g, Hs[i], attr, mu, sigma, K, root=Rs[i], bias=bias)
+            parts, _ = ops.gmm_bwd_edge(g, Ds[i], Hs[i], attr, mu, sigma, K)
+            y, beta = ops.feast_fwd(g, Hs[i], Ps[i], cvec, K, bias=bias)
+            dz, rs = ops.feast_bwd_edge(g, Ds[i], Hs[i], beta, K)
+            st.append((w, parts, beta, dz, rs))
+            del y
+        q = alternate({
+            "spmm": lambda i: ops.spmm(g, Hs[i], out=Wide),
+            "fwd": lambda i: ops.gmm_fwd(g, Hs[i], attr, mu, sigma, K, root=Rs[i], bias=bias, out=Out),
+            "feast_fwd": lambda i: ops.feast_fwd(g, Hs[i], Ps[i], cvec, K, bias=bias, out=Out),
+            "bwd_edge": lambda i: ops.gmm_bwd_edge(g, Ds[i], Hs[i], attr, mu, sigma, K),
+            "bwd_edge+dattr": lambda i: ops.gmm_bwd_edge(g, Ds[i], Hs[i], attr, mu, sigma, K, want_dattr=True),
+            "feast_bwd_edge": lambda i: ops.feast_bwd_edge(g, Ds[i], Hs[i], st[i][2], K),
+            "bwd_node": lambda i: ops.gmm_bwd_node(g, Ds[i], st[i][0], K, out=G, root=True),
+            "feast_bwd_node": lambda i: ops.feast_bwd_node(g, Ds[i], st[i][2], st[i][3], st[i][4], K, out=Gf),
+            "dc": lambda i: ops.feast_dc(st[i][1], 2 * kd)}, reps, R)
+        wide, narrow, ent, node, edges = 4.0 * nn_ * hc, 4.0 * nn_ * C, 4.0 * g.nnz, 4.0 * nn_, 4.0 * g.nnz_in
+        alg = {"spmm": 2 * wide + ent + 2 * node,
+               "fwd": wide + 3 * narrow + ent * K + edges * (dim + 1) + 3 * ent + node,
+               "feast_fwd": wide + narrow + ent * K + node * K + 2 * ent + node,
+               "bwd_edge": wide + narrow + 2 * ent * K + edges * (dim + 1) + 2 * node * kd + 3 * ent + node,
+               "bwd_edge+dattr": wide + narrow + 2 * ent * K + edges * (2 * dim + 1) + 2 * node * kd + 3 * ent + node,
+               "feast_bwd_edge": wide + narrow + 2 * ent * K + node * K + ent + node,
+               "bwd_node": wide + 2 * narrow + ent * K + 2 * ent + node,
+               "feast_bwd_node": wide + narrow + 2 * ent * K + 2 * node * K + 2 * ent + node,
+               "dc": 2 * node * kd}
+        pair = {"fwd": "feast_fwd", "bwd_edge": "feast_bwd_edge", "bwd_edge+dattr": "feast_bwd_edge", "bwd_node": "feast_bwd_node"}
+        lines.append("K=%d C=%d (gathered width %d, %d buffer sets):" % (K, C, hc, R))
+        for k in alg:
+            extra = ("  x%.2f of %s (bytes x%.2f)" % (q[k][2] / q[pair[k]][2], pair[k], alg[k] / alg[pair[k]])) if k in pair else ""
+            lines.append("  %-15s %s  %7.0f MB  %.2f TB/s alg  x%.2f of the valued spmm%s" % (
+                k, fmt(q[k]), alg[k] / 1e6, alg[k] / q[k][2] / 1e6, q[k][2] / q["spmm"][2], extra))
+        print("\n".join(lines[-(len(alg) + 1):]), flush=True)
+        del Bs, Hs, Rs, Ps, Ds, Out, Wide, G, Gf, st
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gmm_microbench.txt")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
