@@ -3,21 +3,18 @@
 //   q_e[h] = softmax over HEADS of (P[col e, h] - P[row e, h] + c[h]),  beta_e[h] = a_e q_e[h] / deg_i,  deg_i = sum_{row i} a_e,
 //   Y[i,:] = sum_{e in row i} sum_h beta_e[h] Hf[col e, h, :]  (+ bias)
 //
-// over the COALESCED CSR of a valued graph left at all-ones values (a_e = the multiplicity of the entry), the graph of gat.hip.
-// Work layout of gat.hip: a workgroup (4 waves) owns a chunk of 64 consecutive rows, blockIdx -> chunk XCD-aware; 8 lanes x float4
-// per row, 8 rows per wave step, two steps per chunk.  The difference from graph attention: the softmax runs over the heads of ONE
-// entry, and the heads are summed into one output row of width C.  With W = C / 4 float4 per head:
-//   * W in {1, 2, 4}: W lanes per head and 8 / W heads side by side (the 8 lanes cover one 128-byte slab of the gathered row); in the
-//     forward each lane sums its heads and the 8 / W partial rows are combined by a fixed xor tree;
-//   * any other W: the 8 lanes walk the W float4 of a head, 8 at a time, one head after the other.
+// over the COALESCED CSR of a valued graph left at all-ones values (a_e = the multiplicity of the entry), the graph of gat.hip, on
+// the row-gather layout with head passes (row_gather.h).  The difference from graph attention: the softmax runs over the heads of
+// ONE entry, and the heads are summed into one output row of width C.  With W = C / 4 float4 per head:
+//   * W in {1, 2, 4}: the 8 / W heads of a pass sit side by side; in the forward each lane sums its heads and the 8 / W partial rows
+//     are combined by a fixed xor tree;
+//   * any other W: one head after the other.
 // The factors beta (forward) and the dot products g (edge-side backward) are formed with the row's ENTRIES spread over the 8 lanes
 // (each lane takes all heads of its entry: the head softmax needs no shuffle), written to their per-entry arrays and read back by
-// the sibling lanes of the same wave after a workgroup-scope fence, as gat.hip's alpha is.  Entries are gathered 8 at a time with
-// the batch compiled per entry count (unconditional loads, all in flight together; a shorter row re-reads its last entry with
-// factor 0).  An output float4 is accumulated in registers over ALL entries and heads of its row before it is stored: the
-// 1200-entry hub row is exact like any other.  No atomics, no LDS, no barrier; every sum has a fixed order: bitwise reproducible.
-// Every row * stride product is int64.  Widths that are not a multiple of 4 (or unaligned operands) take scalar kernels: one
-// thread per row.  The layout's helpers and the three gather loops live in gather_mix.h, shared with gmm.hip.
+// the sibling lanes of the same wave after a workgroup-scope fence, as gat.hip's alpha is.  A shorter row's re-read last entry
+// enters with factor 0.  An output float4 is accumulated in registers over ALL entries and heads of its row before it is stored:
+// the 1200-entry hub row is exact like any other.  No LDS, no barrier in the gather kernels.  The three gather loops live in
+// gather_mix.h, shared with gmm.hip.
 #include "gather_mix.h"
 
 namespace {
@@ -42,7 +39,7 @@ __global__ __launch_bounds__(256) void feast_fwd_kernel(const int* __restrict__ 
                                                         const float* __restrict__ bias, float* beta, float* __restrict__ Y,
                                                         int64_t ldy, int n_rows, int heads, int C, int lw, int chunks_per_xcd,
                                                         int n_chunks) {
-    FEAST_CHUNK_PROLOGUE
+    HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
@@ -119,7 +116,7 @@ __global__ __launch_bounds__(256) void feast_bwd_edge_kernel(const int* __restri
                                                              const float* __restrict__ Hf, int64_t ldh,
                                                              const float* __restrict__ beta, float* dz, float* rs, int n_rows,
                                                              int heads, int C, int lw, int chunks_per_xcd, int n_chunks) {
-    FEAST_CHUNK_PROLOGUE
+    HEAD_CHUNK_PROLOGUE
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
         const int lr = wave * 8 + grp + qq * 32;
@@ -193,7 +190,7 @@ __global__ __launch_bounds__(256) void feast_bwd_node_kernel(const int* __restri
                                                              float* __restrict__ dHf, int64_t lddh, float* __restrict__ dP,
                                                              int64_t lddp, int n_rows, int heads, int C, int lw, int chunks_per_xcd,
                                                              int n_chunks) {
-    FEAST_CHUNK_PROLOGUE
+    HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
@@ -283,17 +280,17 @@ __global__ __launch_bounds__(1024) void feast_dc_final_kernel(const float* __res
 
 extern "C" int ddmp_feast_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ldh, const float* P, int64_t ldp, int heads, int C,
                                   const float* c, const float* bias, float* beta, float* Y, int64_t ldy, ddmp_stream stream) {
-    ARG_TRY(feast_graph_ok(g) && Hf && P && c && beta && Y && feast_dims_ok(heads, C) && ldh >= (int64_t)heads * C && ldp >= heads &&
+    ARG_TRY(attn_graph_ok(g) && Hf && P && c && beta && Y && feast_dims_ok(heads, C) && ldh >= (int64_t)heads * C && ldp >= heads &&
             ldy >= C && Y != Hf && Y != P);
     if (g->n_rows == 0) return DDMP_OK;
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)g->n_rows;
     if (C % 4 == 0 && ldh % 4 == 0 && ldy % 4 == 0 && al16(Hf) && al16(Y) && (!bias || al16(bias))) {
-        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
-        hipLaunchKernelGGL(feast_fwd_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh, P, ldp, c, bias, beta,
-                           Y, ldy, n, heads, C, lanes_per_head(C), cpx, n_chunks);
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(feast_fwd_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh, P, ldp, c, bias, beta,
+                           Y, ldy, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
     } else {
-        hipLaunchKernelGGL(feast_fwd_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh,
+        hipLaunchKernelGGL(feast_fwd_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh,
                            P, ldp, c, bias, beta, Y, ldy, n, heads, C);
     }
     LAUNCH_TRY();
@@ -302,17 +299,17 @@ extern "C" int ddmp_feast_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t 
 
 extern "C" int ddmp_feast_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Hf, int64_t ldh, int heads,
                                        int C, const float* beta, float* dz, float* rs, ddmp_stream stream) {
-    ARG_TRY(feast_graph_ok(g) && dOut && Hf && beta && dz && rs && feast_dims_ok(heads, C) && lddo >= C &&
+    ARG_TRY(attn_graph_ok(g) && dOut && Hf && beta && dz && rs && feast_dims_ok(heads, C) && lddo >= C &&
             ldh >= (int64_t)heads * C && dz != beta);
     if (g->n_rows == 0) return DDMP_OK;
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)g->n_rows;
     if (C % 4 == 0 && lddo % 4 == 0 && ldh % 4 == 0 && al16(dOut) && al16(Hf)) {
-        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
-        hipLaunchKernelGGL(feast_bwd_edge_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, dOut, lddo, Hf, ldh, beta, dz,
-                           rs, n, heads, C, lanes_per_head(C), cpx, n_chunks);
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(feast_bwd_edge_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, dOut, lddo, Hf, ldh, beta, dz,
+                           rs, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
     } else {
-        hipLaunchKernelGGL(feast_bwd_edge_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, dOut, lddo,
+        hipLaunchKernelGGL(feast_bwd_edge_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, dOut, lddo,
                            Hf, ldh, beta, dz, rs, n, heads, C);
     }
     LAUNCH_TRY();
@@ -322,17 +319,17 @@ extern "C" int ddmp_feast_bwd_edge_f32(const ddmp_graph* g, const float* dOut, i
 extern "C" int ddmp_feast_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, int heads, int C, const float* beta,
                                        const float* dz, const float* rs, float* dHf, int64_t lddh, float* dP, int64_t lddp,
                                        ddmp_stream stream) {
-    ARG_TRY(feast_graph_ok(g) && dOut && beta && dz && rs && dHf && dP && feast_dims_ok(heads, C) && lddo >= C &&
+    ARG_TRY(attn_graph_ok(g) && dOut && beta && dz && rs && dHf && dP && feast_dims_ok(heads, C) && lddo >= C &&
             lddh >= (int64_t)heads * C && lddp >= heads && dHf != dOut && dP != rs);
     if (g->n_rows == 0) return DDMP_OK;
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)g->n_rows;
     if (C % 4 == 0 && lddo % 4 == 0 && lddh % 4 == 0 && al16(dOut) && al16(dHf)) {
-        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
-        hipLaunchKernelGGL(feast_bwd_node_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo, beta,
-                           dz, rs, dHf, lddh, dP, lddp, n, heads, C, lanes_per_head(C), cpx, n_chunks);
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(feast_bwd_node_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo, beta,
+                           dz, rs, dHf, lddh, dP, lddp, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
     } else {
-        hipLaunchKernelGGL(feast_bwd_node_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, g->mirror,
+        hipLaunchKernelGGL(feast_bwd_node_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->mirror,
                            dOut, lddo, beta, dz, rs, dHf, lddh, dP, lddp, n, heads, C);
     }
     LAUNCH_TRY();

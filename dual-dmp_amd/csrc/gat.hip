@@ -4,76 +4,26 @@
 //   Y[i,h,:] = sum_{e in row i} alpha_e Hf[col e, h, :]
 //
 // over the COALESCED CSR of a valued graph left at all-ones values: a_e is the multiplicity of the entry, so the a_e exp(..) terms
-// are the softmax over the multiset of edges.  Work layout of sddmm.hip / spmm_lean.inc:
-//   * a workgroup (4 waves) owns a chunk of 64 consecutive rows, blockIdx -> chunk XCD-aware; 8 lanes x float4 per row, 8 rows per
-//     wave step, two steps per chunk;
-//   * a row is walked in HEAD PASSES, so that a lane's head is fixed while it gathers and a float4 never straddles a head.  With
-//     W = C / 4 float4 per head: W in {1, 2, 4} -> W lanes per head and 8 / W heads per pass (the 8 lanes cover one 128-byte slab
-//     of the row, eight / four / two heads inside it); any other W -> the 8 lanes walk one head's W float4, 8 at a time;
-//   * the per-(row, head) reductions (max, denominator, delta, ds_dst, ds_src, the dot products) are strided over the head's lanes
-//     and combined by a fixed xor tree; a row's entries are gathered 8 at a time with the batch compiled per entry count (the
-//     loads of a batch are unconditional and in flight together; a shorter row re-reads its last entry with factor 0);
+// are the softmax over the multiset of edges.  On the row-gather layout with head passes (row_gather.h); its own part:
+//   * the per-(row, head) reductions (max, denominator, delta, ds_dst, ds_src, the dot products) are strided over the head's lanes;
+//     a shorter row's re-read last entry enters with factor 0;
 //   * a row longer than one batch accumulates through its own output row (same lane, same address, program order): the
 //     1200-entry hub row is exact like any other.
-// No atomics, no LDS, no barrier; every sum has a fixed order: bitwise reproducible.  Every row * stride product is int64.
-// Widths that are not a multiple of 4 (or unaligned operands) take scalar kernels: one thread per row.
-#include "ddmp_common.h"
-
-#include <type_traits>
+// No LDS, no barrier.
+#include "row_gather.h"
 
 namespace {
 
-using namespace ddmp;
-
-constexpr int kRB = 64;            // rows per workgroup
-constexpr int kEB = 8;             // entries per batch
 constexpr int kDR = 256;           // rows per partial of the attention-vector gradient
 
 __device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : slope * x; }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float dot4(float4 a, float4 b, float acc) {
-    return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, fmaf(a.x, b.x, acc))));
-}
-__device__ __forceinline__ void fma4(float4& acc, float s, float4 x) {
-    acc.x = fmaf(s, x.x, acc.x);
-    acc.y = fmaf(s, x.y, acc.y);
-    acc.z = fmaf(s, x.z, acc.z);
-    acc.w = fmaf(s, x.w, acc.w);
-}
-// fixed xor tree over the lw (1, 2, 4, 8; kernel-uniform) lanes of a head
-__device__ __forceinline__ float red_sum(float t, int lw) {
-    if (lw > 1) t += __shfl_xor(t, 1, 64);
-    if (lw > 2) t += __shfl_xor(t, 2, 64);
-    if (lw > 4) t += __shfl_xor(t, 4, 64);
-    return t;
-}
-__device__ __forceinline__ float red_max(float t, int lw) {
-    if (lw > 1) t = fmaxf(t, __shfl_xor(t, 1, 64));
-    if (lw > 2) t = fmaxf(t, __shfl_xor(t, 2, 64));
-    if (lw > 4) t = fmaxf(t, __shfl_xor(t, 4, 64));
-    return t;
-}
-inline int lanes_per_head(int C) {
-    const int W = C / 4;
-    return (W == 1 || W == 2 || W == 4) ? W : 8;
-}
-
-// This workgroup's chunk, the lane's 8-lane row group and its place in a head pass (lw lanes per head, hp heads per pass).
-#define GAT_CHUNK_PROLOGUE                                                                         \
-    const int chunk = (blockIdx.x & (kXcd - 1)) * chunks_per_xcd + (blockIdx.x >> 3);              \
-    if (chunk >= n_chunks) return;                                                                 \
-    const int r0 = chunk * kRB;                                                                    \
-    const int nr = min(kRB, n_rows - r0);                                                          \
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;                                    \
-    const int grp = lane >> 3, sl = lane & 7;                                                      \
-    const int hp = 8 / lw, sub = sl / lw, q0 = sl & (lw - 1);
 
 // ------------------------------------------------------------------------------------------------ scores
 __global__ __launch_bounds__(256) void gat_scores_kernel(const float* __restrict__ Hf, int64_t ldh, int n_rows, int heads, int C,
                                                          const float* __restrict__ att_src, const float* __restrict__ att_dst,
                                                          float* __restrict__ s_src, float* __restrict__ s_dst, int lw,
                                                          int chunks_per_xcd, int n_chunks) {
-    GAT_CHUNK_PROLOGUE
+    HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
@@ -136,10 +86,6 @@ __device__ __forceinline__ void gather_pass(const int* __restrict__ col, const i
     }
 #pragma unroll 1
     for (int b0 = 0; b0 < nn; b0 += kEB) {
-        // entry slots of this batch: the longest row's count among the wave's rows (wave-uniform, from ballots)
-        int ne_w = 0;
-#pragma unroll
-        for (int k = 0; k < kEB; ++k) ne_w += __any(b0 + k < nn) ? 1 : 0;
         auto batch = [&](auto ne_tag) {
             constexpr int NE = decltype(ne_tag)::value;
             const float* xp[NE];
@@ -163,16 +109,7 @@ __device__ __forceinline__ void gather_pass(const int* __restrict__ col, const i
                 if (hv) *reinterpret_cast<float4*>(op) = acc;
             }
         };
-        switch (ne_w) {
-            case 1: batch(std::integral_constant<int, 1>()); break;
-            case 2: batch(std::integral_constant<int, 2>()); break;
-            case 3: batch(std::integral_constant<int, 3>()); break;
-            case 4: batch(std::integral_constant<int, 4>()); break;
-            case 5: batch(std::integral_constant<int, 5>()); break;
-            case 6: batch(std::integral_constant<int, 6>()); break;
-            case 7: batch(std::integral_constant<int, 7>()); break;
-            default: batch(std::integral_constant<int, 8>()); break;
-        }
+        ROW_BATCH_SWITCH(b0, nn, batch)
     }
 }
 
@@ -182,7 +119,7 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const int* __restrict__ ro
                                                       const float* __restrict__ s_src, const float* __restrict__ s_dst, float slope,
                                                       const float* __restrict__ bias, float* alpha, float* Y, int64_t ldy, int n_rows,
                                                       int heads, int C, int lw, int chunks_per_xcd, int n_chunks) {
-    GAT_CHUNK_PROLOGUE
+    HEAD_CHUNK_PROLOGUE
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
         const int lr = wave * 8 + grp + qq * 32;
@@ -254,7 +191,7 @@ __global__ __launch_bounds__(256) void gat_bwd_edge_kernel(const int* __restrict
                                                            float slope, const float* __restrict__ alpha, float* ds,
                                                            float* __restrict__ ds_dst, int n_rows, int heads, int C, int lw,
                                                            int chunks_per_xcd, int n_chunks) {
-    GAT_CHUNK_PROLOGUE
+    HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
@@ -273,9 +210,6 @@ __global__ __launch_bounds__(256) void gat_bwd_edge_kernel(const int* __restrict
             float delta = 0.f;
 #pragma unroll 1
             for (int b0 = 0; b0 < nn; b0 += kEB) {
-                int ne_w = 0;
-#pragma unroll
-                for (int k = 0; k < kEB; ++k) ne_w += __any(b0 + k < nn) ? 1 : 0;
                 auto batch = [&](auto ne_tag) {
                     constexpr int NE = decltype(ne_tag)::value;
                     const float* xp[NE];
@@ -305,16 +239,7 @@ __global__ __launch_bounds__(256) void gat_bwd_edge_kernel(const int* __restrict
                         if (ok && hv && q0 == (k & (lw - 1))) ds[e * heads + h] = t;
                     }
                 };
-                switch (ne_w) {
-                    case 1: batch(std::integral_constant<int, 1>()); break;
-                    case 2: batch(std::integral_constant<int, 2>()); break;
-                    case 3: batch(std::integral_constant<int, 3>()); break;
-                    case 4: batch(std::integral_constant<int, 4>()); break;
-                    case 5: batch(std::integral_constant<int, 5>()); break;
-                    case 6: batch(std::integral_constant<int, 6>()); break;
-                    case 7: batch(std::integral_constant<int, 7>()); break;
-                    default: batch(std::integral_constant<int, 8>()); break;
-                }
+                ROW_BATCH_SWITCH(b0, nn, batch)
             }
             // ds_e = alpha_e (dalpha_e - delta) leaky'(z_e), and its row sum
             const float sd = s_dst[(int64_t)row * heads + hh];
@@ -371,7 +296,7 @@ __global__ __launch_bounds__(256) void gat_bwd_node_kernel(const int* __restrict
                                                            const float* __restrict__ att_dst, float* dHf, int64_t lddh,
                                                            float* __restrict__ ds_src, int n_rows, int heads, int C, int lw,
                                                            int chunks_per_xcd, int n_chunks) {
-    GAT_CHUNK_PROLOGUE
+    HEAD_CHUNK_PROLOGUE
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
         const int lr = wave * 8 + grp + qq * 32;
@@ -464,10 +389,6 @@ __global__ __launch_bounds__(256) void gat_datt_final_kernel(const float* __rest
     }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool gat_graph_ok(const ddmp_graph* g) {
-    return g && (g->valued & DDMP_GV_VALUED) && g->a && g->mirror && g->n_cols == g->n_rows && g->n_rows < (int64_t)INT32_MAX;
-}
 inline bool gat_dims_ok(int heads, int C) { return heads > 0 && C > 0 && (int64_t)heads * C < (1 << 24); }
 
 }  // namespace
@@ -480,11 +401,11 @@ extern "C" int ddmp_gat_scores_f32(const float* Hf, int64_t ldh, int64_t n_rows,
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)n_rows;
     if (C % 4 == 0 && ldh % 4 == 0 && al16(Hf) && al16(att_src) && al16(att_dst)) {
-        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
-        hipLaunchKernelGGL(gat_scores_kernel, dim3(cpx * kXcd), dim3(256), 0, st, Hf, ldh, n, heads, C, att_src, att_dst, s_src, s_dst,
-                           lanes_per_head(C), cpx, n_chunks);
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(gat_scores_kernel, rg.grid, dim3(256), 0, st, Hf, ldh, n, heads, C, att_src, att_dst, s_src, s_dst,
+                           lanes_per_head(C), rg.cpx, rg.n_chunks);
     } else {
-        hipLaunchKernelGGL(gat_scores_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, Hf, ldh, n, heads, C, att_src,
+        hipLaunchKernelGGL(gat_scores_scalar_kernel, scalar_grid(n), dim3(256), 0, st, Hf, ldh, n, heads, C, att_src,
                            att_dst, s_src, s_dst);
     }
     LAUNCH_TRY();
@@ -494,17 +415,17 @@ extern "C" int ddmp_gat_scores_f32(const float* Hf, int64_t ldh, int64_t n_rows,
 extern "C" int ddmp_gat_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ldh, int heads, int C, const float* s_src,
                                 const float* s_dst, float slope, const float* bias, float* alpha, float* Y, int64_t ldy,
                                 ddmp_stream stream) {
-    ARG_TRY(gat_graph_ok(g) && Hf && s_src && s_dst && alpha && Y && gat_dims_ok(heads, C) && ldh >= (int64_t)heads * C &&
+    ARG_TRY(attn_graph_ok(g) && Hf && s_src && s_dst && alpha && Y && gat_dims_ok(heads, C) && ldh >= (int64_t)heads * C &&
             ldy >= (int64_t)heads * C && Y != Hf);
     if (g->n_rows == 0) return DDMP_OK;
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)g->n_rows;
     if (C % 4 == 0 && ldh % 4 == 0 && ldy % 4 == 0 && al16(Hf) && al16(Y) && (!bias || al16(bias))) {
-        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
-        hipLaunchKernelGGL(gat_fwd_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh, s_src, s_dst, slope,
-                           bias, alpha, Y, ldy, n, heads, C, lanes_per_head(C), cpx, n_chunks);
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(gat_fwd_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh, s_src, s_dst, slope,
+                           bias, alpha, Y, ldy, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
     } else {
-        hipLaunchKernelGGL(gat_fwd_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh,
+        hipLaunchKernelGGL(gat_fwd_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh,
                            s_src, s_dst, slope, bias, alpha, Y, ldy, n, heads, C);
     }
     LAUNCH_TRY();
@@ -514,17 +435,17 @@ extern "C" int ddmp_gat_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ld
 extern "C" int ddmp_gat_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Hf, int64_t ldh, int heads,
                                      int C, const float* s_src, const float* s_dst, float slope, const float* alpha, float* ds,
                                      float* ds_dst, ddmp_stream stream) {
-    ARG_TRY(gat_graph_ok(g) && dOut && Hf && s_src && s_dst && alpha && ds && ds_dst && gat_dims_ok(heads, C) &&
+    ARG_TRY(attn_graph_ok(g) && dOut && Hf && s_src && s_dst && alpha && ds && ds_dst && gat_dims_ok(heads, C) &&
             lddo >= (int64_t)heads * C && ldh >= (int64_t)heads * C && ds != alpha);
     if (g->n_rows == 0) return DDMP_OK;
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)g->n_rows;
     if (C % 4 == 0 && lddo % 4 == 0 && ldh % 4 == 0 && al16(dOut) && al16(Hf)) {
-        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
-        hipLaunchKernelGGL(gat_bwd_edge_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, dOut, lddo, Hf, ldh, s_src,
-                           s_dst, slope, alpha, ds, ds_dst, n, heads, C, lanes_per_head(C), cpx, n_chunks);
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(gat_bwd_edge_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, dOut, lddo, Hf, ldh, s_src,
+                           s_dst, slope, alpha, ds, ds_dst, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
     } else {
-        hipLaunchKernelGGL(gat_bwd_edge_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, dOut, lddo,
+        hipLaunchKernelGGL(gat_bwd_edge_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, dOut, lddo,
                            Hf, ldh, s_src, s_dst, slope, alpha, ds, ds_dst, n, heads, C);
     }
     LAUNCH_TRY();
@@ -534,17 +455,17 @@ extern "C" int ddmp_gat_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int
 extern "C" int ddmp_gat_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, int heads, int C, const float* alpha,
                                      const float* ds, const float* ds_dst, const float* att_src, const float* att_dst, float* dHf,
                                      int64_t lddh, float* ds_src, ddmp_stream stream) {
-    ARG_TRY(gat_graph_ok(g) && dOut && alpha && ds && ds_dst && att_src && att_dst && dHf && ds_src && gat_dims_ok(heads, C) &&
+    ARG_TRY(attn_graph_ok(g) && dOut && alpha && ds && ds_dst && att_src && att_dst && dHf && ds_src && gat_dims_ok(heads, C) &&
             lddo >= (int64_t)heads * C && lddh >= (int64_t)heads * C && dHf != dOut);
     if (g->n_rows == 0) return DDMP_OK;
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)g->n_rows;
     if (C % 4 == 0 && lddo % 4 == 0 && lddh % 4 == 0 && al16(dOut) && al16(dHf) && al16(att_src) && al16(att_dst)) {
-        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
-        hipLaunchKernelGGL(gat_bwd_node_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo, alpha,
-                           ds, ds_dst, att_src, att_dst, dHf, lddh, ds_src, n, heads, C, lanes_per_head(C), cpx, n_chunks);
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(gat_bwd_node_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo, alpha,
+                           ds, ds_dst, att_src, att_dst, dHf, lddh, ds_src, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
     } else {
-        hipLaunchKernelGGL(gat_bwd_node_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, g->mirror,
+        hipLaunchKernelGGL(gat_bwd_node_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->mirror,
                            dOut, lddo, alpha, ds, ds_dst, att_src, att_dst, dHf, lddh, ds_src, n, heads, C);
     }
     LAUNCH_TRY();

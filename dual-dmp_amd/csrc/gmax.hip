@@ -8,65 +8,26 @@
 // change a maximum).  The backward relies on the SYMMETRIC structure: row j's own entries enumerate the rows j feeds, and arg
 // holds node ids, so no mirror map is read.  Ties go to the first entry in CSR order (the smallest source id): the running
 // maximum starts at the row's first entry and is replaced on a strict > only.
-// Work layout of gat.hip / feast.hip: a workgroup (4 waves) owns a chunk of 64 consecutive rows, blockIdx -> chunk XCD-aware;
-// 8 lanes x float4 per row, 8 rows per wave step, two steps per chunk; the 8 lanes walk the C / 4 float4 of the row 8 at a time.
-// Entries are gathered 8 at a time with the batch compiled per entry count (unconditional loads, all in flight together; a
-// shorter row re-reads its last entry, which can neither win a strict > nor -- masked -- add to a sum).  The running maximum and
-// its id (forward) and the sum (backward) stay in registers over ALL entries of the row: the 1200-entry hub row is exact like any
-// other.  No atomics, no LDS, no barrier, fixed orders: bitwise reproducible.  Every row * stride product is int64.  Widths that
-// are not a multiple of 4 (or unaligned operands) take scalar kernels: one thread per row.
-#include "ddmp_common.h"
-
-#include <type_traits>
+// On the row-gather layout (row_gather.h) without heads: the 8 lanes of a row group walk the C / 4 float4 of the row 8 at a time.
+// A shorter row's re-read last entry can neither win a strict > nor -- masked -- add to a sum.  The running maximum and its id
+// (forward) and the sum (backward) stay in registers over ALL entries of the row: the 1200-entry hub row is exact like any other.
+// No LDS, no barrier.
+#include "row_gather.h"
 
 namespace {
 
-using namespace ddmp;
-
-constexpr int kRB = 64;            // rows per workgroup
-constexpr int kEB = 8;             // entries per batch
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ int4 ld4i(const int* p) { return *reinterpret_cast<const int4*>(p); }
 __device__ __forceinline__ void take(float& m, int& id, float v, int j) {
     const bool w = v > m;
     m = w ? v : m;
     id = w ? j : id;
 }
 
-// This workgroup's chunk and the lane's 8-lane row group.
-#define GMAX_CHUNK_PROLOGUE                                                                        \
-    const int chunk = (blockIdx.x & (kXcd - 1)) * chunks_per_xcd + (blockIdx.x >> 3);              \
-    if (chunk >= n_chunks) return;                                                                 \
-    const int r0 = chunk * kRB;                                                                    \
-    const int nr = min(kRB, n_rows - r0);                                                          \
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;                                    \
-    const int grp = lane >> 3, sl = lane & 7;
-
-// Run `batch` with the entry count of this batch as a compile-time constant: the longest row's count among the wave's active
-// rows (wave-uniform, from ballots).
-#define GMAX_BATCH_SWITCH(b0, nn, batch)                                                           \
-    {                                                                                              \
-        int ne_w = 0;                                                                              \
-        _Pragma("unroll") for (int k = 0; k < kEB; ++k) ne_w += __any((b0) + k < (nn)) ? 1 : 0;     \
-        switch (ne_w) {                                                                            \
-            case 1: batch(std::integral_constant<int, 1>()); break;                                \
-            case 2: batch(std::integral_constant<int, 2>()); break;                                \
-            case 3: batch(std::integral_constant<int, 3>()); break;                                \
-            case 4: batch(std::integral_constant<int, 4>()); break;                                \
-            case 5: batch(std::integral_constant<int, 5>()); break;                                \
-            case 6: batch(std::integral_constant<int, 6>()); break;                                \
-            case 7: batch(std::integral_constant<int, 7>()); break;                                \
-            default: batch(std::integral_constant<int, 8>()); break;                               \
-        }                                                                                          \
-    }
-
 // ------------------------------------------------------------------------------------------------ forward
 __global__ __launch_bounds__(256) void gather_max_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                          const float* __restrict__ B, int64_t ldb, const float* __restrict__ A,
                                                          int64_t lda, float* __restrict__ Y, int64_t ldy, int* __restrict__ arg,
                                                          int64_t ldg, int n_rows, int C, int chunks_per_xcd, int n_chunks) {
-    GMAX_CHUNK_PROLOGUE
+    ROW_CHUNK_PROLOGUE
     const int W = C >> 2;
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
@@ -106,7 +67,7 @@ __global__ __launch_bounds__(256) void gather_max_kernel(const int* __restrict__
                         take(m.w, id.w, x[k].w, j[k]);
                     }
                 };
-                GMAX_BATCH_SWITCH(b0, nn, batch)
+                ROW_BATCH_SWITCH(b0, nn, batch)
             }
             if (A) {
                 const float4 a = ld4(A + (int64_t)row * lda + q * 4);
@@ -151,7 +112,7 @@ __global__ __launch_bounds__(256) void gather_max_bwd_kernel(const int* __restri
                                                              const int* __restrict__ arg, int64_t ldg, float* __restrict__ dA,
                                                              int64_t ldda, float* __restrict__ dB, int64_t lddb, int n_rows, int C,
                                                              int chunks_per_xcd, int n_chunks) {
-    GMAX_CHUNK_PROLOGUE
+    ROW_CHUNK_PROLOGUE
     const int W = C >> 2;
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
@@ -195,7 +156,7 @@ __global__ __launch_bounds__(256) void gather_max_bwd_kernel(const int* __restri
                         acc.w += w[k].w == me ? x[k].w : 0.f;
                     }
                 };
-                GMAX_BATCH_SWITCH(b0, nn, batch)
+                ROW_BATCH_SWITCH(b0, nn, batch)
             }
             *reinterpret_cast<float4*>(brow + q * 4) = acc;
         }
@@ -221,27 +182,22 @@ __global__ __launch_bounds__(256) void gather_max_bwd_scalar_kernel(const int* _
     }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool gmax_graph_ok(const ddmp_graph* g) {
-    return g && (g->valued & DDMP_GV_VALUED) && g->n_cols == g->n_rows && g->n_rows < (int64_t)INT32_MAX;
-}
-
 }  // namespace
 
 extern "C" int ddmp_gather_max_f32(const ddmp_graph* g, const float* B, int64_t ldb, const float* A, int64_t lda, int C, float* Y,
                                    int64_t ldy, int32_t* arg, int64_t ldarg, ddmp_stream stream) {
-    ARG_TRY(gmax_graph_ok(g) && B && Y && C >= 1 && ldb >= C && ldy >= C && (!A || lda >= C) && (!arg || ldarg >= C) && Y != B &&
+    ARG_TRY(attn_graph_ok(g, false) && B && Y && C >= 1 && ldb >= C && ldy >= C && (!A || lda >= C) && (!arg || ldarg >= C) && Y != B &&
             Y != A);
     if (g->n_rows == 0) return DDMP_OK;
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)g->n_rows;
     if (C % 4 == 0 && ldb % 4 == 0 && ldy % 4 == 0 && al16(B) && al16(Y) && (!A || (lda % 4 == 0 && al16(A))) &&
         (!arg || (ldarg % 4 == 0 && al16(arg)))) {
-        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
-        hipLaunchKernelGGL(gather_max_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, B, ldb, A, lda, Y, ldy, arg,
-                           ldarg, n, C, cpx, n_chunks);
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(gather_max_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, B, ldb, A, lda, Y, ldy, arg,
+                           ldarg, n, C, rg.cpx, rg.n_chunks);
     } else {
-        hipLaunchKernelGGL(gather_max_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, B, ldb, A,
+        hipLaunchKernelGGL(gather_max_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, B, ldb, A,
                            lda, Y, ldy, arg, ldarg, n, C);
     }
     LAUNCH_TRY();
@@ -250,18 +206,18 @@ extern "C" int ddmp_gather_max_f32(const ddmp_graph* g, const float* B, int64_t 
 
 extern "C" int ddmp_gather_max_bwd_f32(const ddmp_graph* g, const float* dG, int64_t lddg, const int32_t* arg, int64_t ldarg, int C,
                                        float* dA, int64_t ldda, float* dB, int64_t lddb, ddmp_stream stream) {
-    ARG_TRY(gmax_graph_ok(g) && dG && arg && dA && dB && C >= 1 && lddg >= C && ldarg >= C && ldda >= C && lddb >= C && dA != dG &&
+    ARG_TRY(attn_graph_ok(g, false) && dG && arg && dA && dB && C >= 1 && lddg >= C && ldarg >= C && ldda >= C && lddb >= C && dA != dG &&
             dB != dG && dA != dB);
     if (g->n_rows == 0) return DDMP_OK;
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)g->n_rows;
     if (C % 4 == 0 && lddg % 4 == 0 && ldarg % 4 == 0 && ldda % 4 == 0 && lddb % 4 == 0 && al16(dG) && al16(arg) && al16(dA) &&
         al16(dB)) {
-        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
-        hipLaunchKernelGGL(gather_max_bwd_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, dG, lddg, arg, ldarg, dA,
-                           ldda, dB, lddb, n, C, cpx, n_chunks);
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(gather_max_bwd_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, dG, lddg, arg, ldarg, dA,
+                           ldda, dB, lddb, n, C, rg.cpx, rg.n_chunks);
     } else {
-        hipLaunchKernelGGL(gather_max_bwd_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, dG, lddg,
+        hipLaunchKernelGGL(gather_max_bwd_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, dG, lddg,
                            arg, ldarg, dA, ldda, dB, lddb, n, C);
     }
     LAUNCH_TRY();

@@ -6,12 +6,10 @@
 //
 // over the COALESCED CSR of a valued graph built WITHOUT loop handling (flags 0) and left at all-ones values; an entry's input
 // edges come from its ee_ptr / ee_idx span, in input order -- exact for duplicate edges whose pseudo-coordinates differ.
-// Work layout and gather loops are feast.hip's (gather_mix.h): 64-row chunks per workgroup, 8 lanes x float4 per row, the
-// per-entry factors formed with the row's entries spread over the 8 lanes, written to their [entries, K] array and read back by the
-// sibling lanes behind a workgroup-scope fence.  mu, 1 / (EPS + sigma^2) and sigma are staged once per workgroup in LDS (K * dim
-// <= 128 floats each; one barrier before the first row).  No atomics; every sum has a fixed order: bitwise reproducible.  Every
-// row * stride product is int64.  Widths that are not a multiple of 4 (or unaligned operands) take scalar kernels: one thread per
-// row.
+// On the row-gather layout with head passes (row_gather.h) and the gather loops of gather_mix.h, shared with feast.hip: the
+// per-entry factors are formed with the row's entries spread over the 8 lanes, written to their [entries, K] array and read back by
+// the sibling lanes behind a workgroup-scope fence.  mu, 1 / (EPS + sigma^2) and sigma are staged once per workgroup in LDS (K * dim
+// <= 128 floats each; one barrier before the first row).
 #include "gather_mix.h"
 
 namespace {
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(256) void gmm_fwd_kernel(const int* __restrict__ ro
                                                       const float* __restrict__ bias, float* w, float* __restrict__ Y, int64_t ldy,
                                                       int n_rows, int K, int C, int lw, int chunks_per_xcd, int n_chunks) {
     GMM_TABLES
-    FEAST_CHUNK_PROLOGUE
+    HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
@@ -194,7 +192,7 @@ __global__ __launch_bounds__(256) void gmm_bwd_edge_kernel(const int* __restrict
                                                            float* __restrict__ dattr, int n_rows, int K, int C, int lw,
                                                            int chunks_per_xcd, int n_chunks) {
     GMM_TABLES
-    FEAST_CHUNK_PROLOGUE
+    HEAD_CHUNK_PROLOGUE
     const int KD = K * dim;
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
@@ -293,7 +291,7 @@ __global__ __launch_bounds__(256) void gmm_bwd_node_kernel(const int* __restrict
                                                            int64_t lddo, const float* __restrict__ w, float* __restrict__ dHf,
                                                            int64_t lddh, float* __restrict__ dR, int64_t lddr, int n_rows, int K,
                                                            int C, int lw, int chunks_per_xcd, int n_chunks) {
-    FEAST_CHUNK_PROLOGUE
+    HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
 #pragma unroll 1
     for (int qq = 0; qq < 2; ++qq) {
@@ -341,7 +339,7 @@ __global__ __launch_bounds__(256) void gmm_bwd_node_scalar_kernel(const int* __r
 
 // the attention graph WITHOUT loop handling: every input edge belongs to exactly one entry and every entry has input edges
 inline bool gmm_graph_ok(const ddmp_graph* g) {
-    return feast_graph_ok(g) && g->valued == DDMP_GV_VALUED && g->ee_ptr && g->ee_idx;
+    return attn_graph_ok(g) && g->valued == DDMP_GV_VALUED && g->ee_ptr && g->ee_idx;
 }
 inline bool gmm_dims_ok(int K, int dim, int C) { return dim > 0 && K > 0 && (int64_t)K * dim <= kMaxKD && feast_dims_ok(K, C); }
 
@@ -356,11 +354,11 @@ extern "C" int ddmp_gmm_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ld
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)g->n_rows;
     if (C % 4 == 0 && ldh % 4 == 0 && ldy % 4 == 0 && al16(Hf) && al16(Y) && (!bias || al16(bias)) && (!R || (al16(R) && ldr % 4 == 0))) {
-        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
-        hipLaunchKernelGGL(gmm_fwd_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->a, g->ee_ptr, g->ee_idx, Hf, ldh,
-                           attr, dim, mu, sigma, R, ldr, bias, w, Y, ldy, n, K, C, lanes_per_head(C), cpx, n_chunks);
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(gmm_fwd_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->a, g->ee_ptr, g->ee_idx, Hf, ldh,
+                           attr, dim, mu, sigma, R, ldr, bias, w, Y, ldy, n, K, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
     } else {
-        hipLaunchKernelGGL(gmm_fwd_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, g->a, g->ee_ptr,
+        hipLaunchKernelGGL(gmm_fwd_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->a, g->ee_ptr,
                            g->ee_idx, Hf, ldh, attr, dim, mu, sigma, R, ldr, bias, w, Y, ldy, n, K, C);
     }
     LAUNCH_TRY();
@@ -376,11 +374,11 @@ extern "C" int ddmp_gmm_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)g->n_rows;
     if (C % 4 == 0 && lddo % 4 == 0 && ldh % 4 == 0 && al16(dOut) && al16(Hf)) {
-        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
-        hipLaunchKernelGGL(gmm_bwd_edge_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->a, g->ee_ptr, g->ee_idx, dOut,
-                           lddo, Hf, ldh, attr, dim, mu, sigma, ge, parts, dattr, n, K, C, lanes_per_head(C), cpx, n_chunks);
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(gmm_bwd_edge_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->a, g->ee_ptr, g->ee_idx, dOut,
+                           lddo, Hf, ldh, attr, dim, mu, sigma, ge, parts, dattr, n, K, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
     } else {
-        hipLaunchKernelGGL(gmm_bwd_edge_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, g->a,
+        hipLaunchKernelGGL(gmm_bwd_edge_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->a,
                            g->ee_ptr, g->ee_idx, dOut, lddo, Hf, ldh, attr, dim, mu, sigma, ge, parts, dattr, n, K, C);
     }
     LAUNCH_TRY();
@@ -395,11 +393,11 @@ extern "C" int ddmp_gmm_bwd_node_f32(const ddmp_graph* g, const float* dOut, int
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)g->n_rows;
     if (C % 4 == 0 && lddo % 4 == 0 && lddh % 4 == 0 && al16(dOut) && al16(dHf) && (!dR || (al16(dR) && lddr % 4 == 0))) {
-        const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
-        hipLaunchKernelGGL(gmm_bwd_node_kernel, dim3(cpx * kXcd), dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo, w, dHf,
-                           lddh, dR, lddr, n, K, C, lanes_per_head(C), cpx, n_chunks);
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(gmm_bwd_node_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo, w, dHf,
+                           lddh, dR, lddr, n, K, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
     } else {
-        hipLaunchKernelGGL(gmm_bwd_node_scalar_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, g->rowptr, g->col, g->mirror,
+        hipLaunchKernelGGL(gmm_bwd_node_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->mirror,
                            dOut, lddo, w, dHf, lddh, dR, lddr, n, K, C);
     }
     LAUNCH_TRY();

@@ -1,0 +1,121 @@
+// The row-gather work layout of the graph-operator kernels (sddmm.hip, gat.hip, feast.hip, gmm.hip, gmax.hip; gather_mix.h):
+// the one place that fixes it.  (The SpMM files have their own variants of it; they do not include this header.)
+//   * a workgroup (4 waves) owns a chunk of kRB = 64 consecutive rows; blockIdx -> chunk is XCD-aware (block b runs on XCD b % 8,
+//     so XCD x takes the chunks x * chunks_per_xcd ..: the ~deg re-reads of a neighbour row by neighbouring output rows hit that
+//     XCD's L2);
+//   * 8 lanes x float4 cover one 128-byte slab of a row: 8 rows per wave step, two steps per chunk (local row
+//     wave * 8 + grp + qq * 32, qq = 0, 1); the 8 lanes of a row group leave together;
+//   * operators with heads walk a row in HEAD PASSES, so that a lane's head is fixed while it gathers and a float4 never straddles
+//     a head.  With W = C / 4 float4 per head: W in {1, 2, 4} -> lw = W lanes per head and hp = 8 / W heads per pass (the 8 lanes
+//     cover one slab of the row, eight / four / two heads inside it); any other W -> lw = 8, the 8 lanes walk one head's W float4,
+//     8 at a time.  The lanes of the last pass that hold no valid head run head heads - 1 again and store nothing;
+//   * per-(row, head) reductions are strided over the head's lanes and combined by a fixed xor tree;
+//   * a row's entries are gathered kEB = 8 at a time with the batch compiled per entry count: the LONGEST row's count among the
+//     wave's active rows (wave-uniform, from ballots).  The loads of a batch are unconditional -- a per-lane predicate on a load puts
+//     a branch and a full wait behind every one of them, and the loads of a batch must be in flight together; a lane whose row is
+//     shorter re-reads its last entry (an L1 hit) and its kernel masks that slot out.
+// No atomics, every sum in a fixed order: bitwise reproducible.  Every row * stride product is int64.  Widths that are not a
+// multiple of 4 (or operands that fail al16) take scalar kernels, one thread per row, 256 rows per workgroup.
+#pragma once
+#include "ddmp_common.h"
+
+#include <type_traits>
+
+namespace {
+
+using namespace ddmp;
+
+constexpr int kRB = 64;            // rows per workgroup
+constexpr int kEB = 8;             // entries per batch
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ int4 ld4i(const int* p) { return *reinterpret_cast<const int4*>(p); }
+__device__ __forceinline__ float dot4(float4 a, float4 b, float acc) {
+    return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, fmaf(a.x, b.x, acc))));
+}
+__device__ __forceinline__ void fma4(float4& acc, float s, float4 x) {
+    acc.x = fmaf(s, x.x, acc.x);
+    acc.y = fmaf(s, x.y, acc.y);
+    acc.z = fmaf(s, x.z, acc.z);
+    acc.w = fmaf(s, x.w, acc.w);
+}
+// fixed xor tree over the lw (1, 2, 4, 8; kernel-uniform) low lanes of an 8-lane row group: the lanes of one head
+__device__ __forceinline__ float red_sum(float t, int lw) {
+    if (lw > 1) t += __shfl_xor(t, 1, 64);
+    if (lw > 2) t += __shfl_xor(t, 2, 64);
+    if (lw > 4) t += __shfl_xor(t, 4, 64);
+    return t;
+}
+__device__ __forceinline__ float red_max(float t, int lw) {
+    if (lw > 1) t = fmaxf(t, __shfl_xor(t, 1, 64));
+    if (lw > 2) t = fmaxf(t, __shfl_xor(t, 2, 64));
+    if (lw > 4) t = fmaxf(t, __shfl_xor(t, 4, 64));
+    return t;
+}
+// fixed xor tree over the 8 / lw lanes of a row group that hold the same columns (different heads)
+__device__ __forceinline__ float red_heads(float t, int lw) {
+    if (lw < 2) t += __shfl_xor(t, 1, 64);
+    if (lw < 4) t += __shfl_xor(t, 2, 64);
+    if (lw < 8) t += __shfl_xor(t, 4, 64);
+    return t;
+}
+inline int lanes_per_head(int C) {
+    const int W = C / 4;
+    return (W == 1 || W == 2 || W == 4) ? W : 8;
+}
+
+// This workgroup's chunk and the lane's 8-lane row group (kernel parameters n_rows, chunks_per_xcd, n_chunks).
+#define ROW_CHUNK_PROLOGUE                                                                         \
+    const int chunk = (blockIdx.x & (kXcd - 1)) * chunks_per_xcd + (blockIdx.x >> 3);              \
+    if (chunk >= n_chunks) return;                                                                 \
+    const int r0 = chunk * kRB;                                                                    \
+    const int nr = min(kRB, n_rows - r0);                                                          \
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;                                    \
+    const int grp = lane >> 3, sl = lane & 7;
+
+// The same, and the lane's place in a head pass (kernel parameter lw: lanes per head; hp heads per pass).
+#define HEAD_CHUNK_PROLOGUE                                                                        \
+    ROW_CHUNK_PROLOGUE                                                                             \
+    const int hp = 8 / lw, sub = sl / lw, q0 = sl & (lw - 1);
+
+// Run `batch` with the entry count of this batch as a compile-time constant: the longest row's count among the wave's active
+// rows (wave-uniform, from ballots).
+#define ROW_BATCH_SWITCH(b0, nn, batch)                                                            \
+    {                                                                                              \
+        int ne_w = 0;                                                                              \
+        _Pragma("unroll") for (int k = 0; k < kEB; ++k) ne_w += __any((b0) + k < (nn)) ? 1 : 0;     \
+        switch (ne_w) {                                                                            \
+            case 1: batch(std::integral_constant<int, 1>()); break;                                \
+            case 2: batch(std::integral_constant<int, 2>()); break;                                \
+            case 3: batch(std::integral_constant<int, 3>()); break;                                \
+            case 4: batch(std::integral_constant<int, 4>()); break;                                \
+            case 5: batch(std::integral_constant<int, 5>()); break;                                \
+            case 6: batch(std::integral_constant<int, 6>()); break;                                \
+            case 7: batch(std::integral_constant<int, 7>()); break;                                \
+            default: batch(std::integral_constant<int, 8>()); break;                               \
+        }                                                                                          \
+    }
+
+// ------------------------------------------------------------------------------------------------ host side
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The attention graph: the coalesced square structure of a valued graph.  `values`: the kernels also read the entries'
+// multiplicities (g->a) and the mirror map; the arg-max gather reads neither.
+inline bool attn_graph_ok(const ddmp_graph* g, bool values = true) {
+    return g && (g->valued & DDMP_GV_VALUED) && (!values || (g->a && g->mirror)) && g->n_cols == g->n_rows &&
+           g->n_rows < (int64_t)INT32_MAX;
+}
+
+// Launch geometry for n rows.  Vector kernels: `grid` workgroups of 256 threads, and the kernel arguments chunks_per_xcd = cpx
+// and n_chunks; scalar kernels: scalar_grid(n) workgroups of 256 threads.
+struct RowGrid {
+    int n_chunks, cpx;
+    dim3 grid;
+};
+inline RowGrid row_grid(int n) {
+    const int n_chunks = (int)cdiv(n, kRB), cpx = (int)cdiv(n_chunks, kXcd);
+    return {n_chunks, cpx, dim3(cpx * kXcd)};
+}
+inline dim3 scalar_grid(int n) { return dim3((unsigned)cdiv(n, 256)); }
+
+}  // namespace

@@ -150,7 +150,85 @@ def _pad_cols(t: torch.Tensor, mult: int = 4) -> torch.Tensor:
     return out
 
 
-class _GCNConvFn(torch.autograd.Function):
+def _pad_rows_like(wp, dyp, cout):
+    """``wp`` ([cout, .]) with zero rows appended to match a ragged output width that ``_pad_cols`` padded (``dyp``)."""
+    if dyp.shape[1] == cout:
+        return wp
+    wrow = torch.zeros((dyp.shape[1], wp.shape[1]), dtype=wp.dtype, device=wp.device)
+    wrow[:cout] = wp
+    return wrow
+
+
+def _bias_grad(dy):
+    """Column sum of ``dy``: ``ops.colsum`` at the power-of-two widths it takes, torch otherwise."""
+    cout = dy.shape[1]
+    pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
+    return ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+
+
+def _packed_rows(blocks, width, device, pad_each=False):
+    """The weight blocks ([rows_k, <= width] each, ``None`` skipped) stacked into ONE zero-padded float32 matrix for a single GEMM:
+    end to end with the total rounded up to a multiple of 4, or (``pad_each``) every block rounded up on its own."""
+    r4 = lambda r: (r + 3) // 4 * 4
+    blocks = [b for b in blocks if b is not None]
+    starts, rows = [], 0
+    for b in blocks:
+        starts.append(rows)
+        rows += r4(b.shape[0]) if pad_each else b.shape[0]
+    wp = torch.zeros((r4(rows), width), dtype=torch.float32, device=device)
+    for r, b in zip(starts, blocks):
+        wp[r:r + b.shape[0], :b.shape[1]] = b
+    return wp
+
+
+def _grad_rows(n, used, padded, device):
+    """An uninitialised float32 [n, padded] gradient row buffer with the columns outside the ``used`` (start, stop) spans -- the
+    padding the kernels never write -- zeroed."""
+    g = torch.empty((n, padded), dtype=torch.float32, device=device)
+    end = 0
+    for a, b in list(used) + [(padded, padded)]:
+        if a > end:
+            g[:, end:a] = 0
+        end = b
+    return g
+
+
+class _Fn(torch.autograd.Function):
+    """Base of the autograd functions below: ``backward`` enters the gradient's device and runs the subclass's ``_backward``."""
+
+    @classmethod
+    def backward(cls, ctx, dy):
+        with ops.on_device(dy):
+            return cls._backward(ctx, dy)
+
+
+def _bias_param(module, bias, n, init=torch.zeros):
+    """``module.bias``: a parameter [n] made by ``init``, or registered as None."""
+    if bias:
+        module.bias = nn.Parameter(init(n))
+    else:
+        module.register_parameter("bias", None)
+
+
+def _no_tuple_x(name, x):
+    if isinstance(x, (tuple, list)):
+        raise ValueError("%s: a tuple x (bipartite graphs) is not implemented on the HIP path" % name)
+
+
+def _check_x(name, x, in_channels, bf16=True):
+    """The refusals every operator shares for its features: bf16 (``bf16=False``: the operator has its own rule), then the shape."""
+    if bf16 and x.dtype == torch.bfloat16:
+        raise ValueError("%s: bf16 features are not supported on the HIP path" % name)
+    if x.dim() != 2 or x.shape[1] != in_channels:
+        raise ValueError("%s: expected x of shape [N, %d]" % (name, in_channels))
+
+
+def _need_gpu(name, x):
+    if not x.is_cuda:
+        raise ops.DdmpError("%s runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback" % name)
+
+
+class _GCNConvFn(_Fn):
     @staticmethod
     def forward(ctx, x, weight, bias, graph):
         cin, cout = weight.shape[1], weight.shape[0]
@@ -172,27 +250,17 @@ class _GCNConvFn(torch.autograd.Function):
         return y
 
     @staticmethod
-    def backward(ctx, dy):
-        with ops.on_device(dy):
-            return _GCNConvFn._backward(ctx, dy)
-
-    @staticmethod
     def _backward(ctx, dy):
         saved, wp = ctx.saved_tensors
         graph, cin = ctx.graph, ctx.cin
         dy = dy.contiguous()
         cout = dy.shape[1]
         dyp = _pad_cols(dy)
-        if dyp.shape[1] != cout:           # ragged output width: pad the weight rows to match
-            wrow = torch.zeros((dyp.shape[1], wp.shape[1]), dtype=wp.dtype, device=wp.device)
-            wrow[:cout] = wp
-        else:
-            wrow = wp
+        wrow = _pad_rows_like(wp, dyp, cout)
         need_x = ctx.needs_input_grad[0]
         db = None
         if ctx.needs_input_grad[2]:
-            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
-            db = ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+            db = _bias_grad(dy)
         if ctx.agg_first:
             dw = ops.gemm_tn(dyp, saved)
             dx = ops.spmm(graph, ops.gemm_nn(dyp, wrow)) if need_x else None
@@ -206,7 +274,7 @@ class _GCNConvFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
-class _GCNConvWFn(torch.autograd.Function):
+class _GCNConvWFn(_Fn):
     """GCNConv on a VALUED graph (edge_weight and / or non-default options): Y = A (X W^T) + b with A = the graph's current
     values, which need not be symmetric -- the backward gathers with A^T (``transpose=True``: same structure, mirrored values).
     The edge_weight gradient is dL/dA per entry (``ops.sddmm`` of the gather's output gradient and the operand the gather
@@ -241,11 +309,6 @@ class _GCNConvWFn(torch.autograd.Function):
         return y
 
     @staticmethod
-    def backward(ctx, dy):
-        with ops.on_device(dy):
-            return _GCNConvWFn._backward(ctx, dy)
-
-    @staticmethod
     def _backward(ctx, dy):
         saved, wp, operand, wsrc = ctx.saved_tensors
         graph, cin = ctx.graph, ctx.cin
@@ -253,16 +316,11 @@ class _GCNConvWFn(torch.autograd.Function):
         dy = dy.contiguous()
         cout = dy.shape[1]
         dyp = _pad_cols(dy)
-        if dyp.shape[1] != cout:           # ragged output width: pad the weight rows to match
-            wrow = torch.zeros((dyp.shape[1], wp.shape[1]), dtype=wp.dtype, device=wp.device)
-            wrow[:cout] = wp
-        else:
-            wrow = wp
+        wrow = _pad_rows_like(wp, dyp, cout)
         need_x, need_ew = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
         db = None
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
-            db = ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+            db = _bias_grad(dy)
         dew = None
         if ctx.agg_first:
             dw = ops.gemm_tn(dyp, saved)
@@ -299,10 +357,7 @@ class GCNConv(nn.Module):
         self.in_channels, self.out_channels = in_channels, out_channels
         self.improved, self.cached, self.add_self_loops, self.normalize = bool(improved), bool(cached), bool(add_self_loops), bool(normalize)
         self.lin = _Lin(in_channels, out_channels)
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(out_channels))
-        else:
-            self.register_parameter("bias", None)
+        _bias_param(self, bias, out_channels)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -313,14 +368,12 @@ class GCNConv(nn.Module):
                 self.bias.zero_()
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_weight=None) -> torch.Tensor:
-        if x.dim() != 2 or x.shape[1] != self.in_channels:
-            raise ValueError("GCNConv: expected x of shape [N, %d]" % self.in_channels)
+        _check_x("GCNConv", x, self.in_channels, bf16=False)
         if edge_weight is not None:
             ops.check_edge_weight(edge_weight, edge_index.shape[1])
             if x.dtype == torch.bfloat16:
                 raise ValueError("GCNConv: bf16 features with edge_weight are not supported on the HIP path")
-        if not x.is_cuda:
-            raise ops.DdmpError("GCNConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        _need_gpu("GCNConv", x)
         default = not self.improved and self.add_self_loops and self.normalize
         with ops.on_device(x):
             if edge_weight is None and default and self.bias is not None:
@@ -339,7 +392,7 @@ class GCNConv(nn.Module):
         return "%d, %d" % (self.in_channels, self.out_channels)
 
 
-class _ChebConvFn(torch.autograd.Function):
+class _ChebConvFn(_Fn):
     """K - 1 fused Chebyshev steps (``ops.spmm_axpby``: gather + three-term recurrence in one launch) into the column
     blocks of ONE [N, K * Cp] buffer, then ONE GEMM against the packed [out, K * Cp] weight.  Backward: one dgrad GEMM,
     one wgrad GEMM, and dX by the Clenshaw recurrence on the same (symmetric) graph, in place in the dgrad's buffer."""
@@ -372,11 +425,6 @@ class _ChebConvFn(torch.autograd.Function):
         return y
 
     @staticmethod
-    def backward(ctx, dy):
-        with ops.on_device(dy):
-            return _ChebConvFn._backward(ctx, dy)
-
-    @staticmethod
     def _backward(ctx, dy):
         t, wp, wsrc = ctx.saved_tensors
         graph, (alpha, beta), (K, cin, cp) = ctx.graph, ctx.coef, ctx.dims
@@ -387,18 +435,12 @@ class _ChebConvFn(torch.autograd.Function):
         dyp = _pad_cols(dy)
         db = None
         if ctx.has_bias and ctx.needs_input_grad[1]:
-            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
-            db = ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+            db = _bias_grad(dy)
         dwp = ops.gemm_tn(dyp, t)
         dws = tuple(dwp[:cout, k * cp:k * cp + cin] if ctx.needs_input_grad[5 + k] else None for k in range(K))
         dx = None
         if ctx.needs_input_grad[0]:
-            if dyp.shape[1] != cout:       # ragged output width: pad the weight rows to match
-                wrow = torch.zeros((dyp.shape[1], wp.shape[1]), dtype=wp.dtype, device=wp.device)
-                wrow[:cout] = wp
-            else:
-                wrow = wp
-            g = ops.gemm_nn(dyp, wrow)     # blocks G_k = dY . W_k
+            g = ops.gemm_nn(dyp, _pad_rows_like(wp, dyp, cout))     # blocks G_k = dY . W_k
             blk = lambda k: g[:, k * cp:(k + 1) * cp] if k < K else None
             # Clenshaw: B_k = G_k + 2 L^ B_{k+1} - B_{k+2} (B_K = B_{K+1} = 0), dX = G_0 + L^ B_1 - B_2; B_k overwrites G_k
             for k in range(K - 2, 0, -1):
@@ -418,10 +460,7 @@ class ChebConv(nn.Module):
             raise ValueError("ChebConv: only normalization='sym' is implemented on the HIP path, got %r" % (normalization,))
         self.in_channels, self.out_channels, self.K, self.normalization = in_channels, out_channels, K, normalization
         self.lins = nn.ModuleList([_Lin(in_channels, out_channels) for _ in range(K)])
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(out_channels))
-        else:
-            self.register_parameter("bias", None)
+        _bias_param(self, bias, out_channels)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -447,10 +486,8 @@ class ChebConv(nn.Module):
             raise ValueError("ChebConv: lambda_max must be a float (a tensor-valued lambda_max is not implemented)")
         if not lambda_max > 0:
             raise ValueError("ChebConv: lambda_max must be positive")
-        if x.dim() != 2 or x.shape[1] != self.in_channels:
-            raise ValueError("ChebConv: expected x of shape [N, %d]" % self.in_channels)
-        if not x.is_cuda:
-            raise ops.DdmpError("ChebConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        _check_x("ChebConv", x, self.in_channels, bf16=False)
+        _need_gpu("ChebConv", x)
         alpha, beta = -2.0 / lambda_max, 2.0 / lambda_max - 1.0
         with ops.on_device(x):
             graph = None                                         # K = 1 needs no graph
@@ -462,7 +499,7 @@ class ChebConv(nn.Module):
         return "%d, %d, K=%d, normalization=%s" % (self.in_channels, self.out_channels, self.K, self.normalization)
 
 
-class _GATConvFn(torch.autograd.Function):
+class _GATConvFn(_Fn):
     """Hf = X W^T (GEMM), the scores, then ONE launch for edge softmax + gather (``ops.gat_fwd``).  Saved: the padded x and weight,
     Hf, the scores and alpha [entries, heads].  Backward: the edge-side launch (ds per entry, ds_dst per node), the node-side launch
     (dHf completely, ds_src), the attention-vector reduction, then the two GEMMs of the linear map.  ``concat=False``: the mean
@@ -489,11 +526,6 @@ class _GATConvFn(torch.autograd.Function):
         return y
 
     @staticmethod
-    def backward(ctx, dy):
-        with ops.on_device(dy):
-            return _GATConvFn._backward(ctx, dy)
-
-    @staticmethod
     def _backward(ctx, dy):
         xp, wp, hf, s_src, s_dst, alpha, asrc, adst = ctx.saved_tensors
         graph, (cin, heads, C, concat, slope) = ctx.graph, ctx.dims
@@ -501,9 +533,7 @@ class _GATConvFn(torch.autograd.Function):
         dy = dy.contiguous().to(torch.float32)
         db = None
         if ctx.has_bias and ctx.needs_input_grad[4]:
-            cout = dy.shape[1]
-            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
-            db = ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+            db = _bias_grad(dy)
         dout = dy if concat else (dy / heads).unsqueeze(1).expand(-1, heads, C).reshape(-1, hc)
         ds, ds_dst = ops.gat_bwd_edge(graph, dout, hf, s_src, s_dst, alpha, heads, slope)
         dhf, ds_src = ops.gat_bwd_node(graph, dout, alpha, ds, ds_dst, asrc, adst, heads)
@@ -512,13 +542,8 @@ class _GATConvFn(torch.autograd.Function):
             datt_src, datt_dst = ops.gat_datt(hf, ds_src, ds_dst, heads)
             datt_src, datt_dst = datt_src.view(1, heads, C), datt_dst.view(1, heads, C)
         dhp = _pad_cols(dhf)
-        if dhp.shape[1] != hc:             # ragged total width: pad the weight rows to match
-            wrow = torch.zeros((dhp.shape[1], wp.shape[1]), dtype=wp.dtype, device=wp.device)
-            wrow[:hc] = wp
-        else:
-            wrow = wp
         dw = ops.gemm_tn(dhp, xp)[:hc, :cin] if ctx.needs_input_grad[1] else None
-        dx = ops.gemm_nn(dhp, wrow)[:, :cin] if ctx.needs_input_grad[0] else None
+        dx = ops.gemm_nn(dhp, _pad_rows_like(wp, dhp, hc))[:, :cin] if ctx.needs_input_grad[0] else None
         return dx, dw, datt_src, datt_dst, db, None, None, None, None
 
 
@@ -539,10 +564,7 @@ class GATConv(nn.Module):
         self.lin_dst = self.lin_src                              # PyG: one Linear under both names when in_channels is an int
         self.att_src = nn.Parameter(torch.empty(1, heads, out_channels))
         self.att_dst = nn.Parameter(torch.empty(1, heads, out_channels))
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(heads * out_channels if concat else out_channels))
-        else:
-            self.register_parameter("bias", None)
+        _bias_param(self, bias, heads * out_channels if concat else out_channels)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -557,8 +579,7 @@ class GATConv(nn.Module):
 
     def forward(self, x, edge_index, edge_attr=None, size=None, return_attention_weights=None) -> torch.Tensor:
         """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
-        if isinstance(x, (tuple, list)):
-            raise ValueError("GATConv: a tuple x (bipartite graphs) is not implemented on the HIP path")
+        _no_tuple_x("GATConv", x)
         if edge_attr is not None:
             raise ValueError("GATConv: edge_attr is not implemented on the HIP path")
         if size is not None:
@@ -567,12 +588,8 @@ class GATConv(nn.Module):
             raise ValueError("GATConv: return_attention_weights is not implemented on the HIP path")
         if self.dropout != 0.0 and self.training:
             raise ValueError("GATConv: attention dropout in training mode is not implemented on the HIP path (dropout=%g)" % self.dropout)
-        if x.dtype == torch.bfloat16:
-            raise ValueError("GATConv: bf16 features are not supported on the HIP path")
-        if x.dim() != 2 or x.shape[1] != self.in_channels:
-            raise ValueError("GATConv: expected x of shape [N, %d]" % self.in_channels)
-        if not x.is_cuda:
-            raise ops.DdmpError("GATConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        _check_x("GATConv", x, self.in_channels)
+        _need_gpu("GATConv", x)
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=self.add_self_loops)
             return _GATConvFn.apply(x, self.lin_src.weight, self.att_src, self.att_dst, self.bias, graph, self.heads, self.concat,
@@ -582,7 +599,7 @@ class GATConv(nn.Module):
         return "%d, %d, heads=%d" % (self.in_channels, self.out_channels, self.heads)
 
 
-class _FeaStConvFn(torch.autograd.Function):
+class _FeaStConvFn(_Fn):
     """ONE GEMM against the packed weight [lin.weight; u.weight] (rows padded to a multiple of 4) gives the row buffer [Hf | P],
     then ONE launch for head softmax + gather (``ops.feast_fwd``).  Saved: the padded x, the packed weight, the [Hf | P] buffer and
     beta [entries, heads].  Backward: the edge-side launch (dz per entry, its row sums rs), the node-side launch that writes
@@ -592,22 +609,14 @@ class _FeaStConvFn(torch.autograd.Function):
     def forward(ctx, x, weight, u, c, bias, graph, heads):
         cin, hc = weight.shape[1], weight.shape[0]
         wt = hc + heads
-        wtp = (wt + 3) // 4 * 4
         xp = _pad_cols(x.detach().to(torch.float32))
-        wp = torch.zeros((wtp, xp.shape[1]), dtype=torch.float32, device=x.device)
-        wp[:hc, :cin] = weight.detach()
-        wp[hc:wt, :cin] = u.detach()
-        buf = ops.gemm_nt(xp, wp)                                # [N, wtp]: Hf | P | zero padding
+        wp = _packed_rows((weight.detach(), u.detach()), xp.shape[1], x.device)
+        buf = ops.gemm_nt(xp, wp)                                # [N, wt rounded up to 4]: Hf | P | zero padding
         b = None if bias is None else bias.detach().contiguous()
         y, beta = ops.feast_fwd(graph, buf[:, :hc], buf[:, hc:wt], c.detach().contiguous(), heads, bias=b)
         ctx.save_for_backward(xp, wp, buf, beta)
         ctx.graph, ctx.dims, ctx.has_bias = graph, (cin, heads, hc), bias is not None
         return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        with ops.on_device(dy):
-            return _FeaStConvFn._backward(ctx, dy)
 
     @staticmethod
     def _backward(ctx, dy):
@@ -617,13 +626,9 @@ class _FeaStConvFn(torch.autograd.Function):
         dy = dy.contiguous().to(torch.float32)
         db = None
         if ctx.has_bias and ctx.needs_input_grad[4]:
-            cout = dy.shape[1]
-            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
-            db = ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+            db = _bias_grad(dy)
         dz, rs = ops.feast_bwd_edge(graph, dy, buf[:, :hc], beta, heads)
-        g = torch.empty((dy.shape[0], wtp), dtype=torch.float32, device=dy.device)
-        if wtp != wt:
-            g[:, wt:] = 0
+        g = _grad_rows(dy.shape[0], [(0, wt)], wtp, dy.device)
         ops.feast_bwd_node(graph, dy, beta, dz, rs, heads, out=g)          # g = [dHf | dP | 0]
         dc = ops.feast_dc(rs, heads) if ctx.needs_input_grad[3] else None
         dw = du = None
@@ -653,10 +658,7 @@ class FeaStConv(nn.Module):
         self.lin = _Lin(in_channels, heads * out_channels)
         self.u = _Lin(in_channels, heads)
         self.c = nn.Parameter(torch.empty(heads))
-        if bias:
-            self.bias = nn.Parameter(torch.empty(out_channels))
-        else:
-            self.register_parameter("bias", None)
+        _bias_param(self, bias, out_channels, torch.empty)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -670,14 +672,9 @@ class FeaStConv(nn.Module):
 
     def forward(self, x, edge_index) -> torch.Tensor:
         """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
-        if isinstance(x, (tuple, list)):
-            raise ValueError("FeaStConv: a tuple x (bipartite graphs) is not implemented on the HIP path")
-        if x.dtype == torch.bfloat16:
-            raise ValueError("FeaStConv: bf16 features are not supported on the HIP path")
-        if x.dim() != 2 or x.shape[1] != self.in_channels:
-            raise ValueError("FeaStConv: expected x of shape [N, %d]" % self.in_channels)
-        if not x.is_cuda:
-            raise ops.DdmpError("FeaStConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        _no_tuple_x("FeaStConv", x)
+        _check_x("FeaStConv", x, self.in_channels)
+        _need_gpu("FeaStConv", x)
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=self.add_self_loops)
             return _FeaStConvFn.apply(x, self.lin.weight, self.u.weight, self.c, self.bias, graph, self.heads)
@@ -686,7 +683,7 @@ class FeaStConv(nn.Module):
         return "%d, %d, heads=%d" % (self.in_channels, self.out_channels, self.heads)
 
 
-class _GMMConvFn(torch.autograd.Function):
+class _GMMConvFn(_Fn):
     """ONE GEMM against the packed weight [g^T ; root.weight] (rows padded to a multiple of 4) gives the row buffer [Hf | R], then
     ONE launch for the per-edge Gaussians + gather + root + bias (``ops.gmm_fwd``).  Saved: the padded x, the packed weight, the
     [Hf | R] buffer, w [entries, K], the float32 pseudo-coordinates (and mu / sigma).  Backward: the edge-side launch (per-row
@@ -698,13 +695,9 @@ class _GMMConvFn(torch.autograd.Function):
         cin, hc = g.shape
         C = hc // K
         wt = hc + (C if root is not None else 0)
-        wtp = (wt + 3) // 4 * 4
         xp = _pad_cols(x.detach().to(torch.float32))
-        wp = torch.zeros((wtp, xp.shape[1]), dtype=torch.float32, device=x.device)
-        wp[:hc, :cin] = g.detach().t()
-        if root is not None:
-            wp[hc:wt, :cin] = root.detach()
-        buf = ops.gemm_nt(xp, wp)                                # [N, wtp]: Hf | R | zero padding
+        wp = _packed_rows((g.detach().t(), None if root is None else root.detach()), xp.shape[1], x.device)
+        buf = ops.gemm_nt(xp, wp)                                # [N, wt rounded up to 4]: Hf | R | zero padding
         b = None if bias is None else bias.detach().contiguous()
         a32 = attr.detach().to(torch.float32).contiguous()       # (float64 pseudo-coordinates are rounded once)
         m, s = mu.detach().contiguous(), sigma.detach().contiguous()
@@ -714,11 +707,6 @@ class _GMMConvFn(torch.autograd.Function):
         return y
 
     @staticmethod
-    def backward(ctx, dy):
-        with ops.on_device(dy):
-            return _GMMConvFn._backward(ctx, dy)
-
-    @staticmethod
     def _backward(ctx, dy):
         xp, wp, buf, w, a32, m, s = ctx.saved_tensors
         graph, (cin, K, hc, wt) = ctx.graph, ctx.dims
@@ -726,13 +714,9 @@ class _GMMConvFn(torch.autograd.Function):
         dy = dy.contiguous().to(torch.float32)
         db = None
         if ctx.has_bias and ctx.needs_input_grad[5]:
-            cout = dy.shape[1]
-            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
-            db = ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+            db = _bias_grad(dy)
         parts, dattr = ops.gmm_bwd_edge(graph, dy, buf[:, :hc], a32, m, s, K, want_dattr=ctx.needs_input_grad[6])
-        gb = torch.empty((dy.shape[0], wtp), dtype=torch.float32, device=dy.device)
-        if wtp != wt:
-            gb[:, wt:] = 0
+        gb = _grad_rows(dy.shape[0], [(0, wt)], wtp, dy.device)
         ops.gmm_bwd_node(graph, dy, w, K, out=gb, root=wt != hc)  # gb = [dHf | dOut | 0]
         dmu = dsigma = None
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
@@ -786,10 +770,7 @@ class GMMConv(nn.Module):
             self.root = _Lin(in_channels, out_channels)
         else:
             self.register_parameter("root", None)
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(out_channels))
-        else:
-            self.register_parameter("bias", None)
+        _bias_param(self, bias, out_channels)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -806,14 +787,10 @@ class GMMConv(nn.Module):
     def forward(self, x, edge_index, edge_attr=None, size=None) -> torch.Tensor:
         """``edge_index`` must have a symmetric structure (both directions of every edge present); ``edge_attr``: [E, dim]
         pseudo-coordinates, float32 or float64 (rounded to float32 once)."""
-        if isinstance(x, (tuple, list)):
-            raise ValueError("GMMConv: a tuple x (bipartite graphs) is not implemented on the HIP path")
+        _no_tuple_x("GMMConv", x)
         if size is not None:
             raise ValueError("GMMConv: size is not implemented on the HIP path")
-        if x.dtype == torch.bfloat16:
-            raise ValueError("GMMConv: bf16 features are not supported on the HIP path")
-        if x.dim() != 2 or x.shape[1] != self.in_channels:
-            raise ValueError("GMMConv: expected x of shape [N, %d]" % self.in_channels)
+        _check_x("GMMConv", x, self.in_channels)
         if not isinstance(edge_attr, torch.Tensor):
             raise ValueError("GMMConv: edge_attr (the pseudo-coordinates, [E, %d]) is required" % self.dim)
         if edge_attr.dim() != 2 or tuple(edge_attr.shape) != (edge_index.shape[1], self.dim):
@@ -845,7 +822,7 @@ def cartesian_pseudo(pos: torch.Tensor, edge_index: torch.Tensor, norm: bool = T
     return cart
 
 
-class _EdgeConvFn(torch.autograd.Function):
+class _EdgeConvFn(_Fn):
     """ONE GEMM against the packed weight [Wa - Wb ; Wb] (each block's rows padded to a multiple of 4) with the bias [b ; 0] gives
     the row buffer [A | B], then ONE launch gathers the per-column maximum of B and who won (``ops.gather_max``).  Saved: the
     padded x, the packed weight and arg [N, out] -- not the row buffer.  Backward: one launch writes [dA | dB]
@@ -858,9 +835,7 @@ class _EdgeConvFn(torch.autograd.Function):
         cp = (cout + 3) // 4 * 4
         xp = _pad_cols(x.detach().to(torch.float32))
         w = weight.detach()
-        wp = torch.zeros((2 * cp, xp.shape[1]), dtype=torch.float32, device=x.device)
-        wp[:cout, :cin] = w[:, :cin] - w[:, cin:]
-        wp[cp:cp + cout, :cin] = w[:, cin:]
+        wp = _packed_rows((w[:, :cin] - w[:, cin:], w[:, cin:]), xp.shape[1], x.device, pad_each=True)
         bp = None
         if bias is not None:
             bp = torch.zeros(2 * cp, dtype=torch.float32, device=x.device)
@@ -873,24 +848,15 @@ class _EdgeConvFn(torch.autograd.Function):
         return y
 
     @staticmethod
-    def backward(ctx, dy):
-        with ops.on_device(dy):
-            return _EdgeConvFn._backward(ctx, dy)
-
-    @staticmethod
     def _backward(ctx, dy):
         xp, wp, arg = ctx.saved_tensors
         graph, (cin, cout, cp) = ctx.graph, ctx.dims
         dy = dy.contiguous().to(torch.float32)
-        g = torch.empty((dy.shape[0], 2 * cp), dtype=torch.float32, device=dy.device)
-        if cp != cout:
-            g[:, cout:cp] = 0
-            g[:, cp + cout:] = 0
+        g = _grad_rows(dy.shape[0], [(0, cout), (cp, cp + cout)], 2 * cp, dy.device)
         da, _ = ops.gather_max_bwd(graph, dy, arg, out=g)        # g = [dA | 0 | dB | 0]
         db = None
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
-            db = ops.colsum(da).to(torch.float32) if pow2 else da.sum(0)
+            db = _bias_grad(da)
         dw = None
         if ctx.needs_input_grad[1]:
             dwp = ops.gemm_tn(g, xp)                             # [dM ; dN]
@@ -948,15 +914,10 @@ class EdgeConv(nn.Module):
 
     def forward(self, x, edge_index) -> torch.Tensor:
         """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
-        if isinstance(x, (tuple, list)):
-            raise ValueError("EdgeConv: a tuple x (bipartite graphs) is not implemented on the HIP path")
-        if x.dtype == torch.bfloat16:
-            raise ValueError("EdgeConv: bf16 features are not supported on the HIP path")
-        if x.dim() != 2 or x.shape[1] != self.in_channels:
-            raise ValueError("EdgeConv: expected x of shape [N, %d]" % self.in_channels)
+        _no_tuple_x("EdgeConv", x)
+        _check_x("EdgeConv", x, self.in_channels)
         _edge_nn(self.nn)                                        # (the module is the user's: it may have been edited since)
-        if not x.is_cuda:
-            raise ops.DdmpError("EdgeConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        _need_gpu("EdgeConv", x)
         return self._core(x, edge_index)
 
     def _core(self, x, edge_index):
