@@ -71,48 +71,6 @@ __global__ __launch_bounds__(256) void gat_scores_scalar_kernel(const float* __r
     }
 }
 
-// ------------------------------------------------------------------------------------------------ the gather of one head pass
-// out[row, hh, :] = init(q) + sum_{e in row} f_e X[col e, hh, :],  f_e = fac[(kMirror ? mirror[e] : e), hh].  The lanes of the
-// pass that hold no valid head (hv false) run head hh = heads - 1 again and store nothing.
-template <bool kMirror, class Init>
-__device__ __forceinline__ void gather_pass(const int* __restrict__ col, const int* __restrict__ mirror, const float* fac,
-                                            const float* __restrict__ X, int64_t ldx, float* orow, int rbase, int nn, int heads,
-                                            int C, int hh, bool hv, int q0, int lw, Init init) {
-    const int W = C >> 2;
-    if (nn == 0) {
-        for (int q = q0; q < W; q += lw)
-            if (hv) *reinterpret_cast<float4*>(orow + hh * C + q * 4) = init(q);
-        return;
-    }
-#pragma unroll 1
-    for (int b0 = 0; b0 < nn; b0 += kEB) {
-        auto batch = [&](auto ne_tag) {
-            constexpr int NE = decltype(ne_tag)::value;
-            const float* xp[NE];
-            float f[NE];
-#pragma unroll
-            for (int k = 0; k < NE; ++k) {
-                const int e = rbase + min(b0 + k, nn - 1);
-                xp[k] = X + (int64_t)col[e] * ldx + hh * C;
-                const int64_t fe = kMirror ? mirror[e] : e;
-                const float v = fac[fe * heads + hh];
-                f[k] = b0 + k < nn ? v : 0.f;
-            }
-            for (int q = q0; q < W; q += lw) {
-                float* op = orow + hh * C + q * 4;
-                float4 acc = b0 == 0 ? init(q) : ld4(op);
-                float4 x[NE];
-#pragma unroll
-                for (int k = 0; k < NE; ++k) x[k] = ld4(xp[k] + q * 4);
-#pragma unroll
-                for (int k = 0; k < NE; ++k) fma4(acc, f[k], x[k]);
-                if (hv) *reinterpret_cast<float4*>(op) = acc;
-            }
-        };
-        ROW_BATCH_SWITCH(b0, nn, batch)
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ forward
 __global__ __launch_bounds__(256) void gat_fwd_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                       const float* __restrict__ mult, const float* __restrict__ Hf, int64_t ldh,

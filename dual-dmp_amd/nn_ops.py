@@ -1,4 +1,5 @@
-"""Drop-in ``GCNConv``, ``ChebConv``, ``GATConv``, ``FeaStConv``, ``EdgeConv`` and ``GMMConv`` on the HIP kernels.
+"""Drop-in ``GCNConv``, ``ChebConv``, ``GATConv``, ``GATv2Conv``, ``FeaStConv``, ``EdgeConv`` and ``GMMConv`` on the HIP kernels
+(``GATv2Conv``: its class docstring and DESIGN.md 4.12).
 
 Same constructor / call signature, parameter names and initialisation as
 ``torch_geometric.nn.GCNConv`` 2.2.0 with the defaults the reference uses
@@ -597,6 +598,156 @@ class GATConv(nn.Module):
 
     def extra_repr(self):
         return "%d, %d, heads=%d" % (self.in_channels, self.out_channels, self.heads)
+
+
+class _GATv2ConvFn(_Fn):
+    """ONE GEMM against the packed weight [lin_l.weight ; lin_r.weight] (``wr`` None = ``share_weights``: lin_l.weight alone) with
+    the packed lin biases as a row broadcast gives the row buffer [Xl | Xr], then ONE launch for the per-edge scores + edge softmax
+    + gather (``ops.gatv2_fwd``).  Saved: the padded x, the packed weight, the row buffer, alpha [entries, heads] and att.
+    Backward: the edge-side launch (dz per entry, dXr, the rows' shares of datt), the node-side launch (dXl), both into ONE row
+    buffer [dXl | dXr] (shared weights: dXr is added into dXl), the datt column sum, the lin bias gradients as column sums of that
+    buffer, then ONE wgrad and ONE dgrad GEMM on it.  ``concat=False``: the mean over heads and its broadcast backward are torch
+    ops around the kernels, as in ``_GATConvFn``."""
+
+    @staticmethod
+    def forward(ctx, x, wl, bl, wr, br, att, bias, graph, heads, concat, slope):
+        cin, hc = wl.shape[1], wl.shape[0]
+        C = hc // heads
+        share = wr is None
+        xp = _pad_cols(x.detach().to(torch.float32))
+        wp = _packed_rows((wl.detach(), None if share else wr.detach()), xp.shape[1], x.device)
+        lb = None
+        if bl is not None:
+            lb = _packed_rows((bl.detach().view(-1, 1), None if share else br.detach().view(-1, 1)), 1, x.device).view(-1)
+        buf = ops.gemm_nt(xp, wp, bias=lb)                       # [N, hc or 2 hc, rounded up to 4]: Xl | Xr | zero padding
+        xl = buf[:, :hc]
+        xr = xl if share else buf[:, hc:2 * hc]
+        a = att.detach().reshape(heads, C).contiguous()
+        b = None if bias is None else bias.detach().contiguous()
+        y, alpha = ops.gatv2_fwd(graph, xl, xr, a, heads, slope, bias=b if concat else None)
+        if not concat:
+            y = y.view(-1, heads, C).mean(1)
+            if b is not None:
+                y = y + b
+        ctx.save_for_backward(xp, wp, buf, alpha, a)
+        ctx.graph, ctx.dims = graph, (cin, heads, C, concat, slope, share)
+        ctx.has_bias, ctx.has_lin_bias = bias is not None, bl is not None
+        return y
+
+    @staticmethod
+    def _backward(ctx, dy):
+        xp, wp, buf, alpha, a = ctx.saved_tensors
+        graph, (cin, heads, C, concat, slope, share) = ctx.graph, ctx.dims
+        hc = heads * C
+        wt = hc if share else 2 * hc
+        need = ctx.needs_input_grad
+        dy = dy.contiguous().to(torch.float32)
+        db = _bias_grad(dy) if ctx.has_bias and need[6] else None
+        dout = dy if concat else (dy / heads).unsqueeze(1).expand(-1, heads, C).reshape(-1, hc)
+        xl = buf[:, :hc]
+        xr = xl if share else buf[:, hc:2 * hc]
+        g = _grad_rows(dy.shape[0], [(0, wt)], wp.shape[0], dy.device)         # [dXl | dXr | 0]
+        dz, dxr, part = ops.gatv2_bwd_edge(graph, dout, xl, xr, a, alpha, heads, slope, out=None if share else g[:, hc:wt],
+                                           want_datt=need[5])
+        ops.gatv2_bwd_node(graph, dout, xl, xr, a, alpha, dz, heads, slope, out=g[:, :hc])
+        if share:
+            g[:, :hc] += dxr
+        datt = ops.gatv2_datt(part, heads).view(1, heads, C) if need[5] else None
+        dbl = dbr = None
+        if ctx.has_lin_bias and need[2]:
+            dbl = _bias_grad(g[:, :hc])
+        if ctx.has_lin_bias and not share and need[4]:
+            dbr = _bias_grad(g[:, hc:wt])
+        dwl = dwr = None
+        if need[1] or (not share and need[3]):
+            dwp = ops.gemm_tn(g, xp)                             # [dW_l ; dW_r]
+            dwl = dwp[:hc, :cin]
+            dwr = None if share else dwp[hc:wt, :cin]
+        dx = ops.gemm_nn(g, wp)[:, :cin] if need[0] else None
+        return dx, dwl, dbl, dwr, dbr, datt, db, None, None, None, None
+
+
+class _LinB(_Lin):
+    """``_Lin`` with PyG ``Linear``'s optional bias [out]."""
+
+    def __init__(self, in_channels, out_channels, bias=True):
+        super().__init__(in_channels, out_channels)
+        _bias_param(self, bias, out_channels, torch.empty)
+
+
+class GATv2Conv(nn.Module):
+    """``torch_geometric.nn.GATv2Conv`` 2.2.0 on the HIP kernels (restated from the published source from memory --
+    PyG cannot be installed here, so this could not be checked against it; the pin is the float64 restatement
+    ``tests/gatv2_ref.py``).
+
+    * parameters ``lin_l`` / ``lin_r``: ``weight`` [heads * out, in] Glorot-uniform and ``bias`` [heads * out]
+      uniform(-1/sqrt(in), 1/sqrt(in)) (absent with ``bias=False``); ``share_weights=True``: ONE module under both names; ``att``
+      [1, heads, out] Glorot; ``bias`` zeros, [heads * out] when ``concat``, else [out].
+    * ``Xl = lin_l(x)``, ``Xr = lin_r(x)`` viewed [N, heads, C]; with ``add_self_loops`` explicit self loops are removed and every
+      node gets exactly one; for an edge j -> i ``z[h] = sum_c att[h,c] leaky_relu(Xl[j,h,c] + Xr[i,h,c], negative_slope)``;
+      ``alpha`` = softmax of z over ALL edges with target i, per head (duplicate edges each take part);
+      ``out[i,h,:] = sum alpha Xl[j,h,:]``; ``concat``: [N, heads * C], else the mean over heads; the bias is added last.
+    * differentiable w.r.t. x, the ``lin_*`` weights and biases, ``att`` and ``bias``; float32, bitwise reproducible.  The graph is
+      GATConv's: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=...)``.  Symmetric edge STRUCTURE only.
+    * refused with ``ValueError`` before any launch: tuple ``in_channels`` or a tuple ``x`` (bipartite), ``edge_dim`` /
+      ``edge_attr``, ``size``, ``return_attention_weights``, ``dropout != 0`` in training mode, bf16 features, CPU tensors."""
+
+    def __init__(self, in_channels, out_channels: int, heads: int = 1, concat: bool = True, negative_slope: float = 0.2,
+                 dropout: float = 0.0, add_self_loops: bool = True, edge_dim=None, fill_value="mean", bias: bool = True,
+                 share_weights: bool = False):
+        super().__init__()
+        if isinstance(in_channels, (tuple, list)):
+            raise ValueError("GATv2Conv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
+        if edge_dim is not None:
+            raise ValueError("GATv2Conv: edge_dim (edge features) is not implemented on the HIP path")
+        if not isinstance(heads, int) or isinstance(heads, bool) or heads < 1:
+            raise ValueError("GATv2Conv: heads must be an integer >= 1, got %r" % (heads,))
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.concat, self.negative_slope, self.dropout = bool(concat), float(negative_slope), float(dropout)
+        self.add_self_loops, self.edge_dim, self.fill_value = bool(add_self_loops), None, fill_value
+        self.share_weights = bool(share_weights)
+        self.lin_l = _LinB(in_channels, heads * out_channels, bias)
+        self.lin_r = self.lin_l if self.share_weights else _LinB(in_channels, heads * out_channels, bias)
+        self.att = nn.Parameter(torch.empty(1, heads, out_channels))
+        _bias_param(self, bias, heads * out_channels if concat else out_channels)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        a = math.sqrt(6.0 / (self.in_channels + self.heads * self.out_channels))     # PyG 'glorot': fan of the last two dims
+        b = math.sqrt(6.0 / (self.heads + self.out_channels))
+        c = 1.0 / math.sqrt(self.in_channels)
+        with torch.no_grad():
+            for lin in (self.lin_l,) if self.share_weights else (self.lin_l, self.lin_r):
+                lin.weight.uniform_(-a, a)
+                if lin.bias is not None:
+                    lin.bias.uniform_(-c, c)
+            self.att.uniform_(-b, b)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def forward(self, x, edge_index, edge_attr=None, size=None, return_attention_weights=None) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
+        _no_tuple_x("GATv2Conv", x)
+        if edge_attr is not None:
+            raise ValueError("GATv2Conv: edge_attr is not implemented on the HIP path")
+        if size is not None:
+            raise ValueError("GATv2Conv: size is not implemented on the HIP path")
+        if return_attention_weights is not None:
+            raise ValueError("GATv2Conv: return_attention_weights is not implemented on the HIP path")
+        if self.dropout != 0.0 and self.training:
+            raise ValueError("GATv2Conv: attention dropout in training mode is not implemented on the HIP path (dropout=%g)" % self.dropout)
+        _check_x("GATv2Conv", x, self.in_channels)
+        if not x.is_cuda:
+            raise ValueError("GATv2Conv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        share = self.share_weights
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=self.add_self_loops)
+            return _GATv2ConvFn.apply(x, self.lin_l.weight, self.lin_l.bias, None if share else self.lin_r.weight,
+                                      None if share else self.lin_r.bias, self.att, self.bias, graph, self.heads, self.concat,
+                                      self.negative_slope)
+
+    def extra_repr(self):
+        return "%d, %d, heads=%d, share_weights=%s" % (self.in_channels, self.out_channels, self.heads, self.share_weights)
 
 
 class _FeaStConvFn(_Fn):

@@ -784,6 +784,101 @@ def gat_datt(hf, ds_src, ds_dst, heads):
     return datt_src, datt_dst
 
 
+# ---------------------------------------------------------------------------------------- dynamic graph attention
+def _gatv2_args(g, xl, xr, att, heads, who):
+    _gat_graph(g)
+    n = g.n_rows
+    xl, ldl, C = _gat_hf(xl, heads, "xl", n)
+    xr, ldr, C2 = _gat_hf(xr, heads, "xr", n)
+    if C2 != C:
+        raise DdmpError("%s: xl and xr differ in width" % who)
+    return n, xl, ldl, xr, ldr, C, _gat_arr(att, (heads, C), "att")
+
+
+def gatv2_fwd(g: Graph, xl, xr, att, heads, slope, bias=None, out=None):
+    """Per-edge scores + edge softmax + gather in one launch (``ddmp_gatv2_fwd_f32``) -> (y [n, heads * C], alpha [g.nnz, heads]).
+    ``xl`` / ``xr``: [n, heads * C] (column blocks of one row buffer, or the same tensor twice); ``att``: [heads, C]; ``bias``:
+    float32 [heads * C] added in the epilogue, or None."""
+    n, xl, ldl, xr, ldr, C, att = _gatv2_args(g, xl, xr, att, heads, "gatv2_fwd")
+    if bias is not None:
+        bias = _gat_arr(bias, (heads * C,), "bias")
+    if out is None:
+        out = torch.empty((n, heads * C), dtype=torch.float32, device=xl.device)
+    out, ldy, _ = _gat_hf(out, heads, "out", n)
+    if out.shape[1] != heads * C:
+        raise DdmpError("gatv2_fwd: out must be [%d, %d]" % (n, heads * C))
+    alpha = torch.empty((g.nnz, heads), dtype=torch.float32, device=xl.device)
+    # algorithmic bytes: xl and xr read once each, y written, alpha written, col + multiplicity, rowptr, att
+    alg = 12.0 * n * heads * C + 4.0 * g.nnz * heads + 8.0 * g.nnz + 4.0 * (n + 1) + 4.0 * heads * C
+    with _timed("gatv2_fwd", _gat_key(g, heads, C), alg, 6.0 * g.nnz * heads * C):
+        st = _lib.lib().ddmp_gatv2_fwd_f32(g.handle, _p(xl), ldl, _p(xr), ldr, heads, C, _p(att), float(slope), _p(bias), _p(alpha),
+                                           _p(out), ldy, _stream())
+    check(st, "ddmp_gatv2_fwd_f32")
+    return out, alpha
+
+
+def gatv2_bwd_edge(g: Graph, dout, xl, xr, att, alpha, heads, slope, out=None, want_datt=True):
+    """Row i's side of the backward (``ddmp_gatv2_bwd_edge_f32``) -> (dz [g.nnz, heads], dxr [n, heads * C] written completely,
+    part [n, heads * C] | None: the rows' shares of datt, for ``gatv2_datt``).  ``out``: where dxr goes (a column block of a row
+    buffer is fine)."""
+    n, xl, ldl, xr, ldr, C, att = _gatv2_args(g, xl, xr, att, heads, "gatv2_bwd_edge")
+    dout, lddo, C2 = _gat_hf(dout, heads, "dout", n)
+    if C2 != C:
+        raise DdmpError("gatv2_bwd_edge: dout and xl differ in width")
+    alpha = _gat_arr(alpha, (g.nnz, heads), "alpha")
+    if out is None:
+        out = torch.empty((n, heads * C), dtype=torch.float32, device=xl.device)
+    out, lddr, C3 = _gat_hf(out, heads, "out", n)
+    if C3 != C:
+        raise DdmpError("gatv2_bwd_edge: out must be [%d, %d]" % (n, heads * C))
+    dz = torch.empty((g.nnz, heads), dtype=torch.float32, device=xl.device)
+    part = torch.empty((n, heads * C), dtype=torch.float32, device=xl.device) if want_datt else None
+    # algorithmic bytes: dout, xl and xr read once each, dxr (and part) written, alpha read, dz written, col, rowptr, att
+    alg = (20.0 if want_datt else 16.0) * n * heads * C + 8.0 * g.nnz * heads + 4.0 * g.nnz + 4.0 * (n + 1) + 4.0 * heads * C
+    with _timed("gatv2_bwd_edge", _gat_key(g, heads, C), alg, 8.0 * g.nnz * heads * C):
+        st = _lib.lib().ddmp_gatv2_bwd_edge_f32(g.handle, _p(dout), lddo, _p(xl), ldl, _p(xr), ldr, heads, C, _p(att), float(slope),
+                                                _p(alpha), _p(dz), _p(out), lddr, _p(part), heads * C, _stream())
+    check(st, "ddmp_gatv2_bwd_edge_f32")
+    return dz, out, part
+
+
+def gatv2_bwd_node(g: Graph, dout, xl, xr, att, alpha, dz, heads, slope, out=None):
+    """Node j's side of the backward (``ddmp_gatv2_bwd_node_f32``) -> dxl [n, heads * C] written completely.  ``out``: where it
+    goes (a column block of a row buffer is fine)."""
+    n, xl, ldl, xr, ldr, C, att = _gatv2_args(g, xl, xr, att, heads, "gatv2_bwd_node")
+    dout, lddo, C2 = _gat_hf(dout, heads, "dout", n)
+    if C2 != C:
+        raise DdmpError("gatv2_bwd_node: dout and xl differ in width")
+    alpha, dz = _gat_arr(alpha, (g.nnz, heads), "alpha"), _gat_arr(dz, (g.nnz, heads), "dz")
+    if out is None:
+        out = torch.empty((n, heads * C), dtype=torch.float32, device=xl.device)
+    out, lddl, C3 = _gat_hf(out, heads, "out", n)
+    if C3 != C:
+        raise DdmpError("gatv2_bwd_node: out must be [%d, %d]" % (n, heads * C))
+    # algorithmic bytes: dout, xr and xl read once each, dxl written, alpha and dz read through the mirror map, col + mirror, rowptr
+    alg = 16.0 * n * heads * C + 8.0 * g.nnz * heads + 8.0 * g.nnz + 4.0 * (n + 1) + 4.0 * heads * C
+    with _timed("gatv2_bwd_node", _gat_key(g, heads, C), alg, 6.0 * g.nnz * heads * C):
+        st = _lib.lib().ddmp_gatv2_bwd_node_f32(g.handle, _p(dout), lddo, _p(xl), ldl, _p(xr), ldr, heads, C, _p(att), float(slope),
+                                                _p(alpha), _p(dz), _p(out), lddl, _stream())
+    check(st, "ddmp_gatv2_bwd_node_f32")
+    return out
+
+
+def gatv2_datt(part, heads):
+    """-> datt [heads, C]: the column sum of the rows' shares ``part`` [n, heads * C] (``ddmp_gatv2_datt_f32``: two-stage column
+    reduction, per-chunk partials in the workspace, fixed order)."""
+    part, ldp, C = _gat_hf(part, heads, "part")
+    n = part.shape[0]
+    L = _lib.lib()
+    need = L.ddmp_gatv2_datt_workspace_bytes(n, heads, C)
+    ws = Workspace.get(need, part.device)
+    datt = torch.empty((heads, C), dtype=torch.float32, device=part.device)
+    with _timed("gatv2_datt", (heads, C), 4.0 * n * heads * C + 2.0 * need, 1.0 * n * heads * C):
+        st = L.ddmp_gatv2_datt_f32(_p(part), ldp, n, heads, C, _p(datt), _p(ws), ws.numel(), _stream())
+    check(st, "ddmp_gatv2_datt_f32")
+    return datt
+
+
 # ---------------------------------------------------------------------------------------- feature-steered convolution (DESIGN.md 4.9)
 def _feast_p(t, heads, name, rows):
     """[n, heads] float32 matrix (a column block of a wider row buffer is fine) -> (tensor, ld)."""

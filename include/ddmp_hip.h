@@ -214,6 +214,43 @@ size_t ddmp_gat_datt_workspace_bytes(int64_t n_rows, int heads, int C);
 int ddmp_gat_datt_f32(const float* Hf, int64_t ldh, int64_t n_rows, int heads, int C, const float* ds_src, const float* ds_dst,
                       float* datt_src, float* datt_dst, void* workspace, size_t workspace_bytes, ddmp_stream stream);
 
+/* ------------------------------------------------------------------ dynamic graph attention (torch_geometric GATv2Conv;
+ * DESIGN.md 4.12).  float32.  Xl = lin_l(x) and Xr = lin_r(x) are [n, heads * C] (head-major columns), each with its own pointer
+ * and leading dimension: column blocks of one packed row buffer [Xl | Xr], or the same matrix twice (share_weights).  att is
+ * [heads, C] contiguous.  The graph is the attention graph above: a VALUED graph left at its all-ones values, a_e = the entry's
+ * multiplicity.  Per-entry arrays (alpha, dz) are entry-major [entries, heads].  No atomics, fixed summation orders: two calls
+ * give the same bits.  The vector kernels need C % 4 == 0, leading dimensions % 4 == 0 and 16-byte aligned matrices; anything
+ * else takes scalar kernels.  An unvalued graph is DDMP_EINVAL.
+ *
+ * forward:   u_e[h,c] = Xl[col e, h, c] + Xr[row e, h, c], z_e[h] = sum_c att[h,c] leaky_relu(u_e[h,c], slope),
+ *            alpha_e = a_e exp(z_e - max_row z) / sum_row a_e exp(..) (written to alpha, saved for the backward; z_e passes
+ *            through the same array), Y[i,h,:] = sum_{e in row i} alpha_e Xl[col e, h, :] (+ bias[h * C + c], nullable).  One
+ *            launch.  A row without entries gets the bias alone and writes no alpha.  exp arguments are <= 0. */
+int ddmp_gatv2_fwd_f32(const ddmp_graph* g, const float* Xl, int64_t ldl, const float* Xr, int64_t ldr, int heads, int C,
+                       const float* att, float slope, const float* bias /*nullable*/, float* alpha, float* Y, int64_t ldy,
+                       ddmp_stream stream);
+/* backward, edge side (row i's side):  dalpha_e = dOut[row e, h, :] . Xl[col e, h, :], delta = sum_row alpha_e dalpha_e,
+ *            dz_e = alpha_e (dalpha_e - delta) -> dz [entries, heads];
+ *            dXr[i,h,c] = sum_{e in row i} dz_e att[h,c] leaky'(u_e[h,c]) (u recomputed from a second gather of Xl; written
+ *            completely, zeros on a row without entries) and, part non-null,
+ *            part[i,h,c] = sum_{e in row i} dz_e leaky_relu(u_e[h,c]): the row's share of datt, [n, heads * C] with leading
+ *            dimension ldp, reduced by ddmp_gatv2_datt_f32. */
+int ddmp_gatv2_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Xl, int64_t ldl, const float* Xr,
+                            int64_t ldr, int heads, int C, const float* att, float slope, const float* alpha, float* dz, float* dXr,
+                            int64_t lddr, float* part /*nullable*/, int64_t ldp, ddmp_stream stream);
+/* backward, node side (node j's side, through the mirror map):
+ *            dXl[j,h,c] = sum_{e' in row j} ( alpha[mirror e', h] dOut[col e', h, c]
+ *                                             + dz[mirror e', h] att[h,c] leaky'(Xl[j,h,c] + Xr[col e', h, c]) )
+ *            (the structure is symmetric: row j's own entries enumerate the targets j feeds).  Writes dXl completely. */
+int ddmp_gatv2_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Xl, int64_t ldl, const float* Xr,
+                            int64_t ldr, int heads, int C, const float* att, float slope, const float* alpha, const float* dz,
+                            float* dXl, int64_t lddl, ddmp_stream stream);
+/* attention-vector gradient:  datt[h,c] = sum_i part[i,h,c]; two stages, per-chunk partials in the caller's workspace, fixed
+ * order. */
+size_t ddmp_gatv2_datt_workspace_bytes(int64_t n_rows, int heads, int C);
+int ddmp_gatv2_datt_f32(const float* part, int64_t ldp, int64_t n_rows, int heads, int C, float* datt, void* workspace,
+                        size_t workspace_bytes, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ feature-steered convolution (torch_geometric FeaStConv;
  * DESIGN.md 4.9).  float32.  Hf is the projected feature matrix [n, heads * C] (head-major columns), P = X u^T the steering
  * projection [n, heads], each with its own pointer and leading dimension (they may be column blocks of one row buffer); c is

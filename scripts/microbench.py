@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|feast|edge|gmm|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|feast|edge|gmm|all] [--rows N] [--iters K]
+gatv2 (not part of all): the dynamic-attention launches (ops.gatv2_fwd, gatv2_bwd_edge, gatv2_bwd_node, gatv2_datt)
+on the same graph and at the same (heads, C) as gat, each alternating in one loop with the gat_* launch of the same role and the
+valued ops.spmm at the same total width; the figures and the algorithmic byte counts go to --out (profiles/gatv2_microbench.txt).
 gmm (not part of all): the Gaussian-mixture launches (ops.gmm_fwd, gmm_bwd_edge, gmm_bwd_node and the feast_dc column sum of the
 [N, 2 K dim] partials) with dim = 3 on the same torus without loops, each alternating in one loop with the valued
 ops.spmm at the gathered width K * C and with the feast_* launch of the same role at the same (heads, C); the figures and the
@@ -42,7 +45,7 @@ ap.add_argument("--widths", default="512,256,128,64,32")
 ap.add_argument("--rotate", type=int, default=1, help="spmm: cycle through this many (input, output) buffer sets so that narrow "
                 "widths are not served from the 256 MB MALL (a 1M x 32 float tensor is 128 MB)")
 ap.add_argument("--weighted", action="store_true", help="spmm: valued graph against the unvalued graph of the same mesh")
-ap.add_argument("--out", default=None, help="gat / feast / edge / gmm: the file the figures are written to (default profiles/<what>_microbench.txt)")
+ap.add_argument("--out", default=None, help="gat / gatv2 / feast / edge / gmm: the file the figures are written to (default profiles/<what>_microbench.txt)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 n = a.rows
@@ -357,6 +360,66 @@ if a.what == "gat":
         print("\n".join(lines[-7:]), flush=True)
         del Hs, Ds, Out, st
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gat_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.what == "gatv2":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    g = ops.graph_for(ei, nn_, norm="gat")
+    reps = max(a.iters, 20)
+    lines = ["dynamic graph attention (GATv2) on the vertex graph of torus(%d, %d) in RCB order: N=%d, entries=%d (loops included), "
+             "float32; median of %d launches [min q1 q3 max], one HIP-event pair per launch, forms alternating in one loop, rotating "
+             "buffer sets; bytes = the algorithmic counts of ops.py (MB)" % (nu_, nv_, nn_, g.nnz, reps)]
+    print(lines[0], flush=True)
+    for heads, C in ((4, 128), (8, 32), (1, 64), (8, 4)):
+        hc = heads * C
+        R = 2 if nn_ * hc * 4 >= (1 << 29) else 4
+        Hs, Rs, Ds = ([torch.randn(nn_, hc, device=dev) for _ in range(R)] for _ in range(3))
+        att, att_d = torch.randn(heads, C, device=dev) * 0.1, torch.randn(heads, C, device=dev) * 0.1
+        Out, Out2 = torch.empty(nn_, hc, device=dev), torch.empty(nn_, hc, device=dev)
+        st = []
+        for i in range(R):                                       # the saved state of a forward per buffer set, both operators
+            s_src, s_dst = ops.gat_scores(Hs[i], att, att_d, heads)
+            y, alpha1 = ops.gat_fwd(g, Hs[i], s_src, s_dst, heads, 0.2)
+            ds, ds_dst = ops.gat_bwd_edge(g, Ds[i], Hs[i], s_src, s_dst, alpha1, heads, 0.2)
+            y, alpha = ops.gatv2_fwd(g, Hs[i], Rs[i], att, heads, 0.2)
+            dz, dxr, part = ops.gatv2_bwd_edge(g, Ds[i], Hs[i], Rs[i], att, alpha, heads, 0.2)
+            st.append((s_src, s_dst, alpha1, ds, ds_dst, alpha, dz, part))
+            del y, dxr
+        q = alternate({
+            "spmm": lambda i: ops.spmm(g, Hs[i], out=Out),
+            "gat_fwd": lambda i: ops.gat_fwd(g, Hs[i], st[i][0], st[i][1], heads, 0.2, out=Out),
+            "fwd": lambda i: ops.gatv2_fwd(g, Hs[i], Rs[i], att, heads, 0.2, out=Out),
+            "gat_bwd_edge": lambda i: ops.gat_bwd_edge(g, Ds[i], Hs[i], st[i][0], st[i][1], st[i][2], heads, 0.2),
+            "bwd_edge": lambda i: ops.gatv2_bwd_edge(g, Ds[i], Hs[i], Rs[i], att, st[i][5], heads, 0.2, out=Out),
+            "bwd_edge_nodatt": lambda i: ops.gatv2_bwd_edge(g, Ds[i], Hs[i], Rs[i], att, st[i][5], heads, 0.2, out=Out, want_datt=False),
+            "gat_bwd_node": lambda i: ops.gat_bwd_node(g, Ds[i], st[i][2], st[i][3], st[i][4], att, att_d, heads),
+            "bwd_node": lambda i: ops.gatv2_bwd_node(g, Ds[i], Hs[i], Rs[i], att, st[i][5], st[i][6], heads, 0.2, out=Out2),
+            "datt": lambda i: ops.gatv2_datt(st[i][7], heads)}, reps, R)
+        feat, ent, node = 4.0 * nn_ * hc, 4.0 * g.nnz, 4.0 * nn_
+        alg = {"spmm": 2 * feat + ent + 2 * node,
+               "gat_fwd": 2 * feat + ent * heads + 2 * node * heads + 2 * ent + node,
+               "fwd": 3 * feat + ent * heads + 2 * ent + node,
+               "gat_bwd_edge": 2 * feat + 2 * ent * heads + 3 * node * heads + ent + node,
+               "bwd_edge": 5 * feat + 2 * ent * heads + ent + node, "bwd_edge_nodatt": 4 * feat + 2 * ent * heads + ent + node,
+               "gat_bwd_node": 2 * feat + 2 * ent * heads + 2 * node * heads + 2 * ent + node,
+               "bwd_node": 4 * feat + 2 * ent * heads + 2 * ent + node, "datt": feat}
+        base = {"fwd": "gat_fwd", "bwd_edge": "gat_bwd_edge", "bwd_edge_nodatt": "gat_bwd_edge", "bwd_node": "gat_bwd_node"}
+        lines.append("heads=%d C=%d (width %d, %d buffer sets):" % (heads, C, hc, R))
+        for k in q:
+            tail = "  x%.2f of %s" % (q[k][2] / q[base[k]][2], base[k]) if k in base else ""
+            lines.append("  %-15s %s  %7.0f MB  %.2f TB/s alg  x%.2f of the valued spmm%s" % (
+                k, fmt(q[k]), alg[k] / 1e6, alg[k] / q[k][2] / 1e6, q[k][2] / q["spmm"][2], tail))
+        print("\n".join(lines[-(len(q) + 1):]), flush=True)
+        del Hs, Rs, Ds, Out, Out2, st
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gatv2_microbench.txt")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
 
