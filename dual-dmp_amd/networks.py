@@ -24,7 +24,10 @@ Two interchangeable forms, both taking the reference's ``Dataset`` object (field
     :class:`nn_ops.EdgeConv` over ``nn.Linear(2 * in, out)`` (static EdgeConv: the maximum over the neighbourhood of a linear
     edge function; parameters ``convN.nn.weight``, ``convN.nn.bias``); ``conv="gmm", K=3`` builds them from
     :class:`nn_ops.GMMConv` with ``dim=3`` and ``kernel_size=K`` (MoNet: K Gaussians over per-edge pseudo-coordinates weigh K
-    weight matrices; parameters ``convN.g``, ``convN.mu``, ``convN.sigma``, ``convN.root.weight``, ``convN.bias``).  Its
+    weight matrices; parameters ``convN.g``, ``convN.mu``, ``convN.sigma``, ``convN.root.weight``, ``convN.bias``);
+    ``conv="transformer", heads=4`` builds them from :class:`nn_ops.TransformerConv` (scaled dot-product attention over the edges
+    with ``out_channels = width // heads`` per head, concatenated, plus the ``lin_skip`` root term; parameters
+    ``convN.lin_query.weight``, ``convN.lin_key.bias`` ...; every width must be divisible by ``heads``).  The GMM operator's
     pseudo-coordinates are the dataset's ``edge_attr`` (vertex graph) / ``face_attr`` (face graph) when it has them, else
     ``nn_ops.cartesian_pseudo`` of the smoothed vertex positions / the noisy face centroids, computed once and cached on the
     dataset.  The fused engine, the trainer, the CLI,
@@ -44,7 +47,7 @@ import torch.nn as nn
 
 from . import ops
 from .engine import ArenaLayout, GcnEngine, NORM_WIDTHS, POS_WIDTHS
-from .nn_ops import ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv, GMMConv, cartesian_pseudo
+from .nn_ops import ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv, GMMConv, TransformerConv, cartesian_pseudo
 
 
 class _EngineFn(torch.autograd.Function):
@@ -266,8 +269,8 @@ class NormalNetFused(_FusedNet):
 
 
 # -------------------------------------------------------------------------------- operator-level form
-_CONVS = ("gcn", "cheb", "gat", "feast", "edge", "gmm")
-_CONV_MSG = "conv must be 'gcn', 'cheb', 'gat', 'feast', 'edge' or 'gmm', got %r"
+_CONVS = ("gcn", "cheb", "gat", "feast", "edge", "gmm", "transformer")
+_CONV_MSG = "conv must be 'gcn', 'cheb', 'gat', 'feast', 'edge', 'gmm' or 'transformer', got %r"
 
 
 class _ModularNet(nn.Module):
@@ -279,13 +282,15 @@ class _ModularNet(nn.Module):
         h = self._widths
         if conv not in _CONVS:
             raise ValueError(_CONV_MSG % (conv,))
-        if conv == "gat":
+        if conv in ("gat", "transformer"):
             bad = [w for w in h[1:13] if not isinstance(heads, int) or heads < 1 or w % heads]
             if bad:
-                raise ValueError("conv='gat': every layer width must be divisible by heads=%r, %r is not" % (heads, bad[0]))
+                raise ValueError("conv=%r: every layer width must be divisible by heads=%r, %r is not" % (conv, heads, bad[0]))
         for i in range(12):
             if conv == "gat":
                 layer = GATConv(h[i], h[i + 1] // heads, heads=heads)
+            elif conv == "transformer":
+                layer = TransformerConv(h[i], h[i + 1] // heads, heads=heads)
             elif conv == "feast":
                 layer = FeaStConv(h[i], h[i + 1], heads=heads)
             elif conv == "edge":

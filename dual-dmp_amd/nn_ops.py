@@ -1,5 +1,5 @@
-"""Drop-in ``GCNConv``, ``ChebConv``, ``GATConv``, ``GATv2Conv``, ``FeaStConv``, ``EdgeConv`` and ``GMMConv`` on the HIP kernels
-(``GATv2Conv``: its class docstring and DESIGN.md 4.12).
+"""Drop-in ``GCNConv``, ``ChebConv``, ``GATConv``, ``GATv2Conv``, ``TransformerConv``, ``FeaStConv``, ``EdgeConv`` and ``GMMConv``
+on the HIP kernels (``GATv2Conv``: its class docstring and DESIGN.md 4.12).
 
 Same constructor / call signature, parameter names and initialisation as
 ``torch_geometric.nn.GCNConv`` 2.2.0 with the defaults the reference uses
@@ -130,6 +130,31 @@ GEOMETRY of an edge: ``edge_attr`` holds per-edge pseudo-coordinates ([E, dim]; 
 * refused with ``ValueError`` before any launch: ``separate_gaussians=True``, ``aggr != "mean"``, tuple ``in_channels`` or a tuple
   ``x`` (bipartite), ``size``, bf16 features, ``edge_attr`` missing, not [E, dim] or not float32 / float64 (float64 is rounded to
   float32 once), ``kernel_size < 1``, ``dim < 1``, ``2 * kernel_size * dim > 256``.
+
+``TransformerConv(in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, edge_dim=None, bias=True,
+root_weight=True)``, ``forward(x, edge_index, edge_attr=None, return_attention_weights=None)`` restates
+``torch_geometric.nn.TransformerConv`` 2.2.0 (Shi et al., "Masked Label Prediction", IJCAI 2021; like the operators above:
+written from the published source from memory -- PyG cannot be installed here, so this could not be checked against it; the pin
+is the float64 restatement ``tests/transformer_ref.py``).  It is the one operator here whose scored stream (K) differs from its
+gathered stream (V).
+
+* parameters ``lin_key`` / ``lin_query`` / ``lin_value`` (weight [heads * out, in], bias [heads * out], always present),
+  ``lin_skip`` (weight [heads * out, in] when ``concat``, else [out, in]; bias only with ``bias=True``), ``lin_beta.weight``
+  [1, 3 * heads * out] (``concat``) or [1, 3 * out], only with ``beta=True`` and ``root_weight=True``; ``lin_edge`` is None.  All
+  uniform(-1/sqrt(in), 1/sqrt(in)) with "in" the layer's own input width.
+* ``z = Q[i,h,:] . K[j,h,:] / sqrt(C)`` for an edge j -> i, ``alpha`` = softmax over ALL edges with target i per head,
+  ``m[i,h,:] = sum alpha V[j,h,:]``, concatenated or averaged over heads; ``out = m + lin_skip(x)``, or the ``beta`` gate
+  ``b x_r + (1 - b) m`` with ``b = sigmoid(lin_beta(cat[m, x_r, m - x_r]))``.  No self loops are added, an explicit loop is an
+  ordinary edge, duplicate edges each take part, a node without incoming edges has ``m = 0``.
+* one GEMM against the packed ``[lin_query ; lin_key ; lin_value ; lin_skip]`` weights (biases as a row broadcast) for the row
+  buffer ``[Q | K | V | S]``, one launch for scores + edge softmax + gather + skip (``ops.tconv_fwd``), two for the backward of
+  the graph part (``ops.tconv_bwd_edge`` / ``ops.tconv_bwd_node``) into ONE row buffer ``[dQ | dK | dV | dS]``, bias gradients as
+  its column sums, one wgrad and one dgrad GEMM.  No [E, heads * out] tensor and no ``index_add_`` exist at any point.  The
+  graph is EdgeConv's: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric edge STRUCTURE only.
+* differentiable w.r.t. x and every parameter in use; float32, bitwise reproducible.
+* refused with ``ValueError`` before any launch: ``edge_dim`` / ``edge_attr``, ``dropout != 0`` in training mode, tuple
+  ``in_channels`` or a tuple ``x`` (bipartite), ``return_attention_weights``, bf16 features, CPU tensors, ``heads < 1``, an ``x``
+  that is not [N, in].
 """
 from __future__ import annotations
 
@@ -198,9 +223,9 @@ class _Fn(torch.autograd.Function):
     """Base of the autograd functions below: ``backward`` enters the gradient's device and runs the subclass's ``_backward``."""
 
     @classmethod
-    def backward(cls, ctx, dy):
-        with ops.on_device(dy):
-            return cls._backward(ctx, dy)
+    def backward(cls, ctx, *dy):
+        with ops.on_device(dy[0]):
+            return cls._backward(ctx, *dy)
 
 
 def _bias_param(module, bias, n, init=torch.zeros):
@@ -748,6 +773,161 @@ class GATv2Conv(nn.Module):
 
     def extra_repr(self):
         return "%d, %d, heads=%d, share_weights=%s" % (self.in_channels, self.out_channels, self.heads, self.share_weights)
+
+
+class _TransformerConvFn(_Fn):
+    """ONE GEMM against the packed weight [lin_query.weight ; lin_key.weight ; lin_value.weight ; lin_skip.weight] (``ws`` None =
+    ``root_weight=False``: no skip block) with the packed lin biases as a row broadcast gives the row buffer [Q | K | V | S], then
+    ONE launch for the dot-product scores + edge softmax + gather (``ops.tconv_fwd``).  Saved: the padded x, the packed weight, the
+    row buffer and alpha [entries, heads].  Backward: the edge-side launch (dz per entry, dQ) and the node-side launch (dK, dV),
+    both into ONE row buffer [dQ | dK | dV | dS], the lin bias gradients as column sums of that buffer, then ONE wgrad and ONE
+    dgrad GEMM on it.  Where the skip goes: ``concat`` without ``beta`` -- added in the forward kernel's epilogue, dS filled by
+    the node-side launch; ``concat=False`` -- the mean over heads, its broadcast backward and the [N, C] skip add are torch ops
+    around the kernels, as in ``_GATv2ConvFn``; ``beta`` -- the function returns (m, x_r) with x_r a view of the S block, and the
+    gradient of x_r lands in the dS block (the gate itself is the module's)."""
+
+    @staticmethod
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv, ws, bs, graph, heads, concat, beta):
+        cin, hc = wq.shape[1], wq.shape[0]
+        C = hc // heads
+        sw = 0 if ws is None else ws.shape[0]                    # the skip block: hc wide when concat, else C; absent without root
+        wt = 3 * hc + sw
+        xp = _pad_cols(x.detach().to(torch.float32))
+        wp = _packed_rows((wq.detach(), wk.detach(), wv.detach(), None if ws is None else ws.detach()), xp.shape[1], x.device)
+        col = lambda b: b.detach().view(-1, 1)
+        sb = None
+        if ws is not None:
+            sb = torch.zeros((sw, 1), dtype=torch.float32, device=x.device) if bs is None else col(bs)
+        lb = _packed_rows((col(bq), col(bk), col(bv), sb), 1, x.device).view(-1)
+        buf = ops.gemm_nt(xp, wp, bias=lb)                       # [N, wt rounded up to 4]: Q | K | V | S | zero padding
+        q, k, v = buf[:, :hc], buf[:, hc:2 * hc], buf[:, 2 * hc:3 * hc]
+        s = buf[:, 3 * hc:wt] if sw else None
+        fused_skip = bool(concat and sw and not beta)
+        y, alpha = ops.tconv_fwd(graph, q, k, v, heads, skip=s if fused_skip else None)
+        if not concat:
+            y = y.view(-1, heads, C).mean(1)
+            if sw and not beta:
+                y = y + s
+        ctx.save_for_backward(xp, wp, buf, alpha)
+        ctx.graph, ctx.dims = graph, (cin, heads, C, sw, concat, beta, fused_skip)
+        ctx.has_skip_bias = bs is not None
+        return (y, s) if beta else y
+
+    @staticmethod
+    def _backward(ctx, dy, dxr=None):
+        xp, wp, buf, alpha = ctx.saved_tensors
+        graph, (cin, heads, C, sw, concat, beta, fused_skip) = ctx.graph, ctx.dims
+        hc = heads * C
+        wt = 3 * hc + sw
+        need = ctx.needs_input_grad
+        dy = dy.contiguous().to(torch.float32)
+        dout = dy if concat else (dy / heads).unsqueeze(1).expand(-1, heads, C).reshape(-1, hc)
+        q, k, v = buf[:, :hc], buf[:, hc:2 * hc], buf[:, 2 * hc:3 * hc]
+        g = _grad_rows(dy.shape[0], [(0, wt)], wp.shape[0], dy.device)         # [dQ | dK | dV | dS | 0]
+        dz, _ = ops.tconv_bwd_edge(graph, dout, k, v, alpha, heads, out=g[:, :hc])
+        ops.tconv_bwd_node(graph, dout, q, alpha, dz, heads, out_k=g[:, hc:2 * hc], out_v=g[:, 2 * hc:3 * hc],
+                           out_s=g[:, 3 * hc:wt] if fused_skip else None)
+        if sw and not fused_skip:
+            g[:, 3 * hc:wt] = dxr.to(torch.float32) if beta else dy
+        dbq = _bias_grad(g[:, :hc]) if need[2] else None
+        dbk = _bias_grad(g[:, hc:2 * hc]) if need[4] else None
+        dbv = _bias_grad(g[:, 2 * hc:3 * hc]) if need[6] else None
+        dbs = _bias_grad(g[:, 3 * hc:wt]) if sw and ctx.has_skip_bias and need[8] else None
+        dwq = dwk = dwv = dws = None
+        if need[1] or need[3] or need[5] or (sw and need[7]):
+            dwp = ops.gemm_tn(g, xp)                             # [dW_q ; dW_k ; dW_v ; dW_s]
+            dwq, dwk, dwv = dwp[:hc, :cin], dwp[hc:2 * hc, :cin], dwp[2 * hc:3 * hc, :cin]
+            dws = dwp[3 * hc:wt, :cin] if sw else None
+        dx = ops.gemm_nn(g, wp)[:, :cin] if need[0] else None
+        return dx, dwq, dbq, dwk, dbk, dwv, dbv, dws, dbs, None, None, None, None
+
+
+class TransformerConv(nn.Module):
+    """``torch_geometric.nn.TransformerConv`` 2.2.0 (Shi et al., "Masked Label Prediction", IJCAI 2021) on the HIP kernels
+    (restated from the published source from memory -- PyG cannot be installed here, so this could not be checked
+    against it; the pin is the float64 restatement ``tests/transformer_ref.py``).
+
+    * parameters ``lin_key`` / ``lin_query`` / ``lin_value``: ``weight`` [heads * out, in] and ``bias`` [heads * out] (always
+      present); ``lin_skip``: ``weight`` [heads * out, in] when ``concat``, else [out, in], its ``bias`` only with ``bias=True`` (the
+      module exists whatever ``root_weight`` says); ``lin_beta.weight`` [1, 3 * heads * out] when ``concat``, else [1, 3 * out],
+      no bias, only with ``beta=True`` (else registered as None); ``lin_edge`` is registered as None.  Everything is
+      uniform(-1/sqrt(in), 1/sqrt(in)) with "in" the layer's own input width.
+    * ``Q = lin_query(x)``, ``K = lin_key(x)``, ``V = lin_value(x)`` viewed [N, heads, C]; for an edge j -> i
+      ``z[h] = Q[i,h,:] . K[j,h,:] / sqrt(C)``; ``alpha`` = softmax of z over ALL edges with target i, per head (duplicate edges
+      each take part); ``m[i,h,:] = sum alpha V[j,h,:]``; ``concat``: [N, heads * C], else the mean over heads.  No self loops are
+      added, an explicit loop is an ordinary edge, a node without incoming edges has ``m = 0``.
+    * ``root_weight``: ``x_r = lin_skip(x)``; ``out = m + x_r``, or with ``beta``
+      ``b = sigmoid(lin_beta(cat[m, x_r, m - x_r]))`` (one scalar per node) and ``out = b x_r + (1 - b) m``.  The gate is torch
+      elementwise ops on [N, .] tensors; no per-edge tensor exists at any point.
+    * differentiable w.r.t. x and every parameter in use; float32, bitwise reproducible.  The graph is EdgeConv's and GMMConv's:
+      ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric edge STRUCTURE only.
+    * refused with ``ValueError`` before any launch: ``edge_dim`` / ``edge_attr``, ``dropout != 0`` in training mode, tuple
+      ``in_channels`` or a tuple ``x`` (bipartite), ``return_attention_weights``, bf16 features, CPU tensors, ``heads < 1``, an
+      ``x`` that is not [N, in]."""
+
+    def __init__(self, in_channels, out_channels: int, heads: int = 1, concat: bool = True, beta: bool = False,
+                 dropout: float = 0.0, edge_dim=None, bias: bool = True, root_weight: bool = True):
+        super().__init__()
+        if isinstance(in_channels, (tuple, list)):
+            raise ValueError("TransformerConv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
+        if edge_dim is not None:
+            raise ValueError("TransformerConv: edge_dim (edge features) is not implemented on the HIP path")
+        if not isinstance(heads, int) or isinstance(heads, bool) or heads < 1:
+            raise ValueError("TransformerConv: heads must be an integer >= 1, got %r" % (heads,))
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.concat, self.root_weight, self.dropout, self.edge_dim = bool(concat), bool(root_weight), float(dropout), None
+        self.beta = bool(beta) and self.root_weight
+        hc = heads * out_channels
+        sw = hc if self.concat else out_channels
+        self.lin_key = _LinB(in_channels, hc)
+        self.lin_query = _LinB(in_channels, hc)
+        self.lin_value = _LinB(in_channels, hc)
+        self.register_parameter("lin_edge", None)
+        self.lin_skip = _LinB(in_channels, sw, bias)
+        if self.beta:
+            self.lin_beta = _LinB(3 * sw, 1, bias=False)
+        else:
+            self.register_parameter("lin_beta", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip, self.lin_beta):
+                if lin is None:
+                    continue
+                a = 1.0 / math.sqrt(lin.weight.shape[1])         # PyG ``Linear``'s default for weight and bias
+                lin.weight.uniform_(-a, a)
+                if lin.bias is not None:
+                    lin.bias.uniform_(-a, a)
+
+    def forward(self, x, edge_index, edge_attr=None, return_attention_weights=None) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
+        _no_tuple_x("TransformerConv", x)
+        if edge_attr is not None:
+            raise ValueError("TransformerConv: edge_attr is not implemented on the HIP path")
+        if return_attention_weights is not None:
+            raise ValueError("TransformerConv: return_attention_weights is not implemented on the HIP path")
+        if self.dropout != 0.0 and self.training:
+            raise ValueError("TransformerConv: attention dropout in training mode is not implemented on the HIP path (dropout=%g)"
+                             % self.dropout)
+        _check_x("TransformerConv", x, self.in_channels)
+        if not x.is_cuda:
+            raise ValueError("TransformerConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        root = self.root_weight
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
+            out = _TransformerConvFn.apply(x, self.lin_query.weight, self.lin_query.bias, self.lin_key.weight, self.lin_key.bias,
+                                           self.lin_value.weight, self.lin_value.bias, self.lin_skip.weight if root else None,
+                                           self.lin_skip.bias if root else None, graph, self.heads, self.concat, self.beta)
+        if not self.beta:
+            return out
+        m, x_r = out
+        b = torch.sigmoid(torch.cat([m, x_r, m - x_r], dim=-1) @ self.lin_beta.weight.t())
+        return b * x_r + (1 - b) * m
+
+    def extra_repr(self):
+        return "%d, %d, heads=%d, concat=%s, beta=%s, root_weight=%s" % (self.in_channels, self.out_channels, self.heads,
+                                                                          self.concat, self.beta, self.root_weight)
 
 
 class _FeaStConvFn(_Fn):

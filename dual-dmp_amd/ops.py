@@ -7,6 +7,7 @@ No wrapper has a CPU path: a non-CUDA tensor raises.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import threading
 import weakref
@@ -877,6 +878,90 @@ def gatv2_datt(part, heads):
         st = L.ddmp_gatv2_datt_f32(_p(part), ldp, n, heads, C, _p(datt), _p(ws), ws.numel(), _stream())
     check(st, "ddmp_gatv2_datt_f32")
     return datt
+
+
+# ---------------------------------------------------------------------------------------- graph transformer
+def _tconv_args(g, heads, who, **mats):
+    """The [n, heads * C] operands of a ``tconv_*`` call by name -> (n, C, {name: (tensor, ld)}); all of one width."""
+    _gat_graph(g)
+    n, C, out = g.n_rows, None, {}
+    for name, t in mats.items():
+        t, ld, c = _gat_hf(t, heads, name, n)
+        if C is not None and c != C:
+            raise DdmpError("%s: %s differs in width from the other operands" % (who, name))
+        C = c
+        out[name] = (t, ld)
+    return n, C, out
+
+
+def _tconv_out(out, n, heads, C, device, who, name="out"):
+    if out is None:
+        out = torch.empty((n, heads * C), dtype=torch.float32, device=device)
+    out, ld, c = _gat_hf(out, heads, name, n)
+    if c != C:
+        raise DdmpError("%s: %s must be [%d, %d]" % (who, name, n, heads * C))
+    return out, ld
+
+
+def tconv_fwd(g: Graph, q, k, v, heads, scale=None, skip=None, out=None):
+    """Dot-product scores + edge softmax + gather in one launch (``ddmp_tconv_fwd_f32``) -> (y [n, heads * C], alpha [g.nnz,
+    heads]).  ``q`` / ``k`` / ``v``: [n, heads * C] (column blocks of one row buffer are fine; ``k`` and ``v`` may be the same
+    tensor); ``scale``: the factor on q . k, default 1 / sqrt(C); ``skip``: [n, heads * C] added in the epilogue, or None."""
+    mats = dict(q=q, k=k, v=v) if skip is None else dict(q=q, k=k, v=v, skip=skip)
+    n, C, m = _tconv_args(g, heads, "tconv_fwd", **mats)
+    (q, ldq), (k, ldk), (v, ldv) = m["q"], m["k"], m["v"]
+    skip, lds = m.get("skip", (None, 0))
+    scale = 1.0 / math.sqrt(C) if scale is None else float(scale)
+    out, ldy = _tconv_out(out, n, heads, C, q.device, "tconv_fwd")
+    alpha = torch.empty((g.nnz, heads), dtype=torch.float32, device=q.device)
+    # algorithmic bytes: q, k and v (and the skip) read once each, y written, alpha written, col + multiplicity, rowptr
+    alg = (16.0 if skip is None else 20.0) * n * heads * C + 4.0 * g.nnz * heads + 8.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("tconv_fwd", _gat_key(g, heads, C), alg, 4.0 * g.nnz * heads * C):
+        st = _lib.lib().ddmp_tconv_fwd_f32(g.handle, _p(q), ldq, _p(k), ldk, _p(v), ldv, heads, C, scale, _p(skip), lds, _p(alpha),
+                                           _p(out), ldy, _stream())
+    check(st, "ddmp_tconv_fwd_f32")
+    return out, alpha
+
+
+def tconv_bwd_edge(g: Graph, dout, k, v, alpha, heads, scale=None, out=None):
+    """Row i's side of the backward (``ddmp_tconv_bwd_edge_f32``) -> (dz [g.nnz, heads], dq [n, heads * C] written completely).
+    ``out``: where dq goes (a column block of a row buffer is fine)."""
+    n, C, m = _tconv_args(g, heads, "tconv_bwd_edge", dout=dout, k=k, v=v)
+    (dout, lddo), (k, ldk), (v, ldv) = m["dout"], m["k"], m["v"]
+    scale = 1.0 / math.sqrt(C) if scale is None else float(scale)
+    alpha = _gat_arr(alpha, (g.nnz, heads), "alpha")
+    out, lddq = _tconv_out(out, n, heads, C, k.device, "tconv_bwd_edge")
+    dz = torch.empty((g.nnz, heads), dtype=torch.float32, device=k.device)
+    # algorithmic bytes: dout, k and v read once each, dq written, alpha read, dz written, col, rowptr
+    alg = 16.0 * n * heads * C + 8.0 * g.nnz * heads + 4.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("tconv_bwd_edge", _gat_key(g, heads, C), alg, 4.0 * g.nnz * heads * C):
+        st = _lib.lib().ddmp_tconv_bwd_edge_f32(g.handle, _p(dout), lddo, _p(k), ldk, _p(v), ldv, heads, C, scale, _p(alpha), _p(dz),
+                                                _p(out), lddq, _stream())
+    check(st, "ddmp_tconv_bwd_edge_f32")
+    return dz, out
+
+
+def tconv_bwd_node(g: Graph, dout, q, alpha, dz, heads, scale=None, out_k=None, out_v=None, out_s=None):
+    """Node j's side of the backward (``ddmp_tconv_bwd_node_f32``) -> (dk, dv) [n, heads * C] each, written completely.
+    ``out_k`` / ``out_v``: where they go; ``out_s``: a [n, heads * C] block that also receives a copy of ``dout`` (the skip
+    term's gradient), or None.  Column blocks of one row buffer are fine."""
+    n, C, m = _tconv_args(g, heads, "tconv_bwd_node", dout=dout, q=q)
+    (dout, lddo), (q, ldq) = m["dout"], m["q"]
+    scale = 1.0 / math.sqrt(C) if scale is None else float(scale)
+    alpha, dz = _gat_arr(alpha, (g.nnz, heads), "alpha"), _gat_arr(dz, (g.nnz, heads), "dz")
+    out_k, lddk = _tconv_out(out_k, n, heads, C, q.device, "tconv_bwd_node", "out_k")
+    out_v, lddv = _tconv_out(out_v, n, heads, C, q.device, "tconv_bwd_node", "out_v")
+    ldds = 0
+    if out_s is not None:
+        out_s, ldds = _tconv_out(out_s, n, heads, C, q.device, "tconv_bwd_node", "out_s")
+    # algorithmic bytes: dout and q read once each, dk and dv (and ds) written, alpha and dz read through the mirror map,
+    # col + mirror, rowptr
+    alg = (16.0 if out_s is None else 20.0) * n * heads * C + 8.0 * g.nnz * heads + 8.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("tconv_bwd_node", _gat_key(g, heads, C), alg, 4.0 * g.nnz * heads * C):
+        st = _lib.lib().ddmp_tconv_bwd_node_f32(g.handle, _p(dout), lddo, _p(q), ldq, heads, C, scale, _p(alpha), _p(dz), _p(out_k),
+                                                lddk, _p(out_v), lddv, _p(out_s), ldds, _stream())
+    check(st, "ddmp_tconv_bwd_node_f32")
+    return out_k, out_v
 
 
 # ---------------------------------------------------------------------------------------- feature-steered convolution (DESIGN.md 4.9)

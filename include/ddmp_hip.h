@@ -251,6 +251,37 @@ size_t ddmp_gatv2_datt_workspace_bytes(int64_t n_rows, int heads, int C);
 int ddmp_gatv2_datt_f32(const float* part, int64_t ldp, int64_t n_rows, int heads, int C, float* datt, void* workspace,
                         size_t workspace_bytes, ddmp_stream stream);
 
+/* ------------------------------------------------------------------ graph transformer (torch_geometric TransformerConv;
+ * DESIGN.md 4.13).  float32.  Q = lin_query(x), K = lin_key(x), V = lin_value(x) and the skip term are [n, heads * C] (head-major
+ * columns), each with its own pointer and leading dimension: column blocks of one packed row buffer [Q | K | V | S].  K and V
+ * may be the same matrix.  scale multiplies the dot product (1 / sqrt(C) in the operator).  The graph is the attention graph
+ * above: a VALUED graph left at its all-ones values, a_e = the entry's multiplicity.  Per-entry arrays (alpha, dz) are entry-major
+ * [entries, heads].  No atomics, fixed summation orders: two calls give the same bits.  The vector kernels need C % 4 == 0, leading
+ * dimensions % 4 == 0 and 16-byte aligned matrices; anything else takes scalar kernels.  heads * C < 2^24.  No output may be one
+ * of the inputs.  An unvalued graph is DDMP_EINVAL.
+ *
+ * forward:   z_e[h] = scale * Q[row e, h, :] . K[col e, h, :], alpha_e = a_e exp(z_e - max_row z) / sum_row a_e exp(..) (written
+ *            to alpha, saved for the backward; z_e passes through the same array),
+ *            Y[i,h,:] = sum_{e in row i} alpha_e V[col e, h, :] (+ skip[i,h,:], nullable, leading dimension lds).  One launch.  A
+ *            row without entries gets its skip row (or zeros) and writes no alpha.  exp arguments are <= 0. */
+int ddmp_tconv_fwd_f32(const ddmp_graph* g, const float* Q, int64_t ldq, const float* K, int64_t ldk, const float* V, int64_t ldv,
+                       int heads, int C, float scale, const float* skip /*nullable*/, int64_t lds, float* alpha, float* Y,
+                       int64_t ldy, ddmp_stream stream);
+/* backward, edge side (row i's side):  dalpha_e = dOut[row e, h, :] . V[col e, h, :], delta = sum_row alpha_e dalpha_e,
+ *            dz_e = alpha_e (dalpha_e - delta) -> dz [entries, heads] (the gradient w.r.t. z_e);
+ *            dQ[i,h,:] = scale sum_{e in row i} dz_e K[col e, h, :] (written completely, zeros on a row without entries). */
+int ddmp_tconv_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* K, int64_t ldk, const float* V,
+                            int64_t ldv, int heads, int C, float scale, const float* alpha, float* dz, float* dQ, int64_t lddq,
+                            ddmp_stream stream);
+/* backward, node side (node j's side, through the mirror map; one launch, both neighbour streams in flight together):
+ *            dK[j,h,:] = scale sum_{e' in row j} dz[mirror e', h] Q[col e', h, :],
+ *            dV[j,h,:] = sum_{e' in row j} alpha[mirror e', h] dOut[col e', h, :]
+ *            (the structure is symmetric: row j's own entries enumerate the targets j feeds) and, dS non-null, the skip term's
+ *            gradient dS[j,:] = dOut[j,:] ([n, heads * C], leading dimension ldds).  Writes dK, dV (and dS) completely. */
+int ddmp_tconv_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Q, int64_t ldq, int heads, int C,
+                            float scale, const float* alpha, const float* dz, float* dK, int64_t lddk, float* dV, int64_t lddv,
+                            float* dS /*nullable*/, int64_t ldds, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ feature-steered convolution (torch_geometric FeaStConv;
  * DESIGN.md 4.9).  float32.  Hf is the projected feature matrix [n, heads * C] (head-major columns), P = X u^T the steering
  * projection [n, heads], each with its own pointer and leading dimension (they may be column blocks of one row buffer); c is

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|feast|edge|gmm|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|feast|edge|gmm|all] [--rows N] [--iters K]
+transformer (not part of all): the dot-product attention launches (ops.tconv_fwd with the skip, tconv_bwd_edge, tconv_bwd_node with
+dS) on the same graph and at the same (heads, C) as gatv2, each alternating in one loop with the gatv2_* launch of
+the same role and the valued ops.spmm at the same total width; the figures and the algorithmic byte counts go to --out
+(profiles/transformer_microbench.txt).
 gatv2 (not part of all): the dynamic-attention launches (ops.gatv2_fwd, gatv2_bwd_edge, gatv2_bwd_node, gatv2_datt)
 on the same graph and at the same (heads, C) as gat, each alternating in one loop with the gat_* launch of the same role and the
 valued ops.spmm at the same total width; the figures and the algorithmic byte counts go to --out (profiles/gatv2_microbench.txt).
@@ -45,7 +49,7 @@ ap.add_argument("--widths", default="512,256,128,64,32")
 ap.add_argument("--rotate", type=int, default=1, help="spmm: cycle through this many (input, output) buffer sets so that narrow "
                 "widths are not served from the 256 MB MALL (a 1M x 32 float tensor is 128 MB)")
 ap.add_argument("--weighted", action="store_true", help="spmm: valued graph against the unvalued graph of the same mesh")
-ap.add_argument("--out", default=None, help="gat / gatv2 / feast / edge / gmm: the file the figures are written to (default profiles/<what>_microbench.txt)")
+ap.add_argument("--out", default=None, help="gat / gatv2 / transformer / feast / edge / gmm: the file the figures are written to (default profiles/<what>_microbench.txt)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 n = a.rows
@@ -420,6 +424,61 @@ if a.what == "gatv2":
         print("\n".join(lines[-(len(q) + 1):]), flush=True)
         del Hs, Rs, Ds, Out, Out2, st
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gatv2_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.what == "transformer":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    g = ops.graph_for(ei, nn_, norm="gat")                       # the gatv2 mode's graph (loops included), for all three operators
+    reps = max(a.iters, 20)
+    lines = ["graph transformer (TransformerConv) on the vertex graph of torus(%d, %d) in RCB order: N=%d, entries=%d (loops "
+             "included, the gatv2 mode's graph), float32; median of %d launches [min q1 q3 max], one HIP-event pair per launch, forms "
+             "alternating in one loop, rotating buffer sets; bytes = the algorithmic counts of ops.py (MB)" % (nu_, nv_, nn_, g.nnz, reps)]
+    print(lines[0], flush=True)
+    for heads, C in ((4, 128), (8, 32), (1, 64), (8, 4)):
+        hc = heads * C
+        R = 2 if nn_ * hc * 4 >= (1 << 29) else 4
+        Qs, Ks, Vs, Ss, Ds = ([torch.randn(nn_, hc, device=dev) for _ in range(R)] for _ in range(5))
+        att = torch.randn(heads, C, device=dev) * 0.1
+        Out, Out2, Out3 = (torch.empty(nn_, hc, device=dev) for _ in range(3))
+        st = []
+        for i in range(R):                                       # the saved state of a forward per buffer set, both operators
+            y, alpha2 = ops.gatv2_fwd(g, Ks[i], Qs[i], att, heads, 0.2)
+            dz2, dxr, _ = ops.gatv2_bwd_edge(g, Ds[i], Ks[i], Qs[i], att, alpha2, heads, 0.2, want_datt=False)
+            y, alpha = ops.tconv_fwd(g, Qs[i], Ks[i], Vs[i], heads, skip=Ss[i])
+            dz, dq = ops.tconv_bwd_edge(g, Ds[i], Ks[i], Vs[i], alpha, heads)
+            st.append((alpha2, dz2, alpha, dz))
+            del y, dxr, dq
+        q = alternate({
+            "spmm": lambda i: ops.spmm(g, Vs[i], out=Out),
+            "gatv2_fwd": lambda i: ops.gatv2_fwd(g, Ks[i], Qs[i], att, heads, 0.2, out=Out),
+            "fwd": lambda i: ops.tconv_fwd(g, Qs[i], Ks[i], Vs[i], heads, skip=Ss[i], out=Out),
+            "gatv2_bwd_edge": lambda i: ops.gatv2_bwd_edge(g, Ds[i], Ks[i], Qs[i], att, st[i][0], heads, 0.2, out=Out, want_datt=False),
+            "bwd_edge": lambda i: ops.tconv_bwd_edge(g, Ds[i], Ks[i], Vs[i], st[i][2], heads, out=Out),
+            "gatv2_bwd_node": lambda i: ops.gatv2_bwd_node(g, Ds[i], Ks[i], Qs[i], att, st[i][0], st[i][1], heads, 0.2, out=Out2),
+            "bwd_node": lambda i: ops.tconv_bwd_node(g, Ds[i], Qs[i], st[i][2], st[i][3], heads, out_k=Out, out_v=Out2, out_s=Out3)},
+            reps, R)
+        feat, ent, node = 4.0 * nn_ * hc, 4.0 * g.nnz, 4.0 * nn_
+        alg = {"spmm": 2 * feat + ent + 2 * node,
+               "gatv2_fwd": 3 * feat + ent * heads + 2 * ent + node, "fwd": 5 * feat + ent * heads + 2 * ent + node,
+               "gatv2_bwd_edge": 4 * feat + 2 * ent * heads + ent + node, "bwd_edge": 4 * feat + 2 * ent * heads + ent + node,
+               "gatv2_bwd_node": 4 * feat + 2 * ent * heads + 2 * ent + node, "bwd_node": 5 * feat + 2 * ent * heads + 2 * ent + node}
+        base = {"fwd": "gatv2_fwd", "bwd_edge": "gatv2_bwd_edge", "bwd_node": "gatv2_bwd_node"}
+        lines.append("heads=%d C=%d (width %d, %d buffer sets):" % (heads, C, hc, R))
+        for k in q:
+            tail = "  x%.2f of %s" % (q[k][2] / q[base[k]][2], base[k]) if k in base else ""
+            lines.append("  %-15s %s  %7.0f MB  %.2f TB/s alg  x%.2f of the valued spmm%s" % (
+                k, fmt(q[k]), alg[k] / 1e6, alg[k] / q[k][2] / 1e6, q[k][2] / q["spmm"][2], tail))
+        print("\n".join(lines[-(len(q) + 1):]), flush=True)
+        del Qs, Ks, Vs, Ss, Ds, Out, Out2, Out3, st
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "transformer_microbench.txt")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
 
