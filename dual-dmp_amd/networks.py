@@ -27,8 +27,10 @@ Two interchangeable forms, both taking the reference's ``Dataset`` object (field
     weight matrices; parameters ``convN.g``, ``convN.mu``, ``convN.sigma``, ``convN.root.weight``, ``convN.bias``);
     ``conv="transformer", heads=4`` builds them from :class:`nn_ops.TransformerConv` (scaled dot-product attention over the edges
     with ``out_channels = width // heads`` per head, concatenated, plus the ``lin_skip`` root term; parameters
-    ``convN.lin_query.weight``, ``convN.lin_key.bias`` ...; every width must be divisible by ``heads``).  The GMM operator's
-    pseudo-coordinates are the dataset's ``edge_attr`` (vertex graph) / ``face_attr`` (face graph) when it has them, else
+    ``convN.lin_query.weight``, ``convN.lin_key.bias`` ...; every width must be divisible by ``heads``); ``conv="resgated"``
+    builds them from :class:`nn_ops.ResGatedGraphConv` (residual gated graph convolution: a per-channel sigmoid gate on every
+    edge plus the ``lin_skip`` root term; parameters ``convN.lin_key.weight``, ``convN.lin_skip.weight``, ``convN.bias`` ...).
+    The GMM operator's pseudo-coordinates are the dataset's ``edge_attr`` (vertex graph) / ``face_attr`` (face graph) if any, else
     ``nn_ops.cartesian_pseudo`` of the smoothed vertex positions / the noisy face centroids, computed once and cached on the
     dataset.  The fused engine, the trainer, the CLI,
     the partitioned path and bf16 features are GCN-only: ``fused=True`` with any other ``conv`` raises.
@@ -47,7 +49,8 @@ import torch.nn as nn
 
 from . import ops
 from .engine import ArenaLayout, GcnEngine, NORM_WIDTHS, POS_WIDTHS
-from .nn_ops import ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv, GMMConv, TransformerConv, cartesian_pseudo
+from .nn_ops import (ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv, GMMConv, ResGatedGraphConv, TransformerConv,
+                     cartesian_pseudo)
 
 
 class _EngineFn(torch.autograd.Function):
@@ -269,8 +272,8 @@ class NormalNetFused(_FusedNet):
 
 
 # -------------------------------------------------------------------------------- operator-level form
-_CONVS = ("gcn", "cheb", "gat", "feast", "edge", "gmm", "transformer")
-_CONV_MSG = "conv must be 'gcn', 'cheb', 'gat', 'feast', 'edge', 'gmm' or 'transformer', got %r"
+_CONVS = ("gcn", "cheb", "gat", "feast", "edge", "gmm", "transformer", "resgated")
+_CONV_MSG = "conv must be 'gcn', 'cheb', 'gat', 'feast', 'edge', 'gmm', 'transformer' or 'resgated', got %r"
 
 
 class _ModularNet(nn.Module):
@@ -291,6 +294,8 @@ class _ModularNet(nn.Module):
                 layer = GATConv(h[i], h[i + 1] // heads, heads=heads)
             elif conv == "transformer":
                 layer = TransformerConv(h[i], h[i + 1] // heads, heads=heads)
+            elif conv == "resgated":
+                layer = ResGatedGraphConv(h[i], h[i + 1])
             elif conv == "feast":
                 layer = FeaStConv(h[i], h[i + 1], heads=heads)
             elif conv == "edge":

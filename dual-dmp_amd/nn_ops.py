@@ -1,5 +1,5 @@
-"""Drop-in ``GCNConv``, ``ChebConv``, ``GATConv``, ``GATv2Conv``, ``TransformerConv``, ``FeaStConv``, ``EdgeConv`` and ``GMMConv``
-on the HIP kernels (``GATv2Conv``: its class docstring and DESIGN.md 4.12).
+"""Drop-in ``GCNConv``, ``ChebConv``, ``GATConv``, ``GATv2Conv``, ``TransformerConv``, ``ResGatedGraphConv``, ``FeaStConv``,
+``EdgeConv`` and ``GMMConv`` on the HIP kernels (``GATv2Conv``: its class docstring and DESIGN.md 4.12).
 
 Same constructor / call signature, parameter names and initialisation as
 ``torch_geometric.nn.GCNConv`` 2.2.0 with the defaults the reference uses
@@ -155,6 +155,28 @@ gathered stream (V).
 * refused with ``ValueError`` before any launch: ``edge_dim`` / ``edge_attr``, ``dropout != 0`` in training mode, tuple
   ``in_channels`` or a tuple ``x`` (bipartite), ``return_attention_weights``, bf16 features, CPU tensors, ``heads < 1``, an ``x``
   that is not [N, in].
+
+``ResGatedGraphConv(in_channels, out_channels, act=Sigmoid(), root_weight=True, bias=True)``, ``forward(x, edge_index)`` restates
+``torch_geometric.nn.ResGatedGraphConv`` 2.2.0 (Bresson & Laurent, "Residual Gated Graph ConvNets", 2017; like the operators
+above: written from the published source from memory -- PyG cannot be installed here, so this could not be checked against it;
+the pin is the float64 restatement ``tests/resgated_ref.py``).  It is the one operator here whose edge weight is as wide as the
+features: a per-channel gate, not a scalar per head.
+
+* parameters ``lin_key`` / ``lin_query`` / ``lin_value`` (weight [out, in], bias [out], always present), ``lin_skip`` (weight
+  [out, in], no bias; None with ``root_weight=False``), ``bias`` [out] zeros (None with ``bias=False``).  The linear layers are
+  uniform(-1/sqrt(in), 1/sqrt(in)).
+* ``out_i = lin_skip(x_i) + bias + sum_{j -> i} sigmoid(lin_key(x_i) + lin_query(x_j)) * lin_value(x_j)``.  No self loops are
+  added, an explicit loop is an ordinary edge, duplicate edges each count, a node without incoming edges returns
+  ``lin_skip(x_i) + bias``.
+* one GEMM against the packed ``[lin_key ; lin_query ; lin_value ; lin_skip]`` weights (biases as a row broadcast) for the row
+  buffer ``[K | Q | V | S]``, one launch for gate + gather + skip + bias (``ops.rgate_fwd``), two for the backward of the graph
+  part (``ops.rgate_bwd_row`` / ``ops.rgate_bwd_node``) into ONE row buffer ``[dK | dQ | dV | dS]``, bias gradients as its column
+  sums, one wgrad and one dgrad GEMM.  NOTHING is stored per edge -- the backward recomputes the gate -- and no ``index_add_``
+  exists at any point.  The graph is EdgeConv's: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric
+  edge STRUCTURE only.
+* differentiable w.r.t. x and every parameter in use; float32, bitwise reproducible.
+* refused with ``ValueError`` before any launch: an ``act`` that is not a ``torch.nn.Sigmoid``, ``aggr`` other than ``"add"``,
+  tuple ``in_channels`` or a tuple ``x`` (bipartite), bf16 features, CPU tensors, an ``x`` that is not [N, in].
 """
 from __future__ import annotations
 
@@ -928,6 +950,125 @@ class TransformerConv(nn.Module):
     def extra_repr(self):
         return "%d, %d, heads=%d, concat=%s, beta=%s, root_weight=%s" % (self.in_channels, self.out_channels, self.heads,
                                                                           self.concat, self.beta, self.root_weight)
+
+
+class _ResGatedFn(_Fn):
+    """ONE GEMM against the packed weight [lin_key.weight ; lin_query.weight ; lin_value.weight ; lin_skip.weight] (``ws`` None =
+    ``root_weight=False``: no skip block) with the packed lin biases as a row broadcast (a zero block for the skip) gives the row
+    buffer [K | Q | V | S], then ONE launch for the per-channel gate + gather with S and ``bias`` as the start of the sums
+    (``ops.rgate_fwd``).  Saved: the padded x, the packed weight and the row buffer -- nothing per entry.  Backward: the row-side
+    launch (dK) and the node-side launch (dQ, dV, and dS = dy copied into the skip block), both recomputing the gate, into ONE
+    row buffer [dK | dQ | dV | dS], the lin bias gradients as column sums of its blocks, then ONE wgrad and ONE dgrad GEMM on
+    it."""
+
+    @staticmethod
+    def forward(ctx, x, wk, bk, wq, bq, wv, bv, ws, bias, graph):
+        cin, C = wk.shape[1], wk.shape[0]
+        sw = 0 if ws is None else C
+        wt = 3 * C + sw
+        xp = _pad_cols(x.detach().to(torch.float32))
+        wp = _packed_rows((wk.detach(), wq.detach(), wv.detach(), None if ws is None else ws.detach()), xp.shape[1], x.device)
+        col = lambda b: b.detach().view(-1, 1)
+        sb = torch.zeros((sw, 1), dtype=torch.float32, device=x.device) if sw else None
+        lb = _packed_rows((col(bk), col(bq), col(bv), sb), 1, x.device).view(-1)
+        buf = ops.gemm_nt(xp, wp, bias=lb)                       # [N, wt rounded up to 4]: K | Q | V | S | zero padding
+        k, q, v = buf[:, :C], buf[:, C:2 * C], buf[:, 2 * C:3 * C]
+        b = None if bias is None else bias.detach().to(torch.float32).contiguous()
+        y = ops.rgate_fwd(graph, k, q, v, skip=buf[:, 3 * C:wt] if sw else None, bias=b)
+        ctx.save_for_backward(xp, wp, buf)
+        ctx.graph, ctx.dims = graph, (cin, C, sw)
+        return y
+
+    @staticmethod
+    def _backward(ctx, dy):
+        xp, wp, buf = ctx.saved_tensors
+        graph, (cin, C, sw) = ctx.graph, ctx.dims
+        wt = 3 * C + sw
+        need = ctx.needs_input_grad
+        dy = dy.contiguous().to(torch.float32)
+        k, q, v = buf[:, :C], buf[:, C:2 * C], buf[:, 2 * C:3 * C]
+        g = _grad_rows(dy.shape[0], [(0, wt)], wp.shape[0], dy.device)         # [dK | dQ | dV | dS | 0]
+        ops.rgate_bwd_row(graph, dy, k, q, v, out=g[:, :C])
+        ops.rgate_bwd_node(graph, dy, k, q, v, out_q=g[:, C:2 * C], out_v=g[:, 2 * C:3 * C], out_s=g[:, 3 * C:wt] if sw else None)
+        dbk = _bias_grad(g[:, :C]) if need[2] else None
+        dbq = _bias_grad(g[:, C:2 * C]) if need[4] else None
+        dbv = _bias_grad(g[:, 2 * C:3 * C]) if need[6] else None
+        db = _bias_grad(dy) if need[8] else None
+        dwk = dwq = dwv = dws = None
+        if need[1] or need[3] or need[5] or (sw and need[7]):
+            dwp = ops.gemm_tn(g, xp)                             # [dW_k ; dW_q ; dW_v ; dW_s]
+            dwk, dwq, dwv = dwp[:C, :cin], dwp[C:2 * C, :cin], dwp[2 * C:3 * C, :cin]
+            dws = dwp[3 * C:wt, :cin] if sw else None
+        dx = ops.gemm_nn(g, wp)[:, :cin] if need[0] else None
+        return dx, dwk, dbk, dwq, dbq, dwv, dbv, dws, db, None
+
+
+class ResGatedGraphConv(nn.Module):
+    """``torch_geometric.nn.ResGatedGraphConv`` 2.2.0 (Bresson & Laurent, "Residual Gated Graph ConvNets", 2017) on the HIP
+    kernels (restated from the published source from memory -- PyG cannot be installed here, so this could not be
+    checked against it; the pin is the float64 restatement ``tests/resgated_ref.py``).
+
+    * parameters ``lin_key`` / ``lin_query`` / ``lin_value``: ``weight`` [out, in] and ``bias`` [out] (always present);
+      ``lin_skip``: ``weight`` [out, in], no bias, registered as None with ``root_weight=False``; ``bias`` [out] zeros, registered
+      as None with ``bias=False``.  The linear layers are uniform(-1/sqrt(in), 1/sqrt(in)).
+    * ``K = lin_key(x)``, ``Q = lin_query(x)``, ``V = lin_value(x)``; for an edge j -> i the gate is PER CHANNEL,
+      ``g = sigmoid(K[i,:] + Q[j,:])``; ``out[i,:] = lin_skip(x_i) + bias + sum_{j -> i} g * V[j,:]`` (duplicate edges each
+      count).  No self loops are added, an explicit loop is an ordinary edge, a node without incoming edges returns
+      ``lin_skip(x_i) + bias``.  No per-edge tensor exists at any point, in the backward either: it recomputes the gate.
+    * differentiable w.r.t. x and every parameter in use; float32, bitwise reproducible.  The graph is EdgeConv's and
+      TransformerConv's: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric edge STRUCTURE only.
+    * refused with ``ValueError`` before any launch: an ``act`` that is not a ``torch.nn.Sigmoid`` instance, ``aggr`` other than
+      ``"add"``, tuple ``in_channels`` or a tuple ``x`` (bipartite), bf16 features, CPU tensors, an ``x`` that is not [N, in]."""
+
+    def __init__(self, in_channels, out_channels: int, act=nn.Sigmoid(), root_weight: bool = True, bias: bool = True, **kwargs):
+        super().__init__()
+        if isinstance(in_channels, (tuple, list)):
+            raise ValueError("ResGatedGraphConv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
+        if not isinstance(act, nn.Sigmoid):
+            raise ValueError("ResGatedGraphConv: the gate of the HIP path is the sigmoid, act must be a torch.nn.Sigmoid, got %r"
+                             % (act,))
+        aggr = kwargs.pop("aggr", "add")
+        if aggr != "add":
+            raise ValueError("ResGatedGraphConv: aggr must be 'add' on the HIP path, got %r" % (aggr,))
+        if kwargs:
+            raise ValueError("ResGatedGraphConv: unsupported arguments %s" % sorted(kwargs))
+        self.in_channels, self.out_channels, self.act, self.root_weight = in_channels, out_channels, act, bool(root_weight)
+        self.lin_key = _LinB(in_channels, out_channels)
+        self.lin_query = _LinB(in_channels, out_channels)
+        self.lin_value = _LinB(in_channels, out_channels)
+        if self.root_weight:
+            self.lin_skip = _LinB(in_channels, out_channels, bias=False)
+        else:
+            self.register_parameter("lin_skip", None)
+        _bias_param(self, bias, out_channels)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip):
+                if lin is None:
+                    continue
+                a = 1.0 / math.sqrt(lin.weight.shape[1])         # PyG ``Linear``'s default for weight and bias
+                lin.weight.uniform_(-a, a)
+                if lin.bias is not None:
+                    lin.bias.uniform_(-a, a)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def forward(self, x, edge_index) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
+        _no_tuple_x("ResGatedGraphConv", x)
+        _check_x("ResGatedGraphConv", x, self.in_channels)
+        if not x.is_cuda:
+            raise ValueError("ResGatedGraphConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
+            return _ResGatedFn.apply(x, self.lin_key.weight, self.lin_key.bias, self.lin_query.weight, self.lin_query.bias,
+                                     self.lin_value.weight, self.lin_value.bias,
+                                     self.lin_skip.weight if self.root_weight else None, self.bias, graph)
+
+    def extra_repr(self):
+        return "%d, %d, root_weight=%s, bias=%s" % (self.in_channels, self.out_channels, self.root_weight, self.bias is not None)
 
 
 class _FeaStConvFn(_Fn):

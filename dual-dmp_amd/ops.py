@@ -964,6 +964,67 @@ def tconv_bwd_node(g: Graph, dout, q, alpha, dz, heads, scale=None, out_k=None, 
     return out_k, out_v
 
 
+# ---------------------------------------------------------------------------------------- residual gated graph conv
+def _rgate_key(g, C):
+    return (C, int(round(g.nnz / max(g.n_rows, 1))))
+
+
+def rgate_fwd(g: Graph, k, q, v, skip=None, bias=None, out=None):
+    """Per-channel sigmoid gate + gather in one launch (``ddmp_rgate_fwd_f32``) -> y [n, C]:
+    ``y[i] = skip[i] + bias + sum_{e in row i} a_e sigmoid(k[i] + q[col e]) * v[col e]``.  ``k`` / ``q`` / ``v``: [n, C] (column
+    blocks of one row buffer are fine); ``skip``: [n, C] and ``bias``: float32 [C], each added in the epilogue, or None.  Nothing
+    is kept per entry."""
+    mats = dict(k=k, q=q, v=v) if skip is None else dict(k=k, q=q, v=v, skip=skip)
+    n, C, m = _tconv_args(g, 1, "rgate_fwd", **mats)
+    (k, ldk), (q, ldq), (v, ldv) = m["k"], m["q"], m["v"]
+    skip, lds = m.get("skip", (None, 0))
+    if bias is not None:
+        bias = _gat_arr(bias, (C,), "bias")
+    out, ldy = _tconv_out(out, n, 1, C, k.device, "rgate_fwd")
+    # algorithmic bytes: k, q and v (and the skip) read once each, y written, col + multiplicity, rowptr, bias
+    alg = (16.0 if skip is None else 20.0) * n * C + 8.0 * g.nnz + 4.0 * (n + 1) + (0.0 if bias is None else 4.0 * C)
+    with _timed("rgate_fwd", _rgate_key(g, C), alg, 6.0 * g.nnz * C):
+        st = _lib.lib().ddmp_rgate_fwd_f32(g.handle, _p(k), ldk, _p(q), ldq, _p(v), ldv, C, _p(skip), lds, _p(bias), _p(out), ldy,
+                                           _stream())
+    check(st, "ddmp_rgate_fwd_f32")
+    return out
+
+
+def rgate_bwd_row(g: Graph, dout, k, q, v, out=None):
+    """Row i's side of the backward (``ddmp_rgate_bwd_row_f32``) -> dk [n, C] written completely; the gate is recomputed.
+    ``out``: where dk goes (a column block of a row buffer is fine)."""
+    n, C, m = _tconv_args(g, 1, "rgate_bwd_row", dout=dout, k=k, q=q, v=v)
+    (dout, lddo), (k, ldk), (q, ldq), (v, ldv) = m["dout"], m["k"], m["q"], m["v"]
+    out, lddk = _tconv_out(out, n, 1, C, k.device, "rgate_bwd_row")
+    # algorithmic bytes: dout, k, q and v read once each, dk written, col + multiplicity, rowptr
+    alg = 20.0 * n * C + 8.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("rgate_bwd_row", _rgate_key(g, C), alg, 9.0 * g.nnz * C):
+        st = _lib.lib().ddmp_rgate_bwd_row_f32(g.handle, _p(dout), lddo, _p(k), ldk, _p(q), ldq, _p(v), ldv, C, _p(out), lddk,
+                                               _stream())
+    check(st, "ddmp_rgate_bwd_row_f32")
+    return out
+
+
+def rgate_bwd_node(g: Graph, dout, k, q, v, out_q=None, out_v=None, out_s=None):
+    """Node j's side of the backward (``ddmp_rgate_bwd_node_f32``) -> (dq, dv) [n, C] each, written completely; the gate is
+    recomputed and the multiplicities are read through the mirror map.  ``out_q`` / ``out_v``: where they go; ``out_s``: a [n, C]
+    block that also receives a copy of ``dout`` (the skip term's gradient), or None.  Column blocks of one row buffer are fine."""
+    n, C, m = _tconv_args(g, 1, "rgate_bwd_node", dout=dout, k=k, q=q, v=v)
+    (dout, lddo), (k, ldk), (q, ldq), (v, ldv) = m["dout"], m["k"], m["q"], m["v"]
+    out_q, lddq = _tconv_out(out_q, n, 1, C, q.device, "rgate_bwd_node", "out_q")
+    out_v, lddv = _tconv_out(out_v, n, 1, C, q.device, "rgate_bwd_node", "out_v")
+    ldds = 0
+    if out_s is not None:
+        out_s, ldds = _tconv_out(out_s, n, 1, C, q.device, "rgate_bwd_node", "out_s")
+    # algorithmic bytes: dout, k, q and v read once each, dq and dv (and ds) written, col + mirror + multiplicity, rowptr
+    alg = (24.0 if out_s is None else 28.0) * n * C + 12.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("rgate_bwd_node", _rgate_key(g, C), alg, 10.0 * g.nnz * C):
+        st = _lib.lib().ddmp_rgate_bwd_node_f32(g.handle, _p(dout), lddo, _p(k), ldk, _p(q), ldq, _p(v), ldv, C, _p(out_q), lddq,
+                                                _p(out_v), lddv, _p(out_s), ldds, _stream())
+    check(st, "ddmp_rgate_bwd_node_f32")
+    return out_q, out_v
+
+
 # ---------------------------------------------------------------------------------------- feature-steered convolution (DESIGN.md 4.9)
 def _feast_p(t, heads, name, rows):
     """[n, heads] float32 matrix (a column block of a wider row buffer is fine) -> (tensor, ld)."""

@@ -282,6 +282,34 @@ int ddmp_tconv_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo
                             float scale, const float* alpha, const float* dz, float* dK, int64_t lddk, float* dV, int64_t lddv,
                             float* dS /*nullable*/, int64_t ldds, ddmp_stream stream);
 
+/* ------------------------------------------------------------------ residual gated graph convolution (torch_geometric
+ * ResGatedGraphConv).  float32.  K = lin_key(x), Q = lin_query(x), V = lin_value(x) and the skip term are [n, C],
+ * each with its own pointer and leading dimension: column blocks of one packed row buffer [K | Q | V | S].  The graph is the
+ * attention graph above: a VALUED graph left at its all-ones values, a_e = the entry's multiplicity.  The gate
+ * g = sigma(K[row e, :] + Q[col e, :]) is PER CHANNEL and is stored nowhere: there is no per-entry array, the backward launches
+ * recompute the gate from the same rows.  sigma(x) = 1 / (1 + exp(-x)) is finite for every finite x.  No atomics, fixed summation
+ * orders: two calls give the same bits.  The vector kernels need C % 4 == 0, leading dimensions % 4 == 0 and 16-byte aligned
+ * matrices (and bias); anything else takes scalar kernels.  C < 2^24.  No output may be one of the inputs or another output.  An
+ * unvalued graph is DDMP_EINVAL.
+ *
+ * forward:   Y[i,:] = skip[i,:] + bias + sum_{e in row i} a_e g_e (.) V[col e, :]  (skip [n, C] with leading dimension lds and bias
+ *            [C] are each nullable).  One launch.  A row without entries gets skip[i,:] + bias exactly. */
+int ddmp_rgate_fwd_f32(const ddmp_graph* g, const float* K, int64_t ldk, const float* Q, int64_t ldq, const float* V, int64_t ldv,
+                       int C, const float* skip /*nullable*/, int64_t lds, const float* bias /*nullable*/, float* Y, int64_t ldy,
+                       ddmp_stream stream);
+/* backward, row side (row i's side):  dK[i,:] = sum_{e in row i} a_e dOut[i,:] (.) V[col e, :] (.) g_e (1 - g_e) (written
+ *            completely, zeros on a row without entries). */
+int ddmp_rgate_bwd_row_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* K, int64_t ldk, const float* Q,
+                           int64_t ldq, const float* V, int64_t ldv, int C, float* dK, int64_t lddk, ddmp_stream stream);
+/* backward, node side (node j's side; row j's own entries e' enumerate the targets i = col e' that j feeds -- the structure is
+ *            symmetric -- with a = the multiplicity of the mirrored entry (i, j) and g = sigma(K[i,:] + Q[j,:])):
+ *            dQ[j,:] = sum_{e'} a dOut[i,:] (.) V[j,:] (.) g (1 - g),   dV[j,:] = sum_{e'} a dOut[i,:] (.) g
+ *            and, dS non-null, the skip term's gradient dS[j,:] = dOut[j,:] ([n, C], leading dimension ldds).  Writes dQ, dV (and
+ *            dS) completely. */
+int ddmp_rgate_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* K, int64_t ldk, const float* Q,
+                            int64_t ldq, const float* V, int64_t ldv, int C, float* dQ, int64_t lddq, float* dV, int64_t lddv,
+                            float* dS /*nullable*/, int64_t ldds, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ feature-steered convolution (torch_geometric FeaStConv;
  * DESIGN.md 4.9).  float32.  Hf is the projected feature matrix [n, heads * C] (head-major columns), P = X u^T the steering
  * projection [n, heads], each with its own pointer and leading dimension (they may be column blocks of one row buffer); c is

@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|feast|edge|gmm|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|all] [--rows N] [--iters K]
+resgated (not part of all): the per-channel gate launches (ops.rgate_fwd with the skip and the bias, rgate_bwd_row, rgate_bwd_node
+with dS) on the vertex graph of a torus with --rows vertices in RCB order, without loops, at the --widths, each
+alternating in one loop with the tconv_* launch of the same role at heads=1 and the same width and with the valued ops.spmm; then
+the torch composition on the same inputs (index_select x3, sigmoid, multiply, index_add_) and its autograd backward; the figures,
+the algorithmic byte counts and each launch's achieved rate on them go to --out (profiles/resgated_microbench.txt).
 transformer (not part of all): the dot-product attention launches (ops.tconv_fwd with the skip, tconv_bwd_edge, tconv_bwd_node with
 dS) on the same graph and at the same (heads, C) as gatv2, each alternating in one loop with the gatv2_* launch of
 the same role and the valued ops.spmm at the same total width; the figures and the algorithmic byte counts go to --out
@@ -49,7 +54,7 @@ ap.add_argument("--widths", default="512,256,128,64,32")
 ap.add_argument("--rotate", type=int, default=1, help="spmm: cycle through this many (input, output) buffer sets so that narrow "
                 "widths are not served from the 256 MB MALL (a 1M x 32 float tensor is 128 MB)")
 ap.add_argument("--weighted", action="store_true", help="spmm: valued graph against the unvalued graph of the same mesh")
-ap.add_argument("--out", default=None, help="gat / gatv2 / transformer / feast / edge / gmm: the file the figures are written to (default profiles/<what>_microbench.txt)")
+ap.add_argument("--out", default=None, help="gat / gatv2 / transformer / resgated / feast / edge / gmm: the file the figures are written to (default profiles/<what>_microbench.txt)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 n = a.rows
@@ -479,6 +484,76 @@ if a.what == "transformer":
         print("\n".join(lines[-(len(q) + 1):]), flush=True)
         del Qs, Ks, Vs, Ss, Ds, Out, Out2, Out3, st
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "transformer_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.what == "resgated":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    g = ops.graph_for(ei, nn_, norm="gat", add_self_loops=False)  # the operator's graph (no loops), for both operators
+    src, dst = ei[0], ei[1]
+    reps = max(a.iters, 20)
+    lines = ["residual gated graph convolution (ResGatedGraphConv) on the vertex graph of torus(%d, %d) in RCB order: N=%d, entries=%d "
+             "(no loops), float32; median of %d launches [min q1 q3 max], one HIP-event pair per launch, forms alternating in one loop, "
+             "rotating buffer sets; bytes = the algorithmic counts of ops.py (MB); tconv_* = the dot-product attention launches at "
+             "heads=1 and the same width on the same graph (the in-tree yardstick); torch = index_select x3, sigmoid, multiply, "
+             "index_add_ on the same inputs (forward) and its autograd backward, mean of 3 runs"
+             % (nu_, nv_, nn_, g.nnz, reps)]
+    print(lines[0], flush=True)
+    for C in [int(c) for c in a.widths.split(",")]:
+        R = 2 if nn_ * C * 4 >= (1 << 29) else 4
+        Ks, Qs, Vs, Ss, Ds = ([torch.randn(nn_, C, device=dev) for _ in range(R)] for _ in range(5))
+        bias = torch.randn(C, device=dev)
+        Out, Out2, Out3 = (torch.empty(nn_, C, device=dev) for _ in range(3))
+        st = []
+        for i in range(R):                                       # the saved state of the attention forward per buffer set
+            y, alpha = ops.tconv_fwd(g, Qs[i], Ks[i], Vs[i], 1, skip=Ss[i])
+            dz, dq = ops.tconv_bwd_edge(g, Ds[i], Ks[i], Vs[i], alpha, 1)
+            st.append((alpha, dz))
+            del y, dq
+        q = alternate({
+            "spmm": lambda i: ops.spmm(g, Vs[i], out=Out),
+            "tconv_fwd": lambda i: ops.tconv_fwd(g, Qs[i], Ks[i], Vs[i], 1, skip=Ss[i], out=Out),
+            "fwd": lambda i: ops.rgate_fwd(g, Ks[i], Qs[i], Vs[i], skip=Ss[i], bias=bias, out=Out),
+            "tconv_bwd_edge": lambda i: ops.tconv_bwd_edge(g, Ds[i], Ks[i], Vs[i], st[i][0], 1, out=Out),
+            "bwd_row": lambda i: ops.rgate_bwd_row(g, Ds[i], Ks[i], Qs[i], Vs[i], out=Out),
+            "tconv_bwd_node": lambda i: ops.tconv_bwd_node(g, Ds[i], Qs[i], st[i][0], st[i][1], 1, out_k=Out, out_v=Out2, out_s=Out3),
+            "bwd_node": lambda i: ops.rgate_bwd_node(g, Ds[i], Ks[i], Qs[i], Vs[i], out_q=Out, out_v=Out2, out_s=Out3)},
+            reps, R)
+        feat, ent, node = 4.0 * nn_ * C, 4.0 * g.nnz, 4.0 * nn_
+        alg = {"spmm": 2 * feat + ent + 2 * node,
+               "tconv_fwd": 5 * feat + 3 * ent + node, "fwd": 5 * feat + 2 * ent + node,
+               "tconv_bwd_edge": 4 * feat + 3 * ent + node, "bwd_row": 5 * feat + 2 * ent + node,
+               "tconv_bwd_node": 5 * feat + 4 * ent + node, "bwd_node": 7 * feat + 3 * ent + node}
+        base = {"fwd": "tconv_fwd", "bwd_row": "tconv_bwd_edge", "bwd_node": "tconv_bwd_node"}
+        lines.append("C=%d (%d buffer sets):" % (C, R))
+        for k in q:
+            tail = "  x%.2f of %s" % (q[k][2] / q[base[k]][2], base[k]) if k in base else ""
+            lines.append("  %-15s %s  %7.0f MB  %.2f TB/s alg = %4.1f%% of 8 TB/s  x%.2f of the valued spmm%s" % (
+                k, fmt(q[k]), alg[k] / 1e6, alg[k] / q[k][2] / 1e6, alg[k] / q[k][2] / 1e6 / 8.0 * 100.0, q[k][2] / q["spmm"][2], tail))
+        # the torch composition on the same inputs: five [E, C] tensors and an index_add_, and its autograd backward
+        kk, qq_, vv_ = (t.clone().requires_grad_(True) for t in (Ks[0], Qs[0], Vs[0]))
+
+        def torch_fwd():
+            gate = torch.sigmoid(kk.index_select(0, dst) + qq_.index_select(0, src))
+            return torch.zeros_like(vv_).index_add_(0, dst, gate * vv_.index_select(0, src)) + Ss[0] + bias
+
+        t_f = timeit(lambda: torch_fwd().detach(), 3)
+        yt = torch_fwd()
+        t_b = timeit(lambda: torch.autograd.grad(yt, (kk, qq_, vv_), Ds[0], retain_graph=True), 3)
+        ours_b = q["bwd_row"][2] + q["bwd_node"][2]
+        err = float((ops.rgate_fwd(g, Ks[0], Qs[0], Vs[0], skip=Ss[0], bias=bias) - yt.detach()).norm() / yt.detach().norm())
+        lines.append("  torch forward %8.0f us = x%.1f of fwd;  torch backward %8.0f us = x%.1f of bwd_row + bwd_node (%.0f us);  "
+                     "rel-L2 fwd vs torch %.1e" % (t_f, t_f / q["fwd"][2], t_b, t_b / ours_b, ours_b, err))
+        print("\n".join(lines[-(len(q) + 2):]), flush=True)
+        del Ks, Qs, Vs, Ss, Ds, Out, Out2, Out3, st, kk, qq_, vv_, yt
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "resgated_microbench.txt")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
 
