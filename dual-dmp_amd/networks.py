@@ -29,8 +29,11 @@ Two interchangeable forms, both taking the reference's ``Dataset`` object (field
     with ``out_channels = width // heads`` per head, concatenated, plus the ``lin_skip`` root term; parameters
     ``convN.lin_query.weight``, ``convN.lin_key.bias`` ...; every width must be divisible by ``heads``); ``conv="resgated"``
     builds them from :class:`nn_ops.ResGatedGraphConv` (residual gated graph convolution: a per-channel sigmoid gate on every
-    edge plus the ``lin_skip`` root term; parameters ``convN.lin_key.weight``, ``convN.lin_skip.weight``, ``convN.bias`` ...).
-    The GMM operator's pseudo-coordinates are the dataset's ``edge_attr`` (vertex graph) / ``face_attr`` (face graph) if any, else
+    edge plus the ``lin_skip`` root term; parameters ``convN.lin_key.weight``, ``convN.lin_skip.weight``, ``convN.bias`` ...);
+    ``conv="spline", K=2`` builds them from :class:`nn_ops.SplineConv` with ``dim=3`` and ``kernel_size=K`` (SplineCNN: every edge
+    mixes the 8 of K^3 weight matrices its pseudo-coordinates select by a linear B-spline basis; parameters ``convN.weight``,
+    ``convN.lin.weight``, ``convN.bias``).
+    The GMM and spline operators' pseudo-coordinates are the dataset's ``edge_attr`` (vertex graph) / ``face_attr`` (face graph) if any, else
     ``nn_ops.cartesian_pseudo`` of the smoothed vertex positions / the noisy face centroids, computed once and cached on the
     dataset.  The fused engine, the trainer, the CLI,
     the partitioned path and bf16 features are GCN-only: ``fused=True`` with any other ``conv`` raises.
@@ -49,7 +52,7 @@ import torch.nn as nn
 
 from . import ops
 from .engine import ArenaLayout, GcnEngine, NORM_WIDTHS, POS_WIDTHS
-from .nn_ops import (ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv, GMMConv, ResGatedGraphConv, TransformerConv,
+from .nn_ops import (ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv, GMMConv, ResGatedGraphConv, SplineConv, TransformerConv,
                      cartesian_pseudo)
 
 
@@ -272,8 +275,8 @@ class NormalNetFused(_FusedNet):
 
 
 # -------------------------------------------------------------------------------- operator-level form
-_CONVS = ("gcn", "cheb", "gat", "feast", "edge", "gmm", "transformer", "resgated")
-_CONV_MSG = "conv must be 'gcn', 'cheb', 'gat', 'feast', 'edge', 'gmm', 'transformer' or 'resgated', got %r"
+_CONVS = ("gcn", "cheb", "gat", "feast", "edge", "gmm", "transformer", "resgated", "spline")
+_CONV_MSG = "conv must be 'gcn', 'cheb', 'gat', 'feast', 'edge', 'gmm', 'transformer', 'resgated' or 'spline', got %r"
 
 
 class _ModularNet(nn.Module):
@@ -302,6 +305,8 @@ class _ModularNet(nn.Module):
                 layer = EdgeConv(nn.Linear(2 * h[i], h[i + 1]))
             elif conv == "gmm":
                 layer = GMMConv(h[i], h[i + 1], dim=3, kernel_size=K)
+            elif conv == "spline":
+                layer = SplineConv(h[i], h[i + 1], dim=3, kernel_size=K)
             else:
                 layer = GCNConv(h[i], h[i + 1]) if conv == "gcn" else ChebConv(h[i], h[i + 1], K)
             setattr(self, "conv%d" % (i + 1), layer)
@@ -348,10 +353,10 @@ class _ModularNet(nn.Module):
 
 
     def _pseudo(self, data, name, pos, edge_index, cols=None):
-        """Pseudo-coordinates of ``conv="gmm"`` (None for every other operator): the dataset's ``name`` attribute when it has
+        """Pseudo-coordinates of ``conv="gmm"`` and ``conv="spline"`` (None for every other operator): the dataset's ``name`` attribute when it has
         one, else ``cartesian_pseudo(pos[:, :cols], edge_index)`` computed once and kept on the dataset like ``_dev``'s copies
         (keyed on the identity and version of the two tensors it was computed from)."""
-        if self.conv_kind != "gmm":
+        if self.conv_kind not in ("gmm", "spline"):
             return None
         if getattr(data, name, None) is not None:
             return self._weight(data, name)

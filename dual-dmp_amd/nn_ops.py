@@ -1,5 +1,6 @@
 """Drop-in ``GCNConv``, ``ChebConv``, ``GATConv``, ``GATv2Conv``, ``TransformerConv``, ``ResGatedGraphConv``, ``FeaStConv``,
-``EdgeConv`` and ``GMMConv`` on the HIP kernels (``GATv2Conv``: its class docstring and DESIGN.md 4.12).
+``EdgeConv``, ``GMMConv`` and ``SplineConv`` on the HIP kernels (``GATv2Conv`` and ``SplineConv``: their class docstrings and
+DESIGN.md 4.12 / 4.15).
 
 Same constructor / call signature, parameter names and initialisation as
 ``torch_geometric.nn.GCNConv`` 2.2.0 with the defaults the reference uses
@@ -1292,6 +1293,145 @@ def cartesian_pseudo(pos: torch.Tensor, edge_index: torch.Tensor, norm: bool = T
         m = cart.abs().max() if max_value is None else max_value
         cart = cart / (2 * m) + 0.5
     return cart
+
+
+class _SplineConvFn(_Fn):
+    """ONE GEMM against the packed weight [weight.permute(0, 2, 1).reshape(K * out, in) ; lin.weight] (rows padded to a multiple of
+    4) gives the row buffer [Hf | R], then ONE launch for the B-spline basis + block gather + root + bias (``ops.spline_fwd``).
+    Saved: the padded x, the packed weight and the float32 pseudo-coordinates -- not the row buffer and nothing per edge: the
+    backward launch evaluates the basis again.  Backward: ONE launch writes [dHf | dOut] into one row buffer
+    (``ops.spline_bwd_node``), then ONE wgrad GEMM ([dweight blocks ; dlin]) and ONE dgrad GEMM (dx)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, root, bias, attr, graph, kernel_size, is_open, mean):
+        K, cin, C = weight.shape
+        hc = K * C
+        wt = hc + (C if root is not None else 0)
+        xp = _pad_cols(x.detach().to(torch.float32))
+        wp = _packed_rows((weight.detach().permute(0, 2, 1).reshape(hc, cin), None if root is None else root.detach()),
+                          xp.shape[1], x.device)
+        buf = ops.gemm_nt(xp, wp)                                # [N, wt rounded up to 4]: Hf | R | zero padding
+        b = None if bias is None else bias.detach().contiguous()
+        a32 = attr.detach().to(torch.float32).contiguous()       # (float64 pseudo-coordinates are rounded once)
+        y = ops.spline_fwd(graph, buf[:, :hc], a32, kernel_size, is_open, root=buf[:, hc:wt] if root is not None else None, bias=b,
+                           mean=mean)
+        ctx.save_for_backward(xp, wp, a32)
+        ctx.graph, ctx.dims, ctx.has_bias, ctx.spline = graph, (cin, K, C, hc, wt), bias is not None, (kernel_size, is_open, mean)
+        return y
+
+    @staticmethod
+    def _backward(ctx, dy):
+        xp, wp, a32 = ctx.saved_tensors
+        graph, (cin, K, C, hc, wt) = ctx.graph, ctx.dims
+        kernel_size, is_open, mean = ctx.spline
+        dy = dy.contiguous().to(torch.float32)
+        db = None
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            db = _bias_grad(dy)
+        gb = _grad_rows(dy.shape[0], [(0, wt)], wp.shape[0], dy.device)
+        ops.spline_bwd_node(graph, dy, a32, kernel_size, is_open, C, mean=mean, out=gb, root=wt != hc)   # gb = [dHf | dOut | 0]
+        dw = droot = None
+        if ctx.needs_input_grad[1] or (wt != hc and ctx.needs_input_grad[2]):
+            dwp = ops.gemm_tn(gb, xp)                            # [dweight as [K * out, in] ; dlin]
+            dw = dwp[:hc, :cin].reshape(K, C, cin).permute(0, 2, 1)
+            droot = dwp[hc:wt, :cin] if wt != hc else None
+        dx = ops.gemm_nn(gb, wp)[:, :cin] if ctx.needs_input_grad[0] else None
+        return dx, dw, droot, db, None, None, None, None, None
+
+
+def _spline_sizes(dim, kernel_size, is_open_spline):
+    """-> (kernel_size, is_open_spline) as tuples of ``dim`` ints / bools, or ``ValueError``."""
+    if not isinstance(dim, int) or isinstance(dim, bool) or dim < 1:
+        raise ValueError("SplineConv: dim must be an integer >= 1, got %r" % (dim,))
+    if dim > ops.SPLINE_MAX_DIM:
+        raise ValueError("SplineConv: dim must be <= %d on the HIP path (2^dim blocks per edge), got %d" % (ops.SPLINE_MAX_DIM, dim))
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    ks = (kernel_size,) * dim if is_int(kernel_size) else kernel_size
+    if not isinstance(ks, (tuple, list)) or len(ks) != dim or not all(is_int(k) and k >= 1 for k in ks):
+        raise ValueError("SplineConv: kernel_size must be an integer >= 1 or a sequence of dim (%d) of them, got %r" % (dim, kernel_size))
+    op = (is_open_spline,) * dim if isinstance(is_open_spline, bool) else is_open_spline
+    if not isinstance(op, (tuple, list)) or len(op) != dim or not all(isinstance(o, bool) for o in op):
+        raise ValueError("SplineConv: is_open_spline must be a bool or a sequence of dim (%d) bools, got %r" % (dim, is_open_spline))
+    return tuple(ks), tuple(op)
+
+
+class SplineConv(nn.Module):
+    """``torch_geometric.nn.SplineConv`` 2.2.0 (Fey et al., SplineCNN, CVPR 2018) with ``degree=1`` on the HIP kernels
+    (DESIGN.md 4.15), without the ``torch_spline_conv`` extension: parameters ``weight`` [K, in, out] with K = prod(kernel_size),
+    uniform(+-1/sqrt(in K)), ``lin.weight`` [out, in] (the root, no bias of its own, uniform(+-1/sqrt(in)); registered as None with
+    ``root_weight=False``) and ``bias`` [out] zeros.  For an edge t: j -> i with pseudo-coordinates ``a_t`` in [0,1]^dim and
+    s in [0, 2^dim) with bits s_d: ``v_d = a_t[d] (kernel_size[d] - is_open_spline[d])``, ``f_d = v_d - floor(v_d)``,
+    ``b_{t,s} = prod_d (s_d ? f_d : 1 - f_d)``, ``k_{t,s} = sum_d ((floor(v_d) + s_d) mod kernel_size[d]) prod_{d' < d}
+    kernel_size[d']``; with ``Hf = x weight`` viewed [N, K, out]:
+    ``out[i] = (1 / n_i) sum_{t -> i} sum_s b_{t,s} Hf[j_t, k_{t,s}, :] + lin(x_i) + bias``, n_i the number of edges into i
+    (``aggr="mean"``) or 1 (``aggr="add"``).  No self loops are added, an explicit loop is an ordinary edge, duplicate edges each
+    count with their own pseudo-coordinates, a node without incoming edges gets ``lin(x_i) + bias``.  Written from the published
+    sources from memory -- PyG cannot be installed here, so this could not be checked against it; the pin is the float64
+    restatement ``tests/spline_ref.py``.  Differentiable w.r.t. x and every parameter, NOT w.r.t. ``edge_attr`` (refused when it
+    requires grad); pseudo-coordinates outside [0, 1] are memory-safe but otherwise unspecified."""
+
+    def __init__(self, in_channels, out_channels: int, dim: int, kernel_size, is_open_spline=True, degree: int = 1,
+                 aggr: str = "mean", root_weight: bool = True, bias: bool = True, **kwargs):
+        super().__init__()
+        if isinstance(in_channels, (tuple, list)):
+            raise ValueError("SplineConv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
+        if degree != 1:
+            raise ValueError("SplineConv: only degree=1 is implemented on the HIP path, got %r" % (degree,))
+        if aggr not in ("mean", "add"):
+            raise ValueError("SplineConv: only aggr='mean' and aggr='add' are implemented on the HIP path, got %r" % (aggr,))
+        if kwargs:
+            raise TypeError("SplineConv: unexpected keyword arguments %s" % sorted(kwargs))
+        ks, op = _spline_sizes(dim, kernel_size, is_open_spline)
+        self.in_channels, self.out_channels, self.dim, self.degree, self.aggr = in_channels, out_channels, dim, 1, aggr
+        self.kernel_size, self.is_open_spline, self.K = ks, op, math.prod(ks)
+        if self.K * out_channels >= 1 << 24:
+            raise ValueError("SplineConv: prod(kernel_size) * out_channels must be below 2^24 on the HIP path, got %d"
+                             % (self.K * out_channels))
+        self.weight = nn.Parameter(torch.empty(self.K, in_channels, out_channels))
+        if root_weight:
+            self.lin = _Lin(in_channels, out_channels)
+        else:
+            self.register_parameter("lin", None)
+        _bias_param(self, bias, out_channels)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            a = 1.0 / math.sqrt(self.in_channels * self.K)
+            self.weight.uniform_(-a, a)
+            if self.lin is not None:
+                a = 1.0 / math.sqrt(self.in_channels)
+                self.lin.weight.uniform_(-a, a)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def forward(self, x, edge_index, edge_attr=None, size=None) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present); ``edge_attr``: [E, dim]
+        pseudo-coordinates in [0, 1], float32 or float64 (rounded to float32 once), not requiring grad."""
+        _no_tuple_x("SplineConv", x)
+        if size is not None:
+            raise ValueError("SplineConv: size is not implemented on the HIP path")
+        _check_x("SplineConv", x, self.in_channels)
+        if not isinstance(edge_attr, torch.Tensor):
+            raise ValueError("SplineConv: edge_attr (the pseudo-coordinates, [E, %d]) is required" % self.dim)
+        if edge_attr.dim() != 2 or tuple(edge_attr.shape) != (edge_index.shape[1], self.dim):
+            raise ValueError("SplineConv: edge_attr must be [%d, %d], got %s" % (edge_index.shape[1], self.dim, tuple(edge_attr.shape)))
+        if edge_attr.dtype not in (torch.float32, torch.float64):
+            raise ValueError("SplineConv: edge_attr must be float32 or float64, got %s" % edge_attr.dtype)
+        if edge_attr.requires_grad:
+            raise ValueError("SplineConv: the gradient with respect to edge_attr is not implemented on the HIP path: pass "
+                             "edge_attr.detach()")
+        if not x.is_cuda or not edge_attr.is_cuda:
+            raise ops.DdmpError("SplineConv runs on the HIP path only: x and edge_attr must be CUDA (ROCm) tensors, there is no CPU "
+                                "fallback")
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
+            return _SplineConvFn.apply(x, self.weight, None if self.lin is None else self.lin.weight, self.bias, edge_attr, graph,
+                                       self.kernel_size, self.is_open_spline, self.aggr == "mean")
+
+    def extra_repr(self):
+        return "%d, %d, dim=%d, kernel_size=%s, aggr=%s" % (self.in_channels, self.out_channels, self.dim, list(self.kernel_size),
+                                                            self.aggr)
 
 
 class _EdgeConvFn(_Fn):

@@ -1235,6 +1235,89 @@ def gmm_bwd_node(g: Graph, dout, w, K, out=None, root=False):
     return dhf, dr
 
 
+# ---------------------------------------------------------------------------------------- B-spline convolution
+SPLINE_MAX_DIM = 5          # S = 2^dim <= 32 selected blocks per edge
+
+
+def _spline_params(g, attr, kernel_size, is_open, C):
+    """-> (attr, ks, op, dim, K, S) checked: attr contiguous float32 [g.nnz_in, dim], ``kernel_size`` / ``is_open`` sequences of
+    dim ints >= 1 / bools as ctypes int32 arrays (host), K = prod(kernel_size), S = 2^dim."""
+    _chk(attr, torch.float32, "attr")
+    if attr.dim() != 2 or attr.shape[0] != g.nnz_in or attr.shape[1] < 1 or not attr.is_contiguous():
+        raise DdmpError("attr must be a contiguous float32 [%d, dim] (one row per input edge), got %s" % (g.nnz_in, tuple(attr.shape)))
+    dim = attr.shape[1]
+    kernel_size, is_open = [int(k) for k in kernel_size], [int(bool(o)) for o in is_open]
+    if not 1 <= dim <= SPLINE_MAX_DIM or len(kernel_size) != dim or len(is_open) != dim or min(kernel_size) < 1:
+        raise DdmpError("kernel_size and is_open must have dim (%d, in [1, %d]) entries, every kernel_size >= 1; got %r, %r"
+                        % (dim, SPLINE_MAX_DIM, kernel_size, is_open))
+    K = math.prod(kernel_size)
+    if K * C >= 1 << 24:
+        raise DdmpError("prod(kernel_size) (%d) x C (%d) must be below 2^24" % (K, C))
+    i32 = ctypes.c_int32 * dim
+    return attr, i32(*kernel_size), i32(*is_open), dim, K, 1 << dim
+
+
+def spline_fwd(g: Graph, hf, attr, kernel_size, is_open, root=None, bias=None, mean=True, out=None):
+    """B-spline basis + block gather in one launch (``ddmp_spline_fwd_f32``) -> y [n, C].  ``hf``: [n, K * C] with
+    K = prod(kernel_size) blocks (the first coordinate varies fastest), ``root``: [n, C] added per row or None (both may be column
+    blocks of one row buffer), ``attr``: [g.nnz_in, dim] pseudo-coordinates of the input edges, ``kernel_size`` / ``is_open``:
+    dim ints / bools, ``bias``: float32 [C] or None, ``mean``: divide a row's sum by its number of input edges."""
+    _gmm_graph(g)
+    n = g.n_rows
+    K = math.prod(int(k) for k in kernel_size)
+    hf, ldh, C = _gat_hf(hf, K, "hf", n)
+    attr, ks, op, dim, K, S = _spline_params(g, attr, kernel_size, is_open, C)
+    ldr = 0
+    if root is not None:
+        root, ldr = _feast_p(root, C, "root", n)
+    if bias is not None:
+        bias = _gat_arr(bias, (C,), "bias")
+    if out is None:
+        out = torch.empty((n, C), dtype=torch.float32, device=hf.device)
+    out, ldy = _mat(_chk(out, torch.float32, "out"), "out")
+    if out.shape[0] < n or out.shape[1] != C:
+        raise DdmpError("spline_fwd: out must be [%d, %d]" % (n, C))
+    # algorithmic bytes: the S selected blocks (C wide) of the neighbour's row per input edge -- not its K blocks --, the output row
+    # written once, the root block read, the attribute rows read once, col + ee_ptr, ee_idx, rowptr
+    alg = (4.0 * g.nnz_in * S * C + 4.0 * n * (1 + (root is not None)) * C + 4.0 * g.nnz_in * (dim + 1) + 8.0 * g.nnz
+           + 4.0 * (n + 1))
+    with _timed("spline_fwd", _gat_key(g, K, C) + (dim,), alg, 2.0 * g.nnz_in * S * C):
+        st = _lib.lib().ddmp_spline_fwd_f32(g.handle, _p(hf), ldh, _p(attr), dim, ks, op, C, _p(root), ldr, _p(bias), int(bool(mean)),
+                                            _p(out), ldy, _stream())
+    check(st, "ddmp_spline_fwd_f32")
+    return out
+
+
+def spline_bwd_node(g: Graph, dout, attr, kernel_size, is_open, C, mean=True, out=None, root=False):
+    """The backward of the graph part in one launch (``ddmp_spline_bwd_node_f32``) -> (dhf [n, K * C] written completely -- blocks
+    no edge selects are zero --, droot [n, C] | None): with ``root`` the launch also copies ``dout`` into the root block's columns.
+    ``dout``: [n, C]; ``out``: a float32 [n, >= K * C (+ C)] row buffer that receives [dhf | droot] in its leading columns (the
+    results are then views of it; further columns are left untouched); None: a buffer of its own."""
+    _gmm_graph(g)
+    n = g.n_rows
+    dout, lddo = _mat(_chk(dout, torch.float32, "dout"), "dout")
+    if dout.shape[0] < n or dout.shape[1] != C or C < 1:
+        raise DdmpError("spline_bwd_node: dout must be [>= %d, %d], got %s" % (n, C, tuple(dout.shape)))
+    attr, ks, op, dim, K, S = _spline_params(g, attr, kernel_size, is_open, C)
+    hc = K * C
+    wt = hc + (C if root else 0)
+    if out is None:
+        out = torch.empty((n, wt), dtype=torch.float32, device=dout.device)
+    out, _ = _mat(_chk(out, torch.float32, "out"), "out")
+    if out.shape[0] != n or out.shape[1] < wt:
+        raise DdmpError("spline_bwd_node: out must be [%d, >= %d], got %s" % (n, wt, tuple(out.shape)))
+    dhf, lddh = _mat(out[:, :hc], "dhf")
+    dr, lddr = _mat(out[:, hc:wt], "droot") if root else (None, 0)
+    # algorithmic bytes: dhf (and the root block) written once, dout read once (and once more for the root block), the attribute
+    # rows read once, col + mirror + ee_ptr, ee_idx, rowptr; the S read-modify-writes per edge stay in the row's own cache lines
+    alg = 4.0 * n * (K + 1 + 2 * bool(root)) * C + 4.0 * g.nnz_in * (dim + 1) + 12.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("spline_bwd_node", _gat_key(g, K, C) + (dim,), alg, 2.0 * g.nnz_in * S * C):
+        st = _lib.lib().ddmp_spline_bwd_node_f32(g.handle, _p(dout), lddo, _p(attr), dim, ks, op, C, int(bool(mean)), _p(dhf), lddh,
+                                                 _p(dr), lddr, _stream())
+    check(st, "ddmp_spline_bwd_node_f32")
+    return dhf, dr
+
+
 # ---------------------------------------------------------------------------------------- max aggregation (DESIGN.md 4.10)
 def _gmax_mat(t, name, rows, C=None):
     """[>= rows, C] float32 matrix (a column block of a wider row buffer is fine) -> (tensor, ld)."""

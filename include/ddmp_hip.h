@@ -373,6 +373,34 @@ int ddmp_gmm_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, 
 int ddmp_gmm_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, int K, int C, const float* w, float* dHf,
                           int64_t lddh, float* dR /*nullable*/, int64_t lddr, ddmp_stream stream);
 
+/* ------------------------------------------------------------------ B-spline convolution (torch_geometric SplineConv, degree 1,
+ * mean or add aggregation).  float32.  Hf is the projected feature matrix [n, K * C] with K = prod(kernel_size)
+ * blocks of C columns, block index = sum_d index_d * prod_{d' < d} kernel_size[d'] (the first coordinate varies fastest); attr holds
+ * the pseudo-coordinates of the INPUT edges, contiguous [input edges, dim], in the order of the edge list the graph was created
+ * from; kernel_size and is_open are HOST arrays of dim ints (kernel_size[d] >= 1, is_open[d] 0 or 1).  1 <= dim <= 5 and
+ * K * C < 2^24; anything else is DDMP_EINVAL.  The graph is the one of the Gaussian-mixture kernels (flags 0, all-ones values).
+ * With v_d = attr[t,d] (kernel_size[d] - is_open[d]), f_d = v_d - floor(v_d), s in [0, 2^dim) and s_d its bit d:
+ *            b_{t,s} = prod_d (s_d ? f_d : 1 - f_d),  k_{t,s} = sum_d ((floor(v_d) + s_d) mod kernel_size[d]) prod_{d' < d} kernel_size[d']
+ * (a true non-negative modulo, clamped into [0, kernel_size[d]): the block index is in range for EVERY attr value; the result for
+ * pseudo-coordinates outside [0, 1] or non-finite is otherwise unspecified).  Nothing is stored per edge: both launches evaluate
+ * the basis from attr.  No atomics, fixed summation orders: two calls give the same bits.  The vector kernels need C % 4 == 0,
+ * leading dimensions % 4 == 0 and 16-byte aligned matrices; anything else takes scalar kernels.
+ *
+ * forward:   Y[i,:] = (1 / n_i) sum_{e in row i} sum_{t in the edges of e, input order} sum_s b_{t,s} Hf[col e, k_{t,s}, :]
+ *                     (+ R[i,:], nullable, own leading dimension) (+ bias[C], nullable),
+ *            n_i = the number of input edges into i (mean != 0) or 1 (mean == 0).  Only the 2^dim selected blocks of a gathered
+ *            row are read.  Y is [n, C].  One launch.  A row without entries gets R[i,:] + bias. */
+int ddmp_spline_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ldh, const float* attr, int dim, const int32_t* kernel_size,
+                        const int32_t* is_open, int C, const float* R /*nullable*/, int64_t ldr, const float* bias /*nullable*/,
+                        int mean, float* Y, int64_t ldy, ddmp_stream stream);
+/* backward, node side:  dHf[j,k,:] = sum_{e' in row j} sum_{t in the edges of mirror e'} [sum_{s: k_{t,s} = k} b_{t,s}] dOut[col e', :] / n_{col e'}
+ *            written completely (a block no edge selects is zero; the structure is symmetric: row j's own entries enumerate the
+ *            targets j feeds, the mirrored entry holds the edges j -> col e') and, dR non-null, dR[j,:] = dOut[j,:] (the root
+ *            block's gradient; dHf and dR are meant to be column blocks of one row buffer).  One launch. */
+int ddmp_spline_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* attr, int dim,
+                             const int32_t* kernel_size, const int32_t* is_open, int C, int mean, float* dHf, int64_t lddh,
+                             float* dR /*nullable*/, int64_t lddr, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ max aggregation (torch_geometric EdgeConv with a Linear edge
  * function).  float32.  The graph is the attention graph above (a VALUED graph; its values are not read: the
  * structure is coalesced and a duplicate edge cannot change a maximum); an unvalued graph is DDMP_EINVAL.  Every matrix has its own

@@ -1,6 +1,12 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|spline|all] [--rows N] [--iters K]
+spline (not part of all): the two B-spline launches (ops.spline_fwd with the root block and the bias, ops.spline_bwd_node with dR;
+DESIGN.md 4.15) with dim = 3 and kernel_size 2 and 5 on the vertex graph of a torus with --rows vertices in RCB order, without loops,
+each alternating in one loop with gmm_fwd / gmm_bwd_node at K = 8 (the number of blocks an edge selects) on the same graph and
+width; then the torch edge-list composition on the same inputs (the basis, a [E, 8, C] block gather, multiply, sum, index_add_) and
+its autograd backward; the figures, the algorithmic byte counts and each launch's achieved rate on them go to --out
+(profiles/spline_microbench.txt).
 resgated (not part of all): the per-channel gate launches (ops.rgate_fwd with the skip and the bias, rgate_bwd_row, rgate_bwd_node
 with dS) on the vertex graph of a torus with --rows vertices in RCB order, without loops, at the --widths, each
 alternating in one loop with the tconv_* launch of the same role at heads=1 and the same width and with the valued ops.spmm; then
@@ -54,7 +60,7 @@ ap.add_argument("--widths", default="512,256,128,64,32")
 ap.add_argument("--rotate", type=int, default=1, help="spmm: cycle through this many (input, output) buffer sets so that narrow "
                 "widths are not served from the 256 MB MALL (a 1M x 32 float tensor is 128 MB)")
 ap.add_argument("--weighted", action="store_true", help="spmm: valued graph against the unvalued graph of the same mesh")
-ap.add_argument("--out", default=None, help="gat / gatv2 / transformer / resgated / feast / edge / gmm: the file the figures are written to (default profiles/<what>_microbench.txt)")
+ap.add_argument("--out", default=None, help="gat / gatv2 / transformer / resgated / feast / edge / gmm / spline: the file the figures are written to (default profiles/<what>_microbench.txt)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 n = a.rows
@@ -719,5 +725,90 @@ if a.what == "gmm":
         print("\n".join(lines[-(len(alg) + 1):]), flush=True)
         del Bs, Hs, Rs, Ps, Ds, Out, Wide, G, Gf, st
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gmm_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.what == "spline":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    src, dst = ei[0], ei[1]
+    g = ops.graph_for(ei, nn_, norm="gat", add_self_loops=False)
+    reps = max(a.iters, 20)
+    dim, S = 3, 8
+    lines = ["B-spline convolution (SplineConv, degree 1, dim = %d, open, mean) on the vertex graph of torus(%d, %d) in RCB order: N=%d, "
+             "entries=%d (no loops), input edges=%d, float32; median of %d launches [min q1 q3 max], one HIP-event pair per launch, "
+             "forms alternating in one loop, rotating buffer sets; gmm_* are the Gaussian-mixture launches of the same role at K = 8 "
+             "(the blocks an edge selects) and the same C on the same graph; [Hf | R] and [dHf | dR] are one row buffer each; bytes = "
+             "the algorithmic counts of ops.py (MB): the forward reads S C floats per input edge, not K C; torch = the edge-list "
+             "composition (basis, [E, 8, C] block gather, multiply, sum, index_add_, mean) and its autograd backward, mean of 3 runs"
+             % (dim, nu_, nv_, nn_, g.nnz, g.nnz_in, reps)]
+    print(lines[0], flush=True)
+    attr = torch.rand(g.nnz_in, dim, device=dev)
+    mu, sigma = torch.rand(8, dim, device=dev), 0.3 + 0.7 * torch.rand(8, dim, device=dev)
+
+    def torch_basis(ksz):
+        b = torch.ones(attr.shape[0], S, device=dev)
+        k = torch.zeros(attr.shape[0], S, dtype=torch.long, device=dev)
+        bits, stride = torch.arange(S, device=dev), 1
+        for d in range(dim):
+            vv = attr[:, d] * (ksz - 1)
+            fl = torch.floor(vv)
+            fr, up = (vv - fl).unsqueeze(1), ((bits >> d) & 1).unsqueeze(0)
+            b = b * torch.where(up.bool(), fr, 1 - fr)
+            k = k + torch.remainder(fl.long().unsqueeze(1) + up, ksz) * stride
+            stride *= ksz
+        return b, k
+
+    cnt = torch.zeros(nn_, device=dev).index_add_(0, dst, torch.ones(dst.shape[0], device=dev)).clamp(min=1).unsqueeze(1)
+    for ksz, C in ((2, 32), (2, 128), (5, 32)):
+        ks, op, K = [ksz] * dim, [True] * dim, ksz ** dim
+        hc, gc = K * C, 8 * C
+        R = 2 if nn_ * hc * 4 >= (1 << 29) else 4
+        Bs = [torch.randn(nn_, hc + C, device=dev) for _ in range(R)]
+        Hs, Rs = [b[:, :hc] for b in Bs], [b[:, hc:] for b in Bs]
+        Gb = Bs if K == 8 else [torch.randn(nn_, gc + C, device=dev) for _ in range(R)]     # gmm's [Hf | R] at K = 8
+        GHs, GRs = [b[:, :gc] for b in Gb], [b[:, gc:] for b in Gb]
+        Ds = [torch.randn(nn_, C, device=dev) for _ in range(R)]
+        bias = torch.randn(C, device=dev)
+        Out, G, Gg = torch.empty(nn_, C, device=dev), torch.empty(nn_, hc + C, device=dev), torch.empty(nn_, gc + C, device=dev)
+        ws = [ops.gmm_fwd(g, GHs[i], attr, mu, sigma, 8, root=GRs[i], bias=bias)[1] for i in range(R)]
+        q = alternate({
+            "fwd": lambda i: ops.spline_fwd(g, Hs[i], attr, ks, op, root=Rs[i], bias=bias, out=Out),
+            "gmm_fwd": lambda i: ops.gmm_fwd(g, GHs[i], attr, mu, sigma, 8, root=GRs[i], bias=bias, out=Out),
+            "bwd_node": lambda i: ops.spline_bwd_node(g, Ds[i], attr, ks, op, C, out=G, root=True),
+            "gmm_bwd_node": lambda i: ops.gmm_bwd_node(g, Ds[i], ws[i], 8, out=Gg, root=True)}, reps, R)
+        narrow, ent, node, edges = 4.0 * nn_ * C, 4.0 * g.nnz, 4.0 * nn_, 4.0 * g.nnz_in
+        alg = {"fwd": edges * S * C + 2 * narrow + edges * (dim + 1) + 2 * ent + node,
+               "gmm_fwd": 4.0 * nn_ * gc + 3 * narrow + ent * 8 + edges * (dim + 1) + 3 * ent + node,
+               "bwd_node": 4.0 * nn_ * hc + 3 * narrow + edges * (dim + 1) + 3 * ent + node,
+               "gmm_bwd_node": 4.0 * nn_ * gc + 2 * narrow + ent * 8 + 2 * ent + node}
+        pair = {"fwd": "gmm_fwd", "bwd_node": "gmm_bwd_node"}
+        lines.append("kernel_size=%d K=%d C=%d (row width %d, %d buffer sets; gmm at K=8: row width %d):" % (ksz, K, C, hc, R, gc))
+        for k_ in alg:
+            extra = ("  x%.2f of %s (bytes x%.2f)" % (q[k_][2] / q[pair[k_]][2], pair[k_], alg[k_] / alg[pair[k_]])) if k_ in pair else ""
+            lines.append("  %-13s %s  %7.0f MB  %.2f TB/s alg%s" % (k_, fmt(q[k_]), alg[k_] / 1e6, alg[k_] / q[k_][2] / 1e6, extra))
+        # the torch edge-list composition on the same inputs, and its autograd backward
+        hh = Hs[0].clone().requires_grad_(True)
+
+        def torch_fwd():
+            b, k = torch_basis(ksz)
+            msg = (b.unsqueeze(-1) * hh.view(nn_, K, C)[src.unsqueeze(1), k]).sum(1)
+            return torch.zeros(nn_, C, device=dev).index_add_(0, dst, msg) / cnt + Rs[0] + bias
+
+        t_f = timeit(lambda: torch_fwd().detach(), 3)
+        yt = torch_fwd()
+        t_b = timeit(lambda: torch.autograd.grad(yt, (hh,), Ds[0], retain_graph=True), 3)
+        err = float((ops.spline_fwd(g, Hs[0], attr, ks, op, root=Rs[0], bias=bias) - yt.detach()).norm() / yt.detach().norm())
+        lines.append("  torch forward %8.0f us = x%.1f of fwd;  torch backward %8.0f us = x%.1f of bwd_node;  rel-L2 fwd vs torch %.1e"
+                     % (t_f, t_f / q["fwd"][2], t_b, t_b / q["bwd_node"][2], err))
+        print("\n".join(lines[-(len(alg) + 2):]), flush=True)
+        del Bs, Hs, Rs, Gb, GHs, GRs, Ds, Out, G, Gg, ws, hh, yt
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "spline_microbench.txt")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
