@@ -15,6 +15,7 @@
 // enters with factor 0.  An output float4 is accumulated in registers over ALL entries and heads of its row before it is stored:
 // the 1200-entry hub row is exact like any other.  No LDS, no barrier in the gather kernels.  The three gather loops live in
 // gather_mix.h, shared with gmm.hip.
+#include "colsum_final.h"
 #include "gather_mix.h"
 
 namespace {
@@ -41,13 +42,7 @@ __global__ __launch_bounds__(256) void feast_fwd_kernel(const int* __restrict__ 
                                                         int n_chunks) {
     HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         float* yrow = Y + (int64_t)row * ldy;
         if (nn == 0) {                                            // a row without entries: the bias alone
             for (int q = sl; q < W; q += 8)
@@ -117,13 +112,7 @@ __global__ __launch_bounds__(256) void feast_bwd_edge_kernel(const int* __restri
                                                              const float* __restrict__ beta, float* dz, float* rs, int n_rows,
                                                              int heads, int C, int lw, int chunks_per_xcd, int n_chunks) {
     HEAD_CHUNK_PROLOGUE
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         const float* grow = dOut + (int64_t)row * lddo;
         float* rrow = rs + (int64_t)row * heads;
         if (nn == 0) {
@@ -192,19 +181,9 @@ __global__ __launch_bounds__(256) void feast_bwd_node_kernel(const int* __restri
                                                              int n_chunks) {
     HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         float* orow = dHf + (int64_t)row * lddh;
-#pragma unroll 1
-        for (int hg = 0; hg < heads; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < heads;
-            const int hh = hv ? h : heads - 1;
+        FOR_HEAD_PASSES(heads) {
             // dP[j,h] = sum_{e'} dz[mirror e', h] - rs[j,h]: the head's lw lanes take the entries lw apart
             float p = 0.f;
             for (int e = q0; e < nn; e += lw) p += dz[(int64_t)mirror[rbase + e] * heads + hh];
@@ -263,19 +242,6 @@ __global__ __launch_bounds__(256) void feast_dc_partial_kernel(const float* __re
     }
 }
 
-// stage 2: one workgroup; four lanes per head take the partials 4 apart (float64), combined in a fixed order
-__global__ __launch_bounds__(1024) void feast_dc_final_kernel(const float* __restrict__ partial, int n_chunks, int heads,
-                                                              float* __restrict__ dc) {
-    __shared__ double sm[4][kMaxHeads];
-    const int h = threadIdx.x & (kMaxHeads - 1), part = threadIdx.x >> 8;
-    double a = 0.0;
-    if (h < heads)
-        for (int ch = part; ch < n_chunks; ch += 4) a += (double)partial[(int64_t)ch * heads + h];
-    sm[part][h] = a;
-    __syncthreads();
-    if (part == 0 && h < heads) dc[h] = (float)(((sm[0][h] + sm[1][h]) + sm[2][h]) + sm[3][h]);
-}
-
 }  // namespace
 
 extern "C" int ddmp_feast_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ldh, const float* P, int64_t ldp, int heads, int C,
@@ -283,18 +249,9 @@ extern "C" int ddmp_feast_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t 
     ARG_TRY(attn_graph_ok(g) && Hf && P && c && beta && Y && feast_dims_ok(heads, C) && ldh >= (int64_t)heads * C && ldp >= heads &&
             ldy >= C && Y != Hf && Y != P);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && ldh % 4 == 0 && ldy % 4 == 0 && al16(Hf) && al16(Y) && (!bias || al16(bias))) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(feast_fwd_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh, P, ldp, c, bias, beta,
-                           Y, ldy, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(feast_fwd_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh,
-                           P, ldp, c, bias, beta, Y, ldy, n, heads, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && ldh % 4 == 0 && ldy % 4 == 0 && al16(Hf) && al16(Y) && (!bias || al16(bias));
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), feast_fwd_kernel, feast_fwd_scalar_kernel,
+                            g->rowptr, g->col, g->a, Hf, ldh, P, ldp, c, bias, beta, Y, ldy, (int)g->n_rows, heads, C);
 }
 
 extern "C" int ddmp_feast_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Hf, int64_t ldh, int heads,
@@ -302,18 +259,10 @@ extern "C" int ddmp_feast_bwd_edge_f32(const ddmp_graph* g, const float* dOut, i
     ARG_TRY(attn_graph_ok(g) && dOut && Hf && beta && dz && rs && feast_dims_ok(heads, C) && lddo >= C &&
             ldh >= (int64_t)heads * C && dz != beta);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && lddo % 4 == 0 && ldh % 4 == 0 && al16(dOut) && al16(Hf)) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(feast_bwd_edge_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, dOut, lddo, Hf, ldh, beta, dz,
-                           rs, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(feast_bwd_edge_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, dOut, lddo,
-                           Hf, ldh, beta, dz, rs, n, heads, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && lddo % 4 == 0 && ldh % 4 == 0 && al16(dOut) && al16(Hf);
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), feast_bwd_edge_kernel,
+                            feast_bwd_edge_scalar_kernel, g->rowptr, g->col, dOut, lddo, Hf, ldh, beta, dz, rs, (int)g->n_rows,
+                            heads, C);
 }
 
 extern "C" int ddmp_feast_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, int heads, int C, const float* beta,
@@ -322,18 +271,10 @@ extern "C" int ddmp_feast_bwd_node_f32(const ddmp_graph* g, const float* dOut, i
     ARG_TRY(attn_graph_ok(g) && dOut && beta && dz && rs && dHf && dP && feast_dims_ok(heads, C) && lddo >= C &&
             lddh >= (int64_t)heads * C && lddp >= heads && dHf != dOut && dP != rs);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && lddo % 4 == 0 && lddh % 4 == 0 && al16(dOut) && al16(dHf)) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(feast_bwd_node_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo, beta,
-                           dz, rs, dHf, lddh, dP, lddp, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(feast_bwd_node_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->mirror,
-                           dOut, lddo, beta, dz, rs, dHf, lddh, dP, lddp, n, heads, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && lddo % 4 == 0 && lddh % 4 == 0 && al16(dOut) && al16(dHf);
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), feast_bwd_node_kernel,
+                            feast_bwd_node_scalar_kernel, g->rowptr, g->col, g->mirror, dOut, lddo, beta, dz, rs, dHf, lddh, dP,
+                            lddp, (int)g->n_rows, heads, C);
 }
 
 extern "C" size_t ddmp_feast_dc_workspace_bytes(int64_t n_rows, int heads) {
@@ -350,7 +291,5 @@ extern "C" int ddmp_feast_dc_f32(const float* rs, int64_t n_rows, int heads, flo
     float* partial = static_cast<float*>(workspace);
     hipLaunchKernelGGL(feast_dc_partial_kernel, dim3(n_chunks), dim3(256), 0, st, rs, n_rows, heads, partial);
     LAUNCH_TRY();
-    hipLaunchKernelGGL(feast_dc_final_kernel, dim3(1), dim3(1024), 0, st, partial, n_chunks, heads, dc);
-    LAUNCH_TRY();
-    return DDMP_OK;
+    return launch_colsum_final(st, partial, n_chunks, heads, dc, nullptr, heads);
 }

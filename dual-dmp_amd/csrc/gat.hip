@@ -10,7 +10,7 @@
 //   * a row longer than one batch accumulates through its own output row (same lane, same address, program order): the
 //     1200-entry hub row is exact like any other.
 // No LDS, no barrier.
-#include "row_gather.h"
+#include "colsum_final.h"
 
 namespace {
 
@@ -25,17 +25,9 @@ __global__ __launch_bounds__(256) void gat_scores_kernel(const float* __restrict
                                                          int chunks_per_xcd, int n_chunks) {
     HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
+    FOR_CHUNK_ROWS {
         const float* hrow = Hf + (int64_t)row * ldh;
-#pragma unroll 1
-        for (int hg = 0; hg < heads; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < heads;
-            const int hh = hv ? h : heads - 1;
+        FOR_HEAD_PASSES(heads) {
             float as = 0.f, ad = 0.f;
             for (int q = q0; q < W; q += lw) {
                 const float4 x = ld4(hrow + hh * C + q * 4);
@@ -78,19 +70,9 @@ __global__ __launch_bounds__(256) void gat_fwd_kernel(const int* __restrict__ ro
                                                       const float* __restrict__ bias, float* alpha, float* Y, int64_t ldy, int n_rows,
                                                       int heads, int C, int lw, int chunks_per_xcd, int n_chunks) {
     HEAD_CHUNK_PROLOGUE
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         float* yrow = Y + (int64_t)row * ldy;
-#pragma unroll 1
-        for (int hg = 0; hg < heads; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < heads;
-            const int hh = hv ? h : heads - 1;
+        FOR_HEAD_PASSES(heads) {
             const float sd = s_dst[(int64_t)row * heads + hh];
             // softmax of the row's entries for head hh: the head's lw lanes take the entries lw apart
             float m = -INFINITY;
@@ -151,19 +133,9 @@ __global__ __launch_bounds__(256) void gat_bwd_edge_kernel(const int* __restrict
                                                            int chunks_per_xcd, int n_chunks) {
     HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         const float* grow = dOut + (int64_t)row * lddo;
-#pragma unroll 1
-        for (int hg = 0; hg < heads; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < heads;
-            const int hh = hv ? h : heads - 1;
+        FOR_HEAD_PASSES(heads) {
             // dalpha_e for every entry (parked in ds) and delta = sum_e alpha_e dalpha_e, entries in ascending order
             float delta = 0.f;
 #pragma unroll 1
@@ -255,19 +227,9 @@ __global__ __launch_bounds__(256) void gat_bwd_node_kernel(const int* __restrict
                                                            float* __restrict__ ds_src, int n_rows, int heads, int C, int lw,
                                                            int chunks_per_xcd, int n_chunks) {
     HEAD_CHUNK_PROLOGUE
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         float* orow = dHf + (int64_t)row * lddh;
-#pragma unroll 1
-        for (int hg = 0; hg < heads; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < heads;
-            const int hh = hv ? h : heads - 1;
+        FOR_HEAD_PASSES(heads) {
             float p = 0.f;
             for (int e = q0; e < nn; e += lw) p += ds[(int64_t)mirror[rbase + e] * heads + hh];
             p = red_sum(p, lw);
@@ -326,27 +288,6 @@ __global__ __launch_bounds__(256) void gat_datt_partial_kernel(const float* __re
     partial[((int64_t)blockIdx.x * 2 + 1) * HC + c] = pd;
 }
 
-// stage 2: 64 columns per workgroup; four lanes per column take the partials 4 apart (float64), combined in a fixed order
-__global__ __launch_bounds__(256) void gat_datt_final_kernel(const float* __restrict__ partial, int n_chunks, int HC,
-                                                             float* __restrict__ datt_src, float* __restrict__ datt_dst) {
-    __shared__ double sm[2][4][64];
-    const int cl = threadIdx.x & 63, part = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    double a = 0.0, b = 0.0;
-    if (c < HC)
-        for (int ch = part; ch < n_chunks; ch += 4) {
-            a += (double)partial[((int64_t)ch * 2 + 0) * HC + c];
-            b += (double)partial[((int64_t)ch * 2 + 1) * HC + c];
-        }
-    sm[0][part][cl] = a;
-    sm[1][part][cl] = b;
-    __syncthreads();
-    if (part == 0 && c < HC) {
-        datt_src[c] = (float)(((sm[0][0][cl] + sm[0][1][cl]) + sm[0][2][cl]) + sm[0][3][cl]);
-        datt_dst[c] = (float)(((sm[1][0][cl] + sm[1][1][cl]) + sm[1][2][cl]) + sm[1][3][cl]);
-    }
-}
-
 inline bool gat_dims_ok(int heads, int C) { return heads > 0 && C > 0 && (int64_t)heads * C < (1 << 24); }
 
 }  // namespace
@@ -356,18 +297,9 @@ extern "C" int ddmp_gat_scores_f32(const float* Hf, int64_t ldh, int64_t n_rows,
     ARG_TRY(Hf && att_src && att_dst && s_src && s_dst && n_rows >= 0 && n_rows < (int64_t)INT32_MAX && gat_dims_ok(heads, C) &&
             ldh >= (int64_t)heads * C);
     if (n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)n_rows;
-    if (C % 4 == 0 && ldh % 4 == 0 && al16(Hf) && al16(att_src) && al16(att_dst)) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(gat_scores_kernel, rg.grid, dim3(256), 0, st, Hf, ldh, n, heads, C, att_src, att_dst, s_src, s_dst,
-                           lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(gat_scores_scalar_kernel, scalar_grid(n), dim3(256), 0, st, Hf, ldh, n, heads, C, att_src,
-                           att_dst, s_src, s_dst);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && ldh % 4 == 0 && al16(Hf) && al16(att_src) && al16(att_dst);
+    return launch_head_rows((hipStream_t)stream, (int)n_rows, vec, lanes_per_head(C), gat_scores_kernel, gat_scores_scalar_kernel, Hf,
+                            ldh, (int)n_rows, heads, C, att_src, att_dst, s_src, s_dst);
 }
 
 extern "C" int ddmp_gat_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ldh, int heads, int C, const float* s_src,
@@ -376,18 +308,9 @@ extern "C" int ddmp_gat_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ld
     ARG_TRY(attn_graph_ok(g) && Hf && s_src && s_dst && alpha && Y && gat_dims_ok(heads, C) && ldh >= (int64_t)heads * C &&
             ldy >= (int64_t)heads * C && Y != Hf);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && ldh % 4 == 0 && ldy % 4 == 0 && al16(Hf) && al16(Y) && (!bias || al16(bias))) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(gat_fwd_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh, s_src, s_dst, slope,
-                           bias, alpha, Y, ldy, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(gat_fwd_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->a, Hf, ldh,
-                           s_src, s_dst, slope, bias, alpha, Y, ldy, n, heads, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && ldh % 4 == 0 && ldy % 4 == 0 && al16(Hf) && al16(Y) && (!bias || al16(bias));
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), gat_fwd_kernel, gat_fwd_scalar_kernel,
+                            g->rowptr, g->col, g->a, Hf, ldh, s_src, s_dst, slope, bias, alpha, Y, ldy, (int)g->n_rows, heads, C);
 }
 
 extern "C" int ddmp_gat_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Hf, int64_t ldh, int heads,
@@ -396,18 +319,10 @@ extern "C" int ddmp_gat_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int
     ARG_TRY(attn_graph_ok(g) && dOut && Hf && s_src && s_dst && alpha && ds && ds_dst && gat_dims_ok(heads, C) &&
             lddo >= (int64_t)heads * C && ldh >= (int64_t)heads * C && ds != alpha);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && lddo % 4 == 0 && ldh % 4 == 0 && al16(dOut) && al16(Hf)) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(gat_bwd_edge_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, dOut, lddo, Hf, ldh, s_src,
-                           s_dst, slope, alpha, ds, ds_dst, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(gat_bwd_edge_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, dOut, lddo,
-                           Hf, ldh, s_src, s_dst, slope, alpha, ds, ds_dst, n, heads, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && lddo % 4 == 0 && ldh % 4 == 0 && al16(dOut) && al16(Hf);
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), gat_bwd_edge_kernel,
+                            gat_bwd_edge_scalar_kernel, g->rowptr, g->col, dOut, lddo, Hf, ldh, s_src, s_dst, slope, alpha, ds, ds_dst,
+                            (int)g->n_rows, heads, C);
 }
 
 extern "C" int ddmp_gat_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, int heads, int C, const float* alpha,
@@ -416,18 +331,10 @@ extern "C" int ddmp_gat_bwd_node_f32(const ddmp_graph* g, const float* dOut, int
     ARG_TRY(attn_graph_ok(g) && dOut && alpha && ds && ds_dst && att_src && att_dst && dHf && ds_src && gat_dims_ok(heads, C) &&
             lddo >= (int64_t)heads * C && lddh >= (int64_t)heads * C && dHf != dOut);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && lddo % 4 == 0 && lddh % 4 == 0 && al16(dOut) && al16(dHf) && al16(att_src) && al16(att_dst)) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(gat_bwd_node_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo, alpha,
-                           ds, ds_dst, att_src, att_dst, dHf, lddh, ds_src, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(gat_bwd_node_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->mirror,
-                           dOut, lddo, alpha, ds, ds_dst, att_src, att_dst, dHf, lddh, ds_src, n, heads, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && lddo % 4 == 0 && lddh % 4 == 0 && al16(dOut) && al16(dHf) && al16(att_src) && al16(att_dst);
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), gat_bwd_node_kernel,
+                            gat_bwd_node_scalar_kernel, g->rowptr, g->col, g->mirror, dOut, lddo, alpha, ds, ds_dst, att_src, att_dst,
+                            dHf, lddh, ds_src, (int)g->n_rows, heads, C);
 }
 
 extern "C" size_t ddmp_gat_datt_workspace_bytes(int64_t n_rows, int heads, int C) {
@@ -448,8 +355,5 @@ extern "C" int ddmp_gat_datt_f32(const float* Hf, int64_t ldh, int64_t n_rows, i
     hipLaunchKernelGGL(gat_datt_partial_kernel, dim3(n_chunks, (unsigned)cdiv(HC, 256)), dim3(256), 0, st, Hf, ldh, n_rows, heads, C,
                        ds_src, ds_dst, partial);
     LAUNCH_TRY();
-    hipLaunchKernelGGL(gat_datt_final_kernel, dim3((unsigned)cdiv(HC, 64)), dim3(256), 0, st, partial, n_chunks, HC, datt_src,
-                       datt_dst);
-    LAUNCH_TRY();
-    return DDMP_OK;
+    return launch_colsum_final(st, partial, n_chunks, 2 * HC, datt_src, datt_dst, HC);
 }

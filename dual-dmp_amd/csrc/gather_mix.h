@@ -27,11 +27,7 @@ __device__ __forceinline__ float4 mix_gather_row(const int* __restrict__ col, co
                 xp[k] = Hf + (int64_t)col[e] * ldh + q * 4;
                 fp[k] = fac + e * heads;
             }
-#pragma unroll 1
-            for (int hg = 0; hg < heads; hg += hp) {
-                const int h = hg + sub;
-                const bool hv = h < heads;
-                const int hh = hv ? h : heads - 1;
+            FOR_HEAD_PASSES(heads) {
                 float4 x[NE];
                 float f[NE];
 #pragma unroll
@@ -60,11 +56,7 @@ __device__ __forceinline__ void mix_edge_dots(const int* __restrict__ col, const
                                               const float* __restrict__ Hf, int64_t ldh, float* gd, int heads, int C, int lw,
                                               int hp, int sub, int q0, int rbase, int nn) {
     const int W = C >> 2;
-#pragma unroll 1
-    for (int hg = 0; hg < heads; hg += hp) {
-        const int h = hg + sub;
-        const bool hv = h < heads;
-        const int hh = hv ? h : heads - 1;
+    FOR_HEAD_PASSES(heads) {
 #pragma unroll 1
         for (int b0 = 0; b0 < nn; b0 += kEB) {
             auto batch = [&](auto ne_tag) {

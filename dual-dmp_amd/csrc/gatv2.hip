@@ -15,7 +15,7 @@
 //   * u_e is formed by ONE float32 addition everywhere (forward, both backward launches), so the branch of the leaky relu is the
 //     same in all three.
 // No LDS, no barrier, no atomics.
-#include "row_gather.h"
+#include "colsum_final.h"
 
 namespace {
 
@@ -41,19 +41,9 @@ __global__ __launch_bounds__(256) void gatv2_fwd_kernel(const int* __restrict__ 
                                                         int n_chunks) {
     HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         float* yrow = Y + (int64_t)row * ldy;
-#pragma unroll 1
-        for (int hg = 0; hg < heads; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < heads;
-            const int hh = hv ? h : heads - 1;
+        FOR_HEAD_PASSES(heads) {
             const float* rh = Xr + (int64_t)row * ldr + hh * C;
             const float* ah = att + hh * C;
             // z_e for every entry (parked in alpha) and the row's maximum; every lane of the head holds the same sums
@@ -151,18 +141,8 @@ __global__ __launch_bounds__(256) void gatv2_bwd_edge_kernel(const int* __restri
                                                              int chunks_per_xcd, int n_chunks) {
     HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
-#pragma unroll 1
-        for (int hg = 0; hg < heads; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < heads;
-            const int hh = hv ? h : heads - 1;
+    FOR_CHUNK_ROW_ENTRIES {
+        FOR_HEAD_PASSES(heads) {
             const float* gh = dOut + (int64_t)row * lddo + hh * C;
             const float* rh = Xr + (int64_t)row * ldr + hh * C;
             const float* ah = att + hh * C;
@@ -314,18 +294,8 @@ __global__ __launch_bounds__(256) void gatv2_bwd_node_kernel(const int* __restri
                                                              int chunks_per_xcd, int n_chunks) {
     HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
-#pragma unroll 1
-        for (int hg = 0; hg < heads; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < heads;
-            const int hh = hv ? h : heads - 1;
+    FOR_CHUNK_ROW_ENTRIES {
+        FOR_HEAD_PASSES(heads) {
             const float* lh = Xl + (int64_t)row * ldl + hh * C;
             const float* ah = att + hh * C;
             float* orow = dXl + (int64_t)row * lddl + hh * C;
@@ -419,20 +389,6 @@ __global__ __launch_bounds__(256) void gatv2_datt_partial_kernel(const float* __
     partial[(int64_t)blockIdx.x * HC + c] = p;
 }
 
-// stage 2: 64 columns per workgroup; four lanes per column take the partials 4 apart (float64), combined in a fixed order
-__global__ __launch_bounds__(256) void gatv2_datt_final_kernel(const float* __restrict__ partial, int n_chunks, int HC,
-                                                               float* __restrict__ datt) {
-    __shared__ double sm[4][64];
-    const int cl = threadIdx.x & 63, pt = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    double a = 0.0;
-    if (c < HC)
-        for (int ch = pt; ch < n_chunks; ch += 4) a += (double)partial[(int64_t)ch * HC + c];
-    sm[pt][cl] = a;
-    __syncthreads();
-    if (pt == 0 && c < HC) datt[c] = (float)(((sm[0][cl] + sm[1][cl]) + sm[2][cl]) + sm[3][cl]);
-}
-
 inline bool gatv2_dims_ok(int heads, int C) { return heads > 0 && C > 0 && (int64_t)heads * C < (1 << 24); }
 inline bool ld_ok(int64_t ld, int heads, int C) { return ld >= (int64_t)heads * C; }
 
@@ -444,19 +400,10 @@ extern "C" int ddmp_gatv2_fwd_f32(const ddmp_graph* g, const float* Xl, int64_t 
     ARG_TRY(attn_graph_ok(g) && Xl && Xr && att && alpha && Y && gatv2_dims_ok(heads, C) && ld_ok(ldl, heads, C) &&
             ld_ok(ldr, heads, C) && ld_ok(ldy, heads, C) && Y != Xl && Y != Xr);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && ldl % 4 == 0 && ldr % 4 == 0 && ldy % 4 == 0 && al16(Xl) && al16(Xr) && al16(att) && al16(Y) &&
-        (!bias || al16(bias))) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(gatv2_fwd_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->a, Xl, ldl, Xr, ldr, att, slope, bias,
-                           alpha, Y, ldy, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(gatv2_fwd_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->a, Xl, ldl, Xr, ldr, att,
-                           slope, bias, alpha, Y, ldy, n, heads, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && ldl % 4 == 0 && ldr % 4 == 0 && ldy % 4 == 0 && al16(Xl) && al16(Xr) && al16(att) && al16(Y) &&
+                     (!bias || al16(bias));
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), gatv2_fwd_kernel, gatv2_fwd_scalar_kernel,
+                            g->rowptr, g->col, g->a, Xl, ldl, Xr, ldr, att, slope, bias, alpha, Y, ldy, (int)g->n_rows, heads, C);
 }
 
 extern "C" int ddmp_gatv2_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Xl, int64_t ldl,
@@ -467,19 +414,11 @@ extern "C" int ddmp_gatv2_bwd_edge_f32(const ddmp_graph* g, const float* dOut, i
             ld_ok(ldl, heads, C) && ld_ok(ldr, heads, C) && ld_ok(lddr, heads, C) && (!part || ld_ok(ldp, heads, C)) && dz != alpha &&
             dXr != dOut && dXr != Xl && dXr != Xr && part != dXr && part != dOut && part != Xl && part != Xr);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && lddo % 4 == 0 && ldl % 4 == 0 && ldr % 4 == 0 && lddr % 4 == 0 && al16(dOut) && al16(Xl) && al16(Xr) &&
-        al16(att) && al16(dXr) && (!part || (ldp % 4 == 0 && al16(part)))) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(gatv2_bwd_edge_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, dOut, lddo, Xl, ldl, Xr, ldr, att,
-                           slope, alpha, dz, dXr, lddr, part, ldp, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(gatv2_bwd_edge_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, dOut, lddo, Xl, ldl,
-                           Xr, ldr, att, slope, alpha, dz, dXr, lddr, part, ldp, n, heads, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && lddo % 4 == 0 && ldl % 4 == 0 && ldr % 4 == 0 && lddr % 4 == 0 && al16(dOut) && al16(Xl) &&
+                     al16(Xr) && al16(att) && al16(dXr) && (!part || (ldp % 4 == 0 && al16(part)));
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), gatv2_bwd_edge_kernel,
+                            gatv2_bwd_edge_scalar_kernel, g->rowptr, g->col, dOut, lddo, Xl, ldl, Xr, ldr, att, slope, alpha, dz, dXr,
+                            lddr, part, ldp, (int)g->n_rows, heads, C);
 }
 
 extern "C" int ddmp_gatv2_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Xl, int64_t ldl,
@@ -488,19 +427,11 @@ extern "C" int ddmp_gatv2_bwd_node_f32(const ddmp_graph* g, const float* dOut, i
     ARG_TRY(attn_graph_ok(g) && dOut && Xl && Xr && att && alpha && dz && dXl && gatv2_dims_ok(heads, C) && ld_ok(lddo, heads, C) &&
             ld_ok(ldl, heads, C) && ld_ok(ldr, heads, C) && ld_ok(lddl, heads, C) && dXl != dOut && dXl != Xl && dXl != Xr);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && lddo % 4 == 0 && ldl % 4 == 0 && ldr % 4 == 0 && lddl % 4 == 0 && al16(dOut) && al16(Xl) && al16(Xr) &&
-        al16(att) && al16(dXl)) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(gatv2_bwd_node_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo, Xl, ldl, Xr,
-                           ldr, att, slope, alpha, dz, dXl, lddl, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(gatv2_bwd_node_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo,
-                           Xl, ldl, Xr, ldr, att, slope, alpha, dz, dXl, lddl, n, heads, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && lddo % 4 == 0 && ldl % 4 == 0 && ldr % 4 == 0 && lddl % 4 == 0 && al16(dOut) && al16(Xl) &&
+                     al16(Xr) && al16(att) && al16(dXl);
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), gatv2_bwd_node_kernel,
+                            gatv2_bwd_node_scalar_kernel, g->rowptr, g->col, g->mirror, dOut, lddo, Xl, ldl, Xr, ldr, att, slope,
+                            alpha, dz, dXl, lddl, (int)g->n_rows, heads, C);
 }
 
 extern "C" size_t ddmp_gatv2_datt_workspace_bytes(int64_t n_rows, int heads, int C) {
@@ -519,7 +450,5 @@ extern "C" int ddmp_gatv2_datt_f32(const float* part, int64_t ldp, int64_t n_row
     hipLaunchKernelGGL(gatv2_datt_partial_kernel, dim3(n_chunks, (unsigned)cdiv(HC, 256)), dim3(256), 0, st, part, ldp, n_rows, HC,
                        partial);
     LAUNCH_TRY();
-    hipLaunchKernelGGL(gatv2_datt_final_kernel, dim3((unsigned)cdiv(HC, 64)), dim3(256), 0, st, partial, n_chunks, HC, datt);
-    LAUNCH_TRY();
-    return DDMP_OK;
+    return launch_colsum_final(st, partial, n_chunks, HC, datt, nullptr, HC);
 }

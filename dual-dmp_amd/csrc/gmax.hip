@@ -29,13 +29,7 @@ __global__ __launch_bounds__(256) void gather_max_kernel(const int* __restrict__
                                                          int64_t ldg, int n_rows, int C, int chunks_per_xcd, int n_chunks) {
     ROW_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         float* yrow = Y + (int64_t)row * ldy;
         int* grow = arg ? arg + (int64_t)row * ldg : nullptr;
         if (nn == 0) {                                            // a row without entries: 0, not A (the edge function never ran)
@@ -114,13 +108,7 @@ __global__ __launch_bounds__(256) void gather_max_bwd_kernel(const int* __restri
                                                              int chunks_per_xcd, int n_chunks) {
     ROW_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         float* arow = dA + (int64_t)row * ldda;
         float* brow = dB + (int64_t)row * lddb;
         if (nn == 0) {
@@ -189,19 +177,10 @@ extern "C" int ddmp_gather_max_f32(const ddmp_graph* g, const float* B, int64_t 
     ARG_TRY(attn_graph_ok(g, false) && B && Y && C >= 1 && ldb >= C && ldy >= C && (!A || lda >= C) && (!arg || ldarg >= C) && Y != B &&
             Y != A);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && ldb % 4 == 0 && ldy % 4 == 0 && al16(B) && al16(Y) && (!A || (lda % 4 == 0 && al16(A))) &&
-        (!arg || (ldarg % 4 == 0 && al16(arg)))) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(gather_max_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, B, ldb, A, lda, Y, ldy, arg,
-                           ldarg, n, C, rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(gather_max_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, B, ldb, A,
-                           lda, Y, ldy, arg, ldarg, n, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && ldb % 4 == 0 && ldy % 4 == 0 && al16(B) && al16(Y) && (!A || (lda % 4 == 0 && al16(A))) && (!arg
+                     || (ldarg % 4 == 0 && al16(arg)));
+    return launch_rows((hipStream_t)stream, (int)g->n_rows, vec, gather_max_kernel, gather_max_scalar_kernel, g->rowptr, g->col, B,
+                       ldb, A, lda, Y, ldy, arg, ldarg, (int)g->n_rows, C);
 }
 
 extern "C" int ddmp_gather_max_bwd_f32(const ddmp_graph* g, const float* dG, int64_t lddg, const int32_t* arg, int64_t ldarg, int C,
@@ -209,17 +188,8 @@ extern "C" int ddmp_gather_max_bwd_f32(const ddmp_graph* g, const float* dG, int
     ARG_TRY(attn_graph_ok(g, false) && dG && arg && dA && dB && C >= 1 && lddg >= C && ldarg >= C && ldda >= C && lddb >= C && dA != dG &&
             dB != dG && dA != dB);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && lddg % 4 == 0 && ldarg % 4 == 0 && ldda % 4 == 0 && lddb % 4 == 0 && al16(dG) && al16(arg) && al16(dA) &&
-        al16(dB)) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(gather_max_bwd_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, dG, lddg, arg, ldarg, dA,
-                           ldda, dB, lddb, n, C, rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(gather_max_bwd_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, dG, lddg,
-                           arg, ldarg, dA, ldda, dB, lddb, n, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && lddg % 4 == 0 && ldarg % 4 == 0 && ldda % 4 == 0 && lddb % 4 == 0 && al16(dG) && al16(arg) &&
+                     al16(dA) && al16(dB);
+    return launch_rows((hipStream_t)stream, (int)g->n_rows, vec, gather_max_bwd_kernel, gather_max_bwd_scalar_kernel, g->rowptr,
+                       g->col, dG, lddg, arg, ldarg, dA, ldda, dB, lddb, (int)g->n_rows, C);
 }

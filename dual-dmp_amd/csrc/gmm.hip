@@ -107,13 +107,7 @@ __global__ __launch_bounds__(256) void gmm_fwd_kernel(const int* __restrict__ ro
     GMM_TABLES
     HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         float* yrow = Y + (int64_t)row * ldy;
         const float* rrow = R ? R + (int64_t)row * ldr : nullptr;
         if (nn == 0) {                                            // a row without entries: its own root block and the bias
@@ -194,13 +188,7 @@ __global__ __launch_bounds__(256) void gmm_bwd_edge_kernel(const int* __restrict
     GMM_TABLES
     HEAD_CHUNK_PROLOGUE
     const int KD = K * dim;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         const float* grow = dOut + (int64_t)row * lddo;
         float* prow = parts + (int64_t)row * (2 * KD);
         if (nn == 0) {
@@ -293,22 +281,12 @@ __global__ __launch_bounds__(256) void gmm_bwd_node_kernel(const int* __restrict
                                                            int C, int lw, int chunks_per_xcd, int n_chunks) {
     HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         float* orow = dHf + (int64_t)row * lddh;
         if (dR)
             for (int q = sl; q < W; q += 8)
                 *reinterpret_cast<float4*>(dR + (int64_t)row * lddr + q * 4) = ld4(dOut + (int64_t)row * lddo + q * 4);
-#pragma unroll 1
-        for (int hg = 0; hg < K; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < K;
-            const int hh = hv ? h : K - 1;
+        FOR_HEAD_PASSES(K) {
             for (int q = q0; q < W; q += lw) {
                 const float4 acc = mix_node_gather(col, mirror, dOut, lddo, w, K, hh, rbase, nn, q);
                 if (hv) *reinterpret_cast<float4*>(orow + hh * C + q * 4) = acc;
@@ -351,18 +329,11 @@ extern "C" int ddmp_gmm_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t ld
     ARG_TRY(gmm_graph_ok(g) && Hf && attr && mu && sigma && w && Y && gmm_dims_ok(K, dim, C) && ldh >= (int64_t)K * C && ldy >= C &&
             (!R || ldr >= C) && Y != Hf && Y != R);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && ldh % 4 == 0 && ldy % 4 == 0 && al16(Hf) && al16(Y) && (!bias || al16(bias)) && (!R || (al16(R) && ldr % 4 == 0))) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(gmm_fwd_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->a, g->ee_ptr, g->ee_idx, Hf, ldh,
-                           attr, dim, mu, sigma, R, ldr, bias, w, Y, ldy, n, K, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(gmm_fwd_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->a, g->ee_ptr,
-                           g->ee_idx, Hf, ldh, attr, dim, mu, sigma, R, ldr, bias, w, Y, ldy, n, K, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && ldh % 4 == 0 && ldy % 4 == 0 && al16(Hf) && al16(Y) && (!bias || al16(bias)) && (!R || (al16(R)
+                     && ldr % 4 == 0));
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), gmm_fwd_kernel, gmm_fwd_scalar_kernel,
+                            g->rowptr, g->col, g->a, g->ee_ptr, g->ee_idx, Hf, ldh, attr, dim, mu, sigma, R, ldr, bias, w, Y, ldy,
+                            (int)g->n_rows, K, C);
 }
 
 extern "C" int ddmp_gmm_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Hf, int64_t ldh,
@@ -371,18 +342,10 @@ extern "C" int ddmp_gmm_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int
     ARG_TRY(gmm_graph_ok(g) && dOut && Hf && attr && mu && sigma && ge && parts && gmm_dims_ok(K, dim, C) && lddo >= C &&
             ldh >= (int64_t)K * C && dattr != attr);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && lddo % 4 == 0 && ldh % 4 == 0 && al16(dOut) && al16(Hf)) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(gmm_bwd_edge_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->a, g->ee_ptr, g->ee_idx, dOut,
-                           lddo, Hf, ldh, attr, dim, mu, sigma, ge, parts, dattr, n, K, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(gmm_bwd_edge_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->a,
-                           g->ee_ptr, g->ee_idx, dOut, lddo, Hf, ldh, attr, dim, mu, sigma, ge, parts, dattr, n, K, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && lddo % 4 == 0 && ldh % 4 == 0 && al16(dOut) && al16(Hf);
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), gmm_bwd_edge_kernel,
+                            gmm_bwd_edge_scalar_kernel, g->rowptr, g->col, g->a, g->ee_ptr, g->ee_idx, dOut, lddo, Hf, ldh, attr,
+                            dim, mu, sigma, ge, parts, dattr, (int)g->n_rows, K, C);
 }
 
 extern "C" int ddmp_gmm_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, int K, int C, const float* w, float* dHf,
@@ -390,16 +353,9 @@ extern "C" int ddmp_gmm_bwd_node_f32(const ddmp_graph* g, const float* dOut, int
     ARG_TRY(gmm_graph_ok(g) && dOut && w && dHf && feast_dims_ok(K, C) && lddo >= C && lddh >= (int64_t)K * C && (!dR || lddr >= C) &&
             dHf != dOut && dR != dOut);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && lddo % 4 == 0 && lddh % 4 == 0 && al16(dOut) && al16(dHf) && (!dR || (al16(dR) && lddr % 4 == 0))) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(gmm_bwd_node_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo, w, dHf,
-                           lddh, dR, lddr, n, K, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(gmm_bwd_node_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->mirror,
-                           dOut, lddo, w, dHf, lddh, dR, lddr, n, K, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && lddo % 4 == 0 && lddh % 4 == 0 && al16(dOut) && al16(dHf) && (!dR || (al16(dR) && lddr % 4 ==
+                     0));
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), gmm_bwd_node_kernel,
+                            gmm_bwd_node_scalar_kernel, g->rowptr, g->col, g->mirror, dOut, lddo, w, dHf, lddh, dR, lddr,
+                            (int)g->n_rows, K, C);
 }

@@ -62,13 +62,7 @@ __global__ __launch_bounds__(256) void rgate_kernel(const int* __restrict__ rowp
                                                     int chunks_per_xcd, int n_chunks) {
     ROW_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         const float* arow = A + (int64_t)row * lda;
         const float* brow = B ? B + (int64_t)row * ldb : nullptr;
         float* o1 = O1 + (int64_t)row * ldo1;
@@ -166,19 +160,10 @@ int rgate_launch(const ddmp_graph* g, const float* A, int64_t lda, const float* 
                  int64_t ld1, const float* G2, int64_t ld2, float* O1, int64_t ldo1, float* O2, int64_t ldo2, float* dS,
                  int64_t ldds, int C, ddmp_stream stream) {
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && vec_ok(A, lda) && (!B || vec_ok(B, ldb)) && al16(bias) && vec_ok(G1, ld1) && vec_ok(G2, ld2) &&
-        vec_ok(O1, ldo1) && (!O2 || vec_ok(O2, ldo2)) && (!dS || vec_ok(dS, ldds))) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(rgate_kernel<kMode>, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->mirror, g->a, A, lda, B, ldb, bias,
-                           G1, ld1, G2, ld2, O1, ldo1, O2, ldo2, dS, ldds, n, C, rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(rgate_scalar_kernel<kMode>, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->mirror, g->a, A, lda,
-                           B, ldb, bias, G1, ld1, G2, ld2, O1, ldo1, O2, ldo2, dS, ldds, n, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && vec_ok(A, lda) && (!B || vec_ok(B, ldb)) && al16(bias) && vec_ok(G1, ld1) && vec_ok(G2, ld2) &&
+                     vec_ok(O1, ldo1) && (!O2 || vec_ok(O2, ldo2)) && (!dS || vec_ok(dS, ldds));
+    return launch_rows((hipStream_t)stream, (int)g->n_rows, vec, rgate_kernel<kMode>, rgate_scalar_kernel<kMode>, g->rowptr, g->col,
+                       g->mirror, g->a, A, lda, B, ldb, bias, G1, ld1, G2, ld2, O1, ldo1, O2, ldo2, dS, ldds, (int)g->n_rows, C);
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 // The row-gather work layout of the graph-operator kernels (sddmm.hip, gat.hip, gatv2.hip, tconv.hip, rgate.hip, feast.hip,
-// gmm.hip, gmax.hip; gather_mix.h):
+// gmm.hip, gmax.hip, spline.hip; gather_mix.h, colsum_final.h):
 // the one place that fixes it.  (The SpMM files have their own variants of it; they do not include this header.)
 //   * a workgroup (4 waves) owns a chunk of kRB = 64 consecutive rows; blockIdx -> chunk is XCD-aware (block b runs on XCD b % 8,
 //     so XCD x takes the chunks x * chunks_per_xcd ..: the ~deg re-reads of a neighbour row by neighbouring output rows hit that
@@ -17,6 +17,9 @@
 //     shorter re-reads its last entry (an L1 hit) and its kernel masks that slot out.
 // No atomics, every sum in a fixed order: bitwise reproducible.  Every row * stride product is int64.  Widths that are not a
 // multiple of 4 (or operands that fail al16) take scalar kernels, one thread per row, 256 rows per workgroup.
+// Also here, written once: the row loop and the head-pass loop (FOR_CHUNK_ROWS, FOR_CHUNK_ROW_ENTRIES, FOR_HEAD_PASSES) and the host's
+// vector-or-scalar launch of every entry point (launch_rows, launch_head_rows).  The second stage of the two-stage column
+// reductions is colsum_final.h.
 #pragma once
 #include "ddmp_common.h"
 
@@ -97,6 +100,25 @@ inline int lanes_per_head(int C) {
         }                                                                                          \
     }
 
+// The row loop, `FOR_CHUNK_ROWS { ... }`: the rows of this workgroup's chunk that the lane's row group takes, as `row` (the 8 lanes
+// of a row group leave together; `continue` goes to the next row); FOR_CHUNK_ROW_ENTRIES also gives the row's entries rbase ..
+// rbase + nn (kernel parameter rowptr).
+#define FOR_CHUNK_ROWS                                                                             \
+    _Pragma("unroll 1") for (int qq = 0; qq < 2; ++qq)                                             \
+        if (const int lr = wave * 8 + grp + qq * 32; lr < nr)                                      \
+            if (const int row = r0 + lr; true)
+#define FOR_CHUNK_ROW_ENTRIES                                                                      \
+    FOR_CHUNK_ROWS                                                                                 \
+        if (const int rbase = rowptr[row], nn = rowptr[row + 1] - rbase; true)
+
+// The head-pass loop, `FOR_HEAD_PASSES(heads) { ... }`: this lane's head h of every pass, hv: it is a valid one, hh: the head it
+// runs -- a lane of the last pass that holds no valid head runs head heads - 1 again and stores nothing (`continue`: next pass).
+#define FOR_HEAD_PASSES(heads)                                                                     \
+    _Pragma("unroll 1") for (int hg = 0; hg < (heads); hg += hp)                                   \
+        if (const int h = hg + sub; true)                                                          \
+            if (const bool hv = h < (heads); true)                                                 \
+                if (const int hh = hv ? h : (heads) - 1; true)
+
 // ------------------------------------------------------------------------------------------------ the gather of one head pass
 // out[row, hh, :] = init(q) + sum_{e in row} f_e X[col e, hh, :],  f_e = fac[(kMirror ? mirror[e] : e), hh].  The lanes of the
 // pass that hold no valid head (hv false) run head hh = heads - 1 again and store nothing.
@@ -160,5 +182,30 @@ inline RowGrid row_grid(int n) {
     return {n_chunks, cpx, dim3(cpx * kXcd)};
 }
 inline dim3 scalar_grid(int n) { return dim3((unsigned)cdiv(n, 256)); }
+
+// Launch the vector kernel (`vec`: the caller's alignment predicate holds) or the scalar kernel over n > 0 rows.  The vector
+// kernel's parameters are the scalar kernel's, then (launch_head_rows) lw, then chunks_per_xcd, n_chunks.  Returns the status.
+template <class VK, class SK, class... Args>
+inline int launch_rows(hipStream_t st, int n, bool vec, VK vk, SK sk, Args... args) {
+    if (vec) {
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(vk, rg.grid, dim3(256), 0, st, args..., rg.cpx, rg.n_chunks);
+    } else {
+        hipLaunchKernelGGL(sk, scalar_grid(n), dim3(256), 0, st, args...);
+    }
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
+template <class VK, class SK, class... Args>
+inline int launch_head_rows(hipStream_t st, int n, bool vec, int lw, VK vk, SK sk, Args... args) {
+    if (vec) {
+        const RowGrid rg = row_grid(n);
+        hipLaunchKernelGGL(vk, rg.grid, dim3(256), 0, st, args..., lw, rg.cpx, rg.n_chunks);
+    } else {
+        hipLaunchKernelGGL(sk, scalar_grid(n), dim3(256), 0, st, args...);
+    }
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
 
 }  // namespace

@@ -18,13 +18,7 @@ __global__ __launch_bounds__(256) void sddmm_kernel(const int* __restrict__ rowp
                                                     const float* __restrict__ dY, int64_t lddy, const float* __restrict__ H, int64_t ldh,
                                                     float* __restrict__ G, int n_rows, int C, int chunks_per_xcd, int n_chunks) {
     ROW_CHUNK_PROLOGUE
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;                                  // (the 8 lanes of a row group leave together)
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         const float* yp = dY + (int64_t)row * lddy + sl * 4;
 #pragma unroll 1
         for (int b0 = 0; b0 < nn; b0 += kEB) {
@@ -79,15 +73,8 @@ __global__ __launch_bounds__(256) void sddmm_scalar_kernel(const int* __restrict
 extern "C" int ddmp_sddmm_f32(const ddmp_graph* g, const float* dY, int64_t lddy, const float* H, int64_t ldh, int C, float* G,
                               ddmp_stream stream) {
     ARG_TRY(g && dY && H && G && C > 0 && lddy >= C && ldh >= C);
-    hipStream_t st = (hipStream_t)stream;
     if (g->nnz == 0) return DDMP_OK;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && lddy % 4 == 0 && ldh % 4 == 0 && al16(dY) && al16(H)) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(sddmm_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, dY, lddy, H, ldh, G, n, C, rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(sddmm_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, dY, lddy, H, ldh, G, n, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && lddy % 4 == 0 && ldh % 4 == 0 && al16(dY) && al16(H);
+    return launch_rows((hipStream_t)stream, (int)g->n_rows, vec, sddmm_kernel, sddmm_scalar_kernel, g->rowptr, g->col, dY, lddy, H, ldh,
+                       G, (int)g->n_rows, C);
 }

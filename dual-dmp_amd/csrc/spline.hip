@@ -101,13 +101,7 @@ __global__ __launch_bounds__(256) void spline_fwd_kernel(const int* __restrict__
     constexpr int S = 1 << DIM;
     const int W = C >> 2;
     const int gbase = lane & ~7;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         float* yrow = Y + (int64_t)row * ldy;
         const float* rrow = R ? R + (int64_t)row * ldr : nullptr;
         const int n_in = nn > 0 ? ee_ptr[rbase + nn] - ee_ptr[rbase] : 0;
@@ -235,13 +229,7 @@ __global__ __launch_bounds__(256) void spline_bwd_node_kernel(const int* __restr
     bool distinct = true;
 #pragma unroll
     for (int d = 0; d < DIM; ++d) distinct = distinct && tab.ks[d] >= 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         float* orow = dHf + (int64_t)row * lddh;
         if (dR)
             for (int q = sl; q < W; q += 8)
@@ -409,24 +397,13 @@ extern "C" int ddmp_spline_fwd_f32(const ddmp_graph* g, const float* Hf, int64_t
     ARG_TRY(spline_graph_ok(g) && Hf && attr && Y && spline_tab(dim, kernel_size, is_open, C, tab, K) && ldh >= (int64_t)K * C &&
             ldy >= C && (!R || ldr >= C) && Y != Hf && Y != R && Y != attr && Y != bias);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && vec_ok(Hf, ldh) && vec_ok(Y, ldy) && al16(bias) && (!R || vec_ok(R, ldr))) {
-        const RowGrid rg = row_grid(n);
-#define LAUNCH(D)                                                                                                            \
-    hipLaunchKernelGGL(spline_fwd_kernel<D>, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->ee_ptr, g->ee_idx, Hf, ldh, attr, tab, \
-                       R, ldr, bias, mean, Y, ldy, n, C, lanes_per_head(C), rg.cpx, rg.n_chunks)
-        SPLINE_DIM_SWITCH(dim, LAUNCH)
+    const bool vec = C % 4 == 0 && vec_ok(Hf, ldh) && vec_ok(Y, ldy) && al16(bias) && (!R || vec_ok(R, ldr));
+#define LAUNCH(D)                                                                                                                \
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), spline_fwd_kernel<D>,                   \
+                            spline_fwd_scalar_kernel<D>, g->rowptr, g->col, g->ee_ptr, g->ee_idx, Hf, ldh, attr, tab, R, ldr, bias, \
+                            mean, Y, ldy, (int)g->n_rows, C)
+    SPLINE_DIM_SWITCH(dim, LAUNCH)
 #undef LAUNCH
-    } else {
-#define LAUNCH(D)                                                                                                            \
-    hipLaunchKernelGGL(spline_fwd_scalar_kernel<D>, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->ee_ptr, g->ee_idx, Hf,  \
-                       ldh, attr, tab, R, ldr, bias, mean, Y, ldy, n, C)
-        SPLINE_DIM_SWITCH(dim, LAUNCH)
-#undef LAUNCH
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
 }
 
 extern "C" int ddmp_spline_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* attr, int dim,
@@ -437,22 +414,11 @@ extern "C" int ddmp_spline_bwd_node_f32(const ddmp_graph* g, const float* dOut, 
     ARG_TRY(spline_graph_ok(g) && dOut && attr && dHf && spline_tab(dim, kernel_size, is_open, C, tab, K) && lddo >= C &&
             lddh >= (int64_t)K * C && (!dR || lddr >= C) && dHf != dOut && dR != dOut && dHf != attr && dR != attr && dR != dHf);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && vec_ok(dOut, lddo) && vec_ok(dHf, lddh) && (!dR || vec_ok(dR, lddr))) {
-        const RowGrid rg = row_grid(n);
-#define LAUNCH(D)                                                                                                            \
-    hipLaunchKernelGGL(spline_bwd_node_kernel<D>, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->mirror, g->ee_ptr, g->ee_idx,    \
-                       dOut, lddo, attr, tab, mean, dHf, lddh, dR, lddr, n, K, C, lanes_per_head(C), rg.cpx, rg.n_chunks)
-        SPLINE_DIM_SWITCH(dim, LAUNCH)
+    const bool vec = C % 4 == 0 && vec_ok(dOut, lddo) && vec_ok(dHf, lddh) && (!dR || vec_ok(dR, lddr));
+#define LAUNCH(D)                                                                                                                \
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), spline_bwd_node_kernel<D>,              \
+                            spline_bwd_node_scalar_kernel<D>, g->rowptr, g->col, g->mirror, g->ee_ptr, g->ee_idx, dOut, lddo, attr, \
+                            tab, mean, dHf, lddh, dR, lddr, (int)g->n_rows, K, C)
+    SPLINE_DIM_SWITCH(dim, LAUNCH)
 #undef LAUNCH
-    } else {
-#define LAUNCH(D)                                                                                                            \
-    hipLaunchKernelGGL(spline_bwd_node_scalar_kernel<D>, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->mirror, g->ee_ptr, \
-                       g->ee_idx, dOut, lddo, attr, tab, mean, dHf, lddh, dR, lddr, n, K, C)
-        SPLINE_DIM_SWITCH(dim, LAUNCH)
-#undef LAUNCH
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
 }

@@ -28,20 +28,10 @@ __global__ __launch_bounds__(256) void tconv_fwd_kernel(const int* __restrict__ 
                                                         int chunks_per_xcd, int n_chunks) {
     HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         float* yrow = Y + (int64_t)row * ldy;
         const float* srow = skip ? skip + (int64_t)row * lds : nullptr;
-#pragma unroll 1
-        for (int hg = 0; hg < heads; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < heads;
-            const int hh = hv ? h : heads - 1;
+        FOR_HEAD_PASSES(heads) {
             const float* qh = Q + (int64_t)row * ldq + hh * C;
             // z_e for every entry (parked in alpha) and the row's maximum; every lane of the head holds the same sums
             float m = -INFINITY;
@@ -137,18 +127,8 @@ __global__ __launch_bounds__(256) void tconv_bwd_edge_kernel(const int* __restri
                                                              int chunks_per_xcd, int n_chunks) {
     HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
-#pragma unroll 1
-        for (int hg = 0; hg < heads; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < heads;
-            const int hh = hv ? h : heads - 1;
+    FOR_CHUNK_ROW_ENTRIES {
+        FOR_HEAD_PASSES(heads) {
             const float* gh = dOut + (int64_t)row * lddo + hh * C;
             float* xo = dQ + (int64_t)row * lddq + hh * C;
             if (nn == 0) {
@@ -266,21 +246,11 @@ __global__ __launch_bounds__(256) void tconv_bwd_node_kernel(const int* __restri
                                                              int n_chunks) {
     HEAD_CHUNK_PROLOGUE
     const int W = C >> 2;
-#pragma unroll 1
-    for (int qq = 0; qq < 2; ++qq) {
-        const int lr = wave * 8 + grp + qq * 32;
-        if (lr >= nr) continue;
-        const int row = r0 + lr;
-        const int rbase = rowptr[row];
-        const int nn = rowptr[row + 1] - rbase;
+    FOR_CHUNK_ROW_ENTRIES {
         if (dS)
             for (int q = sl; q < heads * W; q += 8)
                 *reinterpret_cast<float4*>(dS + (int64_t)row * ldds + q * 4) = ld4(dOut + (int64_t)row * lddo + q * 4);
-#pragma unroll 1
-        for (int hg = 0; hg < heads; hg += hp) {
-            const int h = hg + sub;
-            const bool hv = h < heads;
-            const int hh = hv ? h : heads - 1;
+        FOR_HEAD_PASSES(heads) {
             float* ko = dK + (int64_t)row * lddk + hh * C;
             float* vo = dV + (int64_t)row * lddv + hh * C;
             if (nn == 0) {
@@ -372,18 +342,9 @@ extern "C" int ddmp_tconv_fwd_f32(const ddmp_graph* g, const float* Q, int64_t l
     ARG_TRY(attn_graph_ok(g) && Q && K && V && alpha && Y && tconv_dims_ok(heads, C) && ld_ok(ldq, heads, C) && ld_ok(ldk, heads, C) &&
             ld_ok(ldv, heads, C) && ld_ok(ldy, heads, C) && (!skip || ld_ok(lds, heads, C)) && Y != Q && Y != K && Y != V && Y != skip);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && vec_ok(Q, ldq) && vec_ok(K, ldk) && vec_ok(V, ldv) && vec_ok(Y, ldy) && (!skip || vec_ok(skip, lds))) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(tconv_fwd_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->a, Q, ldq, K, ldk, V, ldv, scale, skip,
-                           lds, alpha, Y, ldy, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(tconv_fwd_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->a, Q, ldq, K, ldk, V, ldv,
-                           scale, skip, lds, alpha, Y, ldy, n, heads, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && vec_ok(Q, ldq) && vec_ok(K, ldk) && vec_ok(V, ldv) && vec_ok(Y, ldy) && (!skip || vec_ok(skip, lds));
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), tconv_fwd_kernel, tconv_fwd_scalar_kernel,
+                            g->rowptr, g->col, g->a, Q, ldq, K, ldk, V, ldv, scale, skip, lds, alpha, Y, ldy, (int)g->n_rows, heads, C);
 }
 
 extern "C" int ddmp_tconv_bwd_edge_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* K, int64_t ldk,
@@ -392,18 +353,10 @@ extern "C" int ddmp_tconv_bwd_edge_f32(const ddmp_graph* g, const float* dOut, i
     ARG_TRY(attn_graph_ok(g) && dOut && K && V && alpha && dz && dQ && tconv_dims_ok(heads, C) && ld_ok(lddo, heads, C) &&
             ld_ok(ldk, heads, C) && ld_ok(ldv, heads, C) && ld_ok(lddq, heads, C) && dz != alpha && dQ != dOut && dQ != K && dQ != V);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && vec_ok(dOut, lddo) && vec_ok(K, ldk) && vec_ok(V, ldv) && vec_ok(dQ, lddq)) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(tconv_bwd_edge_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, dOut, lddo, K, ldk, V, ldv, scale,
-                           alpha, dz, dQ, lddq, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(tconv_bwd_edge_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, dOut, lddo, K, ldk, V,
-                           ldv, scale, alpha, dz, dQ, lddq, n, heads, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && vec_ok(dOut, lddo) && vec_ok(K, ldk) && vec_ok(V, ldv) && vec_ok(dQ, lddq);
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), tconv_bwd_edge_kernel,
+                            tconv_bwd_edge_scalar_kernel, g->rowptr, g->col, dOut, lddo, K, ldk, V, ldv, scale, alpha, dz, dQ, lddq,
+                            (int)g->n_rows, heads, C);
 }
 
 extern "C" int ddmp_tconv_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Q, int64_t ldq, int heads,
@@ -413,16 +366,9 @@ extern "C" int ddmp_tconv_bwd_node_f32(const ddmp_graph* g, const float* dOut, i
             ld_ok(ldq, heads, C) && ld_ok(lddk, heads, C) && ld_ok(lddv, heads, C) && (!dS || ld_ok(ldds, heads, C)) && dK != dV &&
             dK != dOut && dK != Q && dV != dOut && dV != Q && dS != dOut && dS != Q && dS != dK && dS != dV);
     if (g->n_rows == 0) return DDMP_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)g->n_rows;
-    if (C % 4 == 0 && vec_ok(dOut, lddo) && vec_ok(Q, ldq) && vec_ok(dK, lddk) && vec_ok(dV, lddv) && (!dS || vec_ok(dS, ldds))) {
-        const RowGrid rg = row_grid(n);
-        hipLaunchKernelGGL(tconv_bwd_node_kernel, rg.grid, dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo, Q, ldq, scale,
-                           alpha, dz, dK, lddk, dV, lddv, dS, ldds, n, heads, C, lanes_per_head(C), rg.cpx, rg.n_chunks);
-    } else {
-        hipLaunchKernelGGL(tconv_bwd_node_scalar_kernel, scalar_grid(n), dim3(256), 0, st, g->rowptr, g->col, g->mirror, dOut, lddo,
-                           Q, ldq, scale, alpha, dz, dK, lddk, dV, lddv, dS, ldds, n, heads, C);
-    }
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const bool vec = C % 4 == 0 && vec_ok(dOut, lddo) && vec_ok(Q, ldq) && vec_ok(dK, lddk) && vec_ok(dV, lddv) &&
+                     (!dS || vec_ok(dS, ldds));
+    return launch_head_rows((hipStream_t)stream, (int)g->n_rows, vec, lanes_per_head(C), tconv_bwd_node_kernel,
+                            tconv_bwd_node_scalar_kernel, g->rowptr, g->col, g->mirror, dOut, lddo, Q, ldq, scale, alpha, dz, dK, lddk,
+                            dV, lddv, dS, ldds, (int)g->n_rows, heads, C);
 }

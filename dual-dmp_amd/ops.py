@@ -669,14 +669,52 @@ def _gat_graph(g: Graph):
     return g
 
 
-def _gat_hf(t, heads, name, rows=None):
-    """[n, heads * C] float32 matrix -> (tensor, ld, C)."""
+def _rows(t, name, rows, width=None):
+    """float32 [>= rows, width] row block (a column block of a wider row buffer is fine; ``width=None``: any width) -> (tensor, ld)."""
     t, ld = _mat(_chk(t, torch.float32, name), name)
+    if t.shape[0] < rows or t.shape[1] < 1 or (width is not None and t.shape[1] != width):
+        raise DdmpError("%s must be [>= %d, %s], got %s" % (name, rows, "C" if width is None else width, tuple(t.shape)))
+    return t, ld
+
+
+def _gat_hf(t, heads, name, rows=0):
+    """float32 [>= rows, heads * C] row block -> (tensor, ld, C)."""
+    t, ld = _rows(t, name, rows)
     if heads < 1 or t.shape[1] % heads:
         raise DdmpError("%s: width %d is not heads (%d) x C" % (name, t.shape[1], heads))
-    if rows is not None and t.shape[0] < rows:
-        raise DdmpError("%s has %d rows, the graph has %d" % (name, t.shape[0], rows))
     return t, ld, t.shape[1] // heads
+
+
+def _head_mats(g, heads, who, **mats):
+    """The [n, heads * C] operands of a call by name -> (n, C, {name: (tensor, ld)}); all of one width."""
+    _gat_graph(g)
+    n, C, out = g.n_rows, None, {}
+    for name, t in mats.items():
+        t, ld, c = _gat_hf(t, heads, name, n)
+        if C is not None and c != C:
+            raise DdmpError("%s: %s differs in width from the other operands" % (who, name))
+        C = c
+        out[name] = (t, ld)
+    return n, C, out
+
+
+def _out(out, name, rows, width, device):
+    """An output row block: ``out`` checked as float32 [>= rows, width], or (None) a new [rows, width] -> (tensor, ld)."""
+    if out is None:
+        out = torch.empty((rows, width), dtype=torch.float32, device=device)
+    return _rows(out, name, rows, width)
+
+
+def _out_with_root(out, who, n, hc, C, root, device):
+    """The [dhf | droot] row buffer of a node-side backward: ``out`` checked as float32 [n, >= hc (+ C with ``root``)], or (None) a
+    new one of exactly that width -> ((dhf, ld), (droot, ld) | (None, 0)), views of its leading columns."""
+    wt = hc + (C if root else 0)
+    if out is None:
+        out = torch.empty((n, wt), dtype=torch.float32, device=device)
+    out, _ = _mat(_chk(out, torch.float32, "out"), "out")
+    if out.shape[0] != n or out.shape[1] < wt:
+        raise DdmpError("%s: out must be [%d, >= %d], got %s" % (who, n, wt, tuple(out.shape)))
+    return _mat(out[:, :hc], "dhf"), (_mat(out[:, hc:wt], "droot") if root else (None, 0))
 
 
 def _gat_arr(t, shape, name):
@@ -713,11 +751,7 @@ def gat_fwd(g: Graph, hf, s_src, s_dst, heads, slope, bias=None, out=None):
     s_src, s_dst = _gat_arr(s_src, (hf.shape[0], heads), "s_src"), _gat_arr(s_dst, (hf.shape[0], heads), "s_dst")
     if bias is not None:
         bias = _gat_arr(bias, (heads * C,), "bias")
-    if out is None:
-        out = torch.empty((n, heads * C), dtype=torch.float32, device=hf.device)
-    out, ldy, _ = _gat_hf(out, heads, "out", n)
-    if out.shape[1] != hf.shape[1]:
-        raise DdmpError("gat_fwd: out must be [%d, %d]" % (n, hf.shape[1]))
+    out, ldy = _out(out, "out", n, heads * C, hf.device)
     alpha = torch.empty((g.nnz, heads), dtype=torch.float32, device=hf.device)
     # algorithmic bytes: every feature row read once + written once, alpha written, both scores read, col + multiplicity, rowptr
     alg = 8.0 * n * heads * C + 4.0 * g.nnz * heads + 8.0 * n * heads + 8.0 * g.nnz + 4.0 * (n + 1)
@@ -730,12 +764,8 @@ def gat_fwd(g: Graph, hf, s_src, s_dst, heads, slope, bias=None, out=None):
 
 def gat_bwd_edge(g: Graph, dout, hf, s_src, s_dst, alpha, heads, slope):
     """Edge side of the backward (``ddmp_gat_bwd_edge_f32``) -> (ds [g.nnz, heads], ds_dst [n, heads])."""
-    _gat_graph(g)
-    n = g.n_rows
-    dout, lddo, C = _gat_hf(dout, heads, "dout", n)
-    hf, ldh, C2 = _gat_hf(hf, heads, "hf", n)
-    if C2 != C:
-        raise DdmpError("gat_bwd_edge: dout and hf differ in width")
+    n, C, m = _head_mats(g, heads, "gat_bwd_edge", dout=dout, hf=hf)
+    (dout, lddo), (hf, ldh) = m["dout"], m["hf"]
     s_src, s_dst = _gat_arr(s_src, (hf.shape[0], heads), "s_src"), _gat_arr(s_dst, (hf.shape[0], heads), "s_dst")
     alpha = _gat_arr(alpha, (g.nnz, heads), "alpha")
     ds = torch.empty((g.nnz, heads), dtype=torch.float32, device=hf.device)
@@ -786,28 +816,16 @@ def gat_datt(hf, ds_src, ds_dst, heads):
 
 
 # ---------------------------------------------------------------------------------------- dynamic graph attention
-def _gatv2_args(g, xl, xr, att, heads, who):
-    _gat_graph(g)
-    n = g.n_rows
-    xl, ldl, C = _gat_hf(xl, heads, "xl", n)
-    xr, ldr, C2 = _gat_hf(xr, heads, "xr", n)
-    if C2 != C:
-        raise DdmpError("%s: xl and xr differ in width" % who)
-    return n, xl, ldl, xr, ldr, C, _gat_arr(att, (heads, C), "att")
-
-
 def gatv2_fwd(g: Graph, xl, xr, att, heads, slope, bias=None, out=None):
     """Per-edge scores + edge softmax + gather in one launch (``ddmp_gatv2_fwd_f32``) -> (y [n, heads * C], alpha [g.nnz, heads]).
     ``xl`` / ``xr``: [n, heads * C] (column blocks of one row buffer, or the same tensor twice); ``att``: [heads, C]; ``bias``:
     float32 [heads * C] added in the epilogue, or None."""
-    n, xl, ldl, xr, ldr, C, att = _gatv2_args(g, xl, xr, att, heads, "gatv2_fwd")
+    n, C, m = _head_mats(g, heads, "gatv2_fwd", xl=xl, xr=xr)
+    (xl, ldl), (xr, ldr) = m["xl"], m["xr"]
+    att = _gat_arr(att, (heads, C), "att")
     if bias is not None:
         bias = _gat_arr(bias, (heads * C,), "bias")
-    if out is None:
-        out = torch.empty((n, heads * C), dtype=torch.float32, device=xl.device)
-    out, ldy, _ = _gat_hf(out, heads, "out", n)
-    if out.shape[1] != heads * C:
-        raise DdmpError("gatv2_fwd: out must be [%d, %d]" % (n, heads * C))
+    out, ldy = _out(out, "out", n, heads * C, xl.device)
     alpha = torch.empty((g.nnz, heads), dtype=torch.float32, device=xl.device)
     # algorithmic bytes: xl and xr read once each, y written, alpha written, col + multiplicity, rowptr, att
     alg = 12.0 * n * heads * C + 4.0 * g.nnz * heads + 8.0 * g.nnz + 4.0 * (n + 1) + 4.0 * heads * C
@@ -822,16 +840,10 @@ def gatv2_bwd_edge(g: Graph, dout, xl, xr, att, alpha, heads, slope, out=None, w
     """Row i's side of the backward (``ddmp_gatv2_bwd_edge_f32``) -> (dz [g.nnz, heads], dxr [n, heads * C] written completely,
     part [n, heads * C] | None: the rows' shares of datt, for ``gatv2_datt``).  ``out``: where dxr goes (a column block of a row
     buffer is fine)."""
-    n, xl, ldl, xr, ldr, C, att = _gatv2_args(g, xl, xr, att, heads, "gatv2_bwd_edge")
-    dout, lddo, C2 = _gat_hf(dout, heads, "dout", n)
-    if C2 != C:
-        raise DdmpError("gatv2_bwd_edge: dout and xl differ in width")
-    alpha = _gat_arr(alpha, (g.nnz, heads), "alpha")
-    if out is None:
-        out = torch.empty((n, heads * C), dtype=torch.float32, device=xl.device)
-    out, lddr, C3 = _gat_hf(out, heads, "out", n)
-    if C3 != C:
-        raise DdmpError("gatv2_bwd_edge: out must be [%d, %d]" % (n, heads * C))
+    n, C, m = _head_mats(g, heads, "gatv2_bwd_edge", xl=xl, xr=xr, dout=dout)
+    (xl, ldl), (xr, ldr), (dout, lddo) = m["xl"], m["xr"], m["dout"]
+    att, alpha = _gat_arr(att, (heads, C), "att"), _gat_arr(alpha, (g.nnz, heads), "alpha")
+    out, lddr = _out(out, "out", n, heads * C, xl.device)
     dz = torch.empty((g.nnz, heads), dtype=torch.float32, device=xl.device)
     part = torch.empty((n, heads * C), dtype=torch.float32, device=xl.device) if want_datt else None
     # algorithmic bytes: dout, xl and xr read once each, dxr (and part) written, alpha read, dz written, col, rowptr, att
@@ -846,16 +858,11 @@ def gatv2_bwd_edge(g: Graph, dout, xl, xr, att, alpha, heads, slope, out=None, w
 def gatv2_bwd_node(g: Graph, dout, xl, xr, att, alpha, dz, heads, slope, out=None):
     """Node j's side of the backward (``ddmp_gatv2_bwd_node_f32``) -> dxl [n, heads * C] written completely.  ``out``: where it
     goes (a column block of a row buffer is fine)."""
-    n, xl, ldl, xr, ldr, C, att = _gatv2_args(g, xl, xr, att, heads, "gatv2_bwd_node")
-    dout, lddo, C2 = _gat_hf(dout, heads, "dout", n)
-    if C2 != C:
-        raise DdmpError("gatv2_bwd_node: dout and xl differ in width")
+    n, C, m = _head_mats(g, heads, "gatv2_bwd_node", xl=xl, xr=xr, dout=dout)
+    (xl, ldl), (xr, ldr), (dout, lddo) = m["xl"], m["xr"], m["dout"]
+    att = _gat_arr(att, (heads, C), "att")
     alpha, dz = _gat_arr(alpha, (g.nnz, heads), "alpha"), _gat_arr(dz, (g.nnz, heads), "dz")
-    if out is None:
-        out = torch.empty((n, heads * C), dtype=torch.float32, device=xl.device)
-    out, lddl, C3 = _gat_hf(out, heads, "out", n)
-    if C3 != C:
-        raise DdmpError("gatv2_bwd_node: out must be [%d, %d]" % (n, heads * C))
+    out, lddl = _out(out, "out", n, heads * C, xl.device)
     # algorithmic bytes: dout, xr and xl read once each, dxl written, alpha and dz read through the mirror map, col + mirror, rowptr
     alg = 16.0 * n * heads * C + 8.0 * g.nnz * heads + 8.0 * g.nnz + 4.0 * (n + 1) + 4.0 * heads * C
     with _timed("gatv2_bwd_node", _gat_key(g, heads, C), alg, 6.0 * g.nnz * heads * C):
@@ -881,38 +888,16 @@ def gatv2_datt(part, heads):
 
 
 # ---------------------------------------------------------------------------------------- graph transformer
-def _tconv_args(g, heads, who, **mats):
-    """The [n, heads * C] operands of a ``tconv_*`` call by name -> (n, C, {name: (tensor, ld)}); all of one width."""
-    _gat_graph(g)
-    n, C, out = g.n_rows, None, {}
-    for name, t in mats.items():
-        t, ld, c = _gat_hf(t, heads, name, n)
-        if C is not None and c != C:
-            raise DdmpError("%s: %s differs in width from the other operands" % (who, name))
-        C = c
-        out[name] = (t, ld)
-    return n, C, out
-
-
-def _tconv_out(out, n, heads, C, device, who, name="out"):
-    if out is None:
-        out = torch.empty((n, heads * C), dtype=torch.float32, device=device)
-    out, ld, c = _gat_hf(out, heads, name, n)
-    if c != C:
-        raise DdmpError("%s: %s must be [%d, %d]" % (who, name, n, heads * C))
-    return out, ld
-
-
 def tconv_fwd(g: Graph, q, k, v, heads, scale=None, skip=None, out=None):
     """Dot-product scores + edge softmax + gather in one launch (``ddmp_tconv_fwd_f32``) -> (y [n, heads * C], alpha [g.nnz,
     heads]).  ``q`` / ``k`` / ``v``: [n, heads * C] (column blocks of one row buffer are fine; ``k`` and ``v`` may be the same
     tensor); ``scale``: the factor on q . k, default 1 / sqrt(C); ``skip``: [n, heads * C] added in the epilogue, or None."""
     mats = dict(q=q, k=k, v=v) if skip is None else dict(q=q, k=k, v=v, skip=skip)
-    n, C, m = _tconv_args(g, heads, "tconv_fwd", **mats)
+    n, C, m = _head_mats(g, heads, "tconv_fwd", **mats)
     (q, ldq), (k, ldk), (v, ldv) = m["q"], m["k"], m["v"]
     skip, lds = m.get("skip", (None, 0))
     scale = 1.0 / math.sqrt(C) if scale is None else float(scale)
-    out, ldy = _tconv_out(out, n, heads, C, q.device, "tconv_fwd")
+    out, ldy = _out(out, "out", n, heads * C, q.device)
     alpha = torch.empty((g.nnz, heads), dtype=torch.float32, device=q.device)
     # algorithmic bytes: q, k and v (and the skip) read once each, y written, alpha written, col + multiplicity, rowptr
     alg = (16.0 if skip is None else 20.0) * n * heads * C + 4.0 * g.nnz * heads + 8.0 * g.nnz + 4.0 * (n + 1)
@@ -926,11 +911,11 @@ def tconv_fwd(g: Graph, q, k, v, heads, scale=None, skip=None, out=None):
 def tconv_bwd_edge(g: Graph, dout, k, v, alpha, heads, scale=None, out=None):
     """Row i's side of the backward (``ddmp_tconv_bwd_edge_f32``) -> (dz [g.nnz, heads], dq [n, heads * C] written completely).
     ``out``: where dq goes (a column block of a row buffer is fine)."""
-    n, C, m = _tconv_args(g, heads, "tconv_bwd_edge", dout=dout, k=k, v=v)
+    n, C, m = _head_mats(g, heads, "tconv_bwd_edge", dout=dout, k=k, v=v)
     (dout, lddo), (k, ldk), (v, ldv) = m["dout"], m["k"], m["v"]
     scale = 1.0 / math.sqrt(C) if scale is None else float(scale)
     alpha = _gat_arr(alpha, (g.nnz, heads), "alpha")
-    out, lddq = _tconv_out(out, n, heads, C, k.device, "tconv_bwd_edge")
+    out, lddq = _out(out, "out", n, heads * C, k.device)
     dz = torch.empty((g.nnz, heads), dtype=torch.float32, device=k.device)
     # algorithmic bytes: dout, k and v read once each, dq written, alpha read, dz written, col, rowptr
     alg = 16.0 * n * heads * C + 8.0 * g.nnz * heads + 4.0 * g.nnz + 4.0 * (n + 1)
@@ -945,15 +930,15 @@ def tconv_bwd_node(g: Graph, dout, q, alpha, dz, heads, scale=None, out_k=None, 
     """Node j's side of the backward (``ddmp_tconv_bwd_node_f32``) -> (dk, dv) [n, heads * C] each, written completely.
     ``out_k`` / ``out_v``: where they go; ``out_s``: a [n, heads * C] block that also receives a copy of ``dout`` (the skip
     term's gradient), or None.  Column blocks of one row buffer are fine."""
-    n, C, m = _tconv_args(g, heads, "tconv_bwd_node", dout=dout, q=q)
+    n, C, m = _head_mats(g, heads, "tconv_bwd_node", dout=dout, q=q)
     (dout, lddo), (q, ldq) = m["dout"], m["q"]
     scale = 1.0 / math.sqrt(C) if scale is None else float(scale)
     alpha, dz = _gat_arr(alpha, (g.nnz, heads), "alpha"), _gat_arr(dz, (g.nnz, heads), "dz")
-    out_k, lddk = _tconv_out(out_k, n, heads, C, q.device, "tconv_bwd_node", "out_k")
-    out_v, lddv = _tconv_out(out_v, n, heads, C, q.device, "tconv_bwd_node", "out_v")
+    out_k, lddk = _out(out_k, "out_k", n, heads * C, q.device)
+    out_v, lddv = _out(out_v, "out_v", n, heads * C, q.device)
     ldds = 0
     if out_s is not None:
-        out_s, ldds = _tconv_out(out_s, n, heads, C, q.device, "tconv_bwd_node", "out_s")
+        out_s, ldds = _out(out_s, "out_s", n, heads * C, q.device)
     # algorithmic bytes: dout and q read once each, dk and dv (and ds) written, alpha and dz read through the mirror map,
     # col + mirror, rowptr
     alg = (16.0 if out_s is None else 20.0) * n * heads * C + 8.0 * g.nnz * heads + 8.0 * g.nnz + 4.0 * (n + 1)
@@ -975,12 +960,12 @@ def rgate_fwd(g: Graph, k, q, v, skip=None, bias=None, out=None):
     blocks of one row buffer are fine); ``skip``: [n, C] and ``bias``: float32 [C], each added in the epilogue, or None.  Nothing
     is kept per entry."""
     mats = dict(k=k, q=q, v=v) if skip is None else dict(k=k, q=q, v=v, skip=skip)
-    n, C, m = _tconv_args(g, 1, "rgate_fwd", **mats)
+    n, C, m = _head_mats(g, 1, "rgate_fwd", **mats)
     (k, ldk), (q, ldq), (v, ldv) = m["k"], m["q"], m["v"]
     skip, lds = m.get("skip", (None, 0))
     if bias is not None:
         bias = _gat_arr(bias, (C,), "bias")
-    out, ldy = _tconv_out(out, n, 1, C, k.device, "rgate_fwd")
+    out, ldy = _out(out, "out", n, C, k.device)
     # algorithmic bytes: k, q and v (and the skip) read once each, y written, col + multiplicity, rowptr, bias
     alg = (16.0 if skip is None else 20.0) * n * C + 8.0 * g.nnz + 4.0 * (n + 1) + (0.0 if bias is None else 4.0 * C)
     with _timed("rgate_fwd", _rgate_key(g, C), alg, 6.0 * g.nnz * C):
@@ -993,9 +978,9 @@ def rgate_fwd(g: Graph, k, q, v, skip=None, bias=None, out=None):
 def rgate_bwd_row(g: Graph, dout, k, q, v, out=None):
     """Row i's side of the backward (``ddmp_rgate_bwd_row_f32``) -> dk [n, C] written completely; the gate is recomputed.
     ``out``: where dk goes (a column block of a row buffer is fine)."""
-    n, C, m = _tconv_args(g, 1, "rgate_bwd_row", dout=dout, k=k, q=q, v=v)
+    n, C, m = _head_mats(g, 1, "rgate_bwd_row", dout=dout, k=k, q=q, v=v)
     (dout, lddo), (k, ldk), (q, ldq), (v, ldv) = m["dout"], m["k"], m["q"], m["v"]
-    out, lddk = _tconv_out(out, n, 1, C, k.device, "rgate_bwd_row")
+    out, lddk = _out(out, "out", n, C, k.device)
     # algorithmic bytes: dout, k, q and v read once each, dk written, col + multiplicity, rowptr
     alg = 20.0 * n * C + 8.0 * g.nnz + 4.0 * (n + 1)
     with _timed("rgate_bwd_row", _rgate_key(g, C), alg, 9.0 * g.nnz * C):
@@ -1009,13 +994,13 @@ def rgate_bwd_node(g: Graph, dout, k, q, v, out_q=None, out_v=None, out_s=None):
     """Node j's side of the backward (``ddmp_rgate_bwd_node_f32``) -> (dq, dv) [n, C] each, written completely; the gate is
     recomputed and the multiplicities are read through the mirror map.  ``out_q`` / ``out_v``: where they go; ``out_s``: a [n, C]
     block that also receives a copy of ``dout`` (the skip term's gradient), or None.  Column blocks of one row buffer are fine."""
-    n, C, m = _tconv_args(g, 1, "rgate_bwd_node", dout=dout, k=k, q=q, v=v)
+    n, C, m = _head_mats(g, 1, "rgate_bwd_node", dout=dout, k=k, q=q, v=v)
     (dout, lddo), (k, ldk), (q, ldq), (v, ldv) = m["dout"], m["k"], m["q"], m["v"]
-    out_q, lddq = _tconv_out(out_q, n, 1, C, q.device, "rgate_bwd_node", "out_q")
-    out_v, lddv = _tconv_out(out_v, n, 1, C, q.device, "rgate_bwd_node", "out_v")
+    out_q, lddq = _out(out_q, "out_q", n, C, q.device)
+    out_v, lddv = _out(out_v, "out_v", n, C, q.device)
     ldds = 0
     if out_s is not None:
-        out_s, ldds = _tconv_out(out_s, n, 1, C, q.device, "rgate_bwd_node", "out_s")
+        out_s, ldds = _out(out_s, "out_s", n, C, q.device)
     # algorithmic bytes: dout, k, q and v read once each, dq and dv (and ds) written, col + mirror + multiplicity, rowptr
     alg = (24.0 if out_s is None else 28.0) * n * C + 12.0 * g.nnz + 4.0 * (n + 1)
     with _timed("rgate_bwd_node", _rgate_key(g, C), alg, 10.0 * g.nnz * C):
@@ -1026,29 +1011,17 @@ def rgate_bwd_node(g: Graph, dout, k, q, v, out_q=None, out_v=None, out_s=None):
 
 
 # ---------------------------------------------------------------------------------------- feature-steered convolution (DESIGN.md 4.9)
-def _feast_p(t, heads, name, rows):
-    """[n, heads] float32 matrix (a column block of a wider row buffer is fine) -> (tensor, ld)."""
-    t, ld = _mat(_chk(t, torch.float32, name), name)
-    if t.shape[1] != heads or t.shape[0] < rows:
-        raise DdmpError("%s must be [>= %d, %d], got %s" % (name, rows, heads, tuple(t.shape)))
-    return t, ld
-
-
 def feast_fwd(g: Graph, hf, p, c, heads, bias=None, out=None):
     """Head softmax + gather in one launch (``ddmp_feast_fwd_f32``) -> (y [n, C], beta [g.nnz, heads]).  ``hf``: [n, heads * C],
     ``p``: [n, heads] (both may be column blocks of one row buffer), ``c``: [heads], ``bias``: float32 [C] or None."""
     _gat_graph(g)
     n = g.n_rows
     hf, ldh, C = _gat_hf(hf, heads, "hf", n)
-    p, ldp = _feast_p(p, heads, "p", n)
+    p, ldp = _rows(p, "p", n, heads)
     c = _gat_arr(c, (heads,), "c")
     if bias is not None:
         bias = _gat_arr(bias, (C,), "bias")
-    if out is None:
-        out = torch.empty((n, C), dtype=torch.float32, device=hf.device)
-    out, ldy = _mat(_chk(out, torch.float32, "out"), "out")
-    if out.shape[0] < n or out.shape[1] != C:
-        raise DdmpError("feast_fwd: out must be [%d, %d]" % (n, C))
+    out, ldy = _out(out, "out", n, C, hf.device)
     beta = torch.empty((g.nnz, heads), dtype=torch.float32, device=hf.device)
     # algorithmic bytes: every gathered row (heads * C wide) read once, the output row (C wide) written once, beta written, p read
     # once, col + multiplicity, rowptr
@@ -1066,9 +1039,7 @@ def feast_bwd_edge(g: Graph, dout, hf, beta, heads):
     _gat_graph(g)
     n = g.n_rows
     hf, ldh, C = _gat_hf(hf, heads, "hf", n)
-    dout, lddo = _mat(_chk(dout, torch.float32, "dout"), "dout")
-    if dout.shape[0] < n or dout.shape[1] != C:
-        raise DdmpError("feast_bwd_edge: dout must be [>= %d, %d], got %s" % (n, C, tuple(dout.shape)))
+    dout, lddo = _rows(dout, "dout", n, C)
     beta = _gat_arr(beta, (g.nnz, heads), "beta")
     dz = torch.empty((g.nnz, heads), dtype=torch.float32, device=hf.device)
     rs = torch.empty((n, heads), dtype=torch.float32, device=hf.device)
@@ -1086,10 +1057,8 @@ def feast_bwd_node(g: Graph, dout, beta, dz, rs, heads, out=None):
     then views of it); None: two tensors of their own."""
     _gat_graph(g)
     n = g.n_rows
-    dout, lddo = _mat(_chk(dout, torch.float32, "dout"), "dout")
+    dout, lddo = _rows(dout, "dout", n)
     C = dout.shape[1]
-    if dout.shape[0] < n or C < 1:
-        raise DdmpError("feast_bwd_node: dout must be [>= %d, C], got %s" % (n, tuple(dout.shape)))
     beta, dz = _gat_arr(beta, (g.nnz, heads), "beta"), _gat_arr(dz, (g.nnz, heads), "dz")
     rs = _gat_arr(rs, (n, heads), "rs")
     hc = heads * C
@@ -1162,14 +1131,10 @@ def gmm_fwd(g: Graph, hf, attr, mu, sigma, K, root=None, bias=None, out=None):
     attr, mu, sigma, dim = _gmm_params(g, attr, mu, sigma, K)
     ldr = 0
     if root is not None:
-        root, ldr = _feast_p(root, C, "root", n)
+        root, ldr = _rows(root, "root", n, C)
     if bias is not None:
         bias = _gat_arr(bias, (C,), "bias")
-    if out is None:
-        out = torch.empty((n, C), dtype=torch.float32, device=hf.device)
-    out, ldy = _mat(_chk(out, torch.float32, "out"), "out")
-    if out.shape[0] < n or out.shape[1] != C:
-        raise DdmpError("gmm_fwd: out must be [%d, %d]" % (n, C))
+    out, ldy = _out(out, "out", n, C, hf.device)
     w = torch.empty((g.nnz, K), dtype=torch.float32, device=hf.device)
     # algorithmic bytes: every gathered row (K * C wide) read once, the output row (C wide) written once, the root block read, w
     # written, the attribute rows read once, col + multiplicity + ee_ptr, ee_idx, rowptr
@@ -1188,9 +1153,7 @@ def gmm_bwd_edge(g: Graph, dout, hf, attr, mu, sigma, K, want_dattr=False):
     _gmm_graph(g)
     n = g.n_rows
     hf, ldh, C = _gat_hf(hf, K, "hf", n)
-    dout, lddo = _mat(_chk(dout, torch.float32, "dout"), "dout")
-    if dout.shape[0] < n or dout.shape[1] != C:
-        raise DdmpError("gmm_bwd_edge: dout must be [>= %d, %d], got %s" % (n, C, tuple(dout.shape)))
+    dout, lddo = _rows(dout, "dout", n, C)
     attr, mu, sigma, dim = _gmm_params(g, attr, mu, sigma, K)
     ge = torch.empty((g.nnz, K), dtype=torch.float32, device=hf.device)
     parts = torch.empty((n, 2 * K * dim), dtype=torch.float32, device=hf.device)
@@ -1213,20 +1176,10 @@ def gmm_bwd_node(g: Graph, dout, w, K, out=None, root=False):
     buffer of its own."""
     _gmm_graph(g)
     n = g.n_rows
-    dout, lddo = _mat(_chk(dout, torch.float32, "dout"), "dout")
+    dout, lddo = _rows(dout, "dout", n)
     C = dout.shape[1]
-    if dout.shape[0] < n or C < 1:
-        raise DdmpError("gmm_bwd_node: dout must be [>= %d, C], got %s" % (n, tuple(dout.shape)))
     w = _gat_arr(w, (g.nnz, K), "w")
-    hc = K * C
-    wt = hc + (C if root else 0)
-    if out is None:
-        out = torch.empty((n, wt), dtype=torch.float32, device=dout.device)
-    out, _ = _mat(_chk(out, torch.float32, "out"), "out")
-    if out.shape[0] != n or out.shape[1] < wt:
-        raise DdmpError("gmm_bwd_node: out must be [%d, >= %d], got %s" % (n, wt, tuple(out.shape)))
-    dhf, lddh = _mat(out[:, :hc], "dhf")
-    dr, lddr = _mat(out[:, hc:wt], "droot") if root else (None, 0)
+    (dhf, lddh), (dr, lddr) = _out_with_root(out, "gmm_bwd_node", n, K * C, C, root, dout.device)
     # algorithmic bytes: dout read once, dhf (and the root block) written, w read through the mirror map, col + mirror, rowptr
     alg = 4.0 * n * (K + 1 + bool(root)) * C + 4.0 * g.nnz * K + 8.0 * g.nnz + 4.0 * (n + 1)
     with _timed("gmm_bwd_node", _gat_key(g, K, C), alg, 2.0 * g.nnz * K * C):
@@ -1269,14 +1222,10 @@ def spline_fwd(g: Graph, hf, attr, kernel_size, is_open, root=None, bias=None, m
     attr, ks, op, dim, K, S = _spline_params(g, attr, kernel_size, is_open, C)
     ldr = 0
     if root is not None:
-        root, ldr = _feast_p(root, C, "root", n)
+        root, ldr = _rows(root, "root", n, C)
     if bias is not None:
         bias = _gat_arr(bias, (C,), "bias")
-    if out is None:
-        out = torch.empty((n, C), dtype=torch.float32, device=hf.device)
-    out, ldy = _mat(_chk(out, torch.float32, "out"), "out")
-    if out.shape[0] < n or out.shape[1] != C:
-        raise DdmpError("spline_fwd: out must be [%d, %d]" % (n, C))
+    out, ldy = _out(out, "out", n, C, hf.device)
     # algorithmic bytes: the S selected blocks (C wide) of the neighbour's row per input edge -- not its K blocks --, the output row
     # written once, the root block read, the attribute rows read once, col + ee_ptr, ee_idx, rowptr
     alg = (4.0 * g.nnz_in * S * C + 4.0 * n * (1 + (root is not None)) * C + 4.0 * g.nnz_in * (dim + 1) + 8.0 * g.nnz
@@ -1295,19 +1244,9 @@ def spline_bwd_node(g: Graph, dout, attr, kernel_size, is_open, C, mean=True, ou
     results are then views of it; further columns are left untouched); None: a buffer of its own."""
     _gmm_graph(g)
     n = g.n_rows
-    dout, lddo = _mat(_chk(dout, torch.float32, "dout"), "dout")
-    if dout.shape[0] < n or dout.shape[1] != C or C < 1:
-        raise DdmpError("spline_bwd_node: dout must be [>= %d, %d], got %s" % (n, C, tuple(dout.shape)))
+    dout, lddo = _rows(dout, "dout", n, C)
     attr, ks, op, dim, K, S = _spline_params(g, attr, kernel_size, is_open, C)
-    hc = K * C
-    wt = hc + (C if root else 0)
-    if out is None:
-        out = torch.empty((n, wt), dtype=torch.float32, device=dout.device)
-    out, _ = _mat(_chk(out, torch.float32, "out"), "out")
-    if out.shape[0] != n or out.shape[1] < wt:
-        raise DdmpError("spline_bwd_node: out must be [%d, >= %d], got %s" % (n, wt, tuple(out.shape)))
-    dhf, lddh = _mat(out[:, :hc], "dhf")
-    dr, lddr = _mat(out[:, hc:wt], "droot") if root else (None, 0)
+    (dhf, lddh), (dr, lddr) = _out_with_root(out, "spline_bwd_node", n, K * C, C, root, dout.device)
     # algorithmic bytes: dhf (and the root block) written once, dout read once (and once more for the root block), the attribute
     # rows read once, col + mirror + ee_ptr, ee_idx, rowptr; the S read-modify-writes per edge stay in the row's own cache lines
     alg = 4.0 * n * (K + 1 + 2 * bool(root)) * C + 4.0 * g.nnz_in * (dim + 1) + 12.0 * g.nnz + 4.0 * (n + 1)
@@ -1319,14 +1258,6 @@ def spline_bwd_node(g: Graph, dout, attr, kernel_size, is_open, C, mean=True, ou
 
 
 # ---------------------------------------------------------------------------------------- max aggregation (DESIGN.md 4.10)
-def _gmax_mat(t, name, rows, C=None):
-    """[>= rows, C] float32 matrix (a column block of a wider row buffer is fine) -> (tensor, ld)."""
-    t, ld = _mat(_chk(t, torch.float32, name), name)
-    if t.shape[0] < rows or t.shape[1] < 1 or (C is not None and t.shape[1] != C):
-        raise DdmpError("%s must be [>= %d, %s], got %s" % (name, rows, "C" if C is None else C, tuple(t.shape)))
-    return t, ld
-
-
 def _gmax_arg(arg, n, C):
     _chk(arg, torch.int32, "arg")
     if arg.dim() != 2 or arg.stride(1) != 1 or arg.shape[0] < n or arg.shape[1] != C:
@@ -1341,14 +1272,12 @@ def gather_max(g: Graph, b, a=None, out=None, want_arg=True):
     buffer; ``a=None`` means 0); ``want_arg=False`` skips the store of ``arg`` (a forward without a backward)."""
     _gat_graph(g)
     n = g.n_rows
-    b, ldb = _gmax_mat(b, "b", n)
+    b, ldb = _rows(b, "b", n)
     C = b.shape[1]
     lda = 0
     if a is not None:
-        a, lda = _gmax_mat(a, "a", n, C)
-    if out is None:
-        out = torch.empty((n, C), dtype=torch.float32, device=b.device)
-    out, ldy = _gmax_mat(out, "out", n, C)
+        a, lda = _rows(a, "a", n, C)
+    out, ldy = _out(out, "out", n, C, b.device)
     arg, ldg = None, 0
     if want_arg:
         arg, ldg = _gmax_arg(torch.empty((n, C), dtype=torch.int32, device=b.device), n, C)
@@ -1368,7 +1297,7 @@ def gather_max_bwd(g: Graph, dg, arg, out=None):
     padding columns are left untouched.  ``out=None``: a buffer of its own."""
     _gat_graph(g)
     n = g.n_rows
-    dg, lddg = _gmax_mat(dg, "dg", n)
+    dg, lddg = _rows(dg, "dg", n)
     C = dg.shape[1]
     arg, ldg = _gmax_arg(arg, n, C)
     cp = (C + 3) // 4 * 4

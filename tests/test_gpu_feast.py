@@ -154,6 +154,22 @@ def test_kernels_match_the_reference(dev, graphs, name, loops, C, heads):
         assert e <= bound(yard), (k, e, yard)
 
 
+@pytest.mark.parametrize("heads", [3, 256])
+def test_offset_reduction_over_five_partials(dev, heads):
+    """``feast_dc`` alone on 4100 rows: five partials of 1024 rows, so every one of the final stage's four float64 lanes takes a
+    partial and the first takes a second one (the graphs above stop at two partials).  256 columns is the widest it accepts.
+    Against the float64 column sum, dc's comparison above: the float32 CPU column sum as the yardstick."""
+    from dual_dmp_amd import ops
+    rs = torch.randn(4100, heads, generator=torch.Generator().manual_seed(heads))
+    ref = rs.double().sum(0)
+    got = ops.feast_dc(rs.to(dev), heads)
+    torch.cuda.synchronize()
+    assert got.shape == (heads,)
+    e, yard = relerr(got, ref), relerr(rs.sum(0), ref)
+    print("feast_dc [4100, %d]: rel-L2 %.2e, float32 CPU yardstick %.2e, bound %.2e" % (heads, e, yard, bound(yard)))
+    assert e <= bound(yard), (e, yard)
+
+
 # ------------------------------------------------------------------------------------------------ 2. the operator
 def _operator_run(conv, x, ei, t, full=False):
     x = x.clone().requires_grad_(True)
