@@ -1,26 +1,11 @@
-"""Drop-in ``GCNConv``, ``ChebConv``, ``GATConv``, ``GATv2Conv``, ``TransformerConv``, ``ResGatedGraphConv``, ``FeaStConv``,
-``EdgeConv``, ``GMMConv`` and ``SplineConv`` on the HIP kernels (``GATv2Conv`` and ``SplineConv``: their class docstrings and
-DESIGN.md 4.12 / 4.15).
+"""Drop-ins for ten ``torch_geometric.nn`` 2.2.0 operators on the HIP kernels: same constructor / call signature, parameter names
+and initialisation; the dense part goes through the GEMMs, the graph part through one fused gather launch per direction, and no
+per-edge feature tensor exists at any point.  Each operator is documented once, at its class: ``GCNConv``, ``ChebConv``,
+``GATConv``, ``GATv2Conv``, ``TransformerConv``, ``ResGatedGraphConv``, ``FeaStConv``, ``GMMConv`` (with ``cartesian_pseudo``),
+``SplineConv``, ``EdgeConv``.
 
-Same constructor / call signature, parameter names and initialisation as
-``torch_geometric.nn.GCNConv`` 2.2.0 with the defaults the reference uses
-(``util/networks.py:15-26``: ``GCNConv(in_channels, out_channels)``; ``:51-62``:
-``conv(x, edge_index)``): ``lin.weight`` [out, in] Glorot-uniform, ``bias`` [out] zeros,
-``Y = D^-1/2 (A + I) D^-1/2 (X W^T) + b``, differentiable w.r.t. x, weight and bias.
-
-The normalised graph is built once per ``edge_index`` tensor (cached on its storage + version)
-instead of on every call; aggregation runs on min(in, out) channels.
-
-``ChebConv(in_channels, out_channels, K, normalization="sym", bias=True)`` restates
-``torch_geometric.nn.ChebConv`` 2.2.0: parameters ``lins.0.weight`` ... ``lins.{K-1}.weight`` [out, in]
-Glorot-uniform and ``bias`` [out] zeros, ``forward(x, edge_index, edge_weight=None, batch=None,
-lambda_max=None)`` with ``lambda_max`` a float (default 2.0),
-``Y = sum_k T_k W_k^T + b``, ``T_0 = X``, ``T_1 = L^ X``, ``T_k = 2 L^ T_{k-1} - T_{k-2}``,
-``L^ = -(2 / lambda_max) D^-1/2 A D^-1/2 + (2 / lambda_max - 1) I`` (no self loops; symmetric
-``edge_index`` only).  ``batch``, a tensor ``lambda_max`` and other normalisations raise.
-
-``edge_weight`` (both operators; restated from the published PyG 2.2.0 source from memory -- PyG cannot be installed here, so
-this could not be checked against it; the pin is the dense float64 restatement ``tests/gcnw_ref.py``):
+``edge_weight`` (``GCNConv`` and ``ChebConv``; restated from the published PyG 2.2.0 source from memory -- PyG cannot be installed
+here, so this could not be checked against it; the pin is the dense float64 restatement ``tests/gcnw_ref.py``):
 
 * ``GCNConv(in, out, improved=False, cached=False, add_self_loops=True, normalize=True, bias=True)``,
   ``forward(x, edge_index, edge_weight=None)``.  ``gcn_norm``: ``fill = 2 if improved else 1``; with ``add_self_loops`` explicit
@@ -31,153 +16,12 @@ this could not be checked against it; the pin is the dense float64 restatement `
   ``add_self_loops`` says.  ``cached`` is accepted and has no effect: the graph is always cached by tensor identity.
   Differentiable w.r.t. ``edge_weight`` (an SDDMM over the CSR + the normalisation's chain rule, ``ops.sddmm`` /
   ``ops.graph_weight_grad``).  The edge STRUCTURE must be symmetric; the weights need not be.
-* ``ChebConv.forward(..., edge_weight=w)``: self loops removed, ``S = D^-1/2 A_w D^-1/2``, the recurrence above on the valued S.
+* ``ChebConv.forward(..., edge_weight=w)``: self loops removed, ``S = D^-1/2 A_w D^-1/2``, ChebConv's recurrence on the valued S.
   SYMMETRIC weights only (after coalescing ``w_ij == w_ji`` bit for bit, else ``ValueError``: PyG takes the degree over sources
   here and over targets in ``gcn_norm``; the two agree only for symmetric weights).  No gradient w.r.t. ``edge_weight``.
 * Refused with ``ValueError`` before any gather: non-finite weights, a negative weighted degree, a length other than
   ``edge_index.shape[1]``, a dtype other than float32 / float64 (float64 is rounded to float32 once), a weight tensor that is not
   on the GPU, bf16 features.  ``edge_weight=None`` with default options is the unvalued graph and code path, bit for bit.
-
-``GATConv(in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True, edge_dim=None,
-fill_value="mean", bias=True)``, ``forward(x, edge_index, edge_attr=None, size=None, return_attention_weights=None)`` restates
-``torch_geometric.nn.GATConv`` 2.2.0 (like ``edge_weight`` above: written from the published source from memory -- PyG cannot be
-installed here, so this could not be checked against it; the pin is the float64 restatement ``tests/gat_ref.py``):
-
-* parameters ``lin_src.weight`` [heads * out, in] Glorot-uniform (``a = sqrt(6 / (in + heads * out))``); ``lin_dst`` IS ``lin_src``
-  (``in_channels`` is an int), so ``state_dict()`` carries both keys and ``parameters()`` yields the weight once; ``att_src`` /
-  ``att_dst`` [1, heads, out] Glorot (``a = sqrt(6 / (heads + out))``); ``bias`` zeros, [heads * out] when ``concat``, else [out].
-* ``Hf = x lin_src.weight^T`` viewed [N, heads, C]; ``s_src[j,h] = sum_c Hf[j,h,c] att_src[h,c]``, ``s_dst`` likewise; with
-  ``add_self_loops`` explicit self loops are removed and every node gets exactly one loop; for an edge j -> i
-  ``z = leaky_relu(s_src[j,h] + s_dst[i,h], negative_slope)``; ``alpha`` = softmax of z over ALL edges with target i, per head
-  (duplicate edges each take part); ``out[i,h,:] = sum alpha Hf[j,h,:]``; ``concat``: [N, heads * C], else the mean over heads;
-  the bias is added last.  A node without incoming entries (``add_self_loops=False`` only) gets a zero aggregate plus bias.
-* one launch for scores, one for edge softmax + gather (``ops.gat_fwd``), two for the backward of the graph part
-  (``ops.gat_bwd_edge`` / ``ops.gat_bwd_node``), a two-stage reduction for the attention vectors; the dense part goes through
-  the GEMMs.  The graph is ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=...)``: the coalesced structure whose
-  per-entry multiplicity weighs the softmax terms -- exact for duplicate edges.  Symmetric edge STRUCTURE only.
-* differentiable w.r.t. x, ``lin_src.weight``, ``att_src``, ``att_dst`` and ``bias``; float32, bitwise reproducible.
-* refused with ``ValueError`` before any launch: ``dropout != 0`` in training mode, ``edge_dim`` / ``edge_attr``, tuple
-  ``in_channels`` or a tuple ``x`` (bipartite), ``size``, ``return_attention_weights``, bf16 features.
-
-``FeaStConv(in_channels, out_channels, heads=1, add_self_loops=True, bias=True)``, ``forward(x, edge_index)`` restates
-``torch_geometric.nn.FeaStConv`` 2.2.0 (Verma et al., FeaStNet, CVPR 2018; like GATConv above: written from the published source
-from memory -- PyG cannot be installed here, so this could not be checked against it; the pin is the float64 restatement
-``tests/feast_ref.py``):
-
-* parameters ``lin.weight`` [heads * out, in] and ``u.weight`` [heads, in], both uniform(-1/sqrt(in), 1/sqrt(in)) and without
-  bias; ``c`` [heads] and ``bias`` [out] normal(0, 0.1).  The initialisations are from memory too; the arithmetic is what the
-  tests pin.
-* ``Hf = x lin.weight^T`` viewed [N, heads, out], ``P = x u.weight^T`` [N, heads]; with ``add_self_loops`` explicit self loops are
-  removed and every node gets exactly one loop; for an edge j -> i ``q[h]`` = softmax over the HEADS of ``P[j,h] - P[i,h] + c[h]``
-  (translation invariant in x); ``out[i,:] = (1 / deg_i) sum_{j -> i} sum_h q[h] Hf[j,h,:] + bias`` with ``deg_i`` the number of
-  edges with target i (duplicates each count, the added loop counts).  A node without incoming edges (``add_self_loops=False``
-  only) gets the bias.  With ``heads=1`` this is the plain mean of ``x lin.weight^T`` over the neighbourhood.
-* one GEMM against the packed ``[lin.weight; u.weight]`` for ``[Hf | P]``, one launch for head softmax + gather
-  (``ops.feast_fwd``), two for the backward of the graph part (``ops.feast_bwd_edge`` / ``ops.feast_bwd_node``), a two-stage
-  reduction for ``c`` (``ops.feast_dc``), one wgrad GEMM for ``[dW; dU]`` and one dgrad GEMM for ``dx``.  No [E, heads * out]
-  tensor exists at any point.  The graph is GATConv's: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=...)``, same
-  handle and cache key.  Symmetric edge STRUCTURE only.
-* differentiable w.r.t. x, ``lin.weight``, ``u.weight``, ``c`` and ``bias``; float32, bitwise reproducible.
-* refused with ``ValueError`` before any launch: tuple ``in_channels`` or a tuple ``x`` (bipartite), an ``aggr`` other than
-  ``"mean"``, bf16 features, ``heads < 1``, an ``x`` that is not [N, in].
-
-``EdgeConv(nn, aggr="max")``, ``forward(x, edge_index)`` restates ``torch_geometric.nn.EdgeConv`` 2.2.0 (Wang et al., Dynamic
-Graph CNN, 2019; like the operators above: written from the published source from memory -- PyG cannot be installed here, so this
-could not be checked against it; the pin is the float64 restatement ``tests/edgeconv_ref.py``):
-
-* ``out[i] = max over the edges j -> i of nn(cat[x_i, x_j - x_i])``, a node without incoming edges gets 0.  No self loops are
-  added; an explicit loop is an ordinary edge (it contributes ``nn(cat[x_i, 0])``); a duplicate edge changes nothing.
-* accepted ``nn``: a ``torch.nn.Linear(2 * in, out)`` with or without bias, or a ``torch.nn.Sequential`` whose first module is
-  such a ``Linear`` and whose other modules are all ``ReLU``, ``LeakyReLU(negative_slope >= 0)`` or ``Identity``.  Those are
-  elementwise, non-decreasing in floating point and map 0 to 0, so ``max_j act(z_j) == act(max_j z_j)`` bit for bit and an empty
-  neighbourhood stays 0: they run as ordinary torch modules after the fused core.  (A ``Sigmoid`` fails the second condition, a
-  ``BatchNorm`` the first.)  The module is kept as given under ``self.nn``: ``state_dict()`` has PyG's keys (``nn.weight``,
-  ``nn.bias`` or ``nn.0.weight`` ...) and ``parameters()`` are the user's own tensors.
-* with ``W = [Wa | Wb]``: ``W [x_i ; x_j - x_i] + b = (Wa - Wb) x_i + b + Wb x_j = A[i] + B[j]``, so
-  ``out[i] = A[i] + max_j B[j]``: one GEMM against the packed ``[Wa - Wb ; Wb]`` for the row buffer ``[A | B]``, one launch for the
-  per-column maximum and its winner (``ops.gather_max``; the winner is kept only when a gradient is wanted), one launch for the
-  backward of the graph part (``ops.gather_max_bwd`` -> ``[dA | dB]``), one wgrad GEMM (``dWa = dM``, ``dWb = dN - dM``) and one
-  dgrad GEMM.  No [E, .] tensor exists at any point.  The graph is GATConv's without loops:
-  ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric edge STRUCTURE only.
-* differentiable w.r.t. x and the ``Linear``'s weight and bias; float32, bitwise reproducible.  Deviation: with exact ties PyG's
-  winner is unspecified, ours is the smallest source id -- either one is a valid subgradient.
-* refused with ``ValueError`` before any launch: any other ``nn`` (an arbitrary MLP; a ``Linear`` whose ``in_features`` is odd),
-  ``aggr != "max"``, a tuple ``x`` (bipartite), bf16 features, an ``x`` that is not [N, in].  Not implemented:
-  ``DynamicEdgeConv`` / kNN graphs.
-
-``GMMConv(in_channels, out_channels, dim, kernel_size, separate_gaussians=False, aggr="mean", root_weight=True, bias=True)``,
-``forward(x, edge_index, edge_attr, size=None)`` restates ``torch_geometric.nn.GMMConv`` 2.2.0 (Monti et al., MoNet, CVPR 2017;
-like the operators above: written from the published source from memory -- PyG cannot be installed here, so this could not be
-checked against it; the pin is the float64 restatement ``tests/gmm_ref.py``).  It is the one operator here that consumes the
-GEOMETRY of an edge: ``edge_attr`` holds per-edge pseudo-coordinates ([E, dim]; ``cartesian_pseudo`` below restates PyG's
-``Cartesian`` transform).
-
-* parameters ``g`` [in, K * out], ``mu`` / ``sigma`` [K, dim] and ``root.weight`` [out, in] (no bias; absent with
-  ``root_weight=False``), all Glorot-uniform; ``bias`` [out] zeros, or None.  K = ``kernel_size``.
-* ``Hf = x g`` viewed [N, K, out]; for an edge t: j -> i with pseudo-coordinates ``a_t``
-  ``gamma_t[k] = exp(-1/2 sum_d (a_t[d] - mu[k,d])^2 / (1e-15 + sigma[k,d]^2))`` and
-  ``out[i] = (1 / deg_i) sum_{t -> i} sum_k gamma_t[k] Hf[j,k,:] + root(x_i) + bias`` with ``deg_i`` the number of edges with
-  target i (duplicates each count).  No self loops are added, an explicit loop is an ordinary edge, a node without incoming edges
-  gets ``root(x_i) + bias``.
-* one GEMM against the packed ``[g^T ; root.weight]`` for the row buffer ``[Hf | R]``, one launch for the Gaussians + gather + root
-  + bias (``ops.gmm_fwd``), two for the backward of the graph part (``ops.gmm_bwd_edge`` / ``ops.gmm_bwd_node``; the second also
-  copies the output gradient into the root block of the ``[dHf | dR]`` row buffer), the column reduction ``ops.feast_dc`` for
-  ``[dmu | dsigma]``, one wgrad GEMM for ``[dg^T ; droot]`` and one dgrad GEMM for ``dx``.  No [E, K * out] tensor and no
-  ``index_add_`` exist at any point.  The graph is GATConv's without loops: ``ops.graph_for(edge_index, N, norm="gat",
-  add_self_loops=False)``, same handle and cache key; a coalesced entry sums the Gaussians of its input edges in input order, so
-  duplicate edges with different pseudo-coordinates are exact.  Symmetric edge STRUCTURE only.
-* differentiable w.r.t. x, ``g``, ``mu``, ``sigma``, ``root.weight`` and ``bias``, and w.r.t. ``edge_attr`` when it requires grad;
-  float32, bitwise reproducible.
-* refused with ``ValueError`` before any launch: ``separate_gaussians=True``, ``aggr != "mean"``, tuple ``in_channels`` or a tuple
-  ``x`` (bipartite), ``size``, bf16 features, ``edge_attr`` missing, not [E, dim] or not float32 / float64 (float64 is rounded to
-  float32 once), ``kernel_size < 1``, ``dim < 1``, ``2 * kernel_size * dim > 256``.
-
-``TransformerConv(in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, edge_dim=None, bias=True,
-root_weight=True)``, ``forward(x, edge_index, edge_attr=None, return_attention_weights=None)`` restates
-``torch_geometric.nn.TransformerConv`` 2.2.0 (Shi et al., "Masked Label Prediction", IJCAI 2021; like the operators above:
-written from the published source from memory -- PyG cannot be installed here, so this could not be checked against it; the pin
-is the float64 restatement ``tests/transformer_ref.py``).  It is the one operator here whose scored stream (K) differs from its
-gathered stream (V).
-
-* parameters ``lin_key`` / ``lin_query`` / ``lin_value`` (weight [heads * out, in], bias [heads * out], always present),
-  ``lin_skip`` (weight [heads * out, in] when ``concat``, else [out, in]; bias only with ``bias=True``), ``lin_beta.weight``
-  [1, 3 * heads * out] (``concat``) or [1, 3 * out], only with ``beta=True`` and ``root_weight=True``; ``lin_edge`` is None.  All
-  uniform(-1/sqrt(in), 1/sqrt(in)) with "in" the layer's own input width.
-* ``z = Q[i,h,:] . K[j,h,:] / sqrt(C)`` for an edge j -> i, ``alpha`` = softmax over ALL edges with target i per head,
-  ``m[i,h,:] = sum alpha V[j,h,:]``, concatenated or averaged over heads; ``out = m + lin_skip(x)``, or the ``beta`` gate
-  ``b x_r + (1 - b) m`` with ``b = sigmoid(lin_beta(cat[m, x_r, m - x_r]))``.  No self loops are added, an explicit loop is an
-  ordinary edge, duplicate edges each take part, a node without incoming edges has ``m = 0``.
-* one GEMM against the packed ``[lin_query ; lin_key ; lin_value ; lin_skip]`` weights (biases as a row broadcast) for the row
-  buffer ``[Q | K | V | S]``, one launch for scores + edge softmax + gather + skip (``ops.tconv_fwd``), two for the backward of
-  the graph part (``ops.tconv_bwd_edge`` / ``ops.tconv_bwd_node``) into ONE row buffer ``[dQ | dK | dV | dS]``, bias gradients as
-  its column sums, one wgrad and one dgrad GEMM.  No [E, heads * out] tensor and no ``index_add_`` exist at any point.  The
-  graph is EdgeConv's: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric edge STRUCTURE only.
-* differentiable w.r.t. x and every parameter in use; float32, bitwise reproducible.
-* refused with ``ValueError`` before any launch: ``edge_dim`` / ``edge_attr``, ``dropout != 0`` in training mode, tuple
-  ``in_channels`` or a tuple ``x`` (bipartite), ``return_attention_weights``, bf16 features, CPU tensors, ``heads < 1``, an ``x``
-  that is not [N, in].
-
-``ResGatedGraphConv(in_channels, out_channels, act=Sigmoid(), root_weight=True, bias=True)``, ``forward(x, edge_index)`` restates
-``torch_geometric.nn.ResGatedGraphConv`` 2.2.0 (Bresson & Laurent, "Residual Gated Graph ConvNets", 2017; like the operators
-above: written from the published source from memory -- PyG cannot be installed here, so this could not be checked against it;
-the pin is the float64 restatement ``tests/resgated_ref.py``).  It is the one operator here whose edge weight is as wide as the
-features: a per-channel gate, not a scalar per head.
-
-* parameters ``lin_key`` / ``lin_query`` / ``lin_value`` (weight [out, in], bias [out], always present), ``lin_skip`` (weight
-  [out, in], no bias; None with ``root_weight=False``), ``bias`` [out] zeros (None with ``bias=False``).  The linear layers are
-  uniform(-1/sqrt(in), 1/sqrt(in)).
-* ``out_i = lin_skip(x_i) + bias + sum_{j -> i} sigmoid(lin_key(x_i) + lin_query(x_j)) * lin_value(x_j)``.  No self loops are
-  added, an explicit loop is an ordinary edge, duplicate edges each count, a node without incoming edges returns
-  ``lin_skip(x_i) + bias``.
-* one GEMM against the packed ``[lin_key ; lin_query ; lin_value ; lin_skip]`` weights (biases as a row broadcast) for the row
-  buffer ``[K | Q | V | S]``, one launch for gate + gather + skip + bias (``ops.rgate_fwd``), two for the backward of the graph
-  part (``ops.rgate_bwd_row`` / ``ops.rgate_bwd_node``) into ONE row buffer ``[dK | dQ | dV | dS]``, bias gradients as its column
-  sums, one wgrad and one dgrad GEMM.  NOTHING is stored per edge -- the backward recomputes the gate -- and no ``index_add_``
-  exists at any point.  The graph is EdgeConv's: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric
-  edge STRUCTURE only.
-* differentiable w.r.t. x and every parameter in use; float32, bitwise reproducible.
-* refused with ``ValueError`` before any launch: an ``act`` that is not a ``torch.nn.Sigmoid``, ``aggr`` other than ``"add"``,
-  tuple ``in_channels`` or a tuple ``x`` (bipartite), bf16 features, CPU tensors, an ``x`` that is not [N, in].
 """
 from __future__ import annotations
 
@@ -215,31 +59,93 @@ def _bias_grad(dy):
     return ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
 
 
-def _packed_rows(blocks, width, device, pad_each=False):
-    """The weight blocks ([rows_k, <= width] each, ``None`` skipped) stacked into ONE zero-padded float32 matrix for a single GEMM:
-    end to end with the total rounded up to a multiple of 4, or (``pad_each``) every block rounded up on its own."""
-    r4 = lambda r: (r + 3) // 4 * 4
-    blocks = [b for b in blocks if b is not None]
-    starts, rows = [], 0
+def _pack(blocks, width, device, pad_each=False):
+    """The blocks ([rows_k, <= width] each, ``None`` skipped) stacked into ONE zero-padded float32 matrix for a single GEMM: end to
+    end with the total rounded up to a multiple of 4, or (``pad_each``) every block rounded up on its own.  -> (the matrix, the
+    (start, stop) rows of every block in it, ``None`` for a ``None`` block)."""
+    spans, rows = [], 0
     for b in blocks:
-        starts.append(rows)
-        rows += r4(b.shape[0]) if pad_each else b.shape[0]
-    wp = torch.zeros((r4(rows), width), dtype=torch.float32, device=device)
-    for r, b in zip(starts, blocks):
-        wp[r:r + b.shape[0], :b.shape[1]] = b
-    return wp
+        if b is None:
+            spans.append(None)
+            continue
+        spans.append((rows, rows + b.shape[0]))
+        rows = (rows + b.shape[0] + 3) // 4 * 4 if pad_each else rows + b.shape[0]
+    wp = torch.zeros(((rows + 3) // 4 * 4, width), dtype=torch.float32, device=device)
+    for s, b in zip(spans, blocks):
+        if s is not None:
+            wp[s[0]:s[1], :b.shape[1]] = b
+    return wp, spans
+
+
+def _packed_rows(blocks, width, device, pad_each=False):
+    """``_pack``'s matrix alone."""
+    return _pack(blocks, width, device, pad_each)[0]
+
+
+def _cols(m, span):
+    """The column block ``span`` of a row buffer as a view; ``None`` for an absent block."""
+    return None if span is None else m[:, span[0]:span[1]]
 
 
 def _grad_rows(n, used, padded, device):
-    """An uninitialised float32 [n, padded] gradient row buffer with the columns outside the ``used`` (start, stop) spans -- the
-    padding the kernels never write -- zeroed."""
+    """An uninitialised float32 [n, padded] gradient row buffer with the columns outside the ``used`` (start, stop) spans (``None``
+    entries skipped) -- the padding the kernels never write -- zeroed."""
     g = torch.empty((n, padded), dtype=torch.float32, device=device)
     end = 0
-    for a, b in list(used) + [(padded, padded)]:
+    for a, b in [s for s in used if s is not None] + [(padded, padded)]:
         if a > end:
             g[:, end:a] = 0
         end = b
     return g
+
+
+def _packed_gemm(x, weights, biases=None, pad_each=False):
+    """The packed linear map every drop-in below starts with: ONE ``ops.gemm_nt`` of the padded float32 x against the weight blocks
+    ([rows_k, cin] each; a ``None`` entry is an absent block) stacked by ``_pack``.  ``biases`` is parallel to ``weights``:
+    all ``None`` (or no ``biases``) -- the GEMM gets no bias; otherwise they are packed like the weights, with a zero block where a
+    present weight has none.  -> (xp, wp, buf, spans): the padded x, the packed weight, the row buffer ``xp @ wp^T + bias`` and
+    the column span of every block in ``buf`` -- and in the gradient buffer ``_grad_rows(n, spans, wp.shape[0], device)`` that
+    ``_packed_grads`` takes -- ``None`` for an absent block (``_cols(buf, spans[k])`` is block k)."""
+    xp = _pad_cols(x.detach().to(torch.float32))
+    wp, spans = _pack([None if w is None else w.detach() for w in weights], xp.shape[1], x.device, pad_each)
+    lb = None
+    for s, b in zip(spans, biases or ()):
+        if s is not None and b is not None:
+            if lb is None:
+                lb = torch.zeros(wp.shape[0], dtype=torch.float32, device=x.device)
+            lb[s[0]:s[1]] = b.detach()
+    return xp, wp, ops.gemm_nt(xp, wp, bias=lb), spans
+
+
+def _packed_grads(g, xp, wp, spans, cin, need_w, need_b, need_x):
+    """Backward of ``_packed_gemm`` from the gradient row buffer ``g``.  ``need_w`` / ``need_b`` are parallel to ``spans``
+    (``need_b=None``: no bias gradient).  -> (dx, [dW_k], [db_k]): the column sums of the blocks whose bias wants a gradient, ONE
+    ``ops.gemm_tn`` (only when some block's weight wants a gradient; then every present block gets its ``[rows_k, cin]`` slice)
+    and ONE ``ops.gemm_nn`` (``need_x``).  ``None`` where a block is absent or nothing was asked."""
+    n = len(spans)
+    dw, db, want_w = [None] * n, [None] * n, False
+    for k, s in enumerate(spans):
+        if s is not None:
+            want_w = want_w or bool(need_w[k])
+            if need_b is not None and need_b[k]:
+                db[k] = _bias_grad(g[:, s[0]:s[1]])
+    if want_w:
+        dwp = ops.gemm_tn(g, xp)
+        dw = [None if s is None else dwp[s[0]:s[1], :cin] for s in spans]
+    dx = ops.gemm_nn(g, wp)[:, :cin] if need_x else None
+    return dx, dw, db
+
+
+def _heads_mean(y, heads, add=None):
+    """``concat=False``: the mean of y [N, heads * C] over the heads -> [N, C], then ``+ add`` (the bias or the skip) if given."""
+    y = y.view(-1, heads, y.shape[1] // heads).mean(1)
+    return y if add is None else y + add
+
+
+def _heads_mean_bwd(dy, heads):
+    """Backward of ``_heads_mean``: dy [N, C] / heads, broadcast to every head -> [N, heads * C]."""
+    C = dy.shape[1]
+    return (dy / heads).unsqueeze(1).expand(-1, heads, C).reshape(-1, heads * C)
 
 
 class _Fn(torch.autograd.Function):
@@ -259,9 +165,63 @@ def _bias_param(module, bias, n, init=torch.zeros):
         module.register_parameter("bias", None)
 
 
+def _glorot_(t):
+    """PyG's 'glorot' in place: uniform(+-sqrt(6 / (fan of the last two dims)))."""
+    a = math.sqrt(6.0 / (t.shape[-2] + t.shape[-1]))
+    return t.uniform_(-a, a)
+
+
+def _reset_linear(lin):
+    """PyG ``Linear``'s default in place: uniform(+-1/sqrt(in)) on the weight and on the bias, where there is one."""
+    a = 1.0 / math.sqrt(lin.weight.shape[1])
+    lin.weight.uniform_(-a, a)
+    if getattr(lin, "bias", None) is not None:
+        lin.bias.uniform_(-a, a)
+
+
+# The refusals.  The operators differ in a few exception types and wordings (a parameter each); tests and users read the texts.
+
+def _no_tuple_channels(name, in_channels):
+    if isinstance(in_channels, (tuple, list)):
+        raise ValueError("%s: tuple in_channels (bipartite graphs) are not implemented on the HIP path" % name)
+
+
 def _no_tuple_x(name, x):
     if isinstance(x, (tuple, list)):
         raise ValueError("%s: a tuple x (bipartite graphs) is not implemented on the HIP path" % name)
+
+
+def _int_ge1(name, what, v, bool_ok=False):
+    """``v`` (``heads``, ``K``, ``dim`` ...) must be an int >= 1; ``bool_ok``: GATConv and ChebConv let a bool through."""
+    if not isinstance(v, int) or (isinstance(v, bool) and not bool_ok) or v < 1:
+        raise ValueError("%s: %s must be an integer >= 1, got %r" % (name, what, v))
+
+
+def _not_implemented(name, **args):
+    """``ValueError`` for the first of the PyG arguments ``args``, in the order given, that is not None."""
+    for arg, v in args.items():
+        if v is not None:
+            what = "edge_dim (edge features)" if arg == "edge_dim" else arg
+            raise ValueError("%s: %s is not implemented on the HIP path" % (name, what))
+
+
+def _no_attention_dropout(name, module):
+    if module.dropout != 0.0 and module.training:
+        raise ValueError("%s: attention dropout in training mode is not implemented on the HIP path (dropout=%g)" % (name, module.dropout))
+
+
+def _check_aggr(name, aggr, allowed, kwargs, resgated=False):
+    """``aggr`` must be one of ``allowed``, and nothing may be left in the constructor's ``kwargs``.  ``resgated``:
+    ResGatedGraphConv's own wording, and a ``ValueError`` for stray arguments where the others raise ``TypeError``."""
+    if aggr not in allowed:
+        if resgated:
+            raise ValueError("%s: aggr must be %r on the HIP path, got %r" % (name, allowed[0], aggr))
+        which = " and ".join("aggr=%r" % a for a in allowed) + (" is" if len(allowed) == 1 else " are")
+        raise ValueError("%s: only %s implemented on the HIP path, got %r" % (name, which, aggr))
+    if kwargs and resgated:
+        raise ValueError("%s: unsupported arguments %s" % (name, sorted(kwargs)))
+    if kwargs:
+        raise TypeError("%s: unexpected keyword arguments %s" % (name, sorted(kwargs)))
 
 
 def _check_x(name, x, in_channels, bf16=True):
@@ -272,9 +232,27 @@ def _check_x(name, x, in_channels, bf16=True):
         raise ValueError("%s: expected x of shape [N, %d]" % (name, in_channels))
 
 
-def _need_gpu(name, x):
-    if not x.is_cuda:
-        raise ops.DdmpError("%s runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback" % name)
+def _need_gpu(name, x, edge_attr=None, exc=None):
+    """x (and ``edge_attr``, where the operator takes one) must be on the GPU.  ``exc``: ``ops.DdmpError`` unless given (GATv2Conv,
+    TransformerConv and ResGatedGraphConv raise ``ValueError``)."""
+    if x.is_cuda and (edge_attr is None or edge_attr.is_cuda):
+        return
+    what = "x must be a CUDA (ROCm) tensor" if edge_attr is None else "x and edge_attr must be CUDA (ROCm) tensors"
+    raise (exc or ops.DdmpError)("%s runs on the HIP path only: %s, there is no CPU fallback" % (name, what))
+
+
+def _check_pseudo(name, x, edge_attr, n_edges, dim, no_grad=False):
+    """GMMConv's and SplineConv's refusals for the pseudo-coordinates ``edge_attr`` [E, dim], then the GPU requirement on both
+    tensors.  ``no_grad``: SplineConv has no gradient with respect to them."""
+    if not isinstance(edge_attr, torch.Tensor):
+        raise ValueError("%s: edge_attr (the pseudo-coordinates, [E, %d]) is required" % (name, dim))
+    if edge_attr.dim() != 2 or tuple(edge_attr.shape) != (n_edges, dim):
+        raise ValueError("%s: edge_attr must be [%d, %d], got %s" % (name, n_edges, dim, tuple(edge_attr.shape)))
+    if edge_attr.dtype not in (torch.float32, torch.float64):
+        raise ValueError("%s: edge_attr must be float32 or float64, got %s" % (name, edge_attr.dtype))
+    if no_grad and edge_attr.requires_grad:
+        raise ValueError("%s: the gradient with respect to edge_attr is not implemented on the HIP path: pass edge_attr.detach()" % name)
+    _need_gpu(name, x, edge_attr)
 
 
 class _GCNConvFn(_Fn):
@@ -400,6 +378,13 @@ class _Lin(nn.Module):
 
 
 class GCNConv(nn.Module):
+    """``torch_geometric.nn.GCNConv`` 2.2.0 on the HIP kernels: same constructor / call signature, parameter names and
+    initialisation, with the defaults the reference uses (``util/networks.py:15-26``: ``GCNConv(in_channels, out_channels)``;
+    ``:51-62``: ``conv(x, edge_index)``): ``lin.weight`` [out, in] Glorot-uniform, ``bias`` [out] zeros,
+    ``Y = D^-1/2 (A + I) D^-1/2 (X W^T) + b``, differentiable w.r.t. x, weight and bias.  The normalised graph is built once per
+    ``edge_index`` tensor (cached on its storage + version) instead of on every call; aggregation runs on min(in, out) channels.
+    The other options and ``edge_weight``: the module docstring."""
+
     def __init__(self, in_channels: int, out_channels: int, improved: bool = False, cached: bool = False,
                  add_self_loops: bool = True, normalize: bool = True, bias: bool = True):
         super().__init__()
@@ -410,9 +395,8 @@ class GCNConv(nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        a = math.sqrt(6.0 / (self.in_channels + self.out_channels))     # PyG 'glorot'
         with torch.no_grad():
-            self.lin.weight.uniform_(-a, a)
+            _glorot_(self.lin.weight)
             if self.bias is not None:
                 self.bias.zero_()
 
@@ -501,10 +485,16 @@ class _ChebConvFn(_Fn):
 
 
 class ChebConv(nn.Module):
+    """``torch_geometric.nn.ChebConv`` 2.2.0 on the HIP kernels, ``ChebConv(in_channels, out_channels, K,
+    normalization="sym", bias=True)``: parameters ``lins.0.weight`` ... ``lins.{K-1}.weight`` [out, in] Glorot-uniform and ``bias``
+    [out] zeros, ``forward(x, edge_index, edge_weight=None, batch=None, lambda_max=None)`` with ``lambda_max`` a float (default
+    2.0), ``Y = sum_k T_k W_k^T + b``, ``T_0 = X``, ``T_1 = L^ X``, ``T_k = 2 L^ T_{k-1} - T_{k-2}``,
+    ``L^ = -(2 / lambda_max) D^-1/2 A D^-1/2 + (2 / lambda_max - 1) I`` (no self loops; symmetric ``edge_index`` only).
+    ``batch``, a tensor ``lambda_max`` and other normalisations raise.  ``edge_weight``: the module docstring."""
+
     def __init__(self, in_channels: int, out_channels: int, K: int, normalization: str = "sym", bias: bool = True):
         super().__init__()
-        if not isinstance(K, int) or K < 1:
-            raise ValueError("ChebConv: K must be an integer >= 1, got %r" % (K,))
+        _int_ge1("ChebConv", "K", K, bool_ok=True)
         if normalization != "sym":
             raise ValueError("ChebConv: only normalization='sym' is implemented on the HIP path, got %r" % (normalization,))
         self.in_channels, self.out_channels, self.K, self.normalization = in_channels, out_channels, K, normalization
@@ -513,17 +503,15 @@ class ChebConv(nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        a = math.sqrt(6.0 / (self.in_channels + self.out_channels))     # PyG 'glorot'
         with torch.no_grad():
             for lin in self.lins:
-                lin.weight.uniform_(-a, a)
+                _glorot_(lin.weight)
             if self.bias is not None:
                 self.bias.zero_()
 
     def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_weight=None, batch=None, lambda_max=None) -> torch.Tensor:
         """``edge_index`` must be symmetric (both directions of every edge present)."""
-        if batch is not None:
-            raise ValueError("ChebConv: batch is not implemented on the HIP path")
+        _not_implemented("ChebConv", batch=batch)
         if edge_weight is not None:
             ops.check_edge_weight(edge_weight, edge_index.shape[1])
             if edge_weight.requires_grad:
@@ -552,7 +540,7 @@ class _GATConvFn(_Fn):
     """Hf = X W^T (GEMM), the scores, then ONE launch for edge softmax + gather (``ops.gat_fwd``).  Saved: the padded x and weight,
     Hf, the scores and alpha [entries, heads].  Backward: the edge-side launch (ds per entry, ds_dst per node), the node-side launch
     (dHf completely, ds_src), the attention-vector reduction, then the two GEMMs of the linear map.  ``concat=False``: the mean
-    over heads and its broadcast backward are torch ops around the kernels."""
+    over heads and its broadcast backward are torch ops around the kernels (``_heads_mean``)."""
 
     @staticmethod
     def forward(ctx, x, weight, att_src, att_dst, bias, graph, heads, concat, slope):
@@ -567,9 +555,7 @@ class _GATConvFn(_Fn):
         b = None if bias is None else bias.detach().contiguous()
         y, alpha = ops.gat_fwd(graph, hf, s_src, s_dst, heads, slope, bias=b if concat else None)
         if not concat:
-            y = y.view(-1, heads, C).mean(1)
-            if b is not None:
-                y = y + b
+            y = _heads_mean(y, heads, b)
         ctx.save_for_backward(xp, wp, hf, s_src, s_dst, alpha, asrc, adst)
         ctx.graph, ctx.dims, ctx.has_bias = graph, (cin, heads, C, concat, slope), bias is not None
         return y
@@ -583,7 +569,7 @@ class _GATConvFn(_Fn):
         db = None
         if ctx.has_bias and ctx.needs_input_grad[4]:
             db = _bias_grad(dy)
-        dout = dy if concat else (dy / heads).unsqueeze(1).expand(-1, heads, C).reshape(-1, hc)
+        dout = dy if concat else _heads_mean_bwd(dy, heads)
         ds, ds_dst = ops.gat_bwd_edge(graph, dout, hf, s_src, s_dst, alpha, heads, slope)
         dhf, ds_src = ops.gat_bwd_node(graph, dout, alpha, ds, ds_dst, asrc, adst, heads)
         datt_src = datt_dst = None
@@ -597,15 +583,35 @@ class _GATConvFn(_Fn):
 
 
 class GATConv(nn.Module):
+    """``torch_geometric.nn.GATConv`` 2.2.0 on the HIP kernels, ``GATConv(in_channels, out_channels, heads=1,
+    concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True, edge_dim=None, fill_value="mean", bias=True)``,
+    ``forward(x, edge_index, edge_attr=None, size=None, return_attention_weights=None)`` (written from the published source from
+    memory -- PyG cannot be installed here, so this could not be checked against it; the pin is the float64 restatement
+    ``tests/gat_ref.py``):
+
+    * parameters ``lin_src.weight`` [heads * out, in] Glorot-uniform (``a = sqrt(6 / (in + heads * out))``); ``lin_dst`` IS
+      ``lin_src`` (``in_channels`` is an int), so ``state_dict()`` carries both keys and ``parameters()`` yields the weight once;
+      ``att_src`` / ``att_dst`` [1, heads, out] Glorot (``a = sqrt(6 / (heads + out))``); ``bias`` zeros, [heads * out] when
+      ``concat``, else [out].
+    * ``Hf = x lin_src.weight^T`` viewed [N, heads, C]; ``s_src[j,h] = sum_c Hf[j,h,c] att_src[h,c]``, ``s_dst`` likewise; with
+      ``add_self_loops`` explicit self loops are removed and every node gets exactly one loop; for an edge j -> i
+      ``z = leaky_relu(s_src[j,h] + s_dst[i,h], negative_slope)``; ``alpha`` = softmax of z over ALL edges with target i, per head
+      (duplicate edges each take part); ``out[i,h,:] = sum alpha Hf[j,h,:]``; ``concat``: [N, heads * C], else the mean over heads;
+      the bias is added last.  A node without incoming entries (``add_self_loops=False`` only) gets a zero aggregate plus bias.
+    * one launch for scores, one for edge softmax + gather (``ops.gat_fwd``), two for the backward of the graph part
+      (``ops.gat_bwd_edge`` / ``ops.gat_bwd_node``), a two-stage reduction for the attention vectors; the dense part goes through
+      the GEMMs.  The graph is ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=...)``: the coalesced structure whose
+      per-entry multiplicity weighs the softmax terms -- exact for duplicate edges.  Symmetric edge STRUCTURE only.
+    * differentiable w.r.t. x, ``lin_src.weight``, ``att_src``, ``att_dst`` and ``bias``; float32, bitwise reproducible.
+    * refused with ``ValueError`` before any launch: ``dropout != 0`` in training mode, ``edge_dim`` / ``edge_attr``, tuple
+      ``in_channels`` or a tuple ``x`` (bipartite), ``size``, ``return_attention_weights``, bf16 features."""
+
     def __init__(self, in_channels, out_channels: int, heads: int = 1, concat: bool = True, negative_slope: float = 0.2,
                  dropout: float = 0.0, add_self_loops: bool = True, edge_dim=None, fill_value="mean", bias: bool = True):
         super().__init__()
-        if isinstance(in_channels, (tuple, list)):
-            raise ValueError("GATConv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
-        if edge_dim is not None:
-            raise ValueError("GATConv: edge_dim (edge features) is not implemented on the HIP path")
-        if not isinstance(heads, int) or heads < 1:
-            raise ValueError("GATConv: heads must be an integer >= 1, got %r" % (heads,))
+        _no_tuple_channels("GATConv", in_channels)
+        _not_implemented("GATConv", edge_dim=edge_dim)
+        _int_ge1("GATConv", "heads", heads, bool_ok=True)
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
         self.concat, self.negative_slope, self.dropout = bool(concat), float(negative_slope), float(dropout)
         self.add_self_loops, self.edge_dim, self.fill_value = bool(add_self_loops), None, fill_value
@@ -617,26 +623,18 @@ class GATConv(nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        a = math.sqrt(6.0 / (self.in_channels + self.heads * self.out_channels))     # PyG 'glorot': fan of the last two dims
-        b = math.sqrt(6.0 / (self.heads + self.out_channels))
         with torch.no_grad():
-            self.lin_src.weight.uniform_(-a, a)
-            self.att_src.uniform_(-b, b)
-            self.att_dst.uniform_(-b, b)
+            _glorot_(self.lin_src.weight)
+            _glorot_(self.att_src)
+            _glorot_(self.att_dst)
             if self.bias is not None:
                 self.bias.zero_()
 
     def forward(self, x, edge_index, edge_attr=None, size=None, return_attention_weights=None) -> torch.Tensor:
         """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
         _no_tuple_x("GATConv", x)
-        if edge_attr is not None:
-            raise ValueError("GATConv: edge_attr is not implemented on the HIP path")
-        if size is not None:
-            raise ValueError("GATConv: size is not implemented on the HIP path")
-        if return_attention_weights is not None:
-            raise ValueError("GATConv: return_attention_weights is not implemented on the HIP path")
-        if self.dropout != 0.0 and self.training:
-            raise ValueError("GATConv: attention dropout in training mode is not implemented on the HIP path (dropout=%g)" % self.dropout)
+        _not_implemented("GATConv", edge_attr=edge_attr, size=size, return_attention_weights=return_attention_weights)
+        _no_attention_dropout("GATConv", self)
         _check_x("GATConv", x, self.in_channels)
         _need_gpu("GATConv", x)
         with ops.on_device(x):
@@ -659,59 +657,35 @@ class _GATv2ConvFn(_Fn):
 
     @staticmethod
     def forward(ctx, x, wl, bl, wr, br, att, bias, graph, heads, concat, slope):
-        cin, hc = wl.shape[1], wl.shape[0]
-        C = hc // heads
-        share = wr is None
-        xp = _pad_cols(x.detach().to(torch.float32))
-        wp = _packed_rows((wl.detach(), None if share else wr.detach()), xp.shape[1], x.device)
-        lb = None
-        if bl is not None:
-            lb = _packed_rows((bl.detach().view(-1, 1), None if share else br.detach().view(-1, 1)), 1, x.device).view(-1)
-        buf = ops.gemm_nt(xp, wp, bias=lb)                       # [N, hc or 2 hc, rounded up to 4]: Xl | Xr | zero padding
-        xl = buf[:, :hc]
-        xr = xl if share else buf[:, hc:2 * hc]
-        a = att.detach().reshape(heads, C).contiguous()
+        xp, wp, buf, spans = _packed_gemm(x, (wl, wr), (bl, br))   # buf [N, hc or 2 hc, rounded up to 4]: Xl | Xr | zero padding
+        xl = _cols(buf, spans[0])
+        xr = xl if wr is None else _cols(buf, spans[1])
+        a = att.detach().reshape(heads, wl.shape[0] // heads).contiguous()
         b = None if bias is None else bias.detach().contiguous()
         y, alpha = ops.gatv2_fwd(graph, xl, xr, a, heads, slope, bias=b if concat else None)
         if not concat:
-            y = y.view(-1, heads, C).mean(1)
-            if b is not None:
-                y = y + b
+            y = _heads_mean(y, heads, b)
         ctx.save_for_backward(xp, wp, buf, alpha, a)
-        ctx.graph, ctx.dims = graph, (cin, heads, C, concat, slope, share)
-        ctx.has_bias, ctx.has_lin_bias = bias is not None, bl is not None
+        ctx.graph, ctx.spans, ctx.dims = graph, spans, (wl.shape[1], heads, concat, slope)
         return y
 
     @staticmethod
     def _backward(ctx, dy):
         xp, wp, buf, alpha, a = ctx.saved_tensors
-        graph, (cin, heads, C, concat, slope, share) = ctx.graph, ctx.dims
-        hc = heads * C
-        wt = hc if share else 2 * hc
+        graph, (sl, sr), (cin, heads, concat, slope) = ctx.graph, ctx.spans, ctx.dims
         need = ctx.needs_input_grad
         dy = dy.contiguous().to(torch.float32)
-        db = _bias_grad(dy) if ctx.has_bias and need[6] else None
-        dout = dy if concat else (dy / heads).unsqueeze(1).expand(-1, heads, C).reshape(-1, hc)
-        xl = buf[:, :hc]
-        xr = xl if share else buf[:, hc:2 * hc]
-        g = _grad_rows(dy.shape[0], [(0, wt)], wp.shape[0], dy.device)         # [dXl | dXr | 0]
-        dz, dxr, part = ops.gatv2_bwd_edge(graph, dout, xl, xr, a, alpha, heads, slope, out=None if share else g[:, hc:wt],
-                                           want_datt=need[5])
-        ops.gatv2_bwd_node(graph, dout, xl, xr, a, alpha, dz, heads, slope, out=g[:, :hc])
-        if share:
-            g[:, :hc] += dxr
-        datt = ops.gatv2_datt(part, heads).view(1, heads, C) if need[5] else None
-        dbl = dbr = None
-        if ctx.has_lin_bias and need[2]:
-            dbl = _bias_grad(g[:, :hc])
-        if ctx.has_lin_bias and not share and need[4]:
-            dbr = _bias_grad(g[:, hc:wt])
-        dwl = dwr = None
-        if need[1] or (not share and need[3]):
-            dwp = ops.gemm_tn(g, xp)                             # [dW_l ; dW_r]
-            dwl = dwp[:hc, :cin]
-            dwr = None if share else dwp[hc:wt, :cin]
-        dx = ops.gemm_nn(g, wp)[:, :cin] if need[0] else None
+        db = _bias_grad(dy) if need[6] else None
+        dout = dy if concat else _heads_mean_bwd(dy, heads)
+        xl = _cols(buf, sl)
+        xr = xl if sr is None else _cols(buf, sr)
+        g = _grad_rows(dy.shape[0], ctx.spans, wp.shape[0], dy.device)         # [dXl | dXr | 0]
+        dz, dxr, part = ops.gatv2_bwd_edge(graph, dout, xl, xr, a, alpha, heads, slope, out=_cols(g, sr), want_datt=need[5])
+        ops.gatv2_bwd_node(graph, dout, xl, xr, a, alpha, dz, heads, slope, out=_cols(g, sl))
+        if sr is None:                                           # share_weights: Xr is Xl
+            g[:, :sl[1]] += dxr
+        datt = ops.gatv2_datt(part, heads).view(1, heads, -1) if need[5] else None
+        dx, (dwl, dwr), (dbl, dbr) = _packed_grads(g, xp, wp, ctx.spans, cin, (need[1], need[3]), (need[2], need[4]), need[0])
         return dx, dwl, dbl, dwr, dbr, datt, db, None, None, None, None
 
 
@@ -744,12 +718,9 @@ class GATv2Conv(nn.Module):
                  dropout: float = 0.0, add_self_loops: bool = True, edge_dim=None, fill_value="mean", bias: bool = True,
                  share_weights: bool = False):
         super().__init__()
-        if isinstance(in_channels, (tuple, list)):
-            raise ValueError("GATv2Conv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
-        if edge_dim is not None:
-            raise ValueError("GATv2Conv: edge_dim (edge features) is not implemented on the HIP path")
-        if not isinstance(heads, int) or isinstance(heads, bool) or heads < 1:
-            raise ValueError("GATv2Conv: heads must be an integer >= 1, got %r" % (heads,))
+        _no_tuple_channels("GATv2Conv", in_channels)
+        _not_implemented("GATv2Conv", edge_dim=edge_dim)
+        _int_ge1("GATv2Conv", "heads", heads)
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
         self.concat, self.negative_slope, self.dropout = bool(concat), float(negative_slope), float(dropout)
         self.add_self_loops, self.edge_dim, self.fill_value = bool(add_self_loops), None, fill_value
@@ -761,32 +732,23 @@ class GATv2Conv(nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        a = math.sqrt(6.0 / (self.in_channels + self.heads * self.out_channels))     # PyG 'glorot': fan of the last two dims
-        b = math.sqrt(6.0 / (self.heads + self.out_channels))
         c = 1.0 / math.sqrt(self.in_channels)
         with torch.no_grad():
             for lin in (self.lin_l,) if self.share_weights else (self.lin_l, self.lin_r):
-                lin.weight.uniform_(-a, a)
+                _glorot_(lin.weight)
                 if lin.bias is not None:
                     lin.bias.uniform_(-c, c)
-            self.att.uniform_(-b, b)
+            _glorot_(self.att)
             if self.bias is not None:
                 self.bias.zero_()
 
     def forward(self, x, edge_index, edge_attr=None, size=None, return_attention_weights=None) -> torch.Tensor:
         """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
         _no_tuple_x("GATv2Conv", x)
-        if edge_attr is not None:
-            raise ValueError("GATv2Conv: edge_attr is not implemented on the HIP path")
-        if size is not None:
-            raise ValueError("GATv2Conv: size is not implemented on the HIP path")
-        if return_attention_weights is not None:
-            raise ValueError("GATv2Conv: return_attention_weights is not implemented on the HIP path")
-        if self.dropout != 0.0 and self.training:
-            raise ValueError("GATv2Conv: attention dropout in training mode is not implemented on the HIP path (dropout=%g)" % self.dropout)
+        _not_implemented("GATv2Conv", edge_attr=edge_attr, size=size, return_attention_weights=return_attention_weights)
+        _no_attention_dropout("GATv2Conv", self)
         _check_x("GATv2Conv", x, self.in_channels)
-        if not x.is_cuda:
-            raise ValueError("GATv2Conv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        _need_gpu("GATv2Conv", x, exc=ValueError)
         share = self.share_weights
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=self.add_self_loops)
@@ -811,77 +773,53 @@ class _TransformerConvFn(_Fn):
 
     @staticmethod
     def forward(ctx, x, wq, bq, wk, bk, wv, bv, ws, bs, graph, heads, concat, beta):
-        cin, hc = wq.shape[1], wq.shape[0]
-        C = hc // heads
-        sw = 0 if ws is None else ws.shape[0]                    # the skip block: hc wide when concat, else C; absent without root
-        wt = 3 * hc + sw
-        xp = _pad_cols(x.detach().to(torch.float32))
-        wp = _packed_rows((wq.detach(), wk.detach(), wv.detach(), None if ws is None else ws.detach()), xp.shape[1], x.device)
-        col = lambda b: b.detach().view(-1, 1)
-        sb = None
-        if ws is not None:
-            sb = torch.zeros((sw, 1), dtype=torch.float32, device=x.device) if bs is None else col(bs)
-        lb = _packed_rows((col(bq), col(bk), col(bv), sb), 1, x.device).view(-1)
-        buf = ops.gemm_nt(xp, wp, bias=lb)                       # [N, wt rounded up to 4]: Q | K | V | S | zero padding
-        q, k, v = buf[:, :hc], buf[:, hc:2 * hc], buf[:, 2 * hc:3 * hc]
-        s = buf[:, 3 * hc:wt] if sw else None
-        fused_skip = bool(concat and sw and not beta)
+        # buf [N, 3 hc + the skip's width (hc when concat, else C; absent without root), rounded up to 4]: Q | K | V | S | zero padding
+        xp, wp, buf, spans = _packed_gemm(x, (wq, wk, wv, ws), (bq, bk, bv, bs))
+        q, k, v, s = (_cols(buf, sp) for sp in spans)
+        fused_skip = bool(concat and s is not None and not beta)
         y, alpha = ops.tconv_fwd(graph, q, k, v, heads, skip=s if fused_skip else None)
         if not concat:
-            y = y.view(-1, heads, C).mean(1)
-            if sw and not beta:
-                y = y + s
+            y = _heads_mean(y, heads, None if beta else s)
         ctx.save_for_backward(xp, wp, buf, alpha)
-        ctx.graph, ctx.dims = graph, (cin, heads, C, sw, concat, beta, fused_skip)
-        ctx.has_skip_bias = bs is not None
+        ctx.graph, ctx.spans, ctx.dims = graph, spans, (wq.shape[1], heads, concat, beta, fused_skip)
         return (y, s) if beta else y
 
     @staticmethod
     def _backward(ctx, dy, dxr=None):
         xp, wp, buf, alpha = ctx.saved_tensors
-        graph, (cin, heads, C, sw, concat, beta, fused_skip) = ctx.graph, ctx.dims
-        hc = heads * C
-        wt = 3 * hc + sw
+        graph, spans, (cin, heads, concat, beta, fused_skip) = ctx.graph, ctx.spans, ctx.dims
         need = ctx.needs_input_grad
         dy = dy.contiguous().to(torch.float32)
-        dout = dy if concat else (dy / heads).unsqueeze(1).expand(-1, heads, C).reshape(-1, hc)
-        q, k, v = buf[:, :hc], buf[:, hc:2 * hc], buf[:, 2 * hc:3 * hc]
-        g = _grad_rows(dy.shape[0], [(0, wt)], wp.shape[0], dy.device)         # [dQ | dK | dV | dS | 0]
-        dz, _ = ops.tconv_bwd_edge(graph, dout, k, v, alpha, heads, out=g[:, :hc])
-        ops.tconv_bwd_node(graph, dout, q, alpha, dz, heads, out_k=g[:, hc:2 * hc], out_v=g[:, 2 * hc:3 * hc],
-                           out_s=g[:, 3 * hc:wt] if fused_skip else None)
-        if sw and not fused_skip:
-            g[:, 3 * hc:wt] = dxr.to(torch.float32) if beta else dy
-        dbq = _bias_grad(g[:, :hc]) if need[2] else None
-        dbk = _bias_grad(g[:, hc:2 * hc]) if need[4] else None
-        dbv = _bias_grad(g[:, 2 * hc:3 * hc]) if need[6] else None
-        dbs = _bias_grad(g[:, 3 * hc:wt]) if sw and ctx.has_skip_bias and need[8] else None
-        dwq = dwk = dwv = dws = None
-        if need[1] or need[3] or need[5] or (sw and need[7]):
-            dwp = ops.gemm_tn(g, xp)                             # [dW_q ; dW_k ; dW_v ; dW_s]
-            dwq, dwk, dwv = dwp[:hc, :cin], dwp[hc:2 * hc, :cin], dwp[2 * hc:3 * hc, :cin]
-            dws = dwp[3 * hc:wt, :cin] if sw else None
-        dx = ops.gemm_nn(g, wp)[:, :cin] if need[0] else None
+        dout = dy if concat else _heads_mean_bwd(dy, heads)
+        q, k, v, _ = (_cols(buf, sp) for sp in spans)
+        g = _grad_rows(dy.shape[0], spans, wp.shape[0], dy.device)             # [dQ | dK | dV | dS | 0]
+        gq, gk, gv, gs = (_cols(g, sp) for sp in spans)
+        dz, _ = ops.tconv_bwd_edge(graph, dout, k, v, alpha, heads, out=gq)
+        ops.tconv_bwd_node(graph, dout, q, alpha, dz, heads, out_k=gk, out_v=gv, out_s=gs if fused_skip else None)
+        if gs is not None and not fused_skip:
+            gs.copy_(dxr.to(torch.float32) if beta else dy)
+        dx, (dwq, dwk, dwv, dws), (dbq, dbk, dbv, dbs) = _packed_grads(g, xp, wp, spans, cin, need[1:8:2], need[2:9:2], need[0])
         return dx, dwq, dbq, dwk, dbk, dwv, dbv, dws, dbs, None, None, None, None
 
 
 class TransformerConv(nn.Module):
     """``torch_geometric.nn.TransformerConv`` 2.2.0 (Shi et al., "Masked Label Prediction", IJCAI 2021) on the HIP kernels
     (restated from the published source from memory -- PyG cannot be installed here, so this could not be checked
-    against it; the pin is the float64 restatement ``tests/transformer_ref.py``).
+    against it; the pin is the float64 restatement ``tests/transformer_ref.py``).  It is the one operator here whose scored
+    stream (K) differs from its gathered stream (V).
 
     * parameters ``lin_key`` / ``lin_query`` / ``lin_value``: ``weight`` [heads * out, in] and ``bias`` [heads * out] (always
       present); ``lin_skip``: ``weight`` [heads * out, in] when ``concat``, else [out, in], its ``bias`` only with ``bias=True`` (the
       module exists whatever ``root_weight`` says); ``lin_beta.weight`` [1, 3 * heads * out] when ``concat``, else [1, 3 * out],
-      no bias, only with ``beta=True`` (else registered as None); ``lin_edge`` is registered as None.  Everything is
-      uniform(-1/sqrt(in), 1/sqrt(in)) with "in" the layer's own input width.
+      no bias, only with ``beta=True`` and ``root_weight=True`` (else registered as None); ``lin_edge`` is registered as None.
+      Everything is uniform(-1/sqrt(in), 1/sqrt(in)) with "in" the layer's own input width.
     * ``Q = lin_query(x)``, ``K = lin_key(x)``, ``V = lin_value(x)`` viewed [N, heads, C]; for an edge j -> i
       ``z[h] = Q[i,h,:] . K[j,h,:] / sqrt(C)``; ``alpha`` = softmax of z over ALL edges with target i, per head (duplicate edges
       each take part); ``m[i,h,:] = sum alpha V[j,h,:]``; ``concat``: [N, heads * C], else the mean over heads.  No self loops are
       added, an explicit loop is an ordinary edge, a node without incoming edges has ``m = 0``.
     * ``root_weight``: ``x_r = lin_skip(x)``; ``out = m + x_r``, or with ``beta``
       ``b = sigmoid(lin_beta(cat[m, x_r, m - x_r]))`` (one scalar per node) and ``out = b x_r + (1 - b) m``.  The gate is torch
-      elementwise ops on [N, .] tensors; no per-edge tensor exists at any point.
+      elementwise ops on [N, .] tensors; no per-edge tensor and no ``index_add_`` exist at any point.
     * differentiable w.r.t. x and every parameter in use; float32, bitwise reproducible.  The graph is EdgeConv's and GMMConv's:
       ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric edge STRUCTURE only.
     * refused with ``ValueError`` before any launch: ``edge_dim`` / ``edge_attr``, ``dropout != 0`` in training mode, tuple
@@ -891,12 +829,9 @@ class TransformerConv(nn.Module):
     def __init__(self, in_channels, out_channels: int, heads: int = 1, concat: bool = True, beta: bool = False,
                  dropout: float = 0.0, edge_dim=None, bias: bool = True, root_weight: bool = True):
         super().__init__()
-        if isinstance(in_channels, (tuple, list)):
-            raise ValueError("TransformerConv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
-        if edge_dim is not None:
-            raise ValueError("TransformerConv: edge_dim (edge features) is not implemented on the HIP path")
-        if not isinstance(heads, int) or isinstance(heads, bool) or heads < 1:
-            raise ValueError("TransformerConv: heads must be an integer >= 1, got %r" % (heads,))
+        _no_tuple_channels("TransformerConv", in_channels)
+        _not_implemented("TransformerConv", edge_dim=edge_dim)
+        _int_ge1("TransformerConv", "heads", heads)
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
         self.concat, self.root_weight, self.dropout, self.edge_dim = bool(concat), bool(root_weight), float(dropout), None
         self.beta = bool(beta) and self.root_weight
@@ -916,26 +851,16 @@ class TransformerConv(nn.Module):
     def reset_parameters(self):
         with torch.no_grad():
             for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip, self.lin_beta):
-                if lin is None:
-                    continue
-                a = 1.0 / math.sqrt(lin.weight.shape[1])         # PyG ``Linear``'s default for weight and bias
-                lin.weight.uniform_(-a, a)
-                if lin.bias is not None:
-                    lin.bias.uniform_(-a, a)
+                if lin is not None:
+                    _reset_linear(lin)
 
     def forward(self, x, edge_index, edge_attr=None, return_attention_weights=None) -> torch.Tensor:
         """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
         _no_tuple_x("TransformerConv", x)
-        if edge_attr is not None:
-            raise ValueError("TransformerConv: edge_attr is not implemented on the HIP path")
-        if return_attention_weights is not None:
-            raise ValueError("TransformerConv: return_attention_weights is not implemented on the HIP path")
-        if self.dropout != 0.0 and self.training:
-            raise ValueError("TransformerConv: attention dropout in training mode is not implemented on the HIP path (dropout=%g)"
-                             % self.dropout)
+        _not_implemented("TransformerConv", edge_attr=edge_attr, return_attention_weights=return_attention_weights)
+        _no_attention_dropout("TransformerConv", self)
         _check_x("TransformerConv", x, self.in_channels)
-        if not x.is_cuda:
-            raise ValueError("TransformerConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        _need_gpu("TransformerConv", x, exc=ValueError)
         root = self.root_weight
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
@@ -964,50 +889,36 @@ class _ResGatedFn(_Fn):
 
     @staticmethod
     def forward(ctx, x, wk, bk, wq, bq, wv, bv, ws, bias, graph):
-        cin, C = wk.shape[1], wk.shape[0]
-        sw = 0 if ws is None else C
-        wt = 3 * C + sw
-        xp = _pad_cols(x.detach().to(torch.float32))
-        wp = _packed_rows((wk.detach(), wq.detach(), wv.detach(), None if ws is None else ws.detach()), xp.shape[1], x.device)
-        col = lambda b: b.detach().view(-1, 1)
-        sb = torch.zeros((sw, 1), dtype=torch.float32, device=x.device) if sw else None
-        lb = _packed_rows((col(bk), col(bq), col(bv), sb), 1, x.device).view(-1)
-        buf = ops.gemm_nt(xp, wp, bias=lb)                       # [N, wt rounded up to 4]: K | Q | V | S | zero padding
-        k, q, v = buf[:, :C], buf[:, C:2 * C], buf[:, 2 * C:3 * C]
+        xp, wp, buf, spans = _packed_gemm(x, (wk, wq, wv, ws), (bk, bq, bv, None))   # buf: K | Q | V | S | zero padding
+        k, q, v, s = (_cols(buf, sp) for sp in spans)
         b = None if bias is None else bias.detach().to(torch.float32).contiguous()
-        y = ops.rgate_fwd(graph, k, q, v, skip=buf[:, 3 * C:wt] if sw else None, bias=b)
+        y = ops.rgate_fwd(graph, k, q, v, skip=s, bias=b)
         ctx.save_for_backward(xp, wp, buf)
-        ctx.graph, ctx.dims = graph, (cin, C, sw)
+        ctx.graph, ctx.spans, ctx.cin = graph, spans, wk.shape[1]
         return y
 
     @staticmethod
     def _backward(ctx, dy):
         xp, wp, buf = ctx.saved_tensors
-        graph, (cin, C, sw) = ctx.graph, ctx.dims
-        wt = 3 * C + sw
-        need = ctx.needs_input_grad
+        graph, spans, need = ctx.graph, ctx.spans, ctx.needs_input_grad
         dy = dy.contiguous().to(torch.float32)
-        k, q, v = buf[:, :C], buf[:, C:2 * C], buf[:, 2 * C:3 * C]
-        g = _grad_rows(dy.shape[0], [(0, wt)], wp.shape[0], dy.device)         # [dK | dQ | dV | dS | 0]
-        ops.rgate_bwd_row(graph, dy, k, q, v, out=g[:, :C])
-        ops.rgate_bwd_node(graph, dy, k, q, v, out_q=g[:, C:2 * C], out_v=g[:, 2 * C:3 * C], out_s=g[:, 3 * C:wt] if sw else None)
-        dbk = _bias_grad(g[:, :C]) if need[2] else None
-        dbq = _bias_grad(g[:, C:2 * C]) if need[4] else None
-        dbv = _bias_grad(g[:, 2 * C:3 * C]) if need[6] else None
+        k, q, v, _ = (_cols(buf, sp) for sp in spans)
+        g = _grad_rows(dy.shape[0], spans, wp.shape[0], dy.device)             # [dK | dQ | dV | dS | 0]
+        gk, gq, gv, gs = (_cols(g, sp) for sp in spans)
+        ops.rgate_bwd_row(graph, dy, k, q, v, out=gk)
+        ops.rgate_bwd_node(graph, dy, k, q, v, out_q=gq, out_v=gv, out_s=gs)
+        # the lin bias gradients here, not in _packed_grads: they come before db, as they always have (same launches, same order)
+        dbk, dbq, dbv = (_bias_grad(b) if n else None for b, n in zip((gk, gq, gv), need[2:7:2]))
         db = _bias_grad(dy) if need[8] else None
-        dwk = dwq = dwv = dws = None
-        if need[1] or need[3] or need[5] or (sw and need[7]):
-            dwp = ops.gemm_tn(g, xp)                             # [dW_k ; dW_q ; dW_v ; dW_s]
-            dwk, dwq, dwv = dwp[:C, :cin], dwp[C:2 * C, :cin], dwp[2 * C:3 * C, :cin]
-            dws = dwp[3 * C:wt, :cin] if sw else None
-        dx = ops.gemm_nn(g, wp)[:, :cin] if need[0] else None
+        dx, (dwk, dwq, dwv, dws), _ = _packed_grads(g, xp, wp, spans, ctx.cin, need[1:8:2], None, need[0])
         return dx, dwk, dbk, dwq, dbq, dwv, dbv, dws, db, None
 
 
 class ResGatedGraphConv(nn.Module):
     """``torch_geometric.nn.ResGatedGraphConv`` 2.2.0 (Bresson & Laurent, "Residual Gated Graph ConvNets", 2017) on the HIP
     kernels (restated from the published source from memory -- PyG cannot be installed here, so this could not be
-    checked against it; the pin is the float64 restatement ``tests/resgated_ref.py``).
+    checked against it; the pin is the float64 restatement ``tests/resgated_ref.py``).  It is the one operator here whose edge
+    weight is as wide as the features: a per-channel gate, not a scalar per head.
 
     * parameters ``lin_key`` / ``lin_query`` / ``lin_value``: ``weight`` [out, in] and ``bias`` [out] (always present);
       ``lin_skip``: ``weight`` [out, in], no bias, registered as None with ``root_weight=False``; ``bias`` [out] zeros, registered
@@ -1015,7 +926,8 @@ class ResGatedGraphConv(nn.Module):
     * ``K = lin_key(x)``, ``Q = lin_query(x)``, ``V = lin_value(x)``; for an edge j -> i the gate is PER CHANNEL,
       ``g = sigmoid(K[i,:] + Q[j,:])``; ``out[i,:] = lin_skip(x_i) + bias + sum_{j -> i} g * V[j,:]`` (duplicate edges each
       count).  No self loops are added, an explicit loop is an ordinary edge, a node without incoming edges returns
-      ``lin_skip(x_i) + bias``.  No per-edge tensor exists at any point, in the backward either: it recomputes the gate.
+      ``lin_skip(x_i) + bias``.  No per-edge tensor and no ``index_add_`` exist at any point, in the backward either: it
+      recomputes the gate.
     * differentiable w.r.t. x and every parameter in use; float32, bitwise reproducible.  The graph is EdgeConv's and
       TransformerConv's: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric edge STRUCTURE only.
     * refused with ``ValueError`` before any launch: an ``act`` that is not a ``torch.nn.Sigmoid`` instance, ``aggr`` other than
@@ -1023,16 +935,11 @@ class ResGatedGraphConv(nn.Module):
 
     def __init__(self, in_channels, out_channels: int, act=nn.Sigmoid(), root_weight: bool = True, bias: bool = True, **kwargs):
         super().__init__()
-        if isinstance(in_channels, (tuple, list)):
-            raise ValueError("ResGatedGraphConv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
+        _no_tuple_channels("ResGatedGraphConv", in_channels)
         if not isinstance(act, nn.Sigmoid):
             raise ValueError("ResGatedGraphConv: the gate of the HIP path is the sigmoid, act must be a torch.nn.Sigmoid, got %r"
                              % (act,))
-        aggr = kwargs.pop("aggr", "add")
-        if aggr != "add":
-            raise ValueError("ResGatedGraphConv: aggr must be 'add' on the HIP path, got %r" % (aggr,))
-        if kwargs:
-            raise ValueError("ResGatedGraphConv: unsupported arguments %s" % sorted(kwargs))
+        _check_aggr("ResGatedGraphConv", kwargs.pop("aggr", "add"), ("add",), kwargs, resgated=True)
         self.in_channels, self.out_channels, self.act, self.root_weight = in_channels, out_channels, act, bool(root_weight)
         self.lin_key = _LinB(in_channels, out_channels)
         self.lin_query = _LinB(in_channels, out_channels)
@@ -1047,12 +954,8 @@ class ResGatedGraphConv(nn.Module):
     def reset_parameters(self):
         with torch.no_grad():
             for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_skip):
-                if lin is None:
-                    continue
-                a = 1.0 / math.sqrt(lin.weight.shape[1])         # PyG ``Linear``'s default for weight and bias
-                lin.weight.uniform_(-a, a)
-                if lin.bias is not None:
-                    lin.bias.uniform_(-a, a)
+                if lin is not None:
+                    _reset_linear(lin)
             if self.bias is not None:
                 self.bias.zero_()
 
@@ -1060,8 +963,7 @@ class ResGatedGraphConv(nn.Module):
         """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
         _no_tuple_x("ResGatedGraphConv", x)
         _check_x("ResGatedGraphConv", x, self.in_channels)
-        if not x.is_cuda:
-            raise ValueError("ResGatedGraphConv runs on the HIP path only: x must be a CUDA (ROCm) tensor, there is no CPU fallback")
+        _need_gpu("ResGatedGraphConv", x, exc=ValueError)
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
             return _ResGatedFn.apply(x, self.lin_key.weight, self.lin_key.bias, self.lin_query.weight, self.lin_query.bias,
@@ -1080,52 +982,56 @@ class _FeaStConvFn(_Fn):
 
     @staticmethod
     def forward(ctx, x, weight, u, c, bias, graph, heads):
-        cin, hc = weight.shape[1], weight.shape[0]
-        wt = hc + heads
-        xp = _pad_cols(x.detach().to(torch.float32))
-        wp = _packed_rows((weight.detach(), u.detach()), xp.shape[1], x.device)
-        buf = ops.gemm_nt(xp, wp)                                # [N, wt rounded up to 4]: Hf | P | zero padding
+        xp, wp, buf, spans = _packed_gemm(x, (weight, u))         # buf [N, hc + heads rounded up to 4]: Hf | P | zero padding
         b = None if bias is None else bias.detach().contiguous()
-        y, beta = ops.feast_fwd(graph, buf[:, :hc], buf[:, hc:wt], c.detach().contiguous(), heads, bias=b)
+        y, beta = ops.feast_fwd(graph, _cols(buf, spans[0]), _cols(buf, spans[1]), c.detach().contiguous(), heads, bias=b)
         ctx.save_for_backward(xp, wp, buf, beta)
-        ctx.graph, ctx.dims, ctx.has_bias = graph, (cin, heads, hc), bias is not None
+        ctx.graph, ctx.spans, ctx.dims = graph, spans, (weight.shape[1], heads)
         return y
 
     @staticmethod
     def _backward(ctx, dy):
         xp, wp, buf, beta = ctx.saved_tensors
-        graph, (cin, heads, hc) = ctx.graph, ctx.dims
-        wt, wtp = hc + heads, wp.shape[0]
+        graph, spans, (cin, heads), need = ctx.graph, ctx.spans, ctx.dims, ctx.needs_input_grad
         dy = dy.contiguous().to(torch.float32)
-        db = None
-        if ctx.has_bias and ctx.needs_input_grad[4]:
-            db = _bias_grad(dy)
-        dz, rs = ops.feast_bwd_edge(graph, dy, buf[:, :hc], beta, heads)
-        g = _grad_rows(dy.shape[0], [(0, wt)], wtp, dy.device)
+        db = _bias_grad(dy) if need[4] else None
+        dz, rs = ops.feast_bwd_edge(graph, dy, _cols(buf, spans[0]), beta, heads)
+        g = _grad_rows(dy.shape[0], spans, wp.shape[0], dy.device)
         ops.feast_bwd_node(graph, dy, beta, dz, rs, heads, out=g)          # g = [dHf | dP | 0]
-        dc = ops.feast_dc(rs, heads) if ctx.needs_input_grad[3] else None
-        dw = du = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dwp = ops.gemm_tn(g, xp)                             # [dW; dU]
-            dw, du = dwp[:hc, :cin], dwp[hc:wt, :cin]
-        dx = ops.gemm_nn(g, wp)[:, :cin] if ctx.needs_input_grad[0] else None
+        dc = ops.feast_dc(rs, heads) if need[3] else None
+        dx, (dw, du), _ = _packed_grads(g, xp, wp, spans, cin, need[1:3], None, need[0])
         return dx, dw, du, dc, db, None, None
 
 
 class FeaStConv(nn.Module):
-    """``torch_geometric.nn.FeaStConv`` 2.2.0 on the HIP kernels (module docstring)."""
+    """``torch_geometric.nn.FeaStConv`` 2.2.0 (Verma et al., FeaStNet, CVPR 2018) on the HIP kernels,
+    ``FeaStConv(in_channels, out_channels, heads=1, add_self_loops=True, bias=True)``, ``forward(x, edge_index)`` (written from the
+    published source from memory -- PyG cannot be installed here, so this could not be checked against it; the pin is the float64
+    restatement ``tests/feast_ref.py``):
+
+    * parameters ``lin.weight`` [heads * out, in] and ``u.weight`` [heads, in], both uniform(-1/sqrt(in), 1/sqrt(in)) and without
+      bias; ``c`` [heads] and ``bias`` [out] normal(0, 0.1).  The initialisations are from memory too; the arithmetic is what the
+      tests pin.
+    * ``Hf = x lin.weight^T`` viewed [N, heads, out], ``P = x u.weight^T`` [N, heads]; with ``add_self_loops`` explicit self loops
+      are removed and every node gets exactly one loop; for an edge j -> i ``q[h]`` = softmax over the HEADS of
+      ``P[j,h] - P[i,h] + c[h]`` (translation invariant in x); ``out[i,:] = (1 / deg_i) sum_{j -> i} sum_h q[h] Hf[j,h,:] + bias``
+      with ``deg_i`` the number of edges with target i (duplicates each count, the added loop counts).  A node without incoming
+      edges (``add_self_loops=False`` only) gets the bias.  With ``heads=1`` this is the plain mean of ``x lin.weight^T`` over the
+      neighbourhood.
+    * one GEMM against the packed ``[lin.weight; u.weight]`` for ``[Hf | P]``, one launch for head softmax + gather
+      (``ops.feast_fwd``), two for the backward of the graph part (``ops.feast_bwd_edge`` / ``ops.feast_bwd_node``), a two-stage
+      reduction for ``c`` (``ops.feast_dc``), one wgrad GEMM for ``[dW; dU]`` and one dgrad GEMM for ``dx``.  No [E, heads * out]
+      tensor exists at any point.  The graph is GATConv's: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=...)``, same
+      handle and cache key.  Symmetric edge STRUCTURE only.
+    * differentiable w.r.t. x, ``lin.weight``, ``u.weight``, ``c`` and ``bias``; float32, bitwise reproducible.
+    * refused with ``ValueError`` before any launch: tuple ``in_channels`` or a tuple ``x`` (bipartite), an ``aggr`` other than
+      ``"mean"``, bf16 features, ``heads < 1``, an ``x`` that is not [N, in]."""
 
     def __init__(self, in_channels, out_channels: int, heads: int = 1, add_self_loops: bool = True, bias: bool = True, **kwargs):
         super().__init__()
-        if isinstance(in_channels, (tuple, list)):
-            raise ValueError("FeaStConv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
-        aggr = kwargs.pop("aggr", "mean")
-        if aggr != "mean":
-            raise ValueError("FeaStConv: only aggr='mean' is implemented on the HIP path, got %r" % (aggr,))
-        if kwargs:
-            raise TypeError("FeaStConv: unexpected keyword arguments %s" % sorted(kwargs))
-        if not isinstance(heads, int) or isinstance(heads, bool) or heads < 1:
-            raise ValueError("FeaStConv: heads must be an integer >= 1, got %r" % (heads,))
+        _no_tuple_channels("FeaStConv", in_channels)
+        _check_aggr("FeaStConv", kwargs.pop("aggr", "mean"), ("mean",), kwargs)
+        _int_ge1("FeaStConv", "heads", heads)
         self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
         self.add_self_loops = bool(add_self_loops)
         self.lin = _Lin(in_channels, heads * out_channels)
@@ -1135,10 +1041,9 @@ class FeaStConv(nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        a = 1.0 / math.sqrt(self.in_channels)                    # (from memory of the published source, like the arithmetic)
         with torch.no_grad():
-            self.lin.weight.uniform_(-a, a)
-            self.u.weight.uniform_(-a, a)
+            _reset_linear(self.lin)                              # (from memory of the published source, like the arithmetic)
+            _reset_linear(self.u)
             self.c.normal_(0.0, 0.1)
             if self.bias is not None:
                 self.bias.normal_(0.0, 0.1)
@@ -1165,45 +1070,33 @@ class _GMMConvFn(_Fn):
 
     @staticmethod
     def forward(ctx, x, g, mu, sigma, root, bias, attr, graph, K):
-        cin, hc = g.shape
-        C = hc // K
-        wt = hc + (C if root is not None else 0)
-        xp = _pad_cols(x.detach().to(torch.float32))
-        wp = _packed_rows((g.detach().t(), None if root is None else root.detach()), xp.shape[1], x.device)
-        buf = ops.gemm_nt(xp, wp)                                # [N, wt rounded up to 4]: Hf | R | zero padding
+        xp, wp, buf, spans = _packed_gemm(x, (g.t(), root))       # buf [N, K * out (+ out) rounded up to 4]: Hf | R | zero padding
         b = None if bias is None else bias.detach().contiguous()
         a32 = attr.detach().to(torch.float32).contiguous()       # (float64 pseudo-coordinates are rounded once)
         m, s = mu.detach().contiguous(), sigma.detach().contiguous()
-        y, w = ops.gmm_fwd(graph, buf[:, :hc], a32, m, s, K, root=buf[:, hc:wt] if root is not None else None, bias=b)
+        y, w = ops.gmm_fwd(graph, _cols(buf, spans[0]), a32, m, s, K, root=_cols(buf, spans[1]), bias=b)
         ctx.save_for_backward(xp, wp, buf, w, a32, m, s)
-        ctx.graph, ctx.dims, ctx.has_bias, ctx.attr_dtype = graph, (cin, K, hc, wt), bias is not None, attr.dtype
+        ctx.graph, ctx.spans, ctx.dims, ctx.attr_dtype = graph, spans, (g.shape[0], K), attr.dtype
         return y
 
     @staticmethod
     def _backward(ctx, dy):
         xp, wp, buf, w, a32, m, s = ctx.saved_tensors
-        graph, (cin, K, hc, wt) = ctx.graph, ctx.dims
-        wtp, kd = wp.shape[0], m.numel()
+        graph, spans, (cin, K), need = ctx.graph, ctx.spans, ctx.dims, ctx.needs_input_grad
+        kd = m.numel()
         dy = dy.contiguous().to(torch.float32)
-        db = None
-        if ctx.has_bias and ctx.needs_input_grad[5]:
-            db = _bias_grad(dy)
-        parts, dattr = ops.gmm_bwd_edge(graph, dy, buf[:, :hc], a32, m, s, K, want_dattr=ctx.needs_input_grad[6])
-        gb = _grad_rows(dy.shape[0], [(0, wt)], wtp, dy.device)
-        ops.gmm_bwd_node(graph, dy, w, K, out=gb, root=wt != hc)  # gb = [dHf | dOut | 0]
+        db = _bias_grad(dy) if need[5] else None
+        parts, dattr = ops.gmm_bwd_edge(graph, dy, _cols(buf, spans[0]), a32, m, s, K, want_dattr=need[6])
+        gb = _grad_rows(dy.shape[0], spans, wp.shape[0], dy.device)
+        ops.gmm_bwd_node(graph, dy, w, K, out=gb, root=spans[1] is not None)   # gb = [dHf | dOut | 0]
         dmu = dsigma = None
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+        if need[2] or need[3]:
             dms = ops.feast_dc(parts, 2 * kd)                    # [dmu | dsigma]
             dmu, dsigma = dms[:kd].view_as(m), dms[kd:].view_as(s)
-        dg = droot = None
-        if ctx.needs_input_grad[1] or (wt != hc and ctx.needs_input_grad[4]):
-            dwp = ops.gemm_tn(gb, xp)                            # [dg^T ; droot]
-            dg = dwp[:hc, :cin].t()
-            droot = dwp[hc:wt, :cin] if wt != hc else None
-        dx = ops.gemm_nn(gb, wp)[:, :cin] if ctx.needs_input_grad[0] else None
+        dx, (dgt, droot), _ = _packed_grads(gb, xp, wp, spans, cin, (need[1], need[4]), None, need[0])   # [dg^T ; droot]
         if dattr is not None:
             dattr = dattr.to(ctx.attr_dtype)
-        return dx, dg, dmu, dsigma, droot, db, dattr, None, None
+        return dx, None if dgt is None else dgt.t(), dmu, dsigma, droot, db, dattr, None, None
 
 
 class GMMConv(nn.Module):
@@ -1215,22 +1108,28 @@ class GMMConv(nn.Module):
     ``out[i] = (1 / deg_i) sum_{t -> i} sum_k gamma_t[k] Hf[j,k,:] + root(x_i) + bias``; no self loops are added, duplicate edges
     each count, a node without incoming edges gets ``root(x_i) + bias``.  Written from the published PyG source from memory --
     PyG cannot be installed here, so this could not be checked against it; the pin is the float64 restatement
-    ``tests/gmm_ref.py``.  Differentiable w.r.t. x, every parameter, and ``edge_attr`` when it requires grad."""
+    ``tests/gmm_ref.py``.  Differentiable w.r.t. x, every parameter, and ``edge_attr`` when it requires grad.
+
+    * it is the one operator here that consumes the GEOMETRY of an edge: ``forward(x, edge_index, edge_attr, size=None)`` with
+      ``edge_attr`` the per-edge pseudo-coordinates ([E, dim]; ``cartesian_pseudo`` below restates PyG's ``Cartesian`` transform).
+      K = ``kernel_size``; an explicit loop is an ordinary edge; ``deg_i`` is the number of edges with target i.
+    * the launches: ``_GMMConvFn``.  No [E, K * out] tensor and no ``index_add_`` exist at any point.  The graph is GATConv's
+      without loops: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``, same handle and cache key; a coalesced
+      entry sums the Gaussians of its input edges in input order, so duplicate edges with different pseudo-coordinates are exact.
+      Symmetric edge STRUCTURE only.  float32, bitwise reproducible.
+    * refused with ``ValueError`` before any launch: ``separate_gaussians=True``, ``aggr != "mean"``, tuple ``in_channels`` or a
+      tuple ``x`` (bipartite), ``size``, bf16 features, ``edge_attr`` missing, not [E, dim] or not float32 / float64 (float64 is
+      rounded to float32 once), ``kernel_size < 1``, ``dim < 1``, ``2 * kernel_size * dim > 256``."""
 
     def __init__(self, in_channels, out_channels: int, dim: int, kernel_size: int, separate_gaussians: bool = False,
                  aggr: str = "mean", root_weight: bool = True, bias: bool = True, **kwargs):
         super().__init__()
-        if isinstance(in_channels, (tuple, list)):
-            raise ValueError("GMMConv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
+        _no_tuple_channels("GMMConv", in_channels)
         if separate_gaussians:
             raise ValueError("GMMConv: separate_gaussians=True is not implemented on the HIP path")
-        if aggr != "mean":
-            raise ValueError("GMMConv: only aggr='mean' is implemented on the HIP path, got %r" % (aggr,))
-        if kwargs:
-            raise TypeError("GMMConv: unexpected keyword arguments %s" % sorted(kwargs))
-        for name, v in (("kernel_size", kernel_size), ("dim", dim)):
-            if not isinstance(v, int) or isinstance(v, bool) or v < 1:
-                raise ValueError("GMMConv: %s must be an integer >= 1, got %r" % (name, v))
+        _check_aggr("GMMConv", aggr, ("mean",), kwargs)
+        _int_ge1("GMMConv", "kernel_size", kernel_size)
+        _int_ge1("GMMConv", "dim", dim)
         if 2 * kernel_size * dim > 256:
             raise ValueError("GMMConv: 2 * kernel_size * dim must be <= 256 on the HIP path (the dmu / dsigma reduction), got %d"
                              % (2 * kernel_size * dim))
@@ -1247,13 +1146,12 @@ class GMMConv(nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        glorot = lambda t: t.uniform_(-math.sqrt(6.0 / (t.shape[-2] + t.shape[-1])), math.sqrt(6.0 / (t.shape[-2] + t.shape[-1])))
         with torch.no_grad():
-            glorot(self.g)
-            glorot(self.mu)
-            glorot(self.sigma)
+            _glorot_(self.g)
+            _glorot_(self.mu)
+            _glorot_(self.sigma)
             if self.root is not None:
-                glorot(self.root.weight)
+                _glorot_(self.root.weight)
             if self.bias is not None:
                 self.bias.zero_()
 
@@ -1261,18 +1159,9 @@ class GMMConv(nn.Module):
         """``edge_index`` must have a symmetric structure (both directions of every edge present); ``edge_attr``: [E, dim]
         pseudo-coordinates, float32 or float64 (rounded to float32 once)."""
         _no_tuple_x("GMMConv", x)
-        if size is not None:
-            raise ValueError("GMMConv: size is not implemented on the HIP path")
+        _not_implemented("GMMConv", size=size)
         _check_x("GMMConv", x, self.in_channels)
-        if not isinstance(edge_attr, torch.Tensor):
-            raise ValueError("GMMConv: edge_attr (the pseudo-coordinates, [E, %d]) is required" % self.dim)
-        if edge_attr.dim() != 2 or tuple(edge_attr.shape) != (edge_index.shape[1], self.dim):
-            raise ValueError("GMMConv: edge_attr must be [%d, %d], got %s" % (edge_index.shape[1], self.dim, tuple(edge_attr.shape)))
-        if edge_attr.dtype not in (torch.float32, torch.float64):
-            raise ValueError("GMMConv: edge_attr must be float32 or float64, got %s" % edge_attr.dtype)
-        if not x.is_cuda or not edge_attr.is_cuda:
-            raise ops.DdmpError("GMMConv runs on the HIP path only: x and edge_attr must be CUDA (ROCm) tensors, there is no CPU "
-                                "fallback")
+        _check_pseudo("GMMConv", x, edge_attr, edge_index.shape[1], self.dim)
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
             return _GMMConvFn.apply(x, self.g, self.mu, self.sigma, None if self.root is None else self.root.weight, self.bias,
@@ -1305,44 +1194,31 @@ class _SplineConvFn(_Fn):
     @staticmethod
     def forward(ctx, x, weight, root, bias, attr, graph, kernel_size, is_open, mean):
         K, cin, C = weight.shape
-        hc = K * C
-        wt = hc + (C if root is not None else 0)
-        xp = _pad_cols(x.detach().to(torch.float32))
-        wp = _packed_rows((weight.detach().permute(0, 2, 1).reshape(hc, cin), None if root is None else root.detach()),
-                          xp.shape[1], x.device)
-        buf = ops.gemm_nt(xp, wp)                                # [N, wt rounded up to 4]: Hf | R | zero padding
+        # buf [N, K * out (+ out) rounded up to 4]: Hf | R | zero padding
+        xp, wp, buf, spans = _packed_gemm(x, (weight.permute(0, 2, 1).reshape(K * C, cin), root))
         b = None if bias is None else bias.detach().contiguous()
         a32 = attr.detach().to(torch.float32).contiguous()       # (float64 pseudo-coordinates are rounded once)
-        y = ops.spline_fwd(graph, buf[:, :hc], a32, kernel_size, is_open, root=buf[:, hc:wt] if root is not None else None, bias=b,
-                           mean=mean)
+        y = ops.spline_fwd(graph, _cols(buf, spans[0]), a32, kernel_size, is_open, root=_cols(buf, spans[1]), bias=b, mean=mean)
         ctx.save_for_backward(xp, wp, a32)
-        ctx.graph, ctx.dims, ctx.has_bias, ctx.spline = graph, (cin, K, C, hc, wt), bias is not None, (kernel_size, is_open, mean)
+        ctx.graph, ctx.spans, ctx.dims, ctx.spline = graph, spans, (cin, K, C), (kernel_size, is_open, mean)
         return y
 
     @staticmethod
     def _backward(ctx, dy):
         xp, wp, a32 = ctx.saved_tensors
-        graph, (cin, K, C, hc, wt) = ctx.graph, ctx.dims
+        graph, spans, (cin, K, C), need = ctx.graph, ctx.spans, ctx.dims, ctx.needs_input_grad
         kernel_size, is_open, mean = ctx.spline
         dy = dy.contiguous().to(torch.float32)
-        db = None
-        if ctx.has_bias and ctx.needs_input_grad[3]:
-            db = _bias_grad(dy)
-        gb = _grad_rows(dy.shape[0], [(0, wt)], wp.shape[0], dy.device)
-        ops.spline_bwd_node(graph, dy, a32, kernel_size, is_open, C, mean=mean, out=gb, root=wt != hc)   # gb = [dHf | dOut | 0]
-        dw = droot = None
-        if ctx.needs_input_grad[1] or (wt != hc and ctx.needs_input_grad[2]):
-            dwp = ops.gemm_tn(gb, xp)                            # [dweight as [K * out, in] ; dlin]
-            dw = dwp[:hc, :cin].reshape(K, C, cin).permute(0, 2, 1)
-            droot = dwp[hc:wt, :cin] if wt != hc else None
-        dx = ops.gemm_nn(gb, wp)[:, :cin] if ctx.needs_input_grad[0] else None
-        return dx, dw, droot, db, None, None, None, None, None
+        db = _bias_grad(dy) if need[3] else None
+        gb = _grad_rows(dy.shape[0], spans, wp.shape[0], dy.device)
+        ops.spline_bwd_node(graph, dy, a32, kernel_size, is_open, C, mean=mean, out=gb, root=spans[1] is not None)   # gb = [dHf | dOut | 0]
+        dx, (dwt, droot), _ = _packed_grads(gb, xp, wp, spans, cin, need[1:3], None, need[0])   # [dweight as [K * out, in] ; dlin]
+        return dx, None if dwt is None else dwt.reshape(K, C, cin).permute(0, 2, 1), droot, db, None, None, None, None, None
 
 
 def _spline_sizes(dim, kernel_size, is_open_spline):
     """-> (kernel_size, is_open_spline) as tuples of ``dim`` ints / bools, or ``ValueError``."""
-    if not isinstance(dim, int) or isinstance(dim, bool) or dim < 1:
-        raise ValueError("SplineConv: dim must be an integer >= 1, got %r" % (dim,))
+    _int_ge1("SplineConv", "dim", dim)
     if dim > ops.SPLINE_MAX_DIM:
         raise ValueError("SplineConv: dim must be <= %d on the HIP path (2^dim blocks per edge), got %d" % (ops.SPLINE_MAX_DIM, dim))
     is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
@@ -1373,14 +1249,10 @@ class SplineConv(nn.Module):
     def __init__(self, in_channels, out_channels: int, dim: int, kernel_size, is_open_spline=True, degree: int = 1,
                  aggr: str = "mean", root_weight: bool = True, bias: bool = True, **kwargs):
         super().__init__()
-        if isinstance(in_channels, (tuple, list)):
-            raise ValueError("SplineConv: tuple in_channels (bipartite graphs) are not implemented on the HIP path")
+        _no_tuple_channels("SplineConv", in_channels)
         if degree != 1:
             raise ValueError("SplineConv: only degree=1 is implemented on the HIP path, got %r" % (degree,))
-        if aggr not in ("mean", "add"):
-            raise ValueError("SplineConv: only aggr='mean' and aggr='add' are implemented on the HIP path, got %r" % (aggr,))
-        if kwargs:
-            raise TypeError("SplineConv: unexpected keyword arguments %s" % sorted(kwargs))
+        _check_aggr("SplineConv", aggr, ("mean", "add"), kwargs)
         ks, op = _spline_sizes(dim, kernel_size, is_open_spline)
         self.in_channels, self.out_channels, self.dim, self.degree, self.aggr = in_channels, out_channels, dim, 1, aggr
         self.kernel_size, self.is_open_spline, self.K = ks, op, math.prod(ks)
@@ -1400,8 +1272,7 @@ class SplineConv(nn.Module):
             a = 1.0 / math.sqrt(self.in_channels * self.K)
             self.weight.uniform_(-a, a)
             if self.lin is not None:
-                a = 1.0 / math.sqrt(self.in_channels)
-                self.lin.weight.uniform_(-a, a)
+                _reset_linear(self.lin)
             if self.bias is not None:
                 self.bias.zero_()
 
@@ -1409,21 +1280,9 @@ class SplineConv(nn.Module):
         """``edge_index`` must have a symmetric structure (both directions of every edge present); ``edge_attr``: [E, dim]
         pseudo-coordinates in [0, 1], float32 or float64 (rounded to float32 once), not requiring grad."""
         _no_tuple_x("SplineConv", x)
-        if size is not None:
-            raise ValueError("SplineConv: size is not implemented on the HIP path")
+        _not_implemented("SplineConv", size=size)
         _check_x("SplineConv", x, self.in_channels)
-        if not isinstance(edge_attr, torch.Tensor):
-            raise ValueError("SplineConv: edge_attr (the pseudo-coordinates, [E, %d]) is required" % self.dim)
-        if edge_attr.dim() != 2 or tuple(edge_attr.shape) != (edge_index.shape[1], self.dim):
-            raise ValueError("SplineConv: edge_attr must be [%d, %d], got %s" % (edge_index.shape[1], self.dim, tuple(edge_attr.shape)))
-        if edge_attr.dtype not in (torch.float32, torch.float64):
-            raise ValueError("SplineConv: edge_attr must be float32 or float64, got %s" % edge_attr.dtype)
-        if edge_attr.requires_grad:
-            raise ValueError("SplineConv: the gradient with respect to edge_attr is not implemented on the HIP path: pass "
-                             "edge_attr.detach()")
-        if not x.is_cuda or not edge_attr.is_cuda:
-            raise ops.DdmpError("SplineConv runs on the HIP path only: x and edge_attr must be CUDA (ROCm) tensors, there is no CPU "
-                                "fallback")
+        _check_pseudo("SplineConv", x, edge_attr, edge_index.shape[1], self.dim, no_grad=True)
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
             return _SplineConvFn.apply(x, self.weight, None if self.lin is None else self.lin.weight, self.bias, edge_attr, graph,
@@ -1443,39 +1302,24 @@ class _EdgeConvFn(_Fn):
 
     @staticmethod
     def forward(ctx, x, weight, bias, graph, want_arg):
-        cout, cin = weight.shape[0], weight.shape[1] // 2
-        cp = (cout + 3) // 4 * 4
-        xp = _pad_cols(x.detach().to(torch.float32))
+        cin = weight.shape[1] // 2
         w = weight.detach()
-        wp = _packed_rows((w[:, :cin] - w[:, cin:], w[:, cin:]), xp.shape[1], x.device, pad_each=True)
-        bp = None
-        if bias is not None:
-            bp = torch.zeros(2 * cp, dtype=torch.float32, device=x.device)
-            bp[:cout] = bias.detach()
-        buf = ops.gemm_nt(xp, wp, bias=bp)                       # [N, 2 cp]: A | padding | B | padding
+        xp, wp, buf, spans = _packed_gemm(x, (w[:, :cin] - w[:, cin:], w[:, cin:]), (bias, None), pad_each=True)   # buf [N, 2 cp]: A | padding | B | padding
         want = bool(want_arg) and any(ctx.needs_input_grad[:3])
-        y, arg = ops.gather_max(graph, buf[:, cp:cp + cout], a=buf[:, :cout], want_arg=want)
+        y, arg = ops.gather_max(graph, _cols(buf, spans[1]), a=_cols(buf, spans[0]), want_arg=want)
         ctx.save_for_backward(xp, wp, arg)
-        ctx.graph, ctx.dims, ctx.has_bias = graph, (cin, cout, cp), bias is not None
+        ctx.graph, ctx.spans, ctx.cin = graph, spans, cin
         return y
 
     @staticmethod
     def _backward(ctx, dy):
         xp, wp, arg = ctx.saved_tensors
-        graph, (cin, cout, cp) = ctx.graph, ctx.dims
+        need = ctx.needs_input_grad
         dy = dy.contiguous().to(torch.float32)
-        g = _grad_rows(dy.shape[0], [(0, cout), (cp, cp + cout)], 2 * cp, dy.device)
-        da, _ = ops.gather_max_bwd(graph, dy, arg, out=g)        # g = [dA | 0 | dB | 0]
-        db = None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = _bias_grad(da)
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dwp = ops.gemm_tn(g, xp)                             # [dM ; dN]
-            dm, dn = dwp[:cout, :cin], dwp[cp:cp + cout, :cin]
-            dw = torch.cat([dm, dn - dm], 1)
-        dx = ops.gemm_nn(g, wp)[:, :cin] if ctx.needs_input_grad[0] else None
-        return dx, dw, db, None, None
+        g = _grad_rows(dy.shape[0], ctx.spans, wp.shape[0], dy.device)
+        ops.gather_max_bwd(ctx.graph, dy, arg, out=g)            # g = [dA | 0 | dB | 0]
+        dx, (dm, dn), (db, _) = _packed_grads(g, xp, wp, ctx.spans, ctx.cin, (need[1], need[1]), (need[2], False), need[0])   # [dM ; dN]
+        return dx, torch.cat([dm, dn - dm], 1) if need[1] else None, db, None, None
 
 
 def _edge_conv(x, weight, bias, graph):
@@ -1504,14 +1348,33 @@ def _edge_nn(module):
 
 
 class EdgeConv(nn.Module):
-    """``torch_geometric.nn.EdgeConv`` 2.2.0 on the HIP kernels (module docstring)."""
+    """``torch_geometric.nn.EdgeConv`` 2.2.0 (Wang et al., Dynamic Graph CNN, 2019) on the HIP kernels,
+    ``EdgeConv(nn, aggr="max")``, ``forward(x, edge_index)`` (written from the published source from memory -- PyG cannot be
+    installed here, so this could not be checked against it; the pin is the float64 restatement ``tests/edgeconv_ref.py``):
+
+    * ``out[i] = max over the edges j -> i of nn(cat[x_i, x_j - x_i])``, a node without incoming edges gets 0.  No self loops are
+      added; an explicit loop is an ordinary edge (it contributes ``nn(cat[x_i, 0])``); a duplicate edge changes nothing.
+    * accepted ``nn``: a ``torch.nn.Linear(2 * in, out)`` with or without bias, or a ``torch.nn.Sequential`` whose first module is
+      such a ``Linear`` and whose other modules are all ``ReLU``, ``LeakyReLU(negative_slope >= 0)`` or ``Identity``.  Those are
+      elementwise, non-decreasing in floating point and map 0 to 0, so ``max_j act(z_j) == act(max_j z_j)`` bit for bit and an
+      empty neighbourhood stays 0: they run as ordinary torch modules after the fused core.  (A ``Sigmoid`` fails the second
+      condition, a ``BatchNorm`` the first.)  The module is kept as given under ``self.nn``: ``state_dict()`` has PyG's keys
+      (``nn.weight``, ``nn.bias`` or ``nn.0.weight`` ...) and ``parameters()`` are the user's own tensors.
+    * with ``W = [Wa | Wb]``: ``W [x_i ; x_j - x_i] + b = (Wa - Wb) x_i + b + Wb x_j = A[i] + B[j]``, so
+      ``out[i] = A[i] + max_j B[j]``: one GEMM against the packed ``[Wa - Wb ; Wb]`` for the row buffer ``[A | B]``, one launch for
+      the per-column maximum and its winner (``ops.gather_max``; the winner is kept only when a gradient is wanted), one launch for
+      the backward of the graph part (``ops.gather_max_bwd`` -> ``[dA | dB]``), one wgrad GEMM (``dWa = dM``, ``dWb = dN - dM``)
+      and one dgrad GEMM.  No [E, .] tensor exists at any point.  The graph is GATConv's without loops:
+      ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric edge STRUCTURE only.
+    * differentiable w.r.t. x and the ``Linear``'s weight and bias; float32, bitwise reproducible.  Deviation: with exact ties
+      PyG's winner is unspecified, ours is the smallest source id -- either one is a valid subgradient.
+    * refused with ``ValueError`` before any launch: any other ``nn`` (an arbitrary MLP; a ``Linear`` whose ``in_features`` is
+      odd), ``aggr != "max"``, a tuple ``x`` (bipartite), bf16 features, an ``x`` that is not [N, in].  Not implemented:
+      ``DynamicEdgeConv`` / kNN graphs."""
 
     def __init__(self, nn, aggr: str = "max", **kwargs):
         super().__init__()
-        if aggr != "max":
-            raise ValueError("EdgeConv: only aggr='max' is implemented on the HIP path, got %r" % (aggr,))
-        if kwargs:
-            raise TypeError("EdgeConv: unexpected keyword arguments %s" % sorted(kwargs))
+        _check_aggr("EdgeConv", aggr, ("max",), kwargs)
         lin, _ = _edge_nn(nn)
         self.aggr = aggr
         self.in_channels, self.out_channels = lin.in_features // 2, lin.out_features
