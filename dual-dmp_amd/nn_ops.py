@@ -232,6 +232,15 @@ def _check_x(name, x, in_channels, bf16=True):
         raise ValueError("%s: expected x of shape [N, %d]" % (name, in_channels))
 
 
+def _need_entries(name, edge_index, loops=False):
+    """A graph without a single entry -- an empty ``edge_index`` where the operator adds no self loops (``loops``) -- is refused,
+    by every operator alike.  PyG returns the root / skip / bias term alone there; here the per-entry arrays would be empty
+    tensors whose null pointer the library takes for a missing argument."""
+    if isinstance(edge_index, torch.Tensor) and edge_index.dim() == 2 and edge_index.shape[1] == 0 and not loops:
+        raise ValueError("%s: edge_index has no edge and no self loops are added: a graph without any entry is not supported on "
+                         "the HIP path (the result would be the root / skip / bias term alone)" % name)
+
+
 def _need_gpu(name, x, edge_attr=None, exc=None):
     """x (and ``edge_attr``, where the operator takes one) must be on the GPU.  ``exc``: ``ops.DdmpError`` unless given (GATv2Conv,
     TransformerConv and ResGatedGraphConv raise ``ValueError``)."""
@@ -407,6 +416,7 @@ class GCNConv(nn.Module):
             if x.dtype == torch.bfloat16:
                 raise ValueError("GCNConv: bf16 features with edge_weight are not supported on the HIP path")
         _need_gpu("GCNConv", x)
+        _need_entries("GCNConv", edge_index, loops=self.add_self_loops and self.normalize)
         default = not self.improved and self.add_self_loops and self.normalize
         with ops.on_device(x):
             if edge_weight is None and default and self.bias is not None:
@@ -637,6 +647,7 @@ class GATConv(nn.Module):
         _no_attention_dropout("GATConv", self)
         _check_x("GATConv", x, self.in_channels)
         _need_gpu("GATConv", x)
+        _need_entries("GATConv", edge_index, loops=self.add_self_loops)
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=self.add_self_loops)
             return _GATConvFn.apply(x, self.lin_src.weight, self.att_src, self.att_dst, self.bias, graph, self.heads, self.concat,
@@ -749,6 +760,7 @@ class GATv2Conv(nn.Module):
         _no_attention_dropout("GATv2Conv", self)
         _check_x("GATv2Conv", x, self.in_channels)
         _need_gpu("GATv2Conv", x, exc=ValueError)
+        _need_entries("GATv2Conv", edge_index, loops=self.add_self_loops)
         share = self.share_weights
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=self.add_self_loops)
@@ -861,6 +873,7 @@ class TransformerConv(nn.Module):
         _no_attention_dropout("TransformerConv", self)
         _check_x("TransformerConv", x, self.in_channels)
         _need_gpu("TransformerConv", x, exc=ValueError)
+        _need_entries("TransformerConv", edge_index)
         root = self.root_weight
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
@@ -964,6 +977,7 @@ class ResGatedGraphConv(nn.Module):
         _no_tuple_x("ResGatedGraphConv", x)
         _check_x("ResGatedGraphConv", x, self.in_channels)
         _need_gpu("ResGatedGraphConv", x, exc=ValueError)
+        _need_entries("ResGatedGraphConv", edge_index)
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
             return _ResGatedFn.apply(x, self.lin_key.weight, self.lin_key.bias, self.lin_query.weight, self.lin_query.bias,
@@ -1053,6 +1067,7 @@ class FeaStConv(nn.Module):
         _no_tuple_x("FeaStConv", x)
         _check_x("FeaStConv", x, self.in_channels)
         _need_gpu("FeaStConv", x)
+        _need_entries("FeaStConv", edge_index, loops=self.add_self_loops)
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=self.add_self_loops)
             return _FeaStConvFn.apply(x, self.lin.weight, self.u.weight, self.c, self.bias, graph, self.heads)
@@ -1162,6 +1177,7 @@ class GMMConv(nn.Module):
         _not_implemented("GMMConv", size=size)
         _check_x("GMMConv", x, self.in_channels)
         _check_pseudo("GMMConv", x, edge_attr, edge_index.shape[1], self.dim)
+        _need_entries("GMMConv", edge_index)
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
             return _GMMConvFn.apply(x, self.g, self.mu, self.sigma, None if self.root is None else self.root.weight, self.bias,
@@ -1283,6 +1299,7 @@ class SplineConv(nn.Module):
         _not_implemented("SplineConv", size=size)
         _check_x("SplineConv", x, self.in_channels)
         _check_pseudo("SplineConv", x, edge_attr, edge_index.shape[1], self.dim, no_grad=True)
+        _need_entries("SplineConv", edge_index)
         with ops.on_device(x):
             graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
             return _SplineConvFn.apply(x, self.weight, None if self.lin is None else self.lin.weight, self.bias, edge_attr, graph,
@@ -1393,6 +1410,7 @@ class EdgeConv(nn.Module):
         _check_x("EdgeConv", x, self.in_channels)
         _edge_nn(self.nn)                                        # (the module is the user's: it may have been edited since)
         _need_gpu("EdgeConv", x)
+        _need_entries("EdgeConv", edge_index)
         return self._core(x, edge_index)
 
     def _core(self, x, edge_index):

@@ -656,6 +656,8 @@ def graph_weight_grad(g: Graph, G, out=None):
     if out is None:
         out = torch.empty(g.nnz_in, dtype=torch.float32, device=G.device)
     _chk(out, torch.float32, "out")
+    if g.nnz_in == 0:                                           # (only added self loops: no input edge, nothing to write -- and an
+        return out                                              #  empty tensor's null pointer is a missing argument to the library)
     with _timed("graph_weight_grad", (int(round(g.nnz / max(g.n_rows, 1))),), 28.0 * g.nnz + 8.0 * g.nnz_in + 8.0 * g.n_rows):
         check(_lib.lib().ddmp_graph_weight_grad(g.handle, _p(G), _p(out), _stream()), "ddmp_graph_weight_grad")
     return out
@@ -666,6 +668,11 @@ def _gat_graph(g: Graph):
     if not g.valued or g.values_key != ("ones",):
         raise DdmpError("the attention kernels need the graph of graph_for(edge_index, n, norm='gat'): a valued graph left at its "
                         "all-ones values (its entries' multiplicities)")
+    if g.nnz == 0:
+        # the per-entry arrays (alpha, dz, w ...) would be empty tensors with a null pointer, which the library takes for a
+        # missing argument: refused here, before any launch, not with a status from inside it
+        raise ValueError("the graph has no entry at all (no edge and no added self loop): the graph-operator kernels are not "
+                         "defined on it")
     return g
 
 
