@@ -1,8 +1,8 @@
-"""Drop-ins for ten ``torch_geometric.nn`` 2.2.0 operators on the HIP kernels: same constructor / call signature, parameter names
+"""Drop-ins for eleven ``torch_geometric.nn`` 2.2.0 operators on the HIP kernels: same constructor / call signature, parameter names
 and initialisation; the dense part goes through the GEMMs, the graph part through one fused gather launch per direction, and no
 per-edge feature tensor exists at any point.  Each operator is documented once, at its class: ``GCNConv``, ``ChebConv``,
 ``GATConv``, ``GATv2Conv``, ``TransformerConv``, ``ResGatedGraphConv``, ``FeaStConv``, ``GMMConv`` (with ``cartesian_pseudo``),
-``SplineConv``, ``EdgeConv``.
+``SplineConv``, ``EdgeConv``, ``SAGEConv``.
 
 ``edge_weight`` (``GCNConv`` and ``ChebConv``; restated from the published PyG 2.2.0 source from memory -- PyG cannot be installed
 here, so this could not be checked against it; the pin is the dense float64 restatement ``tests/gcnw_ref.py``):
@@ -1424,3 +1424,158 @@ class EdgeConv(nn.Module):
 
     def extra_repr(self):
         return "aggr=%s" % self.aggr
+
+
+_SAGE_AGGRS = ("mean", "add", "sum", "max", "min")
+
+
+def _sage_aggrs(aggr, kwargs):
+    """-> the aggregators of a SAGEConv as a tuple of names out of mean / add / max / min (``"sum"`` is ``"add"``), in the
+    order given, or ``ValueError``: a name outside that list (``"lstm"``, ``"std"``, ``"var"`` ...), an empty list, a repeat, or
+    mean and add together."""
+    given = list(aggr) if isinstance(aggr, (list, tuple)) else [aggr]
+    if not given:
+        raise ValueError("SAGEConv: an empty list of aggregators")
+    for a in given:
+        _check_aggr("SAGEConv", a, _SAGE_AGGRS, kwargs)          # (and nothing may be left in the constructor's kwargs)
+    names = tuple("add" if a == "sum" else a for a in given)
+    if len(set(names)) != len(names):
+        raise ValueError("SAGEConv: an aggregator is listed twice in %r" % (list(aggr),))
+    if "mean" in names and "add" in names:
+        raise ValueError("SAGEConv: mean and add together are not implemented on the HIP path (one sum per launch), got %r" % (list(aggr),))
+    return names
+
+
+class _SAGEConvFn(_Fn):
+    """Both directions of the GCNConv trade, every one with ONE graph launch per direction (``ops.gather_stats`` /
+    ``ops.gather_stats_bwd``):
+
+    * aggregate-first (the only form for max, min and lists): one launch writes ``[A_1 | ... | A_k | X]`` into one row buffer
+      (the X block only with a root weight), ONE GEMM against the column-packed ``[lin_l.weight | lin_r.weight]`` with the bias.
+      Saved: the row buffer, the packed weight, the args of max / min and 1 / deg of mean.  Backward: ONE wgrad GEMM
+      (``[dlin_l | dlin_r]``), ONE dgrad GEMM (``[dA_1 | ... | dA_k | dX0]``) and one launch that scatters every block back to dx.
+    * transform-first (a single mean / add whose padded ``out`` is narrower than the padded ``in``): ONE GEMM against the
+      row-packed ``[lin_l.weight ; lin_r.weight]`` gives ``[L | R]``, one launch computes ``mean(L) + R + bias``.  Saved: the padded
+      x, the packed weight and 1 / deg.  Backward: one launch writes ``[dL | dR]``, then ONE wgrad and ONE dgrad GEMM.
+
+    ``want_arg``: whether a backward can follow (grad mode cannot be read inside ``forward``: ``_sage_conv`` passes it in)."""
+
+    @staticmethod
+    def forward(ctx, x, wl, bl, wr, graph, aggrs, want_arg):
+        n, cin, cout, k = x.shape[0], x.shape[1], wl.shape[0], len(aggrs)
+        b = None if bl is None else bl.detach().contiguous()
+        pad4 = lambda c: (c + 3) // 4 * 4
+        ctx.graph, ctx.aggrs, ctx.dims, ctx.has_root = graph, aggrs, (cin, cout), wr is not None
+        ctx.first = k == 1 and aggrs[0] in ("mean", "add") and pad4(cout) < pad4(cin)
+        if ctx.first:
+            xp, wp, buf, spans = _packed_gemm(x, (wl, wr))       # buf [N, (1 or 2) out rounded up to 4]: L | R | zero padding
+            (y,), _, invdeg = ops.gather_stats(graph, _cols(buf, spans[0]), want=aggrs, root=_cols(buf, spans[1]), bias=b)
+            ctx.save_for_backward(xp, wp, invdeg)
+            ctx.spans = spans
+            return y
+        want = bool(want_arg) and any(ctx.needs_input_grad[:4])
+        used = (k + (wr is not None)) * cin
+        buf = _grad_rows(n, [(0, used)], pad4(used), x.device)   # [A_1 | ... | A_k | X | zero padding]
+        _, args, invdeg = ops.gather_stats(graph, x.detach().to(torch.float32).contiguous(), want=aggrs, copy_x=wr is not None,
+                                           want_arg=want, out=buf)
+        wp = _pad_cols(wl.detach() if wr is None else torch.cat([wl.detach(), wr.detach()], 1))
+        y = ops.gemm_nt(buf, wp, bias=b)
+        ctx.save_for_backward(buf, wp, invdeg, *[a for a in args if a is not None])
+        return y
+
+    @staticmethod
+    def _backward(ctx, dy):
+        graph, aggrs, (cin, cout), need = ctx.graph, ctx.aggrs, ctx.dims, ctx.needs_input_grad
+        dy = dy.contiguous().to(torch.float32)
+        db = _bias_grad(dy) if need[2] else None
+        if ctx.first:
+            xp, wp, invdeg = ctx.saved_tensors
+            gb = _grad_rows(dy.shape[0], ctx.spans, wp.shape[0], dy.device)
+            ops.gather_stats_bwd(graph, ds=dy, invdeg=invdeg, root=ctx.has_root, out=gb)         # gb = [dL | dR | 0]
+            dx, (dwl, dwr), _ = _packed_grads(gb, xp, wp, ctx.spans, cin, (need[1], need[3]), None, need[0])
+            return dx, dwl, db, dwr, None, None, None
+        buf, wp, invdeg, *args = ctx.saved_tensors
+        k = len(aggrs)
+        dyp = _pad_cols(dy)
+        dwl = dwr = dx = None
+        if need[1] or (ctx.has_root and need[3]):
+            dwp = ops.gemm_tn(dyp, buf)                          # [dlin_l | dlin_r]
+            dwl, dwr = dwp[:cout, :k * cin], (dwp[:cout, k * cin:(k + 1) * cin] if ctx.has_root else None)
+        if need[0]:
+            g = ops.gemm_nn(dyp, _pad_rows_like(wp, dyp, cout))  # [dA_1 | ... | dA_k | dX0 | .]
+            args, op = list(args), {}
+            for i, a in enumerate(aggrs):
+                blk = g[:, i * cin:(i + 1) * cin]
+                if a in ("max", "min"):
+                    op["d" + ("mx" if a == "max" else "mn")], op["arg" + ("mx" if a == "max" else "mn")] = blk, args.pop(0)
+                else:
+                    op["ds"], op["invdeg"] = blk, invdeg
+            dx, _ = ops.gather_stats_bwd(graph, dx0=g[:, k * cin:(k + 1) * cin] if ctx.has_root else None, **op)
+        return dx, dwl, db, dwr, None, None, None
+
+
+def _sage_conv(x, wl, bl, wr, graph, aggrs):
+    want = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, wl, bl, wr))
+    return _SAGEConvFn.apply(x, wl, bl, wr, graph, aggrs, want)
+
+
+class SAGEConv(nn.Module):
+    """``torch_geometric.nn.SAGEConv`` 2.2.0 (Hamilton et al., GraphSAGE, NeurIPS 2017) on the HIP kernels,
+    ``SAGEConv(in_channels, out_channels, aggr="mean", normalize=False, root_weight=True, project=False, bias=True)``,
+    ``forward(x, edge_index, size=None)`` (restated from the published source from memory -- PyG cannot be installed here, so this
+    could not be checked against it; the pin is the float64 restatement ``tests/sage_ref.py``):
+
+    * ``out[i] = lin_l(cat_k aggr_k({x_j : j -> i})) + lin_r(x_i)``, with ``normalize`` followed by
+      ``F.normalize(out, p=2, dim=-1)`` (torch elementwise work on [N, out], not fused).  Parameters: ``lin_l.weight``
+      [out, k * in] for k aggregators and ``lin_l.bias`` [out] (only with ``bias=True``), ``lin_r.weight`` [out, in] without a bias
+      (the attribute is absent with ``root_weight=False``), all uniform(+-1/sqrt(fan-in)).
+    * ``aggr``: ``"mean"``, ``"add"`` / ``"sum"``, ``"max"``, ``"min"``, or a list of those, concatenated in list order (PyG's
+      ``MultiAggregation`` in ``cat`` mode).  No self loops are added, an explicit loop is an ordinary edge, duplicate edges each
+      count in mean / add and cannot change max / min, a node without incoming edges aggregates to 0.
+    * the launches: ``_SAGEConvFn`` -- ONE gather launch per direction whatever the number of aggregators: every neighbour row is
+      read once and feeds all of them (``ops.gather_stats``).  No [E, .] tensor and no ``index_add_`` / ``scatter`` exist at any
+      point.  The graph is GATConv's without loops: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric
+      edge STRUCTURE only.
+    * differentiable w.r.t. x and every parameter; float32, bitwise reproducible.  Deviation: with exact ties PyG's max / min
+      winner is unspecified, ours is the smallest source id -- either one is a valid subgradient.
+    * refused with ``ValueError`` before any launch: ``project=True``, any other aggregator (``"lstm"``, ``"std"``, ``"var"`` ...), a
+      list with a repeat or with both mean and add, tuple ``in_channels`` or a tuple ``x`` (bipartite), ``size``, bf16 features, a
+      CPU ``x``, an ``x`` that is not [N, in]."""
+
+    def __init__(self, in_channels, out_channels: int, aggr="mean", normalize: bool = False, root_weight: bool = True,
+                 project: bool = False, bias: bool = True, **kwargs):
+        super().__init__()
+        _no_tuple_channels("SAGEConv", in_channels)
+        if project:
+            raise ValueError("SAGEConv: project=True is not implemented on the HIP path")
+        self._aggrs = _sage_aggrs(aggr, kwargs)
+        self.in_channels, self.out_channels, self.aggr = in_channels, out_channels, aggr
+        self.normalize, self.root_weight, self.project = bool(normalize), bool(root_weight), False
+        self.lin_l = _LinB(len(self._aggrs) * in_channels, out_channels, bias=bias)
+        if root_weight:
+            self.lin_r = _Lin(in_channels, out_channels)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            _reset_linear(self.lin_l)
+            if self.root_weight:
+                _reset_linear(self.lin_r)
+
+    def forward(self, x, edge_index, size=None) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
+        _no_tuple_x("SAGEConv", x)
+        _not_implemented("SAGEConv", size=size)
+        _check_x("SAGEConv", x, self.in_channels)
+        _need_gpu("SAGEConv", x, exc=ValueError)
+        _need_entries("SAGEConv", edge_index)
+        return self._core(x, edge_index)
+
+    def _core(self, x, edge_index):
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
+            y = _sage_conv(x, self.lin_l.weight, self.lin_l.bias, self.lin_r.weight if self.root_weight else None, graph, self._aggrs)
+        return torch.nn.functional.normalize(y, p=2.0, dim=-1) if self.normalize else y
+
+    def extra_repr(self):
+        return "%d, %d, aggr=%s" % (self.in_channels, self.out_channels, self.aggr)

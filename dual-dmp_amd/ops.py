@@ -1322,6 +1322,114 @@ def gather_max_bwd(g: Graph, dg, arg, out=None):
     return da, db
 
 
+# ---------------------------------------------------------------------------------------- neighbour statistics
+STATS = ("mean", "add", "max", "min")
+
+
+def _stats_want(want):
+    """``want`` as a tuple of distinct names out of ``STATS`` with at most one of mean / add, or ``DdmpError``."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in STATS for w in want) or len(set(want)) != len(want) or ("mean" in want and "add" in want):
+        raise DdmpError("want must be a non-empty sequence of distinct names out of %r with at most one of 'mean' / 'add', got %r"
+                        % (STATS, want))
+    return want
+
+
+def gather_stats(g: Graph, x, want=("mean",), root=None, bias=None, copy_x=False, want_arg=True, out=None):
+    """Mean-or-sum / max / min of the neighbours' rows in ONE launch (``ddmp_gather_stats_f32``): every neighbour row is read once
+    and feeds every statistic in ``want`` (names out of ``STATS``, at most one of mean / add).  -> (blocks, args, invdeg):
+
+    * ``blocks``: one [n, C] result per entry of ``want``, in that order, then (``copy_x``) a copy of ``x[:n]``.  They are the
+      consecutive column blocks [k * C, (k + 1) * C) of ``out``, a float32 [n, >= len(blocks) * C] row buffer (further columns are
+      left untouched); ``out=None``: a buffer of its own, exactly that wide.
+    * ``args``: parallel to ``want``: int32 [n, C], the source node id of the winning entry, for max / min (ties: the smallest id;
+      -1 for a row without entries; ``want_arg=False``: not stored, None -- a forward without a backward), None for mean / add.
+    * ``invdeg``: [n], 1 / the number of input edges into the row (0 for a row without entries) when ``want`` has mean, else None.
+
+    mean / add: ``w_i sum_e a_e x[col e] + root[i] + bias`` with ``root`` [n, C] (it may be a column block of the buffer ``x`` is
+    a block of) and ``bias`` [C] both optional and only allowed with mean / add; a row without entries gets ``root + bias`` (or
+    0), and 0 in max / min."""
+    _gmm_graph(g)
+    want = _stats_want(want)
+    n = g.n_rows
+    x, ldx = _rows(x, "x", n)
+    C = x.shape[1]
+    summed = "mean" in want or "add" in want
+    if (root is not None or bias is not None) and not summed:
+        raise DdmpError("gather_stats: root and bias belong to the mean / add block, which was not requested")
+    ldr = 0
+    if root is not None:
+        root, ldr = _rows(root, "root", n, C)
+    if bias is not None:
+        bias = _gat_arr(bias, (C,), "bias")
+    nb = len(want) + bool(copy_x)
+    if out is None:
+        out = torch.empty((n, nb * C), dtype=torch.float32, device=x.device)
+    out, _ = _mat(_chk(out, torch.float32, "out"), "out")
+    if out.shape[0] != n or out.shape[1] < nb * C:
+        raise DdmpError("gather_stats: out must be [%d, >= %d], got %s" % (n, nb * C, tuple(out.shape)))
+    blocks = [out[:, k * C:(k + 1) * C] for k in range(nb)]
+    ptr = {k: (None, 0) for k in ("sum", "max", "min", "amax", "amin", "copy")}
+    args = [None] * len(want)
+    for k, w in enumerate(want):
+        ptr["sum" if w in ("mean", "add") else w] = _mat(blocks[k], w)
+        if w in ("max", "min") and want_arg:
+            args[k] = torch.empty((n, C), dtype=torch.int32, device=x.device)
+            ptr["a" + w] = _gmax_arg(args[k], n, C)
+    if copy_x:
+        ptr["copy"] = _mat(blocks[-1], "copy")
+    invdeg = torch.empty(n, dtype=torch.float32, device=x.device) if "mean" in want else None
+    # algorithmic bytes: every gathered row read ONCE whatever the number of statistics, one row written per block and per arg, the
+    # root block and the row's own features (copy_x) read, invdeg written, col + multiplicity, rowptr
+    n_arg = sum(a is not None for a in args)
+    alg = 4.0 * n * C * (1 + nb + n_arg + (root is not None) + bool(copy_x)) + 4.0 * n * (invdeg is not None) + 8.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("gather_stats", (C, "+".join(want), int(round(g.nnz / max(n, 1)))), alg, 1.0 * g.nnz * C * len(want),
+                survey=8.0 * n * C + 4.0 * g.nnz + 4.0 * (n + 1)):
+        st = _lib.lib().ddmp_gather_stats_f32(g.handle, _p(x), ldx, C, int("mean" in want), _p(root), ldr, _p(bias),
+                                              _p(ptr["sum"][0]), ptr["sum"][1], _p(ptr["max"][0]), ptr["max"][1],
+                                              _p(ptr["amax"][0]), ptr["amax"][1], _p(ptr["min"][0]), ptr["min"][1],
+                                              _p(ptr["amin"][0]), ptr["amin"][1], _p(invdeg), _p(ptr["copy"][0]), ptr["copy"][1],
+                                              _stream())
+    check(st, "ddmp_gather_stats_f32")
+    return tuple(blocks), tuple(args), invdeg
+
+
+def gather_stats_bwd(g: Graph, ds=None, invdeg=None, dmx=None, argmx=None, dmn=None, argmn=None, dx0=None, root=False, out=None):
+    """Backward of ``gather_stats`` in one launch (``ddmp_gather_stats_bwd_f32``) -> (dx [n, C] written completely, droot [n, C] |
+    None): ``dx[j] = dx0[j] + sum_{e' in row j} (a_{mirror e'} w_i ds[i] + (argmx[i] == j ? dmx[i] : 0) + (argmn[i] == j ?
+    dmn[i] : 0))`` with ``i = col e'`` and ``w_i = invdeg[i]`` (the mean) or 1 (``invdeg=None``: the sum).  ``ds``, ``dmx`` (with
+    ``argmx``) and ``dmn`` (with ``argmn``): the gradients of the requested blocks, [n, C] each, at least one; ``dx0``: the
+    gradient that arrived through the ``copy_x`` block, or None.  ``root``: the launch also copies ``ds`` into the root block's
+    columns.  ``out``: a float32 [n, >= C (+ C)] row buffer that receives [dx | droot] in its leading columns (the results are then
+    views of it; further columns are left untouched); None: a buffer of its own."""
+    _gmm_graph(g)
+    n = g.n_rows
+    first = next((t for t in (ds, dmx, dmn) if t is not None), None)
+    if first is None or (dmx is None) != (argmx is None) or (dmn is None) != (argmn is None) or (ds is None and (root or invdeg is not None)):
+        raise DdmpError("gather_stats_bwd: at least one of ds, dmx, dmn; dmx comes with argmx, dmn with argmn; invdeg and root need ds")
+    C = first.shape[1] if isinstance(first, torch.Tensor) and first.dim() == 2 else 0
+    op = {}
+    for name, t in (("ds", ds), ("dmx", dmx), ("dmn", dmn), ("dx0", dx0)):
+        op[name] = (None, 0) if t is None else _rows(t, name, n, C)
+    for name, t in (("argmx", argmx), ("argmn", argmn)):
+        op[name] = (None, 0) if t is None else _gmax_arg(t, n, C)
+    if invdeg is not None:
+        invdeg = _gat_arr(invdeg, (n,), "invdeg")
+    (dx, lddx), (dr, lddr) = _out_with_root(out, "gather_stats_bwd", n, C, C, root, first.device)
+    ns = sum(t is not None for t in (ds, dmx, dmn, dx0))
+    # algorithmic bytes: every requested gradient stream (and each arg) read once, dx (and the root block, with ds once more)
+    # written, invdeg, col + mirror + multiplicity, rowptr
+    alg = (4.0 * n * C * (ns + (argmx is not None) + (argmn is not None) + 1 + 2 * bool(root)) + 4.0 * n * (invdeg is not None)
+           + 12.0 * g.nnz + 4.0 * (n + 1))
+    with _timed("gather_stats_bwd", (C, ns, int(round(g.nnz / max(n, 1)))), alg, 1.0 * g.nnz * C * ns):
+        st = _lib.lib().ddmp_gather_stats_bwd_f32(g.handle, C, _p(op["ds"][0]), op["ds"][1], _p(invdeg), _p(op["dmx"][0]), op["dmx"][1],
+                                                  _p(op["argmx"][0]), op["argmx"][1], _p(op["dmn"][0]), op["dmn"][1],
+                                                  _p(op["argmn"][0]), op["argmn"][1], _p(op["dx0"][0]), op["dx0"][1], _p(dx), lddx,
+                                                  _p(dr), lddr, _stream())
+    check(st, "ddmp_gather_stats_bwd_f32")
+    return dx, dr
+
+
 def spmm_axpby(g: Graph, x, out=None, z=None, z2=None, a=1.0, b=0.0, c=0.0, d=0.0):
     """out[i] = a * (dinv_i * sum_j dinv_j x[j]) + b * x[i] + c * z[i] + d * z2[i], float32 (ddmp_spmm_axpby_f32): one step of a
     three-term recurrence per launch.  ``z`` / ``z2`` optional (their coefficient is then ignored); ``out`` may be ``z`` or ``z2``,

@@ -419,6 +419,47 @@ int ddmp_gather_max_f32(const ddmp_graph* g, const float* B, int64_t ldb, const 
 int ddmp_gather_max_bwd_f32(const ddmp_graph* g, const float* dG, int64_t lddg, const int32_t* arg, int64_t ldarg, int C, float* dA,
                             int64_t ldda, float* dB, int64_t lddb, ddmp_stream stream);
 
+/* ------------------------------------------------------------------ neighbour statistics (torch_geometric SAGEConv with mean, add,
+ * max and min aggregation, one of them or several at once).  float32.  The graph is the one of the Gaussian-mixture
+ * kernels: the attention graph created with flags 0 (no loop handling, so a_e is the number of input edges of entry e) and left at
+ * its all-ones values; an unvalued graph or one with loop handling is DDMP_EINVAL.  Every matrix has its own pointer and leading
+ * dimension (the outputs are meant to be column blocks of one row buffer).  No atomics, fixed orders: two calls give the same bits,
+ * and a block of a fused call has the bits of the same block requested alone.  The vector kernels need C % 4 == 0, leading
+ * dimensions % 4 == 0 and 16-byte aligned matrices (bias included); anything else takes scalar kernels.
+ *
+ * forward:   every neighbour row X[col e, :] is loaded once and feeds any non-empty subset of three outputs (a null pointer: not
+ *            requested; none at all is DDMP_EINVAL):
+ *            S[i,c]  = w_i sum_{e in row i} a_e X[col e, c] in CSR order (+ R[i,c], nullable, own leading dimension) (+ bias[c],
+ *                      nullable), w_i = 1 / deg_i (mean != 0) or 1, deg_i = sum_{e in row i} a_e = the number of input edges into
+ *                      i (duplicates and explicit loops count).  A row without entries gets R[i,:] + bias, or zeros.  mean, R and
+ *                      bias need S.
+ *            Mx[i,c] = max_{e in row i} X[col e, c], argmx[i,c] = col e of the winning entry (int32 [n, C]; nullable: not stored).
+ *                      Multiplicities are ignored.  Ties go to the first entry in CSR order, i.e. the smallest source id (strict >
+ *                      from the row's first entry).  A row without entries gets 0 and -1.
+ *            Mn, argmn: the same for the minimum, with a strict <.
+ *            invdeg[i] (nullable, [n]) = 1 / deg_i, 0 for a row without entries: saved for the backward.
+ *            Xcopy[i,:] (nullable, own leading dimension) = X[i,:]: the row's own features copied into a column block of the
+ *                      output buffer.
+ *            No output may alias X or another operand.  One launch. */
+int ddmp_gather_stats_f32(const ddmp_graph* g, const float* X, int64_t ldx, int C, int mean, const float* R /*nullable*/, int64_t ldr,
+                          const float* bias /*nullable*/, float* S /*nullable*/, int64_t lds, float* Mx /*nullable*/, int64_t ldmx,
+                          int32_t* argmx /*nullable*/, int64_t ldamx, float* Mn /*nullable*/, int64_t ldmn,
+                          int32_t* argmn /*nullable*/, int64_t ldamn, float* invdeg /*nullable*/, float* Xcopy /*nullable*/,
+                          int64_t ldxc, ddmp_stream stream);
+/* backward, node side (the structure is symmetric: row j's own entries e' enumerate the targets i = col e' that j feeds, the
+ *            mirrored entry holds the multiplicity of j -> i, arg holds node ids):
+ *            dX[j,c] = dX0[j,c] + sum_{e' in row j} ( a_{mirror e'} w_i dS[i,c] + (argmx[i,c] == j ? dMx[i,c] : 0)
+ *                                                                              + (argmn[i,c] == j ? dMn[i,c] : 0) ) in CSR order,
+ *            w_i = invdeg[i], or 1 with invdeg null (the sum).  Each of the three gradient streams is nullable (dMx comes with
+ *            argmx, dMn with argmn; none at all is DDMP_EINVAL) and only the requested ones are loaded; dX0 (nullable) is the
+ *            gradient that arrives through the Xcopy block.  dX is written completely: a row without entries gets dX0, or zeros.
+ *            dR[j,:] = dS[j,:] (nullable; needs dS): the gradient of the forward's R block.  One launch. */
+int ddmp_gather_stats_bwd_f32(const ddmp_graph* g, int C, const float* dS /*nullable*/, int64_t ldds,
+                              const float* invdeg /*nullable*/, const float* dMx /*nullable*/, int64_t lddmx,
+                              const int32_t* argmx /*nullable*/, int64_t ldamx, const float* dMn /*nullable*/, int64_t lddmn,
+                              const int32_t* argmn /*nullable*/, int64_t ldamn, const float* dX0 /*nullable*/, int64_t lddx0,
+                              float* dX, int64_t lddx, float* dR /*nullable*/, int64_t lddr, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ dense steps (MFMA; float32 operands and results, the
  * arithmetic is ddmp_set_gemm_mode's: by default SPLIT-precision 16-bit MFMA products with f32 accumulation -- f32-class
  * accuracy, not bit-exact f32; mode 0 = f32-input MFMA, the strict one)

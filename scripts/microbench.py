@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|spline|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|spline|sage|all] [--rows N] [--iters K]
+sage (not part of all): the neighbour-statistics launches (ops.gather_stats, ops.gather_stats_bwd) at C = 64, 128,
+256 on the vertex graph of a torus with --rows vertices in RCB order, without loops, alternating in one loop: the fused mean + max
+and mean + max + min forward against the composition of ops.gather_max and one single-statistic launch per remaining aggregator,
+the single mean with root and bias against ops.gmm_fwd at K = 1, and the backward launch against ops.gather_max_bwd; the figures
+and the algorithmic byte counts go to --out (profiles/sage_microbench.txt).
 spline (not part of all): the two B-spline launches (ops.spline_fwd with the root block and the bias, ops.spline_bwd_node with dR;
 DESIGN.md 4.15) with dim = 3 and kernel_size 2 and 5 on the vertex graph of a torus with --rows vertices in RCB order, without loops,
 each alternating in one loop with gmm_fwd / gmm_bwd_node at K = 8 (the number of blocks an edge selects) on the same graph and
@@ -60,7 +65,7 @@ ap.add_argument("--widths", default="512,256,128,64,32")
 ap.add_argument("--rotate", type=int, default=1, help="spmm: cycle through this many (input, output) buffer sets so that narrow "
                 "widths are not served from the 256 MB MALL (a 1M x 32 float tensor is 128 MB)")
 ap.add_argument("--weighted", action="store_true", help="spmm: valued graph against the unvalued graph of the same mesh")
-ap.add_argument("--out", default=None, help="gat / gatv2 / transformer / resgated / feast / edge / gmm / spline: the file the figures are written to (default profiles/<what>_microbench.txt)")
+ap.add_argument("--out", default=None, help="gat / gatv2 / transformer / resgated / feast / edge / gmm / spline / sage: the file the figures are written to (default profiles/<what>_microbench.txt)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 n = a.rows
@@ -810,5 +815,69 @@ if a.what == "spline":
         print("\n".join(lines[-(len(alg) + 2):]), flush=True)
         del Bs, Hs, Rs, Gb, GHs, GRs, Ds, Out, G, Gg, ws, hh, yt
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "spline_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.what == "sage":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    g = ops.graph_for(ei, nn_, norm="gat", add_self_loops=False)
+    reps = max(a.iters, 20)
+    lines = ["neighbour statistics (SAGEConv) on the vertex graph of torus(%d, %d) in RCB order: N=%d, entries=%d (no loops), float32; "
+             "median of %d launches [min q1 q3 max], one HIP-event pair per launch, forms alternating in one loop, rotating buffer "
+             "sets; fused = ONE ops.gather_stats launch writing its blocks into one row buffer; composed = ops.gather_max for max + "
+             "one single-statistic ops.gather_stats launch per remaining aggregator (the sum of their medians); bytes = the "
+             "algorithmic counts of ops.py and DESIGN.md 4.16 (MB)" % (nu_, nv_, nn_, g.nnz, reps)]
+    print(lines[0], flush=True)
+    attr = torch.rand(g.nnz_in, 3, device=dev)
+    mu, sigma = torch.rand(1, 3, device=dev), torch.rand(1, 3, device=dev) + 0.5
+    for C in (64, 128, 256):
+        R = 2 if nn_ * C * 4 >= (1 << 29) else 4
+        Bs = [torch.randn(nn_, 2 * C, device=dev) for _ in range(R)]           # [L | R] of the transform-first form
+        Xs, Rs = [b[:, :C] for b in Bs], [b[:, C:] for b in Bs]
+        Ds = [torch.randn(nn_, 3 * C, device=dev) for _ in range(R)]           # [dS | dMx | dX0]
+        bias = torch.randn(C, device=dev)
+        O1, O2, O3 = (torch.empty(nn_, k * C, device=dev) for k in (1, 2, 3))
+        Oa, Ob = torch.empty(nn_, C, device=dev), torch.empty(nn_, C, device=dev)
+        G2 = torch.empty(nn_, 2 * C, device=dev)
+        saved = [ops.gather_stats(g, Xs[i], want=("mean", "max")) for i in range(R)]       # the saved state of a forward per buffer set
+        amx, inv = [s[1][1] for s in saved], [s[2] for s in saved]
+        amx_e = [ops.gather_max(g, Xs[i])[1] for i in range(R)]
+        q = alternate({
+            "mean": lambda i: ops.gather_stats(g, Xs[i], want=("mean",), out=Oa),
+            "min": lambda i: ops.gather_stats(g, Xs[i], want=("min",), out=Ob),
+            "gather_max": lambda i: ops.gather_max(g, Xs[i], out=O1),
+            "mean+max": lambda i: ops.gather_stats(g, Xs[i], want=("mean", "max"), out=O2),
+            "mean+max+min": lambda i: ops.gather_stats(g, Xs[i], want=("mean", "max", "min"), out=O3),
+            "mean+root+bias": lambda i: ops.gather_stats(g, Xs[i], want=("mean",), root=Rs[i], bias=bias, out=Oa),
+            "gmm_fwd K=1": lambda i: ops.gmm_fwd(g, Xs[i], attr, mu, sigma, 1, root=Rs[i], bias=bias, out=Ob),
+            "bwd max": lambda i: ops.gather_stats_bwd(g, dmx=Ds[i][:, C:2 * C], argmx=amx[i], out=Oa),
+            "gather_max_bwd": lambda i: ops.gather_max_bwd(g, Ds[i][:, C:2 * C], amx_e[i], out=G2),
+            "bwd mean+max+x0": lambda i: ops.gather_stats_bwd(g, ds=Ds[i][:, :C], invdeg=inv[i], dmx=Ds[i][:, C:2 * C], argmx=amx[i],
+                                                               dx0=Ds[i][:, 2 * C:], out=Oa),
+            "bwd mean+root": lambda i: ops.gather_stats_bwd(g, ds=Ds[i][:, :C], invdeg=inv[i], root=True, out=G2)}, reps, R)
+        feat, ent, node = 4.0 * nn_ * C, 4.0 * g.nnz, 4.0 * nn_
+        alg = {"mean": 2 * feat + 2 * ent + 2 * node, "min": 3 * feat + 2 * ent + node, "gather_max": 3 * feat + ent + node,
+               "mean+max": 4 * feat + 2 * ent + 2 * node, "mean+max+min": 6 * feat + 2 * ent + 2 * node,
+               "mean+root+bias": 3 * feat + 2 * ent + 2 * node, "gmm_fwd K=1": 3 * feat + ent + 4.0 * g.nnz_in * 4 + 3 * ent + node,
+               "bwd max": 3 * feat + 3 * ent + node, "gather_max_bwd": 4 * feat + ent + node,
+               "bwd mean+max+x0": 5 * feat + 3 * ent + 2 * node, "bwd mean+root": 4 * feat + 3 * ent + 2 * node}
+        lines.append("C=%d (%d buffer sets):" % (C, R))
+        for k in alg:
+            lines.append("  %-16s %s  %7.0f MB  %.2f TB/s alg" % (k, fmt(q[k]), alg[k] / 1e6, alg[k] / q[k][2] / 1e6))
+        c2, c3 = q["gather_max"][2] + q["mean"][2], q["gather_max"][2] + q["mean"][2] + q["min"][2]
+        lines.append("  fused mean+max %.0f us vs composed %.0f us: x%.2f;  fused mean+max+min %.0f us vs composed %.0f us: x%.2f;  "
+                     "mean+root+bias x%.2f of gmm_fwd K=1;  bwd max x%.2f of gather_max_bwd"
+                     % (q["mean+max"][2], c2, q["mean+max"][2] / c2, q["mean+max+min"][2], c3, q["mean+max+min"][2] / c3,
+                        q["mean+root+bias"][2] / q["gmm_fwd K=1"][2], q["bwd max"][2] / q["gather_max_bwd"][2]))
+        print("\n".join(lines[-(len(alg) + 2):]), flush=True)
+        del Bs, Xs, Rs, Ds, O1, O2, O3, Oa, Ob, G2, saved, amx, inv, amx_e
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sage_microbench.txt")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
