@@ -329,23 +329,110 @@ __global__ __launch_bounds__(256) void reduce_splits_kernel(const float* __restr
     }
 }
 
+#include "gemm_bf16x.inc"
+#include "gemm_ws.inc"
+#include "gemm_panel.inc"
+#include "gemm_rr.inc"
+
+}  // namespace
+
+// ================================================================================================ host side
+// ---------------------------------------------------------------- switches
+// Each environment variable is read once per process; only the GEMM arithmetic can change afterwards (ddmp_set_gemm_mode).
+static bool env_on(const char* name) {                          // unset, or anything but 0
+    const char* v = getenv(name);
+    return !(v && atoi(v) == 0);
+}
+static int64_t env_rows(const char* name, int64_t dflt) {
+    const char* v = getenv(name);
+    return (v && atoll(v) > 0) ? atoll(v) : dflt;
+}
+// DDMP_GEMM_PANEL=0: tiled kernels instead of the row-panel and the wgrad-panel kernels (A/B comparisons)
+static bool panel_enabled() {
+    static const bool e = env_on("DDMP_GEMM_PANEL");
+    return e;
+}
+// DDMP_GEMM_RR=0 keeps the row-panel kernel for the wide f16x3 GEMMs (A/B comparisons)
+static bool rr_enabled() {
+    static const bool e = env_on("DDMP_GEMM_RR");
+    return e;
+}
+// Row panels leave CUs idle on small inputs (one 512-thread workgroup per 128/256 rows): measured better from ~25k
+// rows (50k-face mesh 4.74 vs 5.02 ms/iteration, 13k-face mesh 4.08 vs 3.03); the wgrad panels from ~30k rows
+// (62k rows: 512x512 243 vs 291 us, 256x256 90 vs 87 us; row splits as short as 256 rows keep every CU busy).
+// (DDMP_PANEL_MIN_ROWS / DDMP_TN_PANEL_MIN_ROWS override the thresholds for A/B runs)
+static const int64_t kPanelMinRows = env_rows("DDMP_PANEL_MIN_ROWS", 20000);
+static const int64_t kTnPanelMinRows = env_rows("DDMP_TN_PANEL_MIN_ROWS", 30000);
+// The wide f16x3 outputs go to the row-register kernel (gemm_rr.inc: 128-row x 256-column work items, two workgroups per CU,
+// half the MFMA work of bf16x6): worth it from far fewer rows than the 512-thread row panels (DDMP_RR_MIN_ROWS)
+// (13,068-face mesh, replayed graph + two streams: 2.29 ms per iteration with 20000, 2.13 with 10000 -- NormalNet's 13k
+// rows on the kernel --, 2.21 with 3000: PosNet's 6.5k rows = 52 work items are too few for it; 49k faces: 4.04 / 4.00 / 3.92)
+static const int64_t kRRMinRows = env_rows("DDMP_RR_MIN_ROWS", 10000);
+
+// GEMM arithmetic: 13 (default) = f16x3 split MFMA in the row-panel kernels (gemm_f16s.inc), bf16x6 everywhere else;
+// 6 = bf16x6 split MFMA everywhere; both f32-class accuracy.  3 = bf16x3 (~2^-16), 0 = f32-input MFMA
+static int g_gemm_mode = -1, g_gemm_f16 = 0;
+static int gemm_mode() {
+    if (g_gemm_mode < 0) {
+        const char* e = getenv("DDMP_GEMM_MODE");
+        int m = e ? atoi(e) : 13;
+        g_gemm_f16 = m == 13 ? m : 0;
+        g_gemm_mode = (m == 0 || m == 3 || m == 6) ? m : 6;
+    }
+    return g_gemm_mode;
+}
+static int gemm_f16() {
+    (void)gemm_mode();
+    return g_gemm_f16;
+}
+extern "C" int ddmp_set_gemm_mode(int mode) {
+    if (mode != 0 && mode != 3 && mode != 6 && mode != 13) return DDMP_EINVAL;
+    g_gemm_f16 = mode > 10 ? mode : 0;
+    g_gemm_mode = mode > 10 ? 6 : mode;
+    return DDMP_OK;
+}
+extern "C" int ddmp_get_gemm_mode(void) { return gemm_f16() ? gemm_f16() : gemm_mode(); }
+// DDMP_GEMM_PANEL=0 / GEMM mode 0: the tiled wgrad kernels
+static bool tn_panel_enabled() { return panel_enabled() && gemm_mode() != 0; }
+
+static int device_cus() {
+    static int n = 0;
+    if (n == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+            n = v;
+        else
+            n = ddmp::kCu;
+    }
+    return n;
+}
+
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// A runtime value as a template argument: f(Const<V>) for the V among Vs that equals v (none of them: no call).
+template <int V>
+using Const = std::integral_constant<int, V>;
+template <int... Vs, class F>
+static inline void pick(int v, F&& f) {
+    (void)(... || (v == Vs ? (f(Const<Vs>{}), true) : false));
+}
+
+// ---------------------------------------------------------------- the split plan of a wgrad
 struct TnPlan {
     int T, n_tiles_m, n_tiles_k, n_splits, rows_per_split;      // T = 4: 512-thread panels of tm x tk (256 x 256; f16x3 route
     int tm, tk;                                                  // of round 4 also 256 x 128 | 128 x 256: gemm_tn_rm.hip)
 };
 
-bool tn_panel_enabled();
-int64_t tn_panel_min_rows();
-
 // narrow_panels: the caller takes the f16x3 route of gemm_tn_rm.hip, which also has 256 x 128 and 128 x 256 panels (the
 // 128 <-> 256 layers)
-TnPlan tn_plan(int64_t n_rows, int M, int K, bool narrow_panels = false) {
+static TnPlan tn_plan(int64_t n_rows, int M, int K, bool narrow_panels = false) {
     TnPlan p;
     p.T = (M >= 128 && K >= 128) ? 2 : 1;
     p.tm = p.tk = 0;
     const bool wide = M >= 256 && K >= 256;
     const bool narrow = narrow_panels && ((M >= 256 && K == 128) || (M == 128 && K >= 256));
-    if ((wide || narrow) && n_rows >= tn_panel_min_rows() && tn_panel_enabled()) {
+    if ((wide || narrow) && n_rows >= kTnPanelMinRows && tn_panel_enabled()) {
         p.T = 4;
         p.tm = M >= 256 ? 256 : 128;
         p.tk = K >= 256 ? 256 : 128;
@@ -385,42 +472,6 @@ TnPlan tn_plan(int64_t n_rows, int M, int K, bool narrow_panels = false) {
     p.n_splits = (int)cdiv(n_rows, rps);
     return p;
 }
-
-#include "gemm_bf16x.inc"
-#include "gemm_ws.inc"
-#include "gemm_panel.inc"
-#include "gemm_rr.inc"
-
-}  // namespace
-
-namespace {
-int64_t tn_panel_min_rows() {
-    static const int64_t v = [] {
-        const char* e = getenv("DDMP_TN_PANEL_MIN_ROWS");
-        return (e && atoll(e) > 0) ? (int64_t)atoll(e) : (int64_t)30000;
-    }();
-    return v;
-}
-bool tn_panel_enabled() {                                       // DDMP_GEMM_PANEL=0 / DDMP_GEMM_MODE=0: tiled kernels
-    const char* v = getenv("DDMP_GEMM_PANEL");
-    return !(v && atoi(v) == 0) && ddmp_get_gemm_mode() != 0;
-}
-}  // namespace
-
-static int device_cus() {
-    static int n = 0;
-    if (n == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            n = v;
-        else
-            n = ddmp::kCu;
-    }
-    return n;
-}
-
-static bool ws_enabled() { return true; }
 
 // ---------------------------------------------------------------- weights prepared once per iteration (round 3)
 // Every GEMM call used to split its weight matrix into 16-bit planes itself: absolute maximum (memset + kernel) + split
@@ -496,332 +547,100 @@ __global__ __launch_bounds__(256) void wprep_split_kernel(WPrepBatch b, const fl
     }
 }
 
-// persistent wave-specialised kernel: pre-split W planes [MD][KD], reduction length KD % 32 == 0, KD >= 96
-template <bool PRO>
-static void launch_ws(int mode, const float* A, int64_t lda, const float* W, int64_t ldw, int transpose, void* planes,
-                      float* Y, int64_t ldy, int n_rows, int KD, int MD, const float* bias, const float* ps,
-                      const float* psh, float slope, hipStream_t st, bool prepared) {
-    const int n_row_tiles = (int)ddmp::cdiv(n_rows, kBM);
-    const int TN = MD > 64 ? 2 : 1;
-    {
-        const int BN = 64 * TN;
-        const int64_t total = ddmp::cdiv(MD, BN) * BN * (int64_t)KD;
-        const int sgrid = (int)std::min<int64_t>(ddmp::cdiv(total, 256), 1024);
-        if (w_prepared(prepared, W, ldw, planes, kWTiled, mode == 6 ? 3 : 2, MD, KD, transpose, BN)) {
-        } else if (mode == 6)
-            hipLaunchKernelGGL((split_w_tiled_kernel<3>), dim3(sgrid), dim3(256), 0, st, W, ldw, MD, KD, transpose, BN, (__bf16*)planes);
-        else
-            hipLaunchKernelGGL((split_w_tiled_kernel<2>), dim3(sgrid), dim3(256), 0, st, W, ldw, MD, KD, transpose, BN, (__bf16*)planes);
-    }
-    const int n_col_tiles = (int)ddmp::cdiv(MD, 64 * TN);
-    const int total = (int)ddmp::cdiv(n_row_tiles, ddmp::kXcd) * ddmp::kXcd * n_col_tiles;
-    const int cus = device_cus() / ddmp::kXcd * ddmp::kXcd;
-    dim3 grid((unsigned)std::min(total, cus)), block(512);
-    const __bf16* Bp = (const __bf16*)planes;
-#define DDMP_WS(TN_, NT_)                                                                                      \
-    hipLaunchKernelGGL((gemm_rows_ws_kernel<TN_, NT_, PRO>), grid, block, 0, st, A, lda, Bp, Y, ldy, n_rows, KD, \
-                       MD, bias, ps, psh, slope, n_row_tiles, n_col_tiles)
-    if (TN == 2) {
-        if (mode == 6) DDMP_WS(2, 3); else DDMP_WS(2, 2);
-    } else {
-        if (mode == 6) DDMP_WS(1, 3); else DDMP_WS(1, 2);
-    }
-#undef DDMP_WS
-}
-// DDMP_GEMM_PANEL=0 disables the row-panel kernel (A/B comparisons)
-static bool panel_enabled() {
-    static int e = -1;
-    if (e < 0) {
-        const char* v = getenv("DDMP_GEMM_PANEL");
-        e = (v && atoi(v) == 0) ? 0 : 1;
-    }
-    return e == 1;
-}
-// Row panels leave CUs idle on small inputs (one 512-thread workgroup per 128/256 rows): measured better from ~25k
-// rows (50k-face mesh 4.74 vs 5.02 ms/iteration, 13k-face mesh 4.08 vs 3.03); the wgrad panels from ~30k rows
-// (62k rows: 512x512 243 vs 291 us, 256x256 90 vs 87 us; row splits as short as 256 rows keep every CU busy).
-static int64_t env_rows(const char* name, int64_t dflt) {
-    const char* v = getenv(name);
-    return (v && atoll(v) > 0) ? atoll(v) : dflt;
-}
-// (DDMP_PANEL_MIN_ROWS / DDMP_TN_PANEL_MIN_ROWS override the thresholds for A/B runs)
-static const int64_t kPanelMinRows = env_rows("DDMP_PANEL_MIN_ROWS", 20000);
-static const int64_t kTnPanelMinRows = env_rows("DDMP_TN_PANEL_MIN_ROWS", 30000);
-static int gemm_f16();
-static bool rr_enabled();
-// The wide f16x3 outputs go to the row-register kernel (gemm_rr.inc: 128-row x 256-column work items, two workgroups per CU,
-// half the MFMA work of bf16x6): worth it from far fewer rows than the 512-thread row panels (DDMP_RR_MIN_ROWS)
-// (13,068-face mesh, replayed graph + two streams: 2.29 ms per iteration with 20000, 2.13 with 10000 -- NormalNet's 13k
-// rows on the kernel --, 2.21 with 3000: PosNet's 6.5k rows = 52 work items are too few for it; 49k faces: 4.04 / 4.00 / 3.92)
-static const int64_t kRRMinRows = env_rows("DDMP_RR_MIN_ROWS", 10000);
-static inline int64_t panel_min_rows(int KD, int MD) {
-    return (MD > 128 && KD >= 64 && KD <= 512 && gemm_f16() && rr_enabled()) ? std::min(kRRMinRows, kPanelMinRows) : kPanelMinRows;
-}
-static inline bool panel_ok(int KD, int MD, const float* Y, int64_t ldy, const void* ws, size_t ws_bytes,
-                            int64_t n_rows) {
-    return panel_enabled() && n_rows >= panel_min_rows(KD, MD) && KD % 32 == 0 && KD >= 32 && (KD >= 64 || MD <= 128) &&
-           MD % 4 == 0 && MD >= 16 && MD <= 512 && ws &&
-           (reinterpret_cast<uintptr_t>(ws) & 15) == 0 && ws_bytes >= ddmp_gemm_rows_workspace_bytes(KD, MD) &&
-           ldy >= MD && Y;
-}
-// DDMP_GEMM_RR=0 keeps the row-panel kernel for the wide f16x3 GEMMs (A/B comparisons); DDMP_RR_MIN_ROWS: threshold
-static bool rr_enabled() {
-    static int e = -1;
-    if (e < 0) {
-        const char* v = getenv("DDMP_GEMM_RR");
-        e = (v && atoi(v) == 0) ? 0 : 1;
-    }
-    return e == 1;
-}
-// (given the f16x3 row-panel route: wide output, f16 mode) does the call take the row-register kernel?
-static inline bool rr_route_ok(int64_t n_rows, int KD, int64_t lda, int64_t lda2) {
-    return rr_enabled() && KD >= 64 && KD <= 512 && n_rows >= kRRMinRows &&
-           n_rows * lda * 4 < ((int64_t)1 << 32) && n_rows * lda2 * 4 < ((int64_t)1 << 32);      // (32-bit lane offsets)
-}
-// slot[0] = max |f(A)|, exactly (pre-pass)
-template <int PM>
-static void f16s_measure(const float* A, int64_t lda, const float* A2, int64_t lda2, int64_t n_rows, int C,
-                         const float* pa, const float* pb, const float* pk1, const float* pk0, float slope, float* slot,
-                         hipStream_t st) {
-    (void)hipMemsetAsync(slot, 0, 16, st);
-    const int64_t total = n_rows * (C / 4);
-    const int grid = (int)std::min<int64_t>(cdiv(total, 256 * 8), 8 * device_cus());
-    hipLaunchKernelGGL((f16s_absmax_kernel<PM>), dim3((unsigned)std::max(grid, 1)), dim3(256), 0, st, A, lda, A2, lda2,
-                       n_rows, C, pa, pb, pk1, pk0, slope, slot);
-}
-
-template <int PM>
-static void launch_panel(int mode, const float* A, int64_t lda, const float* A2, int64_t lda2, const float* W,
-                         int64_t ldw, int transpose, void* planes, float* Y, int64_t ldy, int n_rows, int KD, int MD,
-                         const float* bias, const float* ps, const float* psh, const float* pc1, const float* pc0,
-                         float slope, hipStream_t st, double* stats, double* sums, ddmp::CallCtx& ctx,
-                         const float* red_yp = nullptr, int64_t red_ldyp = 0,
-                         const float* const* red_bn4 = nullptr /* scale, shift, mean, rstd: stats = the backward reductions */) {
-    // wide outputs: 128 x 512 | 256 x 256 blocks (64 x 128 per wave); narrow outputs (MD <= 128): 512-row blocks, 64 x 32 NJ
-    const int WC = MD > 256 ? 4 : MD > 128 ? 2 : 1, WR = 8 / WC;
-    const int NJ = MD > 128 ? 4 : MD > 64 ? 4 : MD > 32 ? 2 : 1;
-    const int MP = 32 * NJ * WC, BMR = 64 * WR;
-    const int n_row_tiles = (int)ddmp::cdiv(n_rows, BMR);
-    const int64_t total = (int64_t)MP * KD;
-    const int sgrid = (int)std::min<int64_t>(ddmp::cdiv(total, 256), 1024);
-    dim3 grid((unsigned)std::min(n_row_tiles, device_cus())), block(512);
-    const int f16 = (mode == 6 && WC > 1 && lda % 4 == 0 && (PM != 2 || lda2 % 4 == 0)) ? gemm_f16() : 0;
-    if (f16) {
-        // two f16 planes of W * wscale; the scale and (without caller slots) the A operand's slot sit behind them
-        char* tail = (char*)planes + (size_t)2 * MP * KD * 2;
-        float* wscale = (float*)tail;
-        float* slot = ctx.slot_a ? ctx.slot_a : (float*)(tail + 16);
-        const bool prime = !ctx.slot_a || ctx.prime;
-        const bool w_ready = w_prepared(ctx.prepared, W, ldw, planes, kWPanelF16, 2, MD, KD, transpose, MP);
-        if (!w_ready) {
-            (void)hipMemsetAsync(wscale, 0, 4, st);               // = max |W| (the kernels derive the power of two)
-            hipLaunchKernelGGL(f16s_wmax_kernel, dim3((unsigned)std::min(transpose ? KD : MD, 128)), dim3(256), 0, st, W, ldw,
-                               transpose ? KD : MD, transpose ? MD : KD, wscale);
-        }
-        // PM = 2 with two column halves (512 <- 512 dgrad): the halves are separate, freely drifting workgroups and BOTH stream
-        // (dZ, Y) -- PMC: the family read 27.3 GB per step for 18.4 GB algorithmic, the second half's rows mostly missing the
-        // XCD's L2 -- while the row-panel kernel reads them once at the same speed (1499 vs 1490-1511 us): that shape keeps it.
-        const bool rr = rr_route_ok(n_rows, KD, lda, PM == 2 ? lda2 : 0) && !(PM == 2 && MD > kRRCols);
-        if (!w_ready)
-            hipLaunchKernelGGL((split_w_panel_kernel<2, _Float16>), dim3(sgrid), dim3(256), 0, st, W, ldw, MD, KD, transpose, MP,
-                               (_Float16*)planes, (const float*)wscale);
-        if (prime) f16s_measure<PM>(A, lda, A2, lda2, n_rows, KD, ps, psh, pc1, pc0, slope, slot, st);
-        const int target = prime ? kF16TargetExact : kF16TargetStale;
-        const void* Bh = planes;
-        if (rr) {
-            // row-register kernel (gemm_rr.inc): 128-row tiles x 256-column halves, two workgroups per CU
-            const int n_halves = MP / kRRCols;
-            const int tiles = (int)ddmp::cdiv(n_rows, kRRRows);
-            // (a multiple of 8 that covers all tiles in ONE round when they fit: surplus blocks return at once)
-            // (round 6: 3/4 or 1/2 of these slots measured +1.1 / +1.9 ms per step at 1M faces, nothing at 125k)
-            const int slots = std::max(8, std::min((tiles + 7) / 8 * 8, 2 * device_cus() / n_halves / 8 * 8));
-            dim3 rgrid((unsigned)(slots * n_halves)), rblock(256);
-            for (int heal = 0; heal <= (prime ? 0 : 1); ++heal) {
-                if (PM == 0 && stats && red_yp)
-                    hipLaunchKernelGGL((gemm_rr_kernel<0, 2, 3>), rgrid, rblock, 0, st, A, lda, A2, lda2, (const _Float16*)Bh, MP,
-                                       Y, ldy, n_rows, KD, MD, bias, ps, psh, pc1, pc0, slope, tiles, stats, slot,
-                                       (const float*)wscale, target, heal, red_yp, red_ldyp, red_bn4[0], red_bn4[1], red_bn4[2],
-                                       red_bn4[3]);
-                else if (PM != 2 && stats)
-                    hipLaunchKernelGGL((gemm_rr_kernel<PM == 2 ? 0 : PM, 1, 3>), rgrid, rblock, 0, st, A, lda, A2, lda2,
-                                       (const _Float16*)Bh, MP, Y, ldy, n_rows, KD, MD, bias, ps, psh, pc1, pc0, slope, tiles,
-                                       stats, slot, (const float*)wscale, target, heal);
-                else
-                    hipLaunchKernelGGL((gemm_rr_kernel<PM, 0, PM == 2 ? 2 : 3>), rgrid, rblock, 0, st, A, lda, A2, lda2, (const _Float16*)Bh, MP,
-                                       Y, ldy, n_rows, KD, MD, bias, ps, psh, pc1, pc0, slope, tiles, stats, slot,
-                                       (const float*)wscale, target, heal);
-            }
-            if (stats && sums) {
-                const size_t pbytes = ((size_t)tiles * 2 * 2 * MP * sizeof(double) + 255) / 256 * 256;
-                fpartials_reduce(stats, tiles * 2, MP, MD, (double*)((char*)stats + pbytes), sums, st, ctx.take_fin(MD));
-            }
-            return;
-        }
-#define DDMP_PANEL_H(WR_, WC_, AR_, HEAL_)                                                                        \
-    hipLaunchKernelGGL((gemm_panel_kernel<WR_, WC_, AR_, PM, 4>), grid, block, 0, st, A, lda, A2, lda2, Bh, Y, ldy,   \
-                       n_rows, KD, MD, bias, ps, psh, pc1, pc0, slope, n_row_tiles, stats, slot, (const float*)wscale, \
-                       target, HEAL_)
-        // stale scale in use: a second launch redoes the product if (and only if) an operand outgrew it (gemm_f16s.inc)
-        for (int heal = 0; heal <= (prime ? 0 : 1); ++heal) {
-            if (WC == 4) {
-                DDMP_PANEL_H(2, 4, 13, heal);
-            } else {
-                DDMP_PANEL_H(4, 2, 13, heal);
-            }
-        }
-#undef DDMP_PANEL_H
-        if (stats && sums) {
-            const size_t pbytes = ((size_t)n_row_tiles * WR * 2 * MP * sizeof(double) + 255) / 256 * 256;
-            fpartials_reduce(stats, n_row_tiles * WR, MP, MD, (double*)((char*)stats + pbytes), sums, st, ctx.take_fin(MD));
-        }
-        return;
-    }
-    if (w_prepared(ctx.prepared, W, ldw, planes, kWPanelB16, mode == 6 ? 3 : 2, MD, KD, transpose, MP)) {
-    } else if (mode == 6)
-        hipLaunchKernelGGL((split_w_panel_kernel<3, __bf16>), dim3(sgrid), dim3(256), 0, st, W, ldw, MD, KD, transpose, MP, (__bf16*)planes, (const float*)nullptr);
-    else
-        hipLaunchKernelGGL((split_w_panel_kernel<2, __bf16>), dim3(sgrid), dim3(256), 0, st, W, ldw, MD, KD, transpose, MP, (__bf16*)planes, (const float*)nullptr);
-    const void* Bp = planes;
-#define DDMP_PANEL(WR_, WC_, NT_, NJ_)                                                                            \
-    hipLaunchKernelGGL((gemm_panel_kernel<WR_, WC_, NT_, PM, NJ_>), grid, block, 0, st, A, lda, A2, lda2, Bp, Y, ldy, \
-                       n_rows, KD, MD, bias, ps, psh, pc1, pc0, slope, n_row_tiles, stats, (float*)nullptr,            \
-                       (const float*)nullptr, 0, 0)
-    if (WC == 1 && PM == 0 && stats && red_yp && (NJ == 4 || NJ == 2)) {
-        // narrow transform-first dgrads (outputs of 128 | 64 columns) with the next BatchNorm-backward reductions
-#define DDMP_PANEL_RS(NT_, NJ_)                                                                                     \
-    hipLaunchKernelGGL((gemm_panel_kernel<8, 1, NT_, 0, NJ_, true>), grid, block, 0, st, A, lda, A2, lda2, Bp, Y, ldy, \
-                       n_rows, KD, MD, bias, ps, psh, pc1, pc0, slope, n_row_tiles, stats, (float*)nullptr,            \
-                       (const float*)nullptr, 0, 0, red_yp, red_ldyp, red_bn4[0], red_bn4[1], red_bn4[2], red_bn4[3])
-        if constexpr (PM == 0) {
-            if (NJ == 4) {
-                if (mode == 6) DDMP_PANEL_RS(3, 4); else DDMP_PANEL_RS(2, 4);
-            } else {
-                if (mode == 6) DDMP_PANEL_RS(3, 2); else DDMP_PANEL_RS(2, 2);
-            }
-        }
-#undef DDMP_PANEL_RS
-    } else if (WC == 4) {
-        if (mode == 6) DDMP_PANEL(2, 4, 3, 4); else DDMP_PANEL(2, 4, 2, 4);
-    } else if (WC == 2) {
-        if (mode == 6) DDMP_PANEL(4, 2, 3, 4); else DDMP_PANEL(4, 2, 2, 4);
-    } else {
-        if (NJ == 4) {
-            if (mode == 6) DDMP_PANEL(8, 1, 3, 4); else DDMP_PANEL(8, 1, 2, 4);
-        } else if (NJ == 2) {
-            if (mode == 6) DDMP_PANEL(8, 1, 3, 2); else DDMP_PANEL(8, 1, 2, 2);
-        } else {
-            if (mode == 6) DDMP_PANEL(8, 1, 3, 1); else DDMP_PANEL(8, 1, 2, 1);
-        }
-    }
-#undef DDMP_PANEL
-    if (stats && sums) {
-        const size_t pbytes = ((size_t)n_row_tiles * WR * 2 * MP * sizeof(double) + 255) / 256 * 256;
-        fpartials_reduce(stats, n_row_tiles * WR, MP, MD, (double*)((char*)stats + pbytes), sums, st, ctx.take_fin(MD));
-    }
-}
-
-static inline bool ws_ok(int KD, int MD, const float* Y, int64_t ldy, const void* ws, size_t ws_bytes) {
-    return ws_enabled() && KD % 32 == 0 && KD >= 96 && MD % 4 == 0 && MD <= 1024 && ldy % 4 == 0 &&
-           (reinterpret_cast<uintptr_t>(Y) & 15) == 0 && ws && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 &&
-           ws_bytes >= ddmp_gemm_rows_workspace_bytes(KD, MD);
-}
-
-// GEMM arithmetic: 13 (default) = f16x3 split MFMA in the row-panel kernels (gemm_f16s.inc), bf16x6 everywhere else;
-// 6 = bf16x6 split MFMA everywhere; both f32-class accuracy.  3 = bf16x3 (~2^-16), 0 = f32-input MFMA
-static int g_gemm_mode = -1, g_gemm_f16 = 0;
-static int gemm_mode() {
-    if (g_gemm_mode < 0) {
-        const char* e = getenv("DDMP_GEMM_MODE");
-        int m = e ? atoi(e) : 13;
-        g_gemm_f16 = m == 13 ? m : 0;
-        g_gemm_mode = (m == 0 || m == 3 || m == 6) ? m : 6;
-    }
-    return g_gemm_mode;
-}
-static int gemm_f16() {
-    (void)gemm_mode();
-    return g_gemm_f16;
-}
-extern "C" int ddmp_set_gemm_mode(int mode) {
-    if (mode != 0 && mode != 3 && mode != 6 && mode != 13) return DDMP_EINVAL;
-    g_gemm_f16 = mode > 10 ? mode : 0;
-    g_gemm_mode = mode > 10 ? 6 : mode;
-    return DDMP_OK;
-}
-extern "C" int ddmp_get_gemm_mode(void) { return gemm_f16() ? gemm_f16() : gemm_mode(); }
-
-extern "C" int ddmp_gemm_scales_roll(float* slots, int n_slots, ddmp_stream stream) {
-    ARG_TRY(slots && n_slots > 0);
-    hipLaunchKernelGGL(f16s_roll_kernel, dim3((unsigned)cdiv(n_slots, 64)), dim3(64), 0, (hipStream_t)stream, slots, n_slots);
-    LAUNCH_TRY();
-    return DDMP_OK;
-}
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 extern "C" size_t ddmp_gemm_rows_workspace_bytes(int K, int M) {
     if (K <= 0 || M <= 0) return 0;
     const size_t kp = ((size_t)K + 127) / 128 * 128, mp = ((size_t)M + 127) / 128 * 128;
     return 3 * kp * mp * 2;                                     // three bf16 planes of W, tile-padded
 }
+static inline bool planes_fit(const void* planes, size_t bytes, int KD, int MD) {
+    return planes && aligned16(planes) && bytes >= ddmp_gemm_rows_workspace_bytes(KD, MD);
+}
 
-// bf16 modes with a workspace: W is split ONCE here instead of by every row-tile workgroup
-static bool presplit_w(const float* W, int64_t ldw, int M, int K, int transpose, void* ws, size_t ws_bytes,
-                       hipStream_t st, bool prepared) {
-    const int mode = gemm_mode();
-    const int RK = transpose ? M : K;                           // reduction length of the consumer
-    if (mode == 0 || !ws || ws_bytes < ddmp_gemm_rows_workspace_bytes(K, M) || RK % 8 != 0 ||
-        (reinterpret_cast<uintptr_t>(ws) & 15))
-        return false;
-    const int grid = (int)std::min<int64_t>(cdiv((int64_t)M * K, 256), 1024);
-    if (w_prepared(prepared, W, ldw, ws, kWPlain, mode == 6 ? 3 : 2, M, K, transpose, 0)) return true;
-    if (mode == 6)
-        hipLaunchKernelGGL((split_w_kernel<3>), dim3(grid), dim3(256), 0, st, W, ldw, M, K, transpose, (__bf16*)ws);
-    else
-        hipLaunchKernelGGL((split_w_kernel<2>), dim3(grid), dim3(256), 0, st, W, ldw, M, K, transpose, (__bf16*)ws);
-    return hipGetLastError() == hipSuccess;
+// ---------------------------------------------------------------- the route of a row product  Y[n, MD] = f(A[n, KD]) . B
+// ONE function decides which kernel family runs, with what geometry, and which plane layout of B it reads (the table of
+// DESIGN.md 4.1 is written from it).  The five row entry points and ddmp_gemm_prepare_weights all ask it, so prepared planes
+// are the planes the call reads.
+enum { kRowPanelF16 = 1, kRowPanelB16, kRowTiled, kRowPresplit, kRowPlain };    // in order of preference
+struct RowRoute {
+    int family;
+    int WC, WR, NJ, MP;      // row panels: waves across x down (64 * WR rows per block), 32-column groups per wave, padded width
+    int BN;                  // tiled and plain kernels: columns per tile (64 | 128)
+    int nterm;               // split terms of B: 3 | 2 (f16: two planes); 0 = f32-input MFMA, B unsplit
+    int kind, P;             // the plane layout wanted: kW* (0: none) and its P
+    bool rr;                 // kRowPanelF16: shape and rows suit the row-register kernel (rr_kernel_ok)
+};
+// shapes the row-panel kernels take: whole 32-wide k steps, outputs of 16 ... 512 columns (the wide blocks stage 64 k at a time)
+static inline bool panel_shape_ok(int KD, int MD) {
+    return KD % 32 == 0 && KD >= 32 && (KD >= 64 || MD <= 128) && MD % 4 == 0 && MD >= 16 && MD <= 512;
+}
+// mode: 0 | 3 | 6; f16: mode 13 (f16x3 in the wide row panels, mode 6 elsewhere); planes_ok: planes_fit() of the workspace;
+// after: only families behind this one (a call whose operands do not fit a family: row_route_call)
+static RowRoute row_route(int64_t n_rows, int KD, int MD, bool has_pro, int mode, bool f16, bool planes_ok, int after = 0) {
+    RowRoute r{};
+    r.BN = MD > 64 ? 128 : 64;
+    r.family = kRowPlain;
+    // f32-input MFMA: mode 0, and a prologue over more columns than the split kernels stage coefficients for.  No planes.
+    if (mode == 0 || (has_pro && KD > kMaxProK)) return r;
+    r.nterm = mode == 6 ? 3 : 2;
+    if (!planes_ok) return r;                                    // the kernel splits B tile by tile itself
+    // wide outputs: 128 x 512 | 256 x 256 blocks (64 x 128 per wave), f16x3 in mode 13, from fewer rows where the row-register
+    // kernel takes them; narrow outputs (MD <= 128): 512-row blocks, 64 x 32 NJ per wave
+    const bool wide = MD > 128;
+    const bool rr_shape = wide && f16 && rr_enabled() && KD >= 64 && KD <= 512;
+    const int64_t min_rows = rr_shape ? std::min(kRRMinRows, kPanelMinRows) : kPanelMinRows;
+    if (after < kRowPanelB16 && panel_enabled() && n_rows >= min_rows && panel_shape_ok(KD, MD)) {
+        r.WC = MD > 256 ? 4 : wide ? 2 : 1;
+        r.WR = 8 / r.WC;
+        r.NJ = MD > 64 ? 4 : MD > 32 ? 2 : 1;
+        r.P = r.MP = 32 * r.NJ * r.WC;
+        if (wide && f16 && after < kRowPanelF16) {
+            r.family = kRowPanelF16, r.kind = kWPanelF16, r.nterm = 2;
+            r.rr = rr_shape && n_rows >= kRRMinRows;
+        } else {
+            r.family = kRowPanelB16, r.kind = kWPanelB16;
+        }
+        return r;
+    }
+    // persistent wave-specialised kernel: whole 32-wide k steps, at least three of them
+    if (after < kRowTiled && KD % 32 == 0 && KD >= 96 && MD % 4 == 0 && MD <= 1024) {
+        r.family = kRowTiled, r.kind = kWTiled, r.P = r.BN;
+        return r;
+    }
+    if (KD % 8 == 0) r.family = kRowPresplit, r.kind = kWPlain;  // B split ONCE instead of by every row-tile workgroup
+    return r;
+}
+// What only a call knows: the f16x3 kernels read A (and A2) as float4, the tiled kernel writes Y as float4.
+// (ddmp_gemm_prepare_weights sees no call and assumes both hold: planes it makes for a call where they do not are re-made.)
+static inline bool route_fits_call(const RowRoute& r, const float* Y, int64_t ldy, int64_t lda, int64_t lda2) {
+    if (r.family == kRowPanelF16) return lda % 4 == 0 && lda2 % 4 == 0;
+    if (r.family == kRowTiled) return ldy % 4 == 0 && aligned16(Y);
+    return true;
+}
+static RowRoute row_route_call(int64_t n_rows, int KD, int MD, bool has_pro, const void* ws, size_t ws_bytes, const float* Y,
+                               int64_t ldy, int64_t lda, int64_t lda2) {
+    const bool planes_ok = planes_fit(ws, ws_bytes, KD, MD);
+    RowRoute r = row_route(n_rows, KD, MD, has_pro, gemm_mode(), gemm_f16() != 0, planes_ok);
+    while (!route_fits_call(r, Y, ldy, lda, lda2))
+        r = row_route(n_rows, KD, MD, has_pro, gemm_mode(), gemm_f16() != 0, planes_ok, r.family);
+    return r;
+}
+// Within kRowPanelF16: the row-register kernel (gemm_rr.inc) or the row-panel kernel?  dual = the (dZ, Yb) operand pair with
+// two column halves (512 <- 512 dgrad): the halves are separate, freely drifting workgroups and BOTH stream (dZ, Y) -- PMC: the
+// family read 27.3 GB per step for 18.4 GB algorithmic, the second half's rows mostly missing the XCD's L2 -- while the
+// row-panel kernel reads them once at the same speed (1499 vs 1490-1511 us): that shape keeps it.
+static inline bool rr_kernel_ok(const RowRoute& r, bool dual, int64_t n_rows, int64_t lda, int64_t lda2) {
+    return r.rr && !(dual && r.MP > kRRCols) && n_rows * lda * 4 < ((int64_t)1 << 32) &&
+           n_rows * lda2 * 4 < ((int64_t)1 << 32);              // (32-bit lane offsets)
 }
 
 // The plane layout the entry points below will want for W [M,K] in the forward (form 0: Y[n,M] = f(A[n,K]) . W^T) or dgrad
-// (form 1: Y[n,K] = A[n,M] . W) product over n_rows rows -- the same tests, in the same order, as those entry points
-// (which stay the ground truth: a layout they do not want is simply ignored and re-made).
+// (form 1: Y[n,K] = A[n,M] . W) product over n_rows rows.
 static WPrepDesc plan_w(int form, int64_t n_rows, const float* W, int64_t ldw, int M, int K, int has_pro, void* planes,
                         size_t planes_bytes) {
-    WPrepDesc d{W, planes, ldw, 0, 0, 0, 0, 0, 0};
-    const int mode = gemm_mode();
-    if (mode == 0 || !planes || (reinterpret_cast<uintptr_t>(planes) & 15) || planes_bytes < ddmp_gemm_rows_workspace_bytes(K, M))
-        return d;
     const int KD = form ? M : K, MD = form ? K : M;              // reduction length / output width
-    d.transpose = form ? 1 : 0;
-    d.nterm = mode == 6 ? 3 : 2;
-    float dummy;
-    if (!(has_pro && KD > 512) && panel_ok(KD, MD, &dummy, MD, planes, planes_bytes, n_rows)) {
-        const int WC = MD > 256 ? 4 : MD > 128 ? 2 : 1;
-        const int NJ = MD > 128 ? 4 : MD > 64 ? 4 : MD > 32 ? 2 : 1;
-        d.P = 32 * NJ * WC;
-        d.MD = MD;
-        d.KD = KD;
-        if (mode == 6 && WC > 1 && gemm_f16()) {
-            d.kind = kWPanelF16;
-            d.nterm = 2;
-        } else {
-            d.kind = kWPanelB16;
-        }
-        return d;
-    }
-    if (ws_ok(KD, MD, (const float*)nullptr, 4, planes, planes_bytes)) {
-        d.kind = kWTiled;
-        d.MD = MD;
-        d.KD = KD;
-        d.P = 64 * (MD > 64 ? 2 : 1);
-        return d;
-    }
-    if (KD % 8 == 0) {                                           // presplit_w(W, ldw, M, K, transpose, ...)
-        d.kind = kWPlain;
-        d.MD = M;
-        d.KD = K;
-    }
-    return d;
+    const RowRoute r = row_route(n_rows, KD, MD, has_pro != 0, gemm_mode(), gemm_f16() != 0, planes_fit(planes, planes_bytes, KD, MD));
+    const bool plain = r.kind == kWPlain;                        // (split_w_kernel takes W's own shape and the orientation)
+    return WPrepDesc{W, planes, ldw, r.kind, r.nterm, plain ? M : MD, plain ? K : KD, form ? 1 : 0, r.P};
 }
 
 // the owner of a plane buffer is about to free it (or to stop maintaining it): drop what this thread recorded for it, so that
@@ -858,6 +677,232 @@ extern "C" int ddmp_gemm_prepare_weights(int n, const float* const* W, const int
     return DDMP_OK;
 }
 
+extern "C" int ddmp_gemm_scales_roll(float* slots, int n_slots, ddmp_stream stream) {
+    ARG_TRY(slots && n_slots > 0);
+    hipLaunchKernelGGL(f16s_roll_kernel, dim3((unsigned)cdiv(n_slots, 64)), dim3(64), 0, (hipStream_t)stream, slots, n_slots);
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
+// slot[0] = max |f(A)|, exactly (pre-pass)
+template <int PM>
+static void f16s_measure(const float* A, int64_t lda, const float* A2, int64_t lda2, int64_t n_rows, int C,
+                         const float* pa, const float* pb, const float* pk1, const float* pk0, float slope, float* slot,
+                         hipStream_t st) {
+    (void)hipMemsetAsync(slot, 0, 16, st);
+    const int64_t total = n_rows * (C / 4);
+    const int grid = (int)std::min<int64_t>(cdiv(total, 256 * 8), 8 * device_cus());
+    hipLaunchKernelGGL((f16s_absmax_kernel<PM>), dim3((unsigned)std::max(grid, 1)), dim3(256), 0, st, A, lda, A2, lda2,
+                       n_rows, C, pa, pb, pk1, pk0, slope, slot);
+}
+
+// ---------------------------------------------------------------- the launches of the row families
+// B = W^T (transpose = 0: W is [MD][KD]) or W (transpose = 1: W is [KD][MD]); `planes` = the workspace planes_fit() took
+struct RowArgs {
+    const float* A;
+    int64_t lda;
+    const float* W;
+    int64_t ldw;
+    int transpose;
+    void* planes;
+    float* Y;
+    int64_t ldy;
+    int n_rows, KD, MD;
+    const float *bias, *ps, *psh;                                // epilogue bias; prologue on A (PM = 1: scale, shift; PM = 2: a, b)
+    float slope;
+};
+
+// the five row-panel geometries as template arguments: f(WR, WC, NJ)
+template <class F>
+static inline void panel_geometry(const RowRoute& r, F&& f) {
+    if (r.WC == 4) f(Const<2>{}, Const<4>{}, Const<4>{});
+    else if (r.WC == 2) f(Const<4>{}, Const<2>{}, Const<4>{});
+    else if (r.NJ == 4) f(Const<8>{}, Const<1>{}, Const<4>{});
+    else if (r.NJ == 2) f(Const<8>{}, Const<1>{}, Const<2>{});
+    else f(Const<8>{}, Const<1>{}, Const<1>{});
+}
+
+// PM: the operand prologue -- 0 none, 1 BatchNorm+LeakyReLU, 2 the BatchNorm+LeakyReLU backward of (A = dZ, A2 = Yb).
+// stats (+ sums): the column sums of Y and Y^2; with red_yp the backward reductions of Y as the gradient behind the previous
+// layer's BatchNorm+LeakyReLU (red_bn4 = its scale, shift, mean, rstd)
+template <int PM>
+static void launch_panel(const RowRoute& r, const RowArgs& g, const float* A2, int64_t lda2, const float* pc1, const float* pc0,
+                         hipStream_t st, double* stats, double* sums, ddmp::CallCtx& ctx, const float* red_yp = nullptr,
+                         int64_t red_ldyp = 0, const float* const* red_bn4 = nullptr) {
+    const float* A = g.A; const float* W = g.W; float* Y = g.Y; void* planes = g.planes;
+    const float *bias = g.bias, *ps = g.ps, *psh = g.psh;
+    const int64_t lda = g.lda, ldw = g.ldw, ldy = g.ldy;
+    const int n_rows = g.n_rows, KD = g.KD, MD = g.MD, transpose = g.transpose, MP = r.MP;
+    const float slope = g.slope;
+    const int n_row_tiles = (int)ddmp::cdiv(n_rows, 64 * r.WR);
+    const int sgrid = (int)std::min<int64_t>(ddmp::cdiv((int64_t)MP * KD, 256), 1024);
+    dim3 grid((unsigned)std::min(n_row_tiles, device_cus())), block(512);
+    int stat_groups = n_row_tiles * r.WR;                        // records of column sums the kernel leaves in `stats`
+    if (r.family == kRowPanelF16) {
+        // two f16 planes of W * wscale; the scale and (without caller slots) the A operand's slot sit behind them
+        char* tail = (char*)planes + (size_t)2 * MP * KD * 2;
+        float* wscale = (float*)tail;
+        float* slot = ctx.slot_a ? ctx.slot_a : (float*)(tail + 16);
+        const bool prime = !ctx.slot_a || ctx.prime;
+        if (!w_prepared(ctx.prepared, W, ldw, planes, kWPanelF16, 2, MD, KD, transpose, MP)) {
+            (void)hipMemsetAsync(wscale, 0, 4, st);               // = max |W| (the kernels derive the power of two)
+            hipLaunchKernelGGL(f16s_wmax_kernel, dim3((unsigned)std::min(transpose ? KD : MD, 128)), dim3(256), 0, st, W, ldw,
+                               transpose ? KD : MD, transpose ? MD : KD, wscale);
+            hipLaunchKernelGGL((split_w_panel_kernel<2, _Float16>), dim3(sgrid), dim3(256), 0, st, W, ldw, MD, KD, transpose, MP,
+                               (_Float16*)planes, (const float*)wscale);
+        }
+        if (prime) f16s_measure<PM>(A, lda, A2, lda2, n_rows, KD, ps, psh, pc1, pc0, slope, slot, st);
+        const int target = prime ? kF16TargetExact : kF16TargetStale;
+        const void* Bh = planes;
+        // stale scale in use: a second launch redoes the product if (and only if) an operand outgrew it (gemm_f16s.inc)
+        const int n_launch = prime ? 1 : 2;
+        if (rr_kernel_ok(r, PM == 2, n_rows, lda, lda2)) {
+            // row-register kernel (gemm_rr.inc): 128-row tiles x 256-column halves, two workgroups per CU
+            const int n_halves = MP / kRRCols;
+            const int tiles = (int)ddmp::cdiv(n_rows, kRRRows);
+            // (a multiple of 8 that covers all tiles in ONE round when they fit: surplus blocks return at once)
+            // (round 6: 3/4 or 1/2 of these slots measured +1.1 / +1.9 ms per step at 1M faces, nothing at 125k)
+            const int slots = std::max(8, std::min((tiles + 7) / 8 * 8, 2 * device_cus() / n_halves / 8 * 8));
+            dim3 rgrid((unsigned)(slots * n_halves)), rblock(256);
+            for (int heal = 0; heal < n_launch; ++heal) {
+                if (PM == 0 && stats && red_yp)
+                    hipLaunchKernelGGL((gemm_rr_kernel<0, 2, 3>), rgrid, rblock, 0, st, A, lda, A2, lda2, (const _Float16*)Bh, MP,
+                                       Y, ldy, n_rows, KD, MD, bias, ps, psh, pc1, pc0, slope, tiles, stats, slot,
+                                       (const float*)wscale, target, heal, red_yp, red_ldyp, red_bn4[0], red_bn4[1], red_bn4[2],
+                                       red_bn4[3]);
+                else if (PM != 2 && stats)
+                    hipLaunchKernelGGL((gemm_rr_kernel<PM == 2 ? 0 : PM, 1, 3>), rgrid, rblock, 0, st, A, lda, A2, lda2,
+                                       (const _Float16*)Bh, MP, Y, ldy, n_rows, KD, MD, bias, ps, psh, pc1, pc0, slope, tiles,
+                                       stats, slot, (const float*)wscale, target, heal);
+                else
+                    hipLaunchKernelGGL((gemm_rr_kernel<PM, 0, PM == 2 ? 2 : 3>), rgrid, rblock, 0, st, A, lda, A2, lda2, (const _Float16*)Bh, MP,
+                                       Y, ldy, n_rows, KD, MD, bias, ps, psh, pc1, pc0, slope, tiles, stats, slot,
+                                       (const float*)wscale, target, heal);
+            }
+            stat_groups = tiles * 2;
+        } else {
+            for (int heal = 0; heal < n_launch; ++heal)
+                panel_geometry(r, [&](auto wr, auto wc, auto nj) {
+                    constexpr int WR = decltype(wr)::value, WC = decltype(wc)::value, NJ = decltype(nj)::value;
+                    if constexpr (WC > 1)                        // (the f16x3 panels are the wide ones)
+                        hipLaunchKernelGGL((gemm_panel_kernel<WR, WC, 13, PM, NJ>), grid, block, 0, st, A, lda, A2, lda2, Bh, Y, ldy,
+                                           n_rows, KD, MD, bias, ps, psh, pc1, pc0, slope, n_row_tiles, stats, slot,
+                                           (const float*)wscale, target, heal);
+                });
+        }
+    } else {
+        if (w_prepared(ctx.prepared, W, ldw, planes, kWPanelB16, r.nterm, MD, KD, transpose, MP)) {
+        } else if (r.nterm == 3)
+            hipLaunchKernelGGL((split_w_panel_kernel<3, __bf16>), dim3(sgrid), dim3(256), 0, st, W, ldw, MD, KD, transpose, MP, (__bf16*)planes, (const float*)nullptr);
+        else
+            hipLaunchKernelGGL((split_w_panel_kernel<2, __bf16>), dim3(sgrid), dim3(256), 0, st, W, ldw, MD, KD, transpose, MP, (__bf16*)planes, (const float*)nullptr);
+        const void* Bp = planes;
+        // narrow transform-first dgrads (outputs of 128 | 64 columns) with the next BatchNorm-backward reductions: RS epilogue
+        const bool rs = PM == 0 && stats && red_yp && r.WC == 1 && r.NJ >= 2;
+        panel_geometry(r, [&](auto wr, auto wc, auto nj) {
+            pick<2, 3>(r.nterm, [&](auto nt) {
+                constexpr int WR = decltype(wr)::value, WC = decltype(wc)::value, NJ = decltype(nj)::value, NT = decltype(nt)::value;
+                if constexpr (PM == 0 && WC == 1 && NJ >= 2) {
+                    if (rs) {
+                        hipLaunchKernelGGL((gemm_panel_kernel<8, 1, NT, 0, NJ, true>), grid, block, 0, st, A, lda, A2, lda2, Bp, Y, ldy,
+                                           n_rows, KD, MD, bias, ps, psh, pc1, pc0, slope, n_row_tiles, stats, (float*)nullptr,
+                                           (const float*)nullptr, 0, 0, red_yp, red_ldyp, red_bn4[0], red_bn4[1], red_bn4[2], red_bn4[3]);
+                        return;
+                    }
+                }
+                hipLaunchKernelGGL((gemm_panel_kernel<WR, WC, NT, PM, NJ>), grid, block, 0, st, A, lda, A2, lda2, Bp, Y, ldy,
+                                   n_rows, KD, MD, bias, ps, psh, pc1, pc0, slope, n_row_tiles, stats, (float*)nullptr,
+                                   (const float*)nullptr, 0, 0);
+            });
+        });
+    }
+    if (stats && sums) {
+        const size_t pbytes = ((size_t)stat_groups * 2 * MP * sizeof(double) + 255) / 256 * 256;
+        fpartials_reduce(stats, stat_groups, MP, MD, (double*)((char*)stats + pbytes), sums, st, ctx.take_fin(MD));
+    }
+}
+
+// persistent wave-specialised kernel on tiled planes [cdiv(MD, BN)][KD][BN]
+template <bool PRO>
+static void launch_tiled(const RowRoute& r, const RowArgs& g, hipStream_t st, bool prepared) {
+    const int n_row_tiles = (int)ddmp::cdiv(g.n_rows, kBM), n_col_tiles = (int)ddmp::cdiv(g.MD, r.BN);
+    const int64_t elems = (int64_t)n_col_tiles * r.BN * g.KD;
+    const int sgrid = (int)std::min<int64_t>(ddmp::cdiv(elems, 256), 1024);
+    if (w_prepared(prepared, g.W, g.ldw, g.planes, kWTiled, r.nterm, g.MD, g.KD, g.transpose, r.BN)) {
+    } else if (r.nterm == 3)
+        hipLaunchKernelGGL((split_w_tiled_kernel<3>), dim3(sgrid), dim3(256), 0, st, g.W, g.ldw, g.MD, g.KD, g.transpose, r.BN, (__bf16*)g.planes);
+    else
+        hipLaunchKernelGGL((split_w_tiled_kernel<2>), dim3(sgrid), dim3(256), 0, st, g.W, g.ldw, g.MD, g.KD, g.transpose, r.BN, (__bf16*)g.planes);
+    const int total = (int)ddmp::cdiv(n_row_tiles, ddmp::kXcd) * ddmp::kXcd * n_col_tiles;
+    const int cus = device_cus() / ddmp::kXcd * ddmp::kXcd;
+    dim3 grid((unsigned)std::min(total, cus)), block(512);
+    pick<1, 2>(r.BN / 64, [&](auto tn) {
+        pick<2, 3>(r.nterm, [&](auto nt) {
+            hipLaunchKernelGGL((gemm_rows_ws_kernel<decltype(tn)::value, decltype(nt)::value, PRO>), grid, block, 0, st, g.A, g.lda,
+                               (const __bf16*)g.planes, g.Y, g.ldy, g.n_rows, g.KD, g.MD, g.bias, g.ps, g.psh, g.slope, n_row_tiles,
+                               n_col_tiles);
+        });
+    });
+}
+
+// 128 x BN tiles, one 256-thread workgroup each: on planes split ONCE here (kRowPresplit: [MD][KD], the reduction index
+// contiguous, so the kernel runs its row-major form on them), or on W itself, split tile by tile (nterm 3 | 2) or not at all
+static void launch_plain(const RowRoute& r, const RowArgs& g, hipStream_t st, bool prepared) {
+    const int n_row_tiles = (int)cdiv(g.n_rows, kBM), n_col_tiles = (int)cdiv(g.MD, r.BN);
+    dim3 grid((unsigned)(cdiv(n_row_tiles, kXcd) * kXcd * n_col_tiles)), block(256);
+    const bool pre = r.family == kRowPresplit;
+    const int M = g.transpose ? g.KD : g.MD, K = g.transpose ? g.MD : g.KD;      // W as stored: [M][K]
+    if (pre && !w_prepared(prepared, g.W, g.ldw, g.planes, kWPlain, r.nterm, M, K, g.transpose, 0)) {
+        const int sgrid = (int)std::min<int64_t>(cdiv((int64_t)M * K, 256), 1024);
+        if (r.nterm == 3)
+            hipLaunchKernelGGL((split_w_kernel<3>), dim3(sgrid), dim3(256), 0, st, g.W, g.ldw, M, K, g.transpose, (__bf16*)g.planes);
+        else
+            hipLaunchKernelGGL((split_w_kernel<2>), dim3(sgrid), dim3(256), 0, st, g.W, g.ldw, M, K, g.transpose, (__bf16*)g.planes);
+    }
+    const float* B = pre ? (const float*)g.planes : g.W;
+    const int64_t ldb = (pre && g.transpose) ? (int64_t)g.KD : g.ldw;
+    pick<1, 2>(r.BN / 64, [&](auto tn) {
+        pick<0, 1>(g.ps != nullptr, [&](auto pro) {
+            pick<0, 1>(g.transpose && !pre, [&](auto kmajor) {
+                constexpr int TN = decltype(tn)::value;
+                constexpr bool PRO = decltype(pro)::value != 0, KMAJOR = decltype(kmajor)::value != 0;
+                if constexpr (!(KMAJOR && PRO)) {                // (no entry point has a prologue on the dgrad form)
+                    if (r.nterm == 0)
+                        hipLaunchKernelGGL((gemm_rows_kernel<TN, KMAJOR, PRO>), grid, block, 0, st, g.A, g.lda, B, ldb, g.Y, g.ldy,
+                                           g.n_rows, g.KD, g.MD, g.bias, g.ps, g.psh, g.slope, n_row_tiles, n_col_tiles);
+                    pick<2, 3>(r.nterm, [&](auto nt) {
+                        pick<0, 1>(g.KD % 16 != 0, [&](auto ktail) {
+                            pick<0, 1>(pre, [&](auto bpre) {
+                                constexpr bool BPRE = decltype(bpre)::value != 0;
+                                if constexpr (!(KMAJOR && BPRE))
+                                    hipLaunchKernelGGL((gemm_rows_bf16_kernel<TN, decltype(nt)::value, KMAJOR, PRO,
+                                                                              decltype(ktail)::value != 0, BPRE>),
+                                                       grid, block, 0, st, g.A, g.lda, B, ldb, g.Y, g.ldy, g.n_rows, g.KD, g.MD, g.bias,
+                                                       g.ps, g.psh, g.slope, n_row_tiles, n_col_tiles);
+                            });
+                        });
+                    });
+                }
+            });
+        });
+    });
+}
+
+static int rows_product(const RowRoute& r, const RowArgs& g, ddmp_stream stream, double* stats, double* sums, ddmp::CallCtx& ctx) {
+    hipStream_t st = (hipStream_t)stream;
+    if (r.family <= kRowPanelB16) {
+        if (g.ps) launch_panel<1>(r, g, nullptr, 0, nullptr, nullptr, st, stats, sums, ctx);
+        else launch_panel<0>(r, g, nullptr, 0, nullptr, nullptr, st, stats, sums, ctx);
+    } else if (r.family == kRowTiled) {
+        if (g.ps) launch_tiled<true>(r, g, st, ctx.prepared);
+        else launch_tiled<false>(r, g, st, ctx.prepared);
+    } else {
+        launch_plain(r, g, st, ctx.prepared);
+    }
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
+
+// ---------------------------------------------------------------- row entry points
 int ddmp_gemm_nt_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y, int64_t ldy, int64_t n_rows, int K,
                      int M, const float* bias, const float* pro_scale, const float* pro_shift, float slope, void* workspace,
                      size_t workspace_bytes, ddmp_stream stream, ddmp::CallCtx& ctx) {
@@ -866,54 +911,9 @@ int ddmp_gemm_nt_f32(const float* A, int64_t lda, const float* W, int64_t ldw, f
     ARG_TRY(aligned16(A) && aligned16(W));
     ARG_TRY((pro_scale == nullptr) == (pro_shift == nullptr));
     ARG_TRY(!pro_scale || (aligned16(pro_scale) && aligned16(pro_shift)));
-    hipStream_t st = (hipStream_t)stream;
-    const int n_row_tiles = (int)cdiv(n_rows, kBM);
-    const int TN = M > 64 ? 2 : 1;
-    const int n_col_tiles = (int)cdiv(M, 64 * TN);
-    dim3 grid((unsigned)(cdiv(n_row_tiles, kXcd) * kXcd * n_col_tiles)), block(256);
-    if (gemm_mode() != 0 && !(pro_scale && K > 512) && panel_ok(K, M, Y, ldy, workspace, workspace_bytes, n_rows)) {
-        if (pro_scale) launch_panel<1>(gemm_mode(), A, lda, nullptr, 0, W, ldw, 0, workspace, Y, ldy, (int)n_rows, K, M, bias, pro_scale, pro_shift, nullptr, nullptr, slope, st, nullptr, nullptr, ctx);
-        else launch_panel<0>(gemm_mode(), A, lda, nullptr, 0, W, ldw, 0, workspace, Y, ldy, (int)n_rows, K, M, bias, nullptr, nullptr, nullptr, nullptr, slope, st, nullptr, nullptr, ctx);
-        LAUNCH_TRY();
-        return DDMP_OK;
-    }
-    if (gemm_mode() != 0 && !(pro_scale && K > 512) && ws_ok(K, M, Y, ldy, workspace, workspace_bytes)) {
-        if (pro_scale) launch_ws<true>(gemm_mode(), A, lda, W, ldw, 0, workspace, Y, ldy, (int)n_rows, K, M, bias, pro_scale, pro_shift, slope, st, ctx.prepared);
-        else launch_ws<false>(gemm_mode(), A, lda, W, ldw, 0, workspace, Y, ldy, (int)n_rows, K, M, bias, nullptr, nullptr, slope, st, ctx.prepared);
-        LAUNCH_TRY();
-        return DDMP_OK;
-    }
-    const bool pre = !(pro_scale && K > 512) && presplit_w(W, ldw, M, K, 0, workspace, workspace_bytes, st, ctx.prepared);
-    const float* Bop = pre ? (const float*)workspace : W;
-#define DDMP_LAUNCH_NT(KERNEL_, PRO_)                                                                    \
-    hipLaunchKernelGGL((KERNEL_), grid, block, 0, st, A, lda, Bop, ldw, Y, ldy, (int)n_rows, K, M, bias, \
-                       pro_scale, pro_shift, slope, n_row_tiles, n_col_tiles)
-#define DDMP_NT_PICK(TN_, NTERM_, PRO_)                                                                   \
-    do {                                                                                                  \
-        if (pre && kt_) DDMP_LAUNCH_NT((gemm_rows_bf16_kernel<TN_, NTERM_, false, PRO_, true, true>), PRO_);   \
-        else if (pre) DDMP_LAUNCH_NT((gemm_rows_bf16_kernel<TN_, NTERM_, false, PRO_, false, true>), PRO_);    \
-        else if (kt_) DDMP_LAUNCH_NT((gemm_rows_bf16_kernel<TN_, NTERM_, false, PRO_, true, false>), PRO_);    \
-        else DDMP_LAUNCH_NT((gemm_rows_bf16_kernel<TN_, NTERM_, false, PRO_, false, false>), PRO_);            \
-    } while (0)
-#define DDMP_NT_BY_MODE(TN_, PRO_)                                                          \
-    do {                                                                                    \
-        const int mode_ = (PRO_ && K > 512) ? 0 : gemm_mode();                              \
-        const bool kt_ = (K % 16) != 0;                                                     \
-        if (mode_ == 6) DDMP_NT_PICK(TN_, 3, PRO_);                                         \
-        else if (mode_ == 3) DDMP_NT_PICK(TN_, 2, PRO_);                                    \
-        else hipLaunchKernelGGL((gemm_rows_kernel<TN_, false, PRO_>), grid, block, 0, st, A, lda, W, ldw, Y, ldy,  \
-                                (int)n_rows, K, M, bias, pro_scale, pro_shift, slope, n_row_tiles, n_col_tiles); \
-    } while (0)
-    if (TN == 2) {
-        if (pro_scale) DDMP_NT_BY_MODE(2, true); else DDMP_NT_BY_MODE(2, false);
-    } else {
-        if (pro_scale) DDMP_NT_BY_MODE(1, true); else DDMP_NT_BY_MODE(1, false);
-    }
-#undef DDMP_NT_PICK
-#undef DDMP_NT_BY_MODE
-#undef DDMP_LAUNCH_NT
-    LAUNCH_TRY();
-    return DDMP_OK;
+    const RowRoute r = row_route_call(n_rows, K, M, pro_scale != nullptr, workspace, workspace_bytes, Y, ldy, lda, 0);
+    const RowArgs g{A, lda, W, ldw, 0, workspace, Y, ldy, (int)n_rows, K, M, bias, pro_scale, pro_shift, slope};
+    return rows_product(r, g, stream, nullptr, nullptr, ctx);
 }
 extern "C" int ddmp_gemm_nt_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y,
                                 int64_t ldy, int64_t n_rows, int K, int M, const float* bias,
@@ -930,63 +930,134 @@ int ddmp_gemm_nn_f32(const float* A, int64_t lda, const float* W, int64_t ldw, f
     ARG_TRY(A && W && Y && n_rows > 0 && K > 0 && M > 0 && n_rows < INT32_MAX);
     ARG_TRY(M % 4 == 0 && K % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && lda >= M && ldw >= K && ldy >= K);
     ARG_TRY(aligned16(A) && aligned16(W));
-    hipStream_t st = (hipStream_t)stream;
-    const int n_row_tiles = (int)cdiv(n_rows, kBM);
-    const int TN = K > 64 ? 2 : 1;
-    const int n_col_tiles = (int)cdiv(K, 64 * TN);
-    dim3 grid((unsigned)(cdiv(n_row_tiles, kXcd) * kXcd * n_col_tiles)), block(256);
-    // pre-split W^T: planes [K_out][M] so that the reduction index M is contiguous; the rows kernel then runs
-    // in its row-major (NT) form on the planes
-    if (gemm_mode() != 0 && panel_ok(M, K, Y, ldy, workspace, workspace_bytes, n_rows)) {
-        launch_panel<0>(gemm_mode(), A, lda, nullptr, 0, W, ldw, 1, workspace, Y, ldy, (int)n_rows, M, K, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, st, nullptr, nullptr, ctx);
-        LAUNCH_TRY();
-        return DDMP_OK;
-    }
-    if (gemm_mode() != 0 && ws_ok(M, K, Y, ldy, workspace, workspace_bytes)) {
-        launch_ws<false>(gemm_mode(), A, lda, W, ldw, 1, workspace, Y, ldy, (int)n_rows, M, K, nullptr, nullptr, nullptr, 0.f, st, ctx.prepared);
-        LAUNCH_TRY();
-        return DDMP_OK;
-    }
-    const bool pre = presplit_w(W, ldw, M, K, 1, workspace, workspace_bytes, st, ctx.prepared);
-#define DDMP_LAUNCH_NN(KERNEL_)                                                                        \
-    hipLaunchKernelGGL((KERNEL_), grid, block, 0, st, A, lda, W, ldw, Y, ldy, (int)n_rows, M, K, nullptr, \
-                       nullptr, nullptr, 0.f, n_row_tiles, n_col_tiles)
-#define DDMP_LAUNCH_NNP(KERNEL_)                                                                       \
-    hipLaunchKernelGGL((KERNEL_), grid, block, 0, st, A, lda, (const float*)workspace, (int64_t)M, Y, ldy, \
-                       (int)n_rows, M, K, nullptr, nullptr, nullptr, 0.f, n_row_tiles, n_col_tiles)
-    const int mode = gemm_mode();
-    const bool kt = (M % 16) != 0;                 // reduction dimension of the NN form is M
-    if (pre) {
-        if (TN == 2) {
-            if (mode == 6 && kt) DDMP_LAUNCH_NNP((gemm_rows_bf16_kernel<2, 3, false, false, true, true>));
-            else if (mode == 6) DDMP_LAUNCH_NNP((gemm_rows_bf16_kernel<2, 3, false, false, false, true>));
-            else if (kt) DDMP_LAUNCH_NNP((gemm_rows_bf16_kernel<2, 2, false, false, true, true>));
-            else DDMP_LAUNCH_NNP((gemm_rows_bf16_kernel<2, 2, false, false, false, true>));
-        } else {
-            if (mode == 6 && kt) DDMP_LAUNCH_NNP((gemm_rows_bf16_kernel<1, 3, false, false, true, true>));
-            else if (mode == 6) DDMP_LAUNCH_NNP((gemm_rows_bf16_kernel<1, 3, false, false, false, true>));
-            else if (kt) DDMP_LAUNCH_NNP((gemm_rows_bf16_kernel<1, 2, false, false, true, true>));
-            else DDMP_LAUNCH_NNP((gemm_rows_bf16_kernel<1, 2, false, false, false, true>));
+    const RowRoute r = row_route_call(n_rows, M, K, false, workspace, workspace_bytes, Y, ldy, lda, 0);
+    const RowArgs g{A, lda, W, ldw, 1, workspace, Y, ldy, (int)n_rows, M, K, nullptr, nullptr, nullptr, 0.f};
+    return rows_product(r, g, stream, nullptr, nullptr, ctx);
+}
+
+// ---- forward GEMM that also returns the BatchNorm statistics of its output (column sums of Y and Y^2, float64 [2M]):
+//      fused into the row-panel kernel's epilogue where that kernel runs, otherwise GEMM + ddmp_bn_stats_f32
+extern "C" size_t ddmp_gemm_nt_stats_workspace_bytes(int64_t n_rows, int M) {
+    if (n_rows <= 0 || M <= 0) return 0;
+    const size_t fused = (size_t)(cdiv(n_rows, 64) + 8) * 2 * 512 * sizeof(double) + 256 + fpartials_mid_bytes(512);
+    return std::max(fused, ddmp_colreduce_workspace_bytes(n_rows, M));
+}
+
+int ddmp_gemm_nt_stats_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y, int64_t ldy, int64_t n_rows, int K,
+                           int M, const float* bias, const float* pro_scale, const float* pro_shift, float slope, double* sums2,
+                           void* workspace, size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes, ddmp_stream stream,
+                           ddmp::CallCtx& ctx) {
+    ARG_TRY(sums2 && stats_ws);
+    if (stats_ws_bytes < ddmp_gemm_nt_stats_workspace_bytes(n_rows, M)) return DDMP_EWORKSPACE;
+    const bool args_ok = A && W && Y && n_rows > 0 && n_rows < INT32_MAX && K > 0 && M > 0 && K % 4 == 0 && lda % 4 == 0 &&
+                         ldw % 4 == 0 && lda >= K && ldw >= K && ldy >= M && aligned16(A) && aligned16(W) &&
+                         (pro_scale == nullptr) == (pro_shift == nullptr);
+    if (args_ok) {
+        const RowRoute r = row_route_call(n_rows, K, M, pro_scale != nullptr, workspace, workspace_bytes, Y, ldy, lda, 0);
+        if (r.family <= kRowPanelB16) {
+            const RowArgs g{A, lda, W, ldw, 0, workspace, Y, ldy, (int)n_rows, K, M, bias, pro_scale, pro_shift, slope};
+            return rows_product(r, g, stream, (double*)stats_ws, sums2, ctx);
         }
-    } else if (TN == 2) {
-        if (mode == 6 && kt) DDMP_LAUNCH_NN((gemm_rows_bf16_kernel<2, 3, true, false, true, false>));
-        else if (mode == 6) DDMP_LAUNCH_NN((gemm_rows_bf16_kernel<2, 3, true, false, false, false>));
-        else if (mode == 3 && kt) DDMP_LAUNCH_NN((gemm_rows_bf16_kernel<2, 2, true, false, true, false>));
-        else if (mode == 3) DDMP_LAUNCH_NN((gemm_rows_bf16_kernel<2, 2, true, false, false, false>));
-        else DDMP_LAUNCH_NN((gemm_rows_kernel<2, true, false>));
-    } else {
-        if (mode == 6 && kt) DDMP_LAUNCH_NN((gemm_rows_bf16_kernel<1, 3, true, false, true, false>));
-        else if (mode == 6) DDMP_LAUNCH_NN((gemm_rows_bf16_kernel<1, 3, true, false, false, false>));
-        else if (mode == 3 && kt) DDMP_LAUNCH_NN((gemm_rows_bf16_kernel<1, 2, true, false, true, false>));
-        else if (mode == 3) DDMP_LAUNCH_NN((gemm_rows_bf16_kernel<1, 2, true, false, false, false>));
-        else DDMP_LAUNCH_NN((gemm_rows_kernel<1, true, false>));
     }
-#undef DDMP_LAUNCH_NNP
-#undef DDMP_LAUNCH_NN
+    int rc = ddmp_gemm_nt_f32(A, lda, W, ldw, Y, ldy, n_rows, K, M, bias, pro_scale, pro_shift, slope, workspace,
+                              workspace_bytes, stream, ctx);
+    if (rc != DDMP_OK) return rc;
+    return ddmp_bn_stats_f32(Y, ldy, n_rows, M, sums2, stats_ws, stats_ws_bytes, stream, ctx);
+}
+extern "C" int ddmp_gemm_nt_stats_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y, int64_t ldy,
+                                      int64_t n_rows, int K, int M, const float* bias, const float* pro_scale,
+                                      const float* pro_shift, float slope, double* sums2, void* workspace,
+                                      size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes,
+                                      ddmp_stream stream) {
+    ddmp::CallCtx ctx;
+    return ddmp_gemm_nt_stats_f32(A, lda, W, ldw, Y, ldy, n_rows, K, M, bias, pro_scale, pro_shift, slope, sums2, workspace,
+                                  workspace_bytes, stats_ws, stats_ws_bytes, stream, ctx);
+}
+
+// ---- BatchNorm+LeakyReLU backward fused into the operand load of the two GEMMs that consume dY (agg-first layers)
+// dgrad of a transform-first layer with the NEXT BatchNorm-backward reductions from its epilogue (row-register kernel):
+//   out[n, K] = A[n, M] . W[M, K]   and   sums2[2K] = (sum_rows g, sum_rows g yhat) of out as the gradient behind the previous
+//   layer's BatchNorm+LeakyReLU (Yp = that layer's conv output [n, K]; scale, shift, mean, rstd = its bn4 rows) --
+//   what ddmp_bn_bwd_reduce_f32(out, Yp, ...) returns, without reading out again
+// -> 1: wide outputs on the row-register kernel (STATS = 2); 2: narrow outputs (128 | 64 columns) on the 512-row panel
+//    kernel's RS epilogue (bf16 split terms); 0: neither
+static int bnred_form(const RowRoute& r, int KD, int MD) {
+    if (r.family == kRowPanelF16 && r.rr) return 1;
+    static const bool narrow = !ddmp::unfused("dgrad_red_narrow");   // (A/B)
+    return (narrow && r.family == kRowPanelB16 && KD <= kMaxProK && (MD == 128 || MD == 64)) ? 2 : 0;
+}
+extern "C" int ddmp_gemm_nn_bnred_supported(int M, int K, int64_t n_rows) {
+    return bnred_form(row_route(n_rows, M, K, false, gemm_mode(), gemm_f16() != 0, true), M, K);
+}
+int ddmp_gemm_nn_bnred_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* out, int64_t ld_out, int64_t n_rows,
+                           int M, int K, const float* Yp, int64_t ldyp, const float* scale, const float* shift, const float* mean,
+                           const float* rstd, float slope, double* sums2, void* workspace, size_t workspace_bytes, void* stats_ws,
+                           size_t stats_ws_bytes, ddmp_stream stream, ddmp::CallCtx& ctx) {
+    ARG_TRY(A && W && out && Yp && scale && shift && mean && rstd && sums2 && n_rows > 0 && n_rows < INT32_MAX);
+    ARG_TRY(M % 4 == 0 && K % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && lda >= M && ldw >= K && ld_out >= K && ldyp >= K);
+    ARG_TRY(aligned16(A) && aligned16(W));
+    const RowRoute r = row_route_call(n_rows, M, K, false, workspace, workspace_bytes, out, ld_out, lda, 0);
+    const int form = bnred_form(r, M, K);
+    if (!form || (form == 1 && !rr_kernel_ok(r, false, n_rows, lda, 0))) return DDMP_EINVAL;
+    if (stats_ws_bytes < ddmp_gemm_nt_stats_workspace_bytes(n_rows, K)) return DDMP_EWORKSPACE;
+    const float* bn4[4] = {scale, shift, mean, rstd};
+    const RowArgs g{A, lda, W, ldw, 1, workspace, out, ld_out, (int)n_rows, M, K, nullptr, nullptr, nullptr, slope};
+    launch_panel<0>(r, g, nullptr, 0, nullptr, nullptr, (hipStream_t)stream, (double*)stats_ws, sums2, ctx, Yp, ldyp, bn4);
     LAUNCH_TRY();
     return DDMP_OK;
 }
+extern "C" int ddmp_gemm_nn_bnred_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* out, int64_t ld_out,
+                                      int64_t n_rows, int M, int K, const float* Yp, int64_t ldyp, const float* scale,
+                                      const float* shift, const float* mean, const float* rstd, float slope, double* sums2,
+                                      void* workspace, size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes,
+                                      ddmp_stream stream) {
+    ddmp::CallCtx ctx;
+    return ddmp_gemm_nn_bnred_f32(A, lda, W, ldw, out, ld_out, n_rows, M, K, Yp, ldyp, scale, shift, mean, rstd, slope, sums2,
+                                  workspace, workspace_bytes, stats_ws, stats_ws_bytes, stream, ctx);
+}
 
+extern "C" int ddmp_gemm_bnbwd_supported(int cout, int cin, int64_t n_rows) {
+    if (!panel_enabled() || !tn_panel_enabled() || n_rows < kTnPanelMinRows) return 0;
+    // wide layers (cin > 128): f16x3 row-register / row-panel dgrad + 256 x 256 wgrad panels; narrow aggregate-first layers
+    // (round 3: 32 -> 64 ... 128 -> 256): the 512-row panel dgrad and the tiled wgrad with the same operand prologue
+    const bool nn = panel_shape_ok(cout, cin) && cout >= 64 && cout <= kMaxProK;
+    const bool tn = cout % 4 == 0 && ((cout >= 256 && cin >= 256) || cin <= 128);
+    static const bool narrow = !ddmp::unfused("bnbwd_narrow");   // (A/B)
+    return (nn && tn && (cin > 128 || narrow)) ? 1 : 0;
+}
+
+// (the wgrad alone: layer 0 has no dgrad)
+extern "C" int ddmp_gemm_tn_bnbwd_supported(int cout, int cin, int64_t n_rows) {
+    if (!tn_panel_enabled() || n_rows < kTnPanelMinRows) return 0;
+    const bool panel = cout >= 256 && cin >= 256;
+    return (cout % 4 == 0 && cin % 4 == 0 && (panel || gemm_mode() == 6 || gemm_mode() == 3)) ? 1 : 0;
+}
+
+int ddmp_gemm_nn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64_t ldyb, const float* W, int64_t ldw, float* out,
+                           int64_t ld_out, int64_t n_rows, int M, int K, const float* a, const float* b, const float* c1,
+                           const float* c0, float slope, void* workspace, size_t workspace_bytes, ddmp_stream stream,
+                           ddmp::CallCtx& ctx) {
+    // out[n,K] = dY[n,M] . W[M,K],  dY = a * dZ * lrelu'(a * Yb + b) + c1 * Yb + c0  (per column of M)
+    ARG_TRY(dZ && Yb && W && out && a && b && c1 && c0 && n_rows > 0 && n_rows < INT32_MAX && M > 0 && K > 0);
+    ARG_TRY(lddz % 4 == 0 && ldyb % 4 == 0 && ldw % 4 == 0 && lddz >= M && ldyb >= M && ldw >= K && ld_out >= K);
+    ARG_TRY(aligned16(dZ) && aligned16(Yb) && aligned16(W));
+    const RowRoute r = row_route_call(n_rows, M, K, false, workspace, workspace_bytes, out, ld_out, lddz, ldyb);
+    if (!ddmp_gemm_bnbwd_supported(M, K, n_rows) || r.family > kRowPanelB16) return DDMP_EINVAL;
+    const RowArgs g{dZ, lddz, W, ldw, 1, workspace, out, ld_out, (int)n_rows, M, K, nullptr, a, b, slope};
+    launch_panel<2>(r, g, Yb, ldyb, c1, c0, (hipStream_t)stream, nullptr, nullptr, ctx);
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
+extern "C" int ddmp_gemm_nn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64_t ldyb, const float* W,
+                                      int64_t ldw, float* out, int64_t ld_out, int64_t n_rows, int M, int K,
+                                      const float* a, const float* b, const float* c1, const float* c0, float slope,
+                                      void* workspace, size_t workspace_bytes, ddmp_stream stream) {
+    ddmp::CallCtx ctx;
+    return ddmp_gemm_nn_bnbwd_f32(dZ, lddz, Yb, ldyb, W, ldw, out, ld_out, n_rows, M, K, a, b, c1, c0, slope, workspace,
+                                  workspace_bytes, stream, ctx);
+}
+
+// ---------------------------------------------------------------- wgrad:  dW[M, K] = g(G)^T . f(Z)
 // The wide f16x3 wgrad: row-major staging kernel of round 4 (gemm_tn_rm.hip).  One split of each operand is one buffer
 // descriptor: its bytes (and the offsets of the rows the kernel requests beyond it: up to 3 stages of 16) fit 31 bits.
 static inline bool tn_wide_ok(int rows_per_split, int64_t ld0, int64_t ld1, int64_t ld2) {
@@ -1012,6 +1083,77 @@ extern "C" size_t ddmp_gemm_tn_workspace_bytes(int64_t n_rows, int M, int K) {
     return (size_t)std::max(p.n_splits, q.n_splits) * (size_t)M * (size_t)K * sizeof(float) + 64;    // + two scale slots (f16 modes)
 }
 
+// Both wgrad entry points, after their own argument checks.  DUAL: G is the BatchNorm+LeakyReLU backward of (G = dZ, G2 = Yb),
+//   dY = a * dZ * lrelu'(a * Yb + b) + c1 * Yb + c0  per column of M, rebuilt on the load; otherwise G2 and the coefficients are
+// null.  f = optional BatchNorm+LeakyReLU prologue on Z (columns of K).  Operands the float4 loads of the f16x3 route cannot
+// reach take the bf16 panel or the tiled kernels (the plain entry point has refused them before).
+template <bool DUAL>
+static int gemm_tn(const float* G, int64_t ldg, const float* G2, int64_t ldg2, const float* Z, int64_t ldz, float* dW, int64_t lddw,
+                   int64_t n_rows, int M, int K, const float* a, const float* b, const float* c1, const float* c0,
+                   const float* pro_scale, const float* pro_shift, float slope, void* workspace, size_t workspace_bytes,
+                   hipStream_t st, ddmp::CallCtx& ctx) {
+    const int mode = gemm_mode();
+    const bool f16_ok = mode == 6 && gemm_f16() && ldg % 4 == 0 && ldg2 % 4 == 0 && ldz % 4 == 0 && aligned16(G) && aligned16(G2) &&
+                        aligned16(Z);
+    TnPlan p = tn_plan(n_rows, M, K, f16_ok);
+    if (p.T == 4 && p.tm + p.tk < 512 && !tn_wide_ok(p.rows_per_split, ldg, ldg2, ldz)) p = tn_plan(n_rows, M, K);
+    const size_t need = (size_t)p.n_splits * (size_t)M * (size_t)K * sizeof(float) + 64;
+    if (!workspace || workspace_bytes < need) return DDMP_EWORKSPACE;
+    float* part = (float*)workspace;
+    const int64_t sstride = (int64_t)M * K;
+    const int n_tiles = p.n_tiles_m * p.n_tiles_k;
+    dim3 grid((unsigned)(cdiv(p.n_splits, kXcd) * kXcd * n_tiles)), block(p.T == 4 ? 512 : 256);
+    const int pro = pro_scale != nullptr;
+    if (p.T == 4 && f16_ok && tn_wide_ok(p.rows_per_split, ldg, ldg2, ldz)) {
+        float* tail = (float*)((char*)workspace + need - 64);
+        const bool own = !(ctx.slot_a && ctx.slot_b);
+        float* gslot = own ? tail : ctx.slot_a;
+        float* zslot = own ? tail + 4 : ctx.slot_b;
+        const bool prime = own || ctx.prime;
+        const int target = prime ? kF16TargetExact : kF16TargetStale;
+        if (prime) {
+            f16s_measure<DUAL ? 2 : 0>(G, ldg, G2, ldg2, n_rows, M, a, b, c1, c0, slope, gslot, st);
+            if (pro) f16s_measure<1>(Z, ldz, nullptr, 0, n_rows, K, pro_scale, pro_shift, nullptr, nullptr, slope, zslot, st);
+            else f16s_measure<0>(Z, ldz, nullptr, 0, n_rows, K, nullptr, nullptr, nullptr, nullptr, slope, zslot, st);
+        }
+        for (int heal = 0; heal <= (prime ? 0 : 1); ++heal)           // second launch: redo on overflow (gemm_f16s.inc)
+            launch_tn_wide(G, ldg, G2, ldg2, Z, ldz, part, sstride, n_rows, M, K, p, pro_scale, pro_shift, a, b, c1, c0, slope, gslot,
+                           zslot, target, heal, st);
+    } else if (p.T == 4) {                                       // 256 x 256 panels, bf16 split terms
+        pick<2, 3>(mode == 6 ? 3 : 2, [&](auto nt) {
+            pick<0, 1>(pro, [&](auto pr) {
+                hipLaunchKernelGGL((gemm_tn_panel_kernel<decltype(nt)::value, decltype(pr)::value != 0, DUAL>), grid, block, 0, st, G,
+                                   ldg, G2, ldg2, Z, ldz, part, (int64_t)K, sstride, (int)n_rows, M, K, p.rows_per_split, p.n_tiles_m,
+                                   p.n_tiles_k, p.n_splits, pro_scale, pro_shift, a, b, c1, c0, slope, (float*)nullptr,
+                                   (float*)nullptr, 0, 0);
+            });
+        });
+    } else {                                                     // 64 x 64 | 128 x 128 tiles
+        pick<1, 2>(p.T, [&](auto t) {
+            pick<0, 1>(pro, [&](auto pr) {
+                constexpr int T = decltype(t)::value;
+                constexpr bool PRO = decltype(pr)::value != 0;
+                if constexpr (!DUAL) {
+                    if (mode == 0)                               // (the dual form has no f32-input kernel: refused before)
+                        hipLaunchKernelGGL((gemm_tn_kernel<T, PRO>), grid, block, 0, st, G, ldg, Z, ldz, part, (int64_t)K, sstride,
+                                           (int)n_rows, M, K, p.rows_per_split, p.n_tiles_m, p.n_tiles_k, p.n_splits, pro_scale,
+                                           pro_shift, slope);
+                }
+                pick<2, 3>(mode == 6 ? 3 : mode == 3 ? 2 : 0, [&](auto nt) {
+                    hipLaunchKernelGGL((gemm_tn_bf16_kernel<T, decltype(nt)::value, PRO, (T == 1 ? 32 : 16), DUAL>), grid, block, 0, st,
+                                       G, ldg, Z, ldz, part, (int64_t)K, sstride, (int)n_rows, M, K, p.rows_per_split, p.n_tiles_m,
+                                       p.n_tiles_k, p.n_splits, pro_scale, pro_shift, slope, G2, ldg2, a, b, c1, c0);
+                });
+            });
+        });
+    }
+    LAUNCH_TRY();
+    hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)cdiv((int64_t)M * K, 256)), dim3(256), 0, st, part, sstride,
+                       p.n_splits, dW, lddw, M, K);
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
+
 int ddmp_gemm_tn_f32(const float* G, int64_t ldg, const float* Z, int64_t ldz, float* dW, int64_t lddw, int64_t n_rows, int M,
                      int K, const float* pro_scale, const float* pro_shift, float slope, void* workspace, size_t workspace_bytes,
                      ddmp_stream stream, ddmp::CallCtx& ctx) {
@@ -1020,240 +1162,20 @@ int ddmp_gemm_tn_f32(const float* G, int64_t ldg, const float* Z, int64_t ldz, f
     ARG_TRY(aligned16(G) && aligned16(Z));
     ARG_TRY((pro_scale == nullptr) == (pro_shift == nullptr));
     ARG_TRY(!pro_scale || (aligned16(pro_scale) && aligned16(pro_shift)));
-    hipStream_t st = (hipStream_t)stream;
-    const bool f16_route = gemm_mode() == 6 && gemm_f16();
-    TnPlan p = tn_plan(n_rows, M, K, f16_route);
-    if (p.T == 4 && p.tm + p.tk < 512 && !tn_wide_ok(p.rows_per_split, ldg, 0, ldz)) p = tn_plan(n_rows, M, K);
-    const size_t need = (size_t)p.n_splits * (size_t)M * (size_t)K * sizeof(float) + 64;
-    if (!workspace || workspace_bytes < need) return DDMP_EWORKSPACE;
-    float* part = (float*)workspace;
-    const int64_t sstride = (int64_t)M * K;
-    const int n_tiles = p.n_tiles_m * p.n_tiles_k;
-    if (p.T == 4) {
-        dim3 pgrid((unsigned)(cdiv(p.n_splits, kXcd) * kXcd * n_tiles)), pblock(512);
-        float* gslot = nullptr;
-        float* zslot = nullptr;
-        int target = 0, heal_ = 0;
-#define DDMP_LAUNCH_TNP(KERNEL_)                                                                              \
-    hipLaunchKernelGGL((KERNEL_), pgrid, pblock, 0, st, G, ldg, (const float*)nullptr, (int64_t)0, Z, ldz, part, \
-                       (int64_t)K, sstride, (int)n_rows, M, K, p.rows_per_split, p.n_tiles_m, p.n_tiles_k,       \
-                       p.n_splits, pro_scale, pro_shift, (const float*)nullptr, (const float*)nullptr,           \
-                       (const float*)nullptr, (const float*)nullptr, slope, gslot, zslot, target, heal_)
-        const int mode_ = gemm_mode();
-        if (mode_ == 6 && gemm_f16() && tn_wide_ok(p.rows_per_split, ldg, 0, ldz)) {
-            float* tail = (float*)((char*)workspace + need - 64);
-            const bool own = !(ctx.slot_a && ctx.slot_b);
-            gslot = own ? tail : ctx.slot_a;
-            zslot = own ? tail + 4 : ctx.slot_b;
-            const bool prime = own || ctx.prime;
-            target = prime ? kF16TargetExact : kF16TargetStale;
-            if (prime) {
-                f16s_measure<0>(G, ldg, nullptr, 0, n_rows, M, nullptr, nullptr, nullptr, nullptr, slope, gslot, st);
-                if (pro_scale) f16s_measure<1>(Z, ldz, nullptr, 0, n_rows, K, pro_scale, pro_shift, nullptr, nullptr, slope, zslot, st);
-                else f16s_measure<0>(Z, ldz, nullptr, 0, n_rows, K, nullptr, nullptr, nullptr, nullptr, slope, zslot, st);
-            }
-            for (heal_ = 0; heal_ <= (prime ? 0 : 1); ++heal_)        // second launch: redo on overflow (gemm_f16s.inc)
-                launch_tn_wide(G, ldg, nullptr, 0, Z, ldz, part, sstride, n_rows, M, K, p, pro_scale, pro_shift, nullptr, nullptr,
-                               nullptr, nullptr, slope, gslot, zslot, target, heal_, st);
-            heal_ = 0;
-        } else if (pro_scale) {
-            if (mode_ == 6) DDMP_LAUNCH_TNP((gemm_tn_panel_kernel<3, true, false>)); else DDMP_LAUNCH_TNP((gemm_tn_panel_kernel<2, true, false>));
-        } else {
-            if (mode_ == 6) DDMP_LAUNCH_TNP((gemm_tn_panel_kernel<3, false, false>)); else DDMP_LAUNCH_TNP((gemm_tn_panel_kernel<2, false, false>));
-        }
-#undef DDMP_LAUNCH_TNP
-        LAUNCH_TRY();
-        hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)cdiv((int64_t)M * K, 256)), dim3(256), 0, st, part,
-                           sstride, p.n_splits, dW, lddw, M, K);
-        LAUNCH_TRY();
-        return DDMP_OK;
-    }
-    dim3 grid((unsigned)(cdiv(p.n_splits, kXcd) * kXcd * n_tiles)), block(256);
-#define DDMP_LAUNCH_TN(KERNEL_)                                                                           \
-    hipLaunchKernelGGL((KERNEL_), grid, block, 0, st, G, ldg, Z, ldz, part, (int64_t)K, sstride, (int)n_rows, \
-                       M, K, p.rows_per_split, p.n_tiles_m, p.n_tiles_k, p.n_splits, pro_scale, pro_shift, slope)
-#define DDMP_TN_BY_MODE(T_, PRO_)                                                 \
-    do {                                                                          \
-        const int mode_ = gemm_mode();                                            \
-        if (mode_ == 6) DDMP_LAUNCH_TN((gemm_tn_bf16_kernel<T_, 3, PRO_, (T_ == 1 ? 32 : 16)>));       \
-        else if (mode_ == 3) DDMP_LAUNCH_TN((gemm_tn_bf16_kernel<T_, 2, PRO_, (T_ == 1 ? 32 : 16)>));  \
-        else DDMP_LAUNCH_TN((gemm_tn_kernel<T_, PRO_>));                          \
-    } while (0)
-    if (p.T == 2) {
-        if (pro_scale) DDMP_TN_BY_MODE(2, true); else DDMP_TN_BY_MODE(2, false);
-    } else {
-        if (pro_scale) DDMP_TN_BY_MODE(1, true); else DDMP_TN_BY_MODE(1, false);
-    }
-#undef DDMP_TN_BY_MODE
-#undef DDMP_LAUNCH_TN
-    LAUNCH_TRY();
-    hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)cdiv((int64_t)M * K, 256)), dim3(256), 0, st, part,
-                       sstride, p.n_splits, dW, lddw, M, K);
-    LAUNCH_TRY();
-    return DDMP_OK;
-}
-
-
-// ---- BatchNorm+LeakyReLU backward fused into the operand load of the two GEMMs that consume dY (agg-first layers)
-// dgrad of a transform-first layer with the NEXT BatchNorm-backward reductions from its epilogue (row-register kernel):
-//   out[n, K] = A[n, M] . W[M, K]   and   sums2[2K] = (sum_rows g, sum_rows g yhat) of out as the gradient behind the previous
-//   layer's BatchNorm+LeakyReLU (Yp = that layer's conv output [n, K]; scale, shift, mean, rstd = its bn4 rows) --
-//   what ddmp_bn_bwd_reduce_f32(out, Yp, ...) returns, without reading out again
-extern "C" int ddmp_gemm_nn_bnred_supported(int M, int K, int64_t n_rows) {
-    if (gemm_mode() == 6 && gemm_f16() && rr_enabled() && panel_enabled() && n_rows >= kRRMinRows && M % 32 == 0 && M >= 64 &&
-        M <= kMaxProK && K > 128 && K <= 512 && K % 4 == 0)
-        return 1;                                                // wide outputs: row-register kernel, STATS = 2
-    static const bool narrow = !ddmp::unfused("dgrad_red_narrow");   // (A/B)
-    // narrow outputs (128 | 64 columns): the 512-row panel kernel's RS epilogue (bf16 split terms)
-    return (narrow && (gemm_mode() == 6 || gemm_mode() == 3) && panel_enabled() && n_rows >= kPanelMinRows && M % 32 == 0 &&
-            M >= 32 && M <= kMaxProK && (K == 128 || K == 64)) ? 2 : 0;
-}
-int ddmp_gemm_nn_bnred_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* out, int64_t ld_out, int64_t n_rows,
-                           int M, int K, const float* Yp, int64_t ldyp, const float* scale, const float* shift, const float* mean,
-                           const float* rstd, float slope, double* sums2, void* workspace, size_t workspace_bytes, void* stats_ws,
-                           size_t stats_ws_bytes, ddmp_stream stream, ddmp::CallCtx& ctx) {
-    ARG_TRY(A && W && out && Yp && scale && shift && mean && rstd && sums2 && n_rows > 0 && n_rows < INT32_MAX);
-    ARG_TRY(M % 4 == 0 && K % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0 && lda >= M && ldw >= K && ld_out >= K && ldyp >= K);
-    ARG_TRY(aligned16(A) && aligned16(W));
-    const int form = ddmp_gemm_nn_bnred_supported(M, K, n_rows);
-    if (!form || (form == 1 && !rr_route_ok(n_rows, M, lda, 0)) || !panel_ok(M, K, out, ld_out, workspace, workspace_bytes, n_rows))
-        return DDMP_EINVAL;
-    if (stats_ws_bytes < ddmp_gemm_nt_stats_workspace_bytes(n_rows, K)) return DDMP_EWORKSPACE;
-    const float* bn4[4] = {scale, shift, mean, rstd};
-    launch_panel<0>(gemm_mode(), A, lda, nullptr, 0, W, ldw, 1, workspace, out, ld_out, (int)n_rows, M, K, nullptr, nullptr, nullptr,
-                    nullptr, nullptr, slope, (hipStream_t)stream, (double*)stats_ws, sums2, ctx, Yp, ldyp, bn4);
-    LAUNCH_TRY();
-    return DDMP_OK;
-}
-extern "C" int ddmp_gemm_nn_bnred_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* out, int64_t ld_out,
-                                      int64_t n_rows, int M, int K, const float* Yp, int64_t ldyp, const float* scale,
-                                      const float* shift, const float* mean, const float* rstd, float slope, double* sums2,
-                                      void* workspace, size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes,
-                                      ddmp_stream stream) {
-    ddmp::CallCtx ctx;
-    return ddmp_gemm_nn_bnred_f32(A, lda, W, ldw, out, ld_out, n_rows, M, K, Yp, ldyp, scale, shift, mean, rstd, slope, sums2,
-                                  workspace, workspace_bytes, stats_ws, stats_ws_bytes, stream, ctx);
-}
-
-extern "C" int ddmp_gemm_bnbwd_supported(int cout, int cin, int64_t n_rows) {
-    if (gemm_mode() == 0 || !panel_enabled() || !tn_panel_enabled() || n_rows < kTnPanelMinRows) return 0;
-    // wide layers (cin > 128): f16x3 row-register / row-panel dgrad + 256 x 256 wgrad panels; narrow aggregate-first layers
-    // (round 3: 32 -> 64 ... 128 -> 256): the 512-row panel dgrad and the tiled wgrad with the same operand prologue
-    const bool nn = cout % 32 == 0 && cout >= 64 && cout <= kMaxProK && cin % 4 == 0 && cin >= 16 && cin <= 512;
-    const bool tn = cout % 4 == 0 && ((cout >= 256 && cin >= 256) || cin <= 128);
-    static const bool narrow = !ddmp::unfused("bnbwd_narrow");   // (A/B)
-    return (nn && tn && (cin > 128 || narrow)) ? 1 : 0;
-}
-
-// (the wgrad alone: layer 0 has no dgrad)
-extern "C" int ddmp_gemm_tn_bnbwd_supported(int cout, int cin, int64_t n_rows) {
-    if (gemm_mode() == 0 || !tn_panel_enabled() || n_rows < kTnPanelMinRows) return 0;
-    const int mode_ = gemm_mode();
-    const bool panel = cout >= 256 && cin >= 256;
-    return (cout % 4 == 0 && cin % 4 == 0 && (panel || mode_ == 6 || mode_ == 3)) ? 1 : 0;
-}
-
-int ddmp_gemm_nn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64_t ldyb, const float* W, int64_t ldw, float* out,
-                           int64_t ld_out, int64_t n_rows, int M, int K, const float* a, const float* b, const float* c1,
-                           const float* c0, float slope, void* workspace, size_t workspace_bytes, ddmp_stream stream,
-                           ddmp::CallCtx& ctx) {
-    // out[n,K] = dY[n,M] . W[M,K],  dY = a * dZ * lrelu'(a * Yb + b) + c1 * Yb + c0  (per column of M)
-    ARG_TRY(dZ && Yb && W && out && a && b && c1 && c0 && n_rows > 0 && n_rows < INT32_MAX && M > 0 && K > 0);
-    ARG_TRY(lddz % 4 == 0 && ldyb % 4 == 0 && ldw % 4 == 0 && lddz >= M && ldyb >= M && ldw >= K && ld_out >= K);
-    ARG_TRY(aligned16(dZ) && aligned16(Yb) && aligned16(W));
-    if (!ddmp_gemm_bnbwd_supported(M, K, n_rows) || !panel_ok(M, K, out, ld_out, workspace, workspace_bytes, n_rows)) return DDMP_EINVAL;
-    launch_panel<2>(gemm_mode(), dZ, lddz, Yb, ldyb, W, ldw, 1, workspace, out, ld_out, (int)n_rows, M, K, nullptr, a, b,
-                    c1, c0, slope, (hipStream_t)stream, nullptr, nullptr, ctx);
-    LAUNCH_TRY();
-    return DDMP_OK;
-}
-extern "C" int ddmp_gemm_nn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64_t ldyb, const float* W,
-                                      int64_t ldw, float* out, int64_t ld_out, int64_t n_rows, int M, int K,
-                                      const float* a, const float* b, const float* c1, const float* c0, float slope,
-                                      void* workspace, size_t workspace_bytes, ddmp_stream stream) {
-    ddmp::CallCtx ctx;
-    return ddmp_gemm_nn_bnbwd_f32(dZ, lddz, Yb, ldyb, W, ldw, out, ld_out, n_rows, M, K, a, b, c1, c0, slope, workspace,
-                                  workspace_bytes, stream, ctx);
+    return gemm_tn<false>(G, ldg, nullptr, 0, Z, ldz, dW, lddw, n_rows, M, K, nullptr, nullptr, nullptr, nullptr, pro_scale, pro_shift,
+                          slope, workspace, workspace_bytes, (hipStream_t)stream, ctx);
 }
 
 int ddmp_gemm_tn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64_t ldyb, const float* Z, int64_t ldz, float* dW,
                            int64_t lddw, int64_t n_rows, int M, int K, const float* a, const float* b, const float* c1,
                            const float* c0, const float* pro_scale, const float* pro_shift, float slope, void* workspace,
                            size_t workspace_bytes, ddmp_stream stream, ddmp::CallCtx& ctx) {
-    // dW[M,K] = dY^T . f(Z),  dY as above (columns of M), f = optional BatchNorm+LeakyReLU prologue on Z (columns of K)
     ARG_TRY(dZ && Yb && Z && dW && a && b && c1 && c0 && n_rows > 0 && n_rows < INT32_MAX && M > 0 && K > 0);
     ARG_TRY(M % 4 == 0 && K % 4 == 0 && lddz >= M && ldyb >= M && ldz >= K && lddw >= K);
     ARG_TRY((pro_scale == nullptr) == (pro_shift == nullptr));
     if (!ddmp_gemm_tn_bnbwd_supported(M, K, n_rows)) return DDMP_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const bool f16_route = gemm_mode() == 6 && gemm_f16() && lddz % 4 == 0 && ldyb % 4 == 0 && ldz % 4 == 0 && aligned16(dZ) &&
-                           aligned16(Yb) && aligned16(Z);
-    TnPlan p = tn_plan(n_rows, M, K, f16_route);
-    if (p.T == 4 && p.tm + p.tk < 512 && !tn_wide_ok(p.rows_per_split, lddz, ldyb, ldz)) p = tn_plan(n_rows, M, K);
-    const size_t need = (size_t)p.n_splits * (size_t)M * (size_t)K * sizeof(float) + 64;
-    if (!workspace || workspace_bytes < need) return DDMP_EWORKSPACE;
-    float* part = (float*)workspace;
-    const int64_t sstride = (int64_t)M * K;
-    const int n_tiles = p.n_tiles_m * p.n_tiles_k;
-    if (p.T != 4) {                                              // narrow layers: 64 x 64 | 128 x 128 tiles, bf16 split terms
-        const int mode_ = gemm_mode();
-        if (mode_ != 6 && mode_ != 3) return DDMP_EINVAL;
-        dim3 grid((unsigned)(cdiv(p.n_splits, kXcd) * kXcd * n_tiles)), block(256);
-#define DDMP_LAUNCH_TNG(T_, NT_, PRO_)                                                                                 \
-    hipLaunchKernelGGL((gemm_tn_bf16_kernel<T_, NT_, PRO_, (T_ == 1 ? 32 : 16), true>), grid, block, 0, st, dZ, lddz, Z, ldz,  \
-                       part, (int64_t)K, sstride, (int)n_rows, M, K, p.rows_per_split, p.n_tiles_m, p.n_tiles_k,       \
-                       p.n_splits, pro_scale, pro_shift, slope, Yb, ldyb, a, b, c1, c0)
-        if (p.T == 2) {
-            if (mode_ == 6) { if (pro_scale) DDMP_LAUNCH_TNG(2, 3, true); else DDMP_LAUNCH_TNG(2, 3, false); }
-            else { if (pro_scale) DDMP_LAUNCH_TNG(2, 2, true); else DDMP_LAUNCH_TNG(2, 2, false); }
-        } else {
-            if (mode_ == 6) { if (pro_scale) DDMP_LAUNCH_TNG(1, 3, true); else DDMP_LAUNCH_TNG(1, 3, false); }
-            else { if (pro_scale) DDMP_LAUNCH_TNG(1, 2, true); else DDMP_LAUNCH_TNG(1, 2, false); }
-        }
-#undef DDMP_LAUNCH_TNG
-        LAUNCH_TRY();
-        hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)cdiv((int64_t)M * K, 256)), dim3(256), 0, st, part, sstride,
-                           p.n_splits, dW, lddw, M, K);
-        LAUNCH_TRY();
-        return DDMP_OK;
-    }
-    dim3 pgrid((unsigned)(cdiv(p.n_splits, kXcd) * kXcd * n_tiles)), pblock(512);
-    float* gslot = nullptr;
-    float* zslot = nullptr;
-    int target = 0, heal_ = 0;
-#define DDMP_LAUNCH_TNP(KERNEL_)                                                                                 \
-    hipLaunchKernelGGL((KERNEL_), pgrid, pblock, 0, st, dZ, lddz, Yb, ldyb, Z, ldz, part, (int64_t)K, sstride,     \
-                       (int)n_rows, M, K, p.rows_per_split, p.n_tiles_m, p.n_tiles_k, p.n_splits, pro_scale,       \
-                       pro_shift, a, b, c1, c0, slope, gslot, zslot, target, heal_)
-    const int mode_ = gemm_mode();
-    if (mode_ == 6 && gemm_f16() && lddz % 4 == 0 && ldyb % 4 == 0 && ldz % 4 == 0 && tn_wide_ok(p.rows_per_split, lddz, ldyb, ldz) &&
-        aligned16(dZ) && aligned16(Yb) && aligned16(Z)) {
-        float* tail = (float*)((char*)workspace + need - 64);
-        const bool own = !(ctx.slot_a && ctx.slot_b);
-        gslot = own ? tail : ctx.slot_a;
-        zslot = own ? tail + 4 : ctx.slot_b;
-        const bool prime = own || ctx.prime;
-        target = prime ? kF16TargetExact : kF16TargetStale;
-        if (prime) {
-            f16s_measure<2>(dZ, lddz, Yb, ldyb, n_rows, M, a, b, c1, c0, slope, gslot, st);
-            if (pro_scale) f16s_measure<1>(Z, ldz, nullptr, 0, n_rows, K, pro_scale, pro_shift, nullptr, nullptr, slope, zslot, st);
-            else f16s_measure<0>(Z, ldz, nullptr, 0, n_rows, K, nullptr, nullptr, nullptr, nullptr, slope, zslot, st);
-        }
-        for (heal_ = 0; heal_ <= (prime ? 0 : 1); ++heal_)            // second launch: redo on overflow (gemm_f16s.inc)
-            launch_tn_wide(dZ, lddz, Yb, ldyb, Z, ldz, part, sstride, n_rows, M, K, p, pro_scale, pro_shift, a, b, c1, c0, slope,
-                           gslot, zslot, target, heal_, st);
-        heal_ = 0;
-    } else if (pro_scale) {
-        if (mode_ == 6) DDMP_LAUNCH_TNP((gemm_tn_panel_kernel<3, true, true>)); else DDMP_LAUNCH_TNP((gemm_tn_panel_kernel<2, true, true>));
-    } else {
-        if (mode_ == 6) DDMP_LAUNCH_TNP((gemm_tn_panel_kernel<3, false, true>)); else DDMP_LAUNCH_TNP((gemm_tn_panel_kernel<2, false, true>));
-    }
-#undef DDMP_LAUNCH_TNP
-    LAUNCH_TRY();
-    hipLaunchKernelGGL(reduce_splits_kernel, dim3((unsigned)cdiv((int64_t)M * K, 256)), dim3(256), 0, st, part, sstride,
-                       p.n_splits, dW, lddw, M, K);
-    LAUNCH_TRY();
-    return DDMP_OK;
+    return gemm_tn<true>(dZ, lddz, Yb, ldyb, Z, ldz, dW, lddw, n_rows, M, K, a, b, c1, c0, pro_scale, pro_shift, slope, workspace,
+                         workspace_bytes, (hipStream_t)stream, ctx);
 }
 extern "C" int ddmp_gemm_tn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64_t ldyb, const float* Z,
                                       int64_t ldz, float* dW, int64_t lddw, int64_t n_rows, int M, int K,
@@ -1265,43 +1187,3 @@ extern "C" int ddmp_gemm_tn_bnbwd_f32(const float* dZ, int64_t lddz, const float
                                   workspace, workspace_bytes, stream, ctx);
 }
 
-
-// ---- forward GEMM that also returns the BatchNorm statistics of its output (column sums of Y and Y^2, float64 [2M]):
-//      fused into the row-panel kernel's epilogue where that kernel runs, otherwise GEMM + ddmp_bn_stats_f32
-extern "C" size_t ddmp_gemm_nt_stats_workspace_bytes(int64_t n_rows, int M) {
-    if (n_rows <= 0 || M <= 0) return 0;
-    const size_t fused = (size_t)(cdiv(n_rows, 64) + 8) * 2 * 512 * sizeof(double) + 256 + fpartials_mid_bytes(512);
-    return std::max(fused, ddmp_colreduce_workspace_bytes(n_rows, M));
-}
-
-int ddmp_gemm_nt_stats_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y, int64_t ldy, int64_t n_rows, int K,
-                           int M, const float* bias, const float* pro_scale, const float* pro_shift, float slope, double* sums2,
-                           void* workspace, size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes, ddmp_stream stream,
-                           ddmp::CallCtx& ctx) {
-    ARG_TRY(sums2 && stats_ws);
-    if (stats_ws_bytes < ddmp_gemm_nt_stats_workspace_bytes(n_rows, M)) return DDMP_EWORKSPACE;
-    const bool fused = A && W && Y && n_rows > 0 && n_rows < INT32_MAX && K > 0 && M > 0 && K % 4 == 0 && lda % 4 == 0 &&
-                       ldw % 4 == 0 && lda >= K && ldw >= K && ldy >= M && aligned16(A) && aligned16(W) &&
-                       (pro_scale == nullptr) == (pro_shift == nullptr) && gemm_mode() != 0 && !(pro_scale && K > 512) &&
-                       panel_ok(K, M, Y, ldy, workspace, workspace_bytes, n_rows);
-    if (fused) {
-        hipStream_t st = (hipStream_t)stream;
-        if (pro_scale) launch_panel<1>(gemm_mode(), A, lda, nullptr, 0, W, ldw, 0, workspace, Y, ldy, (int)n_rows, K, M, bias, pro_scale, pro_shift, nullptr, nullptr, slope, st, (double*)stats_ws, sums2, ctx);
-        else launch_panel<0>(gemm_mode(), A, lda, nullptr, 0, W, ldw, 0, workspace, Y, ldy, (int)n_rows, K, M, bias, nullptr, nullptr, nullptr, nullptr, slope, st, (double*)stats_ws, sums2, ctx);
-        LAUNCH_TRY();
-        return DDMP_OK;
-    }
-    int rc = ddmp_gemm_nt_f32(A, lda, W, ldw, Y, ldy, n_rows, K, M, bias, pro_scale, pro_shift, slope, workspace,
-                              workspace_bytes, stream, ctx);
-    if (rc != DDMP_OK) return rc;
-    return ddmp_bn_stats_f32(Y, ldy, n_rows, M, sums2, stats_ws, stats_ws_bytes, stream, ctx);
-}
-extern "C" int ddmp_gemm_nt_stats_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* Y, int64_t ldy,
-                                      int64_t n_rows, int K, int M, const float* bias, const float* pro_scale,
-                                      const float* pro_shift, float slope, double* sums2, void* workspace,
-                                      size_t workspace_bytes, void* stats_ws, size_t stats_ws_bytes,
-                                      ddmp_stream stream) {
-    ddmp::CallCtx ctx;
-    return ddmp_gemm_nt_stats_f32(A, lda, W, ldw, Y, ldy, n_rows, K, M, bias, pro_scale, pro_shift, slope, sums2, workspace,
-                                  workspace_bytes, stats_ws, stats_ws_bytes, stream, ctx);
-}

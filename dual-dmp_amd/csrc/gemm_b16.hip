@@ -1001,16 +1001,12 @@ extern "C" int ddmp_gemm_tn_bf16(const uint16_t* G, int64_t ldg, const uint16_t*
     const int64_t sstride = (int64_t)M * K;
     const int n_tiles = p.n_tiles_m * p.n_tiles_k;
     dim3 grid((unsigned)(cdiv(p.n_splits, kXcd) * kXcd * n_tiles)), block(512);
-    constexpr int tn_dma = 1;                                    // (0: the register-staged kernel for every wgrad -- an A/B of round 3)
     if (pro_scale)
         hipLaunchKernelGGL((gemm_tn_b16_kernel<true>), grid, block, 0, st, G, ldg, Z, ldz, part, (int64_t)K, sstride,
                            (int)n_rows, M, K, p.rows_per_split, p.n_tiles_m, p.n_tiles_k, p.n_splits, pro_scale, pro_shift, slope);
-    else if (tn_dma)
+    else
         hipLaunchKernelGGL(gemm_tn_b16_dma_kernel, grid, block, 0, st, G, ldg, Z, ldz, part, (int64_t)K, sstride, (int)n_rows, M,
                            K, p.rows_per_split, p.n_tiles_m, p.n_tiles_k, p.n_splits);
-    else
-        hipLaunchKernelGGL((gemm_tn_b16_kernel<false>), grid, block, 0, st, G, ldg, Z, ldz, part, (int64_t)K, sstride,
-                           (int)n_rows, M, K, p.rows_per_split, p.n_tiles_m, p.n_tiles_k, p.n_splits, pro_scale, pro_shift, slope);
     LAUNCH_TRY();
     hipLaunchKernelGGL(reduce_splits_b16_kernel, dim3((unsigned)cdiv((int64_t)M * K, 256)), dim3(256), 0, st, part, sstride,
                        p.n_splits, dW, lddw, M, K);

@@ -782,6 +782,74 @@ def test_prepared_weight_planes_give_the_same_products(dev, n):
     assert torch.equal(ops.gemm_nt(a, ws[0], wplanes=bufs[(0, 0)]), ops.gemm_nt(a, ws[0]))
 
 
+# (n, K = reduction length, M = output width): one shape per plane layout and per threshold between two of them
+PLANE_SHAPES = [(20300, 64, 260), (21000, 96, 384),      # wide row panels (f16 planes in mode 13, bf16 planes in 6 and 3)
+                (20500, 32, 64),                         # narrow row panel
+                (10100, 64, 260),                        # row panel in mode 13 only (row-register threshold), plain otherwise
+                (1000, 128, 64),                         # tiled planes of the wave-specialised kernel
+                (1000, 32, 64), (130, 8, 32)]            # plain planes; the second with a ragged k tail
+
+
+def test_prepared_weight_planes_are_the_ones_the_call_reads(dev):
+    """ddmp_gemm_prepare_weights and the GEMM entry points choose the plane layout with one function: a call that is handed
+    prepared planes reads THEM and does not split again.  Equal results cannot show that (ignored planes are silently
+    re-made), so the weights are overwritten in place after preparing: the call with ``wplanes=`` must still return the OLD
+    product bit for bit, the call without them the new one, and after preparing again both agree.  In mode 0 no planes exist
+    and the call with ``wplanes=`` follows the weights."""
+    from dual_dmp_amd import ops
+    old = ops.get_gemm_mode()
+    scratch = torch.empty(8, device=dev)
+
+    def check(mode, call, a, w, form, has_pro, ref, tag):
+        buf = torch.empty(ops.gemm_rows_workspace_bytes(w.shape[1], w.shape[0]), dtype=torch.uint8, device=dev)
+        item = [(w, form, has_pro, buf)]
+        w0 = w.clone()
+        ops.gemm_prepare_weights(item, a.shape[0], scratch)
+        y0 = [t.clone() for t in call(w, buf)]
+        w.mul_(-0.5).add_(0.25)                          # "an optimizer step" nobody prepared for
+        stale = call(w, buf)
+        fresh = [t.clone() for t in call(w, None)]
+        assert relerr(fresh[0], ref(w)) < GEMM_TOL[mode], tag
+        assert not torch.equal(fresh[0], y0[0]), tag
+        for s, f, y in zip(stale, fresh, y0):
+            assert torch.equal(s, f if mode == 0 else y), tag
+        ops.gemm_prepare_weights(item, a.shape[0], scratch)
+        for s, f in zip(call(w, buf), fresh):
+            assert torch.equal(s, f), tag
+        w.copy_(w0)
+
+    try:
+        for mode in (13, 6, 3, 0):
+            ops.set_gemm_mode(mode)
+            for n, K, M in PLANE_SHAPES:
+                torch.manual_seed(n + K + M)
+                a = torch.randn(n, K, device=dev)
+                ad = a.double()
+                w_nt = torch.randn(M, K, device=dev) / K ** 0.5
+                w_nn = torch.randn(K, M, device=dev) / K ** 0.5
+                tag = (mode, n, K, M)
+                check(mode, lambda w, p: (ops.gemm_nt(a, w, wplanes=p),), a, w_nt, 0, False, lambda w: ad @ w.double().t(),
+                      tag + ("nt",))
+                check(mode, lambda w, p: (ops.gemm_nn(a, w, wplanes=p),), a, w_nn, 1, False, lambda w: ad @ w.double(),
+                      tag + ("nn",))
+                if mode != 0 and (n >= 20000 or (mode == 13 and n >= 10000)):    # the row-panel routes: fused statistics
+                    def stats(w, p):
+                        s = torch.empty(2 * M, dtype=torch.float64, device=dev)
+                        return ops.gemm_nt_stats(a, w, s, wplanes=p), s
+                    check(mode, stats, a, w_nt, 0, False, lambda w: ad @ w.double().t(), tag + ("nt_stats",))
+            # a BatchNorm+LeakyReLU prologue on the operand (K <= 512: the split kernels take it)
+            n, K, M = PLANE_SHAPES[0]
+            torch.manual_seed(7)
+            a = torch.randn(n, K, device=dev)
+            ps, psh = torch.rand(K, device=dev) + 0.5, torch.randn(K, device=dev)
+            fa = f_ref(a.double(), ps.double(), psh.double())
+            w_nt = torch.randn(M, K, device=dev) / K ** 0.5
+            check(mode, lambda w, p: (ops.gemm_nt(a, w, pro=(ps, psh), wplanes=p),), a, w_nt, 0, True,
+                  lambda w: fa @ w.double().t(), (mode, n, K, M, "nt_pro"))
+    finally:
+        ops.set_gemm_mode(old)
+
+
 @pytest.mark.parametrize("kind", [0, 1])
 def test_heads_forward_backward(dev, kind):
     from dual_dmp_amd import ops
