@@ -10,16 +10,50 @@ namespace {
 using namespace ddmp;
 constexpr int kNB = 256;
 
+// a * b - c * d with the rounding error of c * d recovered by one fma (Kahan's difference of products, <= 1.5 ulp).  A plain
+// a * b - c * d is contracted into fma(a, b, -(c * d)), which keeps the rounding error of c * d alone: the cross product of two
+// EQUAL edges (a face with two corners at one position) came out as that error, ~1e-8, and was then normalised to a unit
+// vector instead of the reference's exact (0, 0, 0); and a sliver's normal was off by |a||b| 2^-24 / |a x b|.
+__device__ __forceinline__ float diff_of_products(float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+    const float w = c * d;
+    const float e = fmaf(-c, d, w);      // w - c d, exact
+    const float f = fmaf(a, b, -w);
+    return f + e;
+}
+
+// An edge vector component x - y as hi + lo, exactly (TwoSum): positions of unlike magnitude or sign (z of a flat mesh
+// around 0, say) do not subtract exactly, and on a sliver the 2^-24 |a| that is lost reaches the normal as 2^-24 |a||b| / |a x b|.
+struct Diff {
+    float hi, lo;
+};
+__device__ __forceinline__ Diff two_diff(float x, float y) {
+#pragma clang fp contract(off)
+    const float hi = x - y;
+    const float t = hi - x;
+    return {hi, (x - (hi - t)) + (-y - t)};
+}
+// One component of (a_hi + a_lo) x (b_hi + b_lo): a1 b2 - a2 b1, the first-order terms in the low parts added plainly.  Every
+// product is rounded on its own and paired with its mirror image, so that equal edges give an exact 0.
+__device__ __forceinline__ float cross_component(Diff a1, Diff b2, Diff a2, Diff b1) {
+#pragma clang fp contract(off)
+    return diff_of_products(a1.hi, b2.hi, a2.hi, b1.hi) + ((a1.lo * b2.hi - a2.hi * b1.lo) + (a1.hi * b2.lo - a2.lo * b1.hi));
+}
+
 __global__ __launch_bounds__(256) void face_normals_kernel(int F, const float* __restrict__ pos,
                                                            const int* __restrict__ faces, float* __restrict__ fn,
                                                            float* __restrict__ fa) {
     for (int f = blockIdx.x * 256 + threadIdx.x; f < F; f += gridDim.x * 256) {
         const int i0 = faces[3 * (int64_t)f], i1 = faces[3 * (int64_t)f + 1], i2 = faces[3 * (int64_t)f + 2];
-        const float ax = pos[3 * (int64_t)i1] - pos[3 * (int64_t)i0], ay = pos[3 * (int64_t)i1 + 1] - pos[3 * (int64_t)i0 + 1],
-                    az = pos[3 * (int64_t)i1 + 2] - pos[3 * (int64_t)i0 + 2];
-        const float bx = pos[3 * (int64_t)i2] - pos[3 * (int64_t)i0], by = pos[3 * (int64_t)i2 + 1] - pos[3 * (int64_t)i0 + 1],
-                    bz = pos[3 * (int64_t)i2 + 2] - pos[3 * (int64_t)i0 + 2];
-        const float cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+        Diff a[3], b[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float p0 = pos[3 * (int64_t)i0 + c];
+            a[c] = two_diff(pos[3 * (int64_t)i1 + c], p0);
+            b[c] = two_diff(pos[3 * (int64_t)i2 + c], p0);
+        }
+        const float cx = cross_component(a[1], b[2], a[2], b[1]), cy = cross_component(a[2], b[0], a[0], b[2]),
+                    cz = cross_component(a[0], b[1], a[1], b[0]);
         const float len = sqrtf(cx * cx + cy * cy + cz * cz);
         const float nrm = len + 1e-24f;
         fn[3 * (int64_t)f] = cx / nrm;
@@ -54,52 +88,97 @@ __global__ void mad_final_kernel(const double* __restrict__ partial, int F, doub
 // positions; p_v += (1/|F(v)|) sum_{f in F(v)} ((c_f - p_v) . n_f) n_f.  The reference updates vertices one by one
 // in a Python loop, but each update reads only the centroids computed BEFORE the loop and the vertex's own
 // position, so the sweep is order-independent and a parallel pass is the same computation.
-__global__ __launch_bounds__(256) void face_center_kernel(int F, const float* __restrict__ pos,
-                                                          const int* __restrict__ faces, float* __restrict__ fc) {
+// Two passes per sweep.  Per face: the three scalars d_k = (c_f - p_fk) . n_f, with c_f - p_fk formed from the face's EDGE
+// vectors ((p1 - p0) + (p2 - p0)) / 3, ...: differences of neighbouring float32 positions are exact (or nearly), so d_k is good
+// to 1e-7 of an edge wherever the mesh sits.  (A centroid rounded to float32 first is only good to an ulp of the COORDINATE:
+// at |p| ~ 700 that put 4e-5 of an edge into every component of the update.)  Per vertex: p_v += mean_k d_k n_f over its
+// corners; it reads no other vertex, so the update is in place.
+// With `lo` (ddmp_vertex_update_pair_f32) a position is the float32 pair pos + lo between sweeps: stored as one float32, x and y
+// in the hundreds come back rounded to 6e-5, and the next sweep's d_k carries that through n_f into the small components
+// (measured at 1M faces, three sweeps: 8e-5 where 2e-6 is asked).  `pos` is always the pair's sum rounded once.
+__global__ __launch_bounds__(256) void corner_offset_kernel(int F, const float* __restrict__ pos,
+                                                            const float* __restrict__ lo /*nullable*/,
+                                                            const float* __restrict__ nrm, const int* __restrict__ faces,
+                                                            float* __restrict__ dcorner) {
     for (int f = blockIdx.x * 256 + threadIdx.x; f < F; f += gridDim.x * 256) {
         const int i0 = faces[3 * (int64_t)f], i1 = faces[3 * (int64_t)f + 1], i2 = faces[3 * (int64_t)f + 2];
+        float d0 = 0.f, d1 = 0.f, d2 = 0.f;
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-            fc[3 * (int64_t)f + c] = (pos[3 * (int64_t)i0 + c] + pos[3 * (int64_t)i1 + c] + pos[3 * (int64_t)i2 + c]) / 3.0f;
+        for (int c = 0; c < 3; ++c) {
+            const float p0 = pos[3 * (int64_t)i0 + c], p1 = pos[3 * (int64_t)i1 + c], p2 = pos[3 * (int64_t)i2 + c];
+            float q01 = p1 - p0, q02 = p2 - p0, q12 = p2 - p1;
+            if (lo) {
+                const float l0 = lo[3 * (int64_t)i0 + c], l1 = lo[3 * (int64_t)i1 + c], l2 = lo[3 * (int64_t)i2 + c];
+                q01 += l1 - l0; q02 += l2 - l0; q12 += l2 - l1;
+            }
+            const float n = nrm[3 * (int64_t)f + c];
+            d0 += n * ((q01 + q02) / 3.0f);
+            d1 += n * ((q12 - q01) / 3.0f);
+            d2 -= n * ((q02 + q12) / 3.0f);
+        }
+        dcorner[3 * (int64_t)f] = d0;
+        dcorner[3 * (int64_t)f + 1] = d1;
+        dcorner[3 * (int64_t)f + 2] = d2;
     }
 }
 
-__global__ __launch_bounds__(256) void vertex_update_kernel(int V, float* __restrict__ pos, const float* __restrict__ fc,
-                                                            const float* __restrict__ nrm, const int* __restrict__ vf_ptr,
-                                                            const int* __restrict__ vf_corner) {
+// hi + lo = a + b exactly, hi = fl(a + b) (TwoSum)
+__device__ __forceinline__ void two_sum(float a, float b, float& hi, float& lo) {
+#pragma clang fp contract(off)
+    hi = a + b;
+    const float t = hi - a;
+    lo = (a - (hi - t)) + (b - t);
+}
+
+__global__ __launch_bounds__(256) void vertex_update_kernel(int V, float* __restrict__ pos, float* __restrict__ lo /*nullable*/,
+                                                            const float* __restrict__ dcorner, const float* __restrict__ nrm,
+                                                            const int* __restrict__ vf_ptr, const int* __restrict__ vf_corner) {
     for (int v = blockIdx.x * 256 + threadIdx.x; v < V; v += gridDim.x * 256) {
-        const float px = pos[3 * (int64_t)v], py = pos[3 * (int64_t)v + 1], pz = pos[3 * (int64_t)v + 2];
         float dx = 0.f, dy = 0.f, dz = 0.f;
         const int b = vf_ptr[v], e = vf_ptr[v + 1];
         for (int k = b; k < e; ++k) {
-            const int f = vf_corner[k] / 3;
-            const float nx = nrm[3 * (int64_t)f], ny = nrm[3 * (int64_t)f + 1], nz = nrm[3 * (int64_t)f + 2];
-            const float d = nx * (fc[3 * (int64_t)f] - px) + ny * (fc[3 * (int64_t)f + 1] - py) + nz * (fc[3 * (int64_t)f + 2] - pz);
-            dx += d * nx; dy += d * ny; dz += d * nz;
+            const int corner = vf_corner[k], f = corner / 3;
+            const float d = dcorner[corner];
+            dx += d * nrm[3 * (int64_t)f]; dy += d * nrm[3 * (int64_t)f + 1]; dz += d * nrm[3 * (int64_t)f + 2];
         }
         const float cnt = (float)(e - b);
-        pos[3 * (int64_t)v] = px + dx / cnt;
-        pos[3 * (int64_t)v + 1] = py + dy / cnt;
-        pos[3 * (int64_t)v + 2] = pz + dz / cnt;
+        const float inc[3] = {dx / cnt, dy / cnt, dz / cnt};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (lo) two_sum(pos[3 * (int64_t)v + c], lo[3 * (int64_t)v + c] + inc[c], pos[3 * (int64_t)v + c], lo[3 * (int64_t)v + c]);
+            else pos[3 * (int64_t)v + c] += inc[c];
+        }
     }
+}
+
+int vertex_update(int64_t V, int64_t F, float* pos, const float* norm, const int32_t* faces, const int32_t* vf_ptr,
+                  const int32_t* vf_corner, float* corner_scratch, float* lo, int loop, ddmp_stream stream) {
+    ARG_TRY(V > 0 && V < INT32_MAX / 3 && F > 0 && F < INT32_MAX / 3 && pos && norm && faces && vf_ptr && vf_corner);
+    ARG_TRY(corner_scratch && loop >= 0);
+    hipStream_t st = (hipStream_t)stream;
+    const int gf = (int)std::min<int64_t>(cdiv(F, 256), 2048), gv = (int)std::min<int64_t>(cdiv(V, 256), 2048);
+    if (lo && loop > 0) HIP_TRY(hipMemsetAsync(lo, 0, sizeof(float) * 3 * (size_t)V, st));
+    for (int it = 0; it < loop; ++it) {
+        hipLaunchKernelGGL(corner_offset_kernel, dim3(gf), dim3(256), 0, st, (int)F, pos, lo, norm, faces, corner_scratch);
+        LAUNCH_TRY();
+        hipLaunchKernelGGL(vertex_update_kernel, dim3(gv), dim3(256), 0, st, (int)V, pos, lo, corner_scratch, norm, vf_ptr,
+                           vf_corner);
+        LAUNCH_TRY();
+    }
+    return DDMP_OK;
 }
 }  // namespace
 
 extern "C" int ddmp_vertex_update_f32(int64_t V, int64_t F, float* pos, const float* norm, const int32_t* faces,
                                       const int32_t* vf_ptr, const int32_t* vf_corner, float* fc_scratch, int loop,
                                       ddmp_stream stream) {
-    ARG_TRY(V > 0 && V < INT32_MAX / 3 && F > 0 && F < INT32_MAX / 3 && pos && norm && faces && vf_ptr && vf_corner);
-    ARG_TRY(fc_scratch && loop >= 0);
-    hipStream_t st = (hipStream_t)stream;
-    const int gf = (int)std::min<int64_t>(cdiv(F, 256), 2048), gv = (int)std::min<int64_t>(cdiv(V, 256), 2048);
-    for (int it = 0; it < loop; ++it) {
-        hipLaunchKernelGGL(face_center_kernel, dim3(gf), dim3(256), 0, st, (int)F, pos, faces, fc_scratch);
-        LAUNCH_TRY();
-        hipLaunchKernelGGL(vertex_update_kernel, dim3(gv), dim3(256), 0, st, (int)V, pos, fc_scratch, norm, vf_ptr,
-                           vf_corner);
-        LAUNCH_TRY();
-    }
-    return DDMP_OK;
+    return vertex_update(V, F, pos, norm, faces, vf_ptr, vf_corner, fc_scratch, nullptr, loop, stream);
+}
+extern "C" int ddmp_vertex_update_pair_f32(int64_t V, int64_t F, float* pos, const float* norm, const int32_t* faces,
+                                           const int32_t* vf_ptr, const int32_t* vf_corner, float* corner_scratch,
+                                           float* lo_scratch, int loop, ddmp_stream stream) {
+    ARG_TRY(lo_scratch);
+    return vertex_update(V, F, pos, norm, faces, vf_ptr, vf_corner, corner_scratch, lo_scratch, loop, stream);
 }
 
 extern "C" int ddmp_face_normals_f32(int64_t F, const float* pos, const int32_t* faces, float* fn, float* fa,

@@ -35,7 +35,9 @@ def vertex_updating(pos: torch.Tensor, norm: torch.Tensor, mesh, loop=10) -> tor
     tb = tables_for(mesh, pos.device)
     new_pos = pos.detach().to(torch.float32).clone().contiguous()
     nrm = norm.detach().to(torch.float32).contiguous()
-    fc = torch.empty((tb.F, 3), dtype=torch.float32, device=pos.device)
-    check(_lib.lib().ddmp_vertex_update_f32(tb.V, tb.F, _p(new_pos), _p(nrm), _p(tb.faces), _p(tb.vf_ptr),
-                                            _p(tb.vf_corner), _p(fc), int(loop), _stream()), "ddmp_vertex_update_f32")
+    corner = torch.empty((tb.F, 3), dtype=torch.float32, device=pos.device)
+    lo = torch.empty((tb.V, 3), dtype=torch.float32, device=pos.device)      # positions are a float32 pair between sweeps
+    check(_lib.lib().ddmp_vertex_update_pair_f32(tb.V, tb.F, _p(new_pos), _p(nrm), _p(tb.faces), _p(tb.vf_ptr),
+                                                 _p(tb.vf_corner), _p(corner), _p(lo), int(loop), _stream()),
+          "ddmp_vertex_update_pair_f32")
     return new_pos

@@ -703,10 +703,18 @@ int ddmp_adam_step_dev_f32(float* p, const float* g, float* m, float* v, int64_t
 int ddmp_face_normals_f32(int64_t F, const float* pos, const int32_t* faces, float* fn /*[F,3]*/,
                           float* fa /*[F] nullable*/, ddmp_stream stream);
 /* vertex update from predicted normals (util/models.py:31-44): `loop` sweeps of
- * p_v += mean_{f in F(v)} ((c_f - p_v).n_f) n_f, in place; fc_scratch [F,3] */
+ * p_v += mean_{f in F(v)} ((c_f - p_v).n_f) n_f, in place; fc_scratch [F,3] (holds (c_f - p_fk).n_f per corner, formed
+ * from edge vectors so that the result does not depend on where the mesh sits) */
 int ddmp_vertex_update_f32(int64_t V, int64_t F, float* pos, const float* norm, const int32_t* faces,
                            const int32_t* vf_ptr, const int32_t* vf_corner, float* fc_scratch, int loop,
                            ddmp_stream stream);
+/* the same with the positions kept as a float32 pair pos + lo_scratch [V,3] between sweeps (lo_scratch is zeroed here and
+ * holds the rounding remainder afterwards; `pos` is the pair's sum rounded once): several sweeps of a mesh whose coordinates
+ * are much larger than its edges stay within 1e-7 of an edge of float64, where one float32 per coordinate loses an ulp of
+ * the coordinate per sweep */
+int ddmp_vertex_update_pair_f32(int64_t V, int64_t F, float* pos, const float* norm, const int32_t* faces,
+                                const int32_t* vf_ptr, const int32_t* vf_corner, float* corner_scratch /*[F,3]*/,
+                                float* lo_scratch /*[V,3]*/, int loop, ddmp_stream stream);
 size_t ddmp_mad_workspace_bytes(void);
 int ddmp_mad_f64(int64_t F, const float* n1 /*[F,3] f32*/, const double* n2 /*[F,3] f64*/, double* out /*[1]*/,
                  void* workspace, size_t workspace_bytes, ddmp_stream stream);
