@@ -1112,7 +1112,7 @@ static int gemm_tn(const float* G, int64_t ldg, const float* G2, int64_t ldg2, c
         const bool prime = own || ctx.prime;
         const int target = prime ? kF16TargetExact : kF16TargetStale;
         if (prime) {
-            f16s_measure<DUAL ? 2 : 0>(G, ldg, G2, ldg2, n_rows, M, a, b, c1, c0, slope, gslot, st);
+            f16s_measure<DUAL ? 3 : 0>(G, ldg, G2, ldg2, n_rows, M, a, b, c1, c0, slope, gslot, st);    // (3: dY with its quiet columns lifted)
             if (pro) f16s_measure<1>(Z, ldz, nullptr, 0, n_rows, K, pro_scale, pro_shift, nullptr, nullptr, slope, zslot, st);
             else f16s_measure<0>(Z, ldz, nullptr, 0, n_rows, K, nullptr, nullptr, nullptr, nullptr, slope, zslot, st);
         }

@@ -71,9 +71,42 @@ __device__ __forceinline__ void f16s_publish(float* slot, float amax, float s) {
     }
 }
 
-__device__ __forceinline__ float f16s_operand(float x, float y, float a, float b, float k1, float k0, float slope, int pm) {
+// Column normalisation of a rebuilt dY = a g + k1 y + k0 (the wide wgrad, gemm_tn_rm.hip).  The split is fixed point relative to
+// the operand's global maximum, with a floor 2^-40 below it: a column whose scale a is more than kF16ColGap binades below the
+// largest a of the matrix would keep fewer than 24 - (40 - gap - 24) bits, or none.  Such a column is lifted to the largest a's
+// binade: a, b, k1, k0 times the power of two p = 2^(emax - e) give p dY exactly and leave the gate's sign alone, and row c of
+// dW is multiplied by 1 / p afterwards.  Every other column has p = 1: results are bit for bit those without the lift.
+constexpr int kF16ColGap = 12;
+__device__ __forceinline__ int f16s_expo(float a) {              // biased exponent; 0: zero, subnormal or non-finite (never lifted)
+    const int e = (int)((__float_as_uint(a) >> 23) & 0xffu);
+    return e == 255 ? 0 : e;
+}
+__device__ __forceinline__ float f16s_colnorm(float a, int emax, bool inverse = false) {
+    const int e = f16s_expo(a), k = min(emax - e, 100);
+    if (e == 0 || k <= kF16ColGap) return 1.f;
+    return __uint_as_float((unsigned)(127 + (inverse ? -k : k)) << 23);
+}
+// (emax, emin) of a[0..M) for the whole workgroup through two LDS ints; emin over the columns that have an exponent
+__device__ __forceinline__ int2 f16s_block_expo(const float* __restrict__ a, int M, int* sh) {
+    if (threadIdx.x == 0) { sh[0] = 0; sh[1] = 255; }
+    __syncthreads();
+    int hi = 0, lo = 255;
+    for (int c = threadIdx.x; c < M; c += blockDim.x) {
+        const int e = f16s_expo(a[c]);
+        hi = max(hi, e);
+        if (e) lo = min(lo, e);
+    }
+    atomicMax(&sh[0], hi);
+    atomicMin(&sh[1], lo);
+    __syncthreads();
+    return make_int2(sh[0], sh[1]);
+}
+
+// pm 3: pm 2 with the column normalisation
+__device__ __forceinline__ float f16s_operand(float x, float y, float a, float b, float k1, float k0, float slope, int pm, int emax = 0) {
     if (pm == 1) return lrelu(fmaf(x, a, b), slope);
     if (pm == 2) return fmaf(a, x * lrelu_grad(fmaf(y, a, b), slope), fmaf(k1, y, k0));
+    if (pm == 3) return f16s_colnorm(a, emax) * fmaf(a, x * lrelu_grad(fmaf(y, a, b), slope), fmaf(k1, y, k0));
     return x;
 }
 
@@ -87,24 +120,27 @@ __global__ __launch_bounds__(256) void f16s_absmax_kernel(const float* __restric
     const int cq = C / 4;                                        // C % 4 == 0, rows 16-byte aligned (dispatcher)
     const int64_t total = n_rows * cq;
     float m = 0.f;
+    __shared__ int sh_e[2];
+    int emax = 0;
+    if (PM == 3) emax = f16s_block_expo(pa, C, sh_e).x;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int64_t r = i / cq;
         const int c = (int)(i - r * cq) * 4;
         const float4 x = *reinterpret_cast<const float4*>(A + r * lda + c);
         float4 y = make_float4(0.f, 0.f, 0.f, 0.f), a = y, b = y, k1 = y, k0 = y;
-        if (PM == 2) y = *reinterpret_cast<const float4*>(A2 + r * lda2 + c);
+        if (PM >= 2) y = *reinterpret_cast<const float4*>(A2 + r * lda2 + c);
         if (PM >= 1) {
             a = *reinterpret_cast<const float4*>(pa + c);
             b = *reinterpret_cast<const float4*>(pb + c);
         }
-        if (PM == 2) {
+        if (PM >= 2) {
             k1 = *reinterpret_cast<const float4*>(pk1 + c);
             k0 = *reinterpret_cast<const float4*>(pk0 + c);
         }
-        m = fmaxf(m, fabsf(f16s_operand(x.x, y.x, a.x, b.x, k1.x, k0.x, slope, PM)));
-        m = fmaxf(m, fabsf(f16s_operand(x.y, y.y, a.y, b.y, k1.y, k0.y, slope, PM)));
-        m = fmaxf(m, fabsf(f16s_operand(x.z, y.z, a.z, b.z, k1.z, k0.z, slope, PM)));
-        m = fmaxf(m, fabsf(f16s_operand(x.w, y.w, a.w, b.w, k1.w, k0.w, slope, PM)));
+        m = fmaxf(m, fabsf(f16s_operand(x.x, y.x, a.x, b.x, k1.x, k0.x, slope, PM, emax)));
+        m = fmaxf(m, fabsf(f16s_operand(x.y, y.y, a.y, b.y, k1.y, k0.y, slope, PM, emax)));
+        m = fmaxf(m, fabsf(f16s_operand(x.z, y.z, a.z, b.z, k1.z, k0.z, slope, PM, emax)));
+        m = fmaxf(m, fabsf(f16s_operand(x.w, y.w, a.w, b.w, k1.w, k0.w, slope, PM, emax)));
     }
     m = f16s_wave_max(m);
     if ((threadIdx.x & 63) == 0) {

@@ -68,6 +68,7 @@ __global__ __launch_bounds__(512) void gemm_tn_rm_kernel(const TnRmArgs a) {
     __shared__ __attribute__((aligned(16))) _Float16 Gs[2][2][kRows * TM];      // [buffer][term]
     __shared__ __attribute__((aligned(16))) _Float16 Zs[2][2][kRows * TK];
     __shared__ __attribute__((aligned(16))) float s_co[(GDUAL ? 4 : 0) + (PRO ? 2 : 0) + 1][kT];
+    __shared__ int s_expo[2];
 
     const int n_tiles = a.n_tiles_m * a.n_tiles_k;
     const int xcd = blockIdx.x & (kXcd - 1), local = blockIdx.x >> 3;
@@ -111,14 +112,24 @@ __global__ __launch_bounds__(512) void gemm_tn_rm_kernel(const TnRmArgs a) {
     // two: exact) are folded in -- G: a, b as they are (the gate multiplies by sg or sg * slope), k1 sg, k0 sg; Z: pscale sz, pshift sz (LeakyReLU
     // is positively homogeneous) -- so the conversion needs no separate multiply.
     constexpr int kCoZ = GDUAL ? 4 : 0;
+    // columns whose a is far below the largest a are lifted to it (f16s_colnorm, gemm_f16s.inc); `lifted` is kernel-uniform
+    int emax = 0;
+    bool lifted = false;
+    if (GDUAL) {
+        const int2 ex = f16s_block_expo(a.ga, M, s_expo);
+        emax = ex.x;
+        lifted = ex.x - ex.y > kF16ColGap;
+    }
     if (GDUAL && tid < TM / 4) {                                 // (tid = lane here: c4 = the thread's columns of the table)
         const int tcol = min(tm0 + c4, M - 4);
         const float4 ca = *reinterpret_cast<const float4*>(a.ga + tcol), k1 = *reinterpret_cast<const float4*>(a.gk1 + tcol);
-        const float4 k0 = *reinterpret_cast<const float4*>(a.gk0 + tcol);
-        *reinterpret_cast<float4*>(&s_co[0][c4]) = ca;
-        *reinterpret_cast<float4*>(&s_co[1][c4]) = *reinterpret_cast<const float4*>(a.gb + tcol);
-        *reinterpret_cast<float4*>(&s_co[GDUAL ? 2 : 0][c4]) = make_float4(k1.x * sg, k1.y * sg, k1.z * sg, k1.w * sg);
-        *reinterpret_cast<float4*>(&s_co[GDUAL ? 3 : 0][c4]) = make_float4(k0.x * sg, k0.y * sg, k0.z * sg, k0.w * sg);
+        const float4 k0 = *reinterpret_cast<const float4*>(a.gk0 + tcol), cb = *reinterpret_cast<const float4*>(a.gb + tcol);
+        // (p = 1 unless the column is lifted: undone per row of dW below)
+        const float4 p = make_float4(f16s_colnorm(ca.x, emax), f16s_colnorm(ca.y, emax), f16s_colnorm(ca.z, emax), f16s_colnorm(ca.w, emax));
+        *reinterpret_cast<float4*>(&s_co[0][c4]) = make_float4(ca.x * p.x, ca.y * p.y, ca.z * p.z, ca.w * p.w);
+        *reinterpret_cast<float4*>(&s_co[1][c4]) = make_float4(cb.x * p.x, cb.y * p.y, cb.z * p.z, cb.w * p.w);
+        *reinterpret_cast<float4*>(&s_co[GDUAL ? 2 : 0][c4]) = make_float4(k1.x * p.x * sg, k1.y * p.y * sg, k1.z * p.z * sg, k1.w * p.w * sg);
+        *reinterpret_cast<float4*>(&s_co[GDUAL ? 3 : 0][c4]) = make_float4(k0.x * p.x * sg, k0.y * p.y * sg, k0.z * p.z * sg, k0.w * p.w * sg);
     }
     if (PRO && tid >= 64 && tid < 64 + TK / 4) {
         const int tcol = min(tk0 + c4, K - 4);
@@ -433,7 +444,11 @@ __global__ __launch_bounds__(512) void gemm_tn_rm_kernel(const TnRmArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int m = tm0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (m < M) o[(int64_t)m * a.ld_out + k] = acc[i][j][r] * out_scale;
+                if (m < M) {
+                    float v = acc[i][j][r] * out_scale;
+                    if (GDUAL && lifted) v *= f16s_colnorm(a.ga[m], emax, true);   // (the column's lift, undone)
+                    o[(int64_t)m * a.ld_out + k] = v;
+                }
             }
     }
     if (!a.heal) {

@@ -153,7 +153,7 @@ def bn_bwd_apply(dz, y, bn4, c10, dy, dbias_sums, slope=SLOPE, n_rows=None):
     o = bn4[0].double() * g + c10[0].double() * y[:n].double() + c10[1].double()
     dy[:n].copy_(o)
     if dbias_sums is not None:
-        dbias_sums[:C].copy_(o.sum(0))
+        dbias_sums[:C].copy_(dy[:n].double().sum(0))           # of the values as stored, as the kernel sums them
     return dy
 
 
