@@ -1,8 +1,8 @@
-"""Drop-ins for eleven ``torch_geometric.nn`` 2.2.0 operators on the HIP kernels: same constructor / call signature, parameter names
+"""Drop-ins for twelve ``torch_geometric.nn`` 2.2.0 operators on the HIP kernels: same constructor / call signature, parameter names
 and initialisation; the dense part goes through the GEMMs, the graph part through one fused gather launch per direction, and no
 per-edge feature tensor exists at any point.  Each operator is documented once, at its class: ``GCNConv``, ``ChebConv``,
 ``GATConv``, ``GATv2Conv``, ``TransformerConv``, ``ResGatedGraphConv``, ``FeaStConv``, ``GMMConv`` (with ``cartesian_pseudo``),
-``SplineConv``, ``EdgeConv``, ``SAGEConv``.
+``SplineConv``, ``EdgeConv``, ``SAGEConv``, ``PNAConv`` (with ``degree_histogram``).
 
 ``edge_weight`` (``GCNConv`` and ``ChebConv``; restated from the published PyG 2.2.0 source from memory -- PyG cannot be installed
 here, so this could not be checked against it; the pin is the dense float64 restatement ``tests/gcnw_ref.py``):
@@ -56,11 +56,11 @@ def _bias_grad(dy):
     """Column sum of ``dy``: ``ops.colsum`` at the power-of-two widths it takes, torch otherwise."""
     cout = dy.shape[1]
     pow2 = 8 <= cout <= 1024 and (cout & (cout - 1)) == 0
-    return ops.colsum(dy).to(torch.float32) if pow2 else dy.sum(0)
+    return ops.colsum(dy).to(dy.dtype) if pow2 else dy.sum(0)
 
 
-def _pack(blocks, width, device, pad_each=False):
-    """The blocks ([rows_k, <= width] each, ``None`` skipped) stacked into ONE zero-padded float32 matrix for a single GEMM: end to
+def _pack(blocks, width, device, pad_each=False, dtype=torch.float32):
+    """The blocks ([rows_k, <= width] each, ``None`` skipped) stacked into ONE zero-padded matrix (float32 unless ``dtype``) for a single GEMM: end to
     end with the total rounded up to a multiple of 4, or (``pad_each``) every block rounded up on its own.  -> (the matrix, the
     (start, stop) rows of every block in it, ``None`` for a ``None`` block)."""
     spans, rows = [], 0
@@ -70,16 +70,16 @@ def _pack(blocks, width, device, pad_each=False):
             continue
         spans.append((rows, rows + b.shape[0]))
         rows = (rows + b.shape[0] + 3) // 4 * 4 if pad_each else rows + b.shape[0]
-    wp = torch.zeros(((rows + 3) // 4 * 4, width), dtype=torch.float32, device=device)
+    wp = torch.zeros(((rows + 3) // 4 * 4, width), dtype=dtype, device=device)
     for s, b in zip(spans, blocks):
         if s is not None:
             wp[s[0]:s[1], :b.shape[1]] = b
     return wp, spans
 
 
-def _packed_rows(blocks, width, device, pad_each=False):
+def _packed_rows(blocks, width, device, pad_each=False, dtype=torch.float32):
     """``_pack``'s matrix alone."""
-    return _pack(blocks, width, device, pad_each)[0]
+    return _pack(blocks, width, device, pad_each, dtype)[0]
 
 
 def _cols(m, span):
@@ -87,10 +87,10 @@ def _cols(m, span):
     return None if span is None else m[:, span[0]:span[1]]
 
 
-def _grad_rows(n, used, padded, device):
-    """An uninitialised float32 [n, padded] gradient row buffer with the columns outside the ``used`` (start, stop) spans (``None``
+def _grad_rows(n, used, padded, device, dtype=torch.float32):
+    """An uninitialised [n, padded] gradient row buffer (float32 unless ``dtype``) with the columns outside the ``used`` (start, stop) spans (``None``
     entries skipped) -- the padding the kernels never write -- zeroed."""
-    g = torch.empty((n, padded), dtype=torch.float32, device=device)
+    g = torch.empty((n, padded), dtype=dtype, device=device)
     end = 0
     for a, b in [s for s in used if s is not None] + [(padded, padded)]:
         if a > end:
@@ -99,20 +99,20 @@ def _grad_rows(n, used, padded, device):
     return g
 
 
-def _packed_gemm(x, weights, biases=None, pad_each=False):
-    """The packed linear map every drop-in below starts with: ONE ``ops.gemm_nt`` of the padded float32 x against the weight blocks
+def _packed_gemm(x, weights, biases=None, pad_each=False, dtype=torch.float32):
+    """The packed linear map every drop-in below starts with: ONE ``ops.gemm_nt`` of the padded x (float32 unless ``dtype``) against the weight blocks
     ([rows_k, cin] each; a ``None`` entry is an absent block) stacked by ``_pack``.  ``biases`` is parallel to ``weights``:
     all ``None`` (or no ``biases``) -- the GEMM gets no bias; otherwise they are packed like the weights, with a zero block where a
     present weight has none.  -> (xp, wp, buf, spans): the padded x, the packed weight, the row buffer ``xp @ wp^T + bias`` and
     the column span of every block in ``buf`` -- and in the gradient buffer ``_grad_rows(n, spans, wp.shape[0], device)`` that
     ``_packed_grads`` takes -- ``None`` for an absent block (``_cols(buf, spans[k])`` is block k)."""
-    xp = _pad_cols(x.detach().to(torch.float32))
-    wp, spans = _pack([None if w is None else w.detach() for w in weights], xp.shape[1], x.device, pad_each)
+    xp = _pad_cols(x.detach().to(dtype))
+    wp, spans = _pack([None if w is None else w.detach() for w in weights], xp.shape[1], x.device, pad_each, dtype)
     lb = None
     for s, b in zip(spans, biases or ()):
         if s is not None and b is not None:
             if lb is None:
-                lb = torch.zeros(wp.shape[0], dtype=torch.float32, device=x.device)
+                lb = torch.zeros(wp.shape[0], dtype=dtype, device=x.device)
             lb[s[0]:s[1]] = b.detach()
     return xp, wp, ops.gemm_nt(xp, wp, bias=lb), spans
 
@@ -1579,3 +1579,269 @@ class SAGEConv(nn.Module):
 
     def extra_repr(self):
         return "%d, %d, aggr=%s" % (self.in_channels, self.out_channels, self.aggr)
+
+
+_PNA_AGGRS = ("mean", "sum", "max", "min", "std", "var")
+_PNA_SCALERS = ("identity", "amplification", "attenuation", "linear", "inverse_linear")
+
+
+def _pna_names(what, given, allowed, pairs=()):
+    """-> ``given`` (a list or tuple of names) as a tuple, or ``ValueError``: not a list, empty, a name outside ``allowed``, a
+    repeat, or both names of one of ``pairs``."""
+    if not isinstance(given, (list, tuple)) or not given:
+        raise ValueError("PNAConv: %s must be a non-empty list of names out of %r, got %r" % (what, allowed, given))
+    names = tuple(given)
+    for a in names:
+        if not isinstance(a, str) or a not in allowed:
+            raise ValueError("PNAConv: only the %s %r are implemented on the HIP path, got %r" % (what, allowed, a))
+    if len(set(names)) != len(names):
+        raise ValueError("PNAConv: one of the %s is listed twice in %r" % (what, list(given)))
+    for a, b in pairs:
+        if a in names and b in names:
+            raise ValueError("PNAConv: %s and %s together are not implemented on the HIP path (one %s per launch), got %r"
+                             % (a, b, "sum" if a == "mean" else "second moment", list(given)))
+    return names
+
+
+def degree_histogram(edge_index: torch.Tensor, num_nodes: int) -> torch.Tensor:
+    """The in-degree histogram ``PNAConv``'s ``deg`` expects (as in PyG's own PNA example): int64 [max in-degree + 1], entry k =
+    the number of nodes with k incoming edges (duplicate edges and explicit loops count)."""
+    d = torch.bincount(edge_index[1], minlength=int(num_nodes))
+    return torch.bincount(d)
+
+
+def _pna_scaler_table(graph, edge_index, n, scalers, delta, dtype):
+    """[N, len(scalers)] in the parameters' dtype: every scaler's per-row factor, with ``d_i = max(in-degree_i, 1)``.  It depends
+    on the graph alone, so it is computed once per graph handle (and per scaler set) and kept on it."""
+    tables = graph.__dict__.setdefault("_pna_tables", {})
+    key = (scalers, delta, str(edge_index.device), dtype)
+    if key not in tables:
+        d = torch.bincount(edge_index[1], minlength=n).clamp_(min=1).to(torch.float64)
+        logd = torch.log(d + 1.0)
+        col = {"identity": torch.ones_like(d), "amplification": logd / delta[1], "attenuation": delta[1] / logd,
+               "linear": d / delta[0], "inverse_linear": delta[0] / d}
+        tables[key] = torch.stack([col[s] for s in scalers], 1).to(dtype).contiguous()
+    return tables[key]
+
+
+def _pna_aggr_bwd(graph, aggrs, grads, args, invdeg, mu, values, b, out_a, out_b):
+    """The chain rule of the aggregators of ``A[i] + aggr_j B[j]``.  ``grads``: the gradient reaching every aggregate block, [N, C]
+    each, parallel to ``aggrs``; ``args``: the saved winners of the max / min blocks, in order; ``values``: the forward's blocks
+    ([N, T, F] views; read for std); ``b``: B.  Writes dA into ``out_a`` and dB into ``out_b`` ([N, C] column blocks of one row
+    buffer): torch elementwise work on [N, C] forms dA and the two streams dS / dQ, ONE ``ops.gather_moments_bwd`` launch gathers."""
+    has = (invdeg > 0).view(-1, 1)
+    zero = torch.zeros((), dtype=out_a.dtype, device=out_a.device)
+    weighted = any(a in ("mean", "std", "var") for a in aggrs)   # the dS stream's coefficient: a w_i (else a: the sum alone)
+    args, op, da, ds = list(args), {}, None, None
+    for a, d, v in zip(aggrs, grads, values):
+        if a in ("max", "min"):
+            key = "mx" if a == "max" else "mn"
+            op["d" + key], op["arg" + key] = d, args.pop(0)
+            da = d if da is None else da + d
+        elif a == "mean":
+            ds = d if ds is None else ds + d
+            da = d if da is None else da + d
+        elif a == "sum":
+            # deg_i x dSum is dA's share; next to a mean / std / var it is also the sum's share of the a w_i stream
+            dd = d * torch.where(has, torch.round(1.0 / invdeg.view(-1, 1)), zero)
+            ds = (dd if weighted else d) if ds is None else ds + dd
+            da = dd if da is None else da + dd
+        else:
+            v = v.reshape(d.shape)
+            g = torch.where(v > 0, d / v, zero) if a == "std" else 2.0 * d
+            op["dq"], op["b"] = g, b
+            ds = -(g * mu) if ds is None else ds - g * mu
+    out_a.copy_(zero if da is None else da * has)
+    ops.gather_moments_bwd(graph, ds=ds, invdeg=invdeg if weighted else None, out=out_b, **op)
+
+
+class _PNAConvFn(_Fn):
+    """``PNAConv``'s route (see the class).  Inputs: x, the graph, the [N, S] scaler table, the aggregators, ``want_arg``, then the
+    parameters ``pre_w[T], pre_b[T], post_w[T], post_b[T], lin_w, lin_b``.  Saved: the padded x and centred x, the packed pre weight, the
+    ``[A | B]`` row buffer (the backward multiplies by the row's own B), the tower-major aggregate buffer, the padded ``H = cat_t
+    out_t``, the args, ``mu`` and ``invdeg``.  The chain rule of the aggregators is ``_pna_aggr_bwd``."""
+
+    @staticmethod
+    def forward(ctx, x, graph, sc, aggrs, want_arg, *params):
+        T = (len(params) - 2) // 4
+        pre_w, pre_b, post_w, post_b = (params[k * T:(k + 1) * T] for k in range(4))
+        lin_w, lin_b = params[4 * T:]
+        n, F, fo, A, S = x.shape[0], x.shape[1], post_w[0].shape[0], len(aggrs), sc.shape[1]
+        dev, dt = x.device, lin_w.dtype                         # (float32; the kernels refuse anything else)
+        wa = torch.cat([w.detach()[:, :F] for w in pre_w], 0)
+        wb = torch.cat([w.detach()[:, F:] for w in pre_w], 0)
+        # the message is invariant to a per-column constant c: x_i Wa + x_j Wb + b = (x_i - c) Wa + (x_j - c) Wb + (b + (Wa + Wb) c).
+        # With c = x[0] B is of the size of the features' SPREAD, so a column far from 0 costs std / var and their gradient nothing
+        xd = x.detach().to(dt)
+        c = xd[:1]
+        xp = _pad_cols(xd)
+        bc = torch.cat([b.detach() for b in pre_b]) + ((wa + wb) * c).sum(1)
+        xcp, wp, buf, spans = _packed_gemm(xd - c, (wa, wb), (bc, None), pad_each=True, dtype=dt)   # [A | B]
+        want = bool(want_arg) and (ctx.needs_input_grad[0] or any(ctx.needs_input_grad[5:]))
+        agg = torch.empty((n, T * A * F), dtype=dt, device=dev)                  # [tower][aggregator][F]
+        _, args, invdeg, mu = ops.gather_moments(graph, _cols(buf, spans[1]), want=aggrs, root=_cols(buf, spans[0]),
+                                                 tower_width=F, want_arg=want, out=agg)
+        # the x columns of every tower's post weight in ONE GEMM, with the post biases
+        wx = _packed_rows([torch.cat([w.detach()[:, :F] for w in post_w], 0)], xp.shape[1], dev, dtype=dt)
+        bx = torch.zeros(wx.shape[0], dtype=dt, device=dev)
+        bx[:T * fo] = torch.cat([b.detach() for b in post_b])
+        hx = ops.gemm_nt(xp, wx, bias=bx)
+        hp = torch.zeros((n, (T * fo + 3) // 4 * 4), dtype=dt, device=dev)       # H = cat_t out_t, zero padding
+        wz = []
+        for t in range(T):
+            # tower t's scaler-packed post weight [S * F_out, A * F]: row s * F_out + o = post_w[t][o, F + s * A * F : F + (s + 1) * A * F]
+            w = post_w[t].detach()[:, F:].reshape(fo, S, A * F).transpose(0, 1).reshape(S * fo, A * F)
+            wz.append(_packed_rows([_pad_cols(w)], (A * F + 3) // 4 * 4, dev, dtype=dt))
+            z = ops.gemm_nt(_pad_cols(agg[:, t * A * F:(t + 1) * A * F]), wz[t])            # Z_t [N, S * F_out (+ padding)]
+            hp[:, t * fo:(t + 1) * fo] = hx[:, t * fo:(t + 1) * fo] + (z[:, :S * fo].reshape(n, S, fo) * sc.unsqueeze(-1)).sum(1)
+        wl = _pad_cols(_packed_rows([lin_w.detach()], lin_w.shape[1], dev, dtype=dt))
+        bl = torch.zeros(wl.shape[0], dtype=dt, device=dev)
+        bl[:T * fo] = lin_b.detach()
+        y = ops.gemm_nt(hp, wl, bias=bl)[:, :T * fo]
+        ctx.save_for_backward(xp, xcp, c, wp, buf, agg, hp, sc, wx, wl, invdeg, mu, *wz, *[a for a in args if a is not None])
+        ctx.graph, ctx.aggrs, ctx.spans, ctx.dims = graph, aggrs, spans, (T, F, fo)
+        return y.contiguous()
+
+    @staticmethod
+    def _backward(ctx, dy):
+        xp, xcp, c, wp, buf, agg, hp, sc, wx, wl, invdeg, mu, *rest = ctx.saved_tensors
+        (T, F, fo), aggrs, graph, spans = ctx.dims, ctx.aggrs, ctx.graph, ctx.spans
+        wz, args = rest[:T], list(rest[T:])
+        n, A, S, C, dev, dt = dy.shape[0], len(aggrs), sc.shape[1], T * F, dy.device, hp.dtype
+        dyp = _pad_cols(dy.contiguous().to(dt))
+        # lin
+        dlin_b = _bias_grad(dyp)[:T * fo]
+        dlin_w = ops.gemm_tn(dyp, hp)[:T * fo, :T * fo]
+        dh = ops.gemm_nn(dyp, wl)                               # [N, out (+ padding)], padding columns 0
+        # the x columns of the post weights
+        dpost_b = _bias_grad(dh)[:T * fo]
+        dwx = ops.gemm_tn(dh, xp)[:T * fo, :F]
+        dx = ops.gemm_nn(dh, wx)[:, :F]
+        # per tower: the scaler-weighted gradient of Z_t, its wgrad and dgrad on the tower's columns of the aggregate buffer
+        dblk = torch.empty((n, A * C), dtype=dt, device=dev)                     # [aggregator][tower][F]: plain [N, C] blocks
+        dpost_w = []
+        for t in range(T):
+            dz = torch.zeros((n, wz[t].shape[0]), dtype=dt, device=dev)
+            dz[:, :S * fo] = (dh[:, t * fo:(t + 1) * fo].unsqueeze(1) * sc.unsqueeze(-1)).reshape(n, S * fo)
+            aggt = _pad_cols(agg[:, t * A * F:(t + 1) * A * F])
+            dwz = ops.gemm_tn(dz, aggt)[:S * fo, :A * F]                                      # [S * F_out, A * F]
+            dpost_w.append(torch.cat([dwx[t * fo:(t + 1) * fo], dwz.reshape(S, fo, A * F).transpose(0, 1).reshape(fo, S * A * F)], 1))
+            dagg = ops.gemm_nn(dz, wz[t])                                                    # [N, A * F (+ padding)]
+            dblk.view(n, A, T, F)[:, :, t] = dagg[:, :A * F].reshape(n, A, F)
+        gb = _grad_rows(n, spans, wp.shape[0], dev, dt)
+        _pna_aggr_bwd(graph, aggrs, [dblk[:, k * C:(k + 1) * C] for k in range(A)], args, invdeg, mu,
+                      [agg.view(n, T, A, F)[:, :, k] for k in range(A)], _cols(buf, spans[1]), _cols(gb, spans[0]), _cols(gb, spans[1]))
+        # x was centred: dW = g^T (x - c) + colsum(g) c^T.  colsum(dB) = colsum(dA) (every aggregator hands on all it receives, and
+        # std / var nothing), and dA's is the well-conditioned one: the column sum of the std / var part of dB is an exact 0
+        dxp, (dwa, dwb), (dba, _) = _packed_grads(gb, xcp, wp, spans, F, (True, True), (True, False), True)
+        dx = dx + dxp
+        shift = dba.view(-1, 1) * c
+        dwa, dwb = dwa + shift, dwb + shift
+        dpre_w = [torch.cat([dwa[t * F:(t + 1) * F], dwb[t * F:(t + 1) * F]], 1) for t in range(T)]
+        dpre_b = [dba[t * F:(t + 1) * F] for t in range(T)]
+        dpost_b = [dpost_b[t * fo:(t + 1) * fo] for t in range(T)]
+        return (dx, None, None, None, None, *dpre_w, *dpre_b, *dpost_w, *dpost_b, dlin_w, dlin_b)
+
+
+class _Seq1(nn.Sequential):
+    """A ``Sequential`` of ONE ``Linear`` with a bias: PyG's single-layer pre / post MLP, whose parameters are ``0.weight`` / ``0.bias``."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__(_LinB(in_channels, out_channels))
+
+
+class PNAConv(nn.Module):
+    """``torch_geometric.nn.PNAConv`` 2.2.0 (Corso et al., Principal Neighbourhood Aggregation, NeurIPS 2020) on the HIP kernels
+    (DESIGN.md 4.17), ``PNAConv(in_channels, out_channels, aggregators, scalers, deg, edge_dim=None, towers=1, pre_layers=1,
+    post_layers=1, divide_input=False, act="relu", act_kwargs=None)``, ``forward(x, edge_index, edge_attr=None)`` (restated from
+    the published 2.2.0 source, not checked against an installed PyG; the pin is the float64 restatement ``tests/pna_ref.py``):
+
+    * per tower t: the message ``h_t(j -> i) = pre_nns[t](cat[x_i, x_j])``, aggregated over each target's incoming edges with every
+      aggregator (``mean``, ``sum``, ``max``, ``min``, ``std``, ``var``), multiplied by every scaler (``identity``,
+      ``amplification``, ``attenuation``, ``linear``, ``inverse_linear``; concatenated scaler-major, then aggregator, then F),
+      ``out_t = post_nns[t](cat[x_i, that])``, ``y = lin(cat_t out_t)``.  Parameters: ``pre_nns.{t}.0.weight`` [F, 2 F] and
+      ``.bias``, ``post_nns.{t}.0.weight`` [F_out, (len(aggregators) * len(scalers) + 1) * F] and ``.bias``, ``lin.weight``
+      [out, out] and ``.bias``, with F = in_channels and F_out = out_channels // towers, all uniform(+-1/sqrt(fan-in)).
+      ``act`` / ``act_kwargs`` are accepted and unused: a single-layer MLP has no activation.
+    * scalers: with ``d_i = max(in-degree_i, 1)`` and, from the histogram ``deg`` (``degree_histogram``), ``delta_lin = sum k deg[k]
+      / sum deg`` and ``delta_log = sum log(k + 1) deg[k] / sum deg``: amplification ``log(d + 1) / delta_log``, attenuation
+      ``delta_log / log(d + 1)``, linear ``d / delta_lin``, inverse_linear ``delta_lin / d``.
+    * std: ``sqrt(max(var, 1e-5))``, then 0 where that is ``<= sqrt(1e-5)``, gradient 0 there (``StdAggregation``); var:
+      ``mean(h^2) - mean(h)^2``.  Here both come from sums shifted by the row's first entry (exact where PyG's form cancels).
+    * the route (``_PNAConvFn``): with ``W_t = [Wa_t | Wb_t]`` the message is ``A_t[i] + B_t[j]``, every aggregator of it over j is
+      ``A_t[i] + aggr_j B_t[j]`` (``deg_i A_t[i] +`` for the sum) and std / var do not see ``A`` at all.  ONE GEMM of x against the
+      packed ``[Wa_1; ..; Wa_T; Wb_1; ..; Wb_T]`` gives ``[A | B]``; ONE ``ops.gather_moments`` launch over B with root A writes
+      every aggregator of every tower into one tower-major row buffer; the scalers are per-row scalars, so they are applied AFTER
+      the post GEMM: per tower one GEMM of its ``[N, len(aggregators) * F]`` columns against the scaler-packed post weight gives
+      ``Z_t`` [N, len(scalers) * F_out], one GEMM ``x @ W_x`` covers the x columns of all towers, ``out_t = x W_x + b + sum_s
+      s_s(i) Z_{t,s}[i]`` is elementwise work, then the ``lin`` GEMM.  The [N, len(scalers)] scaler table is computed once per
+      graph.  Backward: the mirrored wgrad / dgrad GEMMs, the chain rule of std / var as torch elementwise work on [N, .], and ONE
+      ``ops.gather_moments_bwd`` launch -> ``[dA | dB]`` for one wgrad and one dgrad GEMM against the packed pre weights.  No
+      [E, .] tensor (PyG holds [E, towers, F]) and no ``index_add_`` / ``scatter`` exist at any point.  The graph is GATConv's
+      without loops: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.  Symmetric edge STRUCTURE only.
+    * duplicate edges count in the degree, mean, sum, std and var and cannot change max / min; a node without incoming edges gets
+      ``post(cat[x_i, 0])``.  Differentiable w.r.t. x and every parameter; float32, bitwise reproducible; a forward without a
+      gradient stores no args.  Deviation: with exact ties PyG's max / min winner is unspecified, ours is the smallest source id.
+    * refused with ``ValueError`` before any launch: ``edge_dim`` / ``edge_attr``, ``pre_layers > 1`` (a per-edge MLP),
+      ``post_layers > 1``, ``divide_input=True``, ``out_channels % towers != 0``, an aggregator or scaler outside the lists above, a
+      repeat, mean and sum together, std and var together, an empty list, tuple inputs, bf16 features, a CPU ``x``, an ``x`` that
+      is not [N, in]."""
+
+    def __init__(self, in_channels, out_channels: int, aggregators, scalers, deg, edge_dim=None, towers: int = 1, pre_layers: int = 1,
+                 post_layers: int = 1, divide_input: bool = False, act="relu", act_kwargs=None, **kwargs):
+        super().__init__()
+        _no_tuple_channels("PNAConv", in_channels)
+        _not_implemented("PNAConv", edge_dim=edge_dim)
+        _int_ge1("PNAConv", "towers", towers)
+        if pre_layers != 1:
+            raise ValueError("PNAConv: pre_layers > 1 (a per-edge MLP) is not implemented on the HIP path, got %r" % (pre_layers,))
+        if post_layers != 1:
+            raise ValueError("PNAConv: post_layers > 1 is not implemented on the HIP path, got %r" % (post_layers,))
+        if divide_input:
+            raise ValueError("PNAConv: divide_input=True is not implemented on the HIP path")
+        if out_channels % towers != 0:
+            raise ValueError("PNAConv: out_channels (%d) must be a multiple of towers (%d)" % (out_channels, towers))
+        self._aggrs = _pna_names("aggregators", aggregators, _PNA_AGGRS, (("mean", "sum"), ("std", "var")))
+        self._scalers = _pna_names("scalers", scalers, _PNA_SCALERS)
+        if kwargs:
+            raise TypeError("PNAConv: unexpected keyword arguments %s" % sorted(kwargs))
+        if not isinstance(deg, torch.Tensor) or deg.dim() != 1 or deg.numel() == 0 or float(deg.sum()) <= 0:
+            raise ValueError("PNAConv: deg must be the in-degree histogram, a 1-D tensor with a positive sum (degree_histogram)")
+        h = deg.detach().to("cpu", torch.float64)
+        k = torch.arange(h.numel(), dtype=torch.float64)
+        self.avg_deg = {"lin": float((k * h).sum() / h.sum()), "log": float((torch.log(k + 1) * h).sum() / h.sum())}
+        self.in_channels, self.out_channels, self.towers = in_channels, out_channels, towers
+        self.aggregators, self.scalers, self.edge_dim, self.divide_input = list(aggregators), list(scalers), None, False
+        self.F_in, self.F_out = in_channels, out_channels // towers
+        self.pre_nns = nn.ModuleList([_Seq1(2 * self.F_in, self.F_in) for _ in range(towers)])
+        self.post_nns = nn.ModuleList([_Seq1((len(self._aggrs) * len(self._scalers) + 1) * self.F_in, self.F_out) for _ in range(towers)])
+        self.lin = _LinB(out_channels, out_channels)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            for seq in list(self.pre_nns) + list(self.post_nns):
+                _reset_linear(seq[0])
+            _reset_linear(self.lin)
+
+    def forward(self, x, edge_index, edge_attr=None) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
+        _no_tuple_x("PNAConv", x)
+        _not_implemented("PNAConv", edge_attr=edge_attr)
+        _check_x("PNAConv", x, self.in_channels)
+        _need_gpu("PNAConv", x, exc=ValueError)
+        _need_entries("PNAConv", edge_index)
+        return self._core(x, edge_index)
+
+    def _core(self, x, edge_index):
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
+            sc = _pna_scaler_table(graph, edge_index, x.shape[0], self._scalers, (self.avg_deg["lin"], self.avg_deg["log"]), self.lin.weight.dtype)
+            params = ([s[0].weight for s in self.pre_nns] + [s[0].bias for s in self.pre_nns] + [s[0].weight for s in self.post_nns]
+                      + [s[0].bias for s in self.post_nns] + [self.lin.weight, self.lin.bias])
+            want = torch.is_grad_enabled() and any(t.requires_grad for t in [x] + params)
+            return _PNAConvFn.apply(x, graph, sc, self._aggrs, want, *params)
+
+    def extra_repr(self):
+        return "%d, %d, towers=%d, aggregators=%s, scalers=%s" % (self.in_channels, self.out_channels, self.towers, self.aggregators,
+                                                                self.scalers)

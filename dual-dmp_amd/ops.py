@@ -1430,6 +1430,130 @@ def gather_stats_bwd(g: Graph, ds=None, invdeg=None, dmx=None, argmx=None, dmn=N
     return dx, dr
 
 
+# ---------------------------------------------------------------------------------------- neighbour moments
+MOMENTS = ("mean", "sum", "max", "min", "std", "var")
+
+
+def _moments_want(want):
+    """``want`` as a tuple of distinct names out of ``MOMENTS`` with at most one of mean / sum and at most one of std / var, or
+    ``DdmpError``."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if (not want or any(w not in MOMENTS for w in want) or len(set(want)) != len(want) or ("mean" in want and "sum" in want)
+            or ("std" in want and "var" in want)):
+        raise DdmpError("want must be a non-empty sequence of distinct names out of %r with at most one of 'mean' / 'sum' and at most "
+                        "one of 'std' / 'var', got %r" % (MOMENTS, want))
+    return want
+
+
+def gather_moments(g: Graph, b, want=("mean",), root=None, tower_width=None, want_arg=True, out=None):
+    """Mean-or-sum / max / min / std-or-var of the neighbours' rows in ONE launch (``ddmp_gather_moments_f32``): every neighbour row
+    of ``b`` [n, C] is read once and feeds every statistic in ``want`` (names out of ``MOMENTS``, at most one of mean / sum and of
+    std / var).  -> (blocks, args, invdeg, mu):
+
+    * ``blocks``: one result per entry of ``want``, in that order, views into ``out``, a float32 [n, >= len(want) * C] row buffer
+      (further columns are left untouched; ``out=None``: a buffer of its own, exactly that wide).  Plain layout
+      (``tower_width`` None or C): block k is the columns [k * C, (k + 1) * C), an [n, C] view.  Tower-major (``tower_width`` = tw,
+      a divisor of C; T = C / tw towers): the buffer is ``[tower][statistic][tw]``, column c of block k lands at
+      ``(c // tw) * len(want) * tw + k * tw + c % tw``, and block k is the [n, T, tw] view of it -- the columns
+      ``[t * len(want) * tw, (t + 1) * len(want) * tw)`` hold every statistic of tower t.
+    * ``args``: parallel to ``want``: int32 [n, C] (plain), the source node id of the winning entry, for max / min (ties: the smallest
+      id; -1 for a row without entries; ``want_arg=False``: not stored, None), None for the others.
+    * ``invdeg``: [n], 1 / the number of input edges into the row (0 for a row without entries), always.
+    * ``mu``: [n, C], the neighbour mean WITHOUT the root, when ``want`` has std or var (the backward needs it), else None.
+
+    std / var: the second central moment from sums shifted by the row's first entry, ``std = var > 1e-5 ? sqrt(var) : 0`` (PyG
+    2.2.0's ``StdAggregation``).  ``root`` [n, C] (it may be a column block of the buffer ``b`` is a block of): on a row with
+    entries it is added to mean / max / min and ``deg * root`` to sum, never to std / var; a row without entries gets 0 in every
+    block whatever ``root`` is."""
+    _gmm_graph(g)
+    want = _moments_want(want)
+    n = g.n_rows
+    b, ldb = _rows(b, "b", n)
+    C = b.shape[1]
+    tw = C if tower_width is None else tower_width
+    if not isinstance(tw, int) or isinstance(tw, bool) or tw < 1 or C % tw:
+        raise DdmpError("gather_moments: tower_width must be a divisor of C = %d, got %r" % (C, tower_width))
+    ldr = 0
+    if root is not None:
+        root, ldr = _rows(root, "root", n, C)
+    nb, T = len(want), C // tw
+    if out is None:
+        out = torch.empty((n, nb * C), dtype=torch.float32, device=b.device)
+    out, ldo = _mat(_chk(out, torch.float32, "out"), "out")
+    if out.shape[0] != n or out.shape[1] < nb * C:
+        raise DdmpError("gather_moments: out must be [%d, >= %d], got %s" % (n, nb * C, tuple(out.shape)))
+    if T == 1:
+        blocks = [out[:, k * C:(k + 1) * C] for k in range(nb)]
+    else:
+        towers = out[:, :nb * C].unflatten(1, (T, nb, tw))
+        blocks = [towers[:, :, k] for k in range(nb)]
+    ptr = {k: (None, 0) for k in ("sum", "max", "min", "var", "amax", "amin")}
+    args = [None] * nb
+    for k, w in enumerate(want):
+        key = "sum" if w in ("mean", "sum") else "var" if w in ("std", "var") else w
+        ptr[key] = (out[:, k * tw:], ldo)                        # (the block's first column; the kernel places the towers)
+        if w in ("max", "min") and want_arg:
+            args[k] = torch.empty((n, C), dtype=torch.int32, device=b.device)
+            ptr["a" + w] = _gmax_arg(args[k], n, C)
+    has_var = ptr["var"][0] is not None
+    mu = torch.empty((n, C), dtype=torch.float32, device=b.device) if has_var else None
+    invdeg = torch.empty(n, dtype=torch.float32, device=b.device)
+    # algorithmic bytes: every gathered row read ONCE whatever the number of statistics, one row written per block, per arg and for mu,
+    # the root block read, invdeg written, col + multiplicity, rowptr
+    n_arg = sum(a is not None for a in args)
+    alg = 4.0 * n * C * (1 + nb + n_arg + (root is not None) + has_var) + 4.0 * n + 8.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("gather_moments", (C, "+".join(want), tw, int(round(g.nnz / max(n, 1)))), alg, 1.0 * g.nnz * C * (nb + has_var),
+                survey=8.0 * n * C + 4.0 * g.nnz + 4.0 * (n + 1)):
+        st = _lib.lib().ddmp_gather_moments_f32(g.handle, _p(b), ldb, C, int("mean" in want), int("std" in want), _p(root), ldr, tw,
+                                                nb * tw, _p(ptr["sum"][0]), ptr["sum"][1], _p(ptr["max"][0]), ptr["max"][1],
+                                                _p(ptr["amax"][0]), ptr["amax"][1], _p(ptr["min"][0]), ptr["min"][1],
+                                                _p(ptr["amin"][0]), ptr["amin"][1], _p(ptr["var"][0]), ptr["var"][1], _p(mu), C,
+                                                _p(invdeg), _stream())
+    check(st, "ddmp_gather_moments_f32")
+    return tuple(blocks), tuple(args), invdeg, mu
+
+
+def gather_moments_bwd(g: Graph, ds=None, dq=None, b=None, invdeg=None, dmx=None, argmx=None, dmn=None, argmn=None,
+                       out=None):
+    """Backward of ``gather_moments`` in one launch (``ddmp_gather_moments_bwd_f32``) -> db [n, C], written completely:
+    ``db[j] = sum_{e' in row j} (a w_i ds[i] + (argmx[i] == j ? dmx[i] : 0) + (argmn[i] == j ? dmn[i] : 0)) + b[j] *
+    sum_{e' in row j} a w_i dq[i]`` with ``i = col e'``, ``a`` the mirrored multiplicity and ``w_i = invdeg[i]`` (None: 1).  All
+    operands [n, C], plain layout.  ``dq`` (with ``b``, and needing ``ds``) is the second stream of the std / var chain rule: with
+    ``G = dstd / std`` where ``std > 0`` (else 0), or ``2 dvar``, pass ``dq = G`` and add ``-G * mu`` to ``ds``.
+    ``out``: a float32 [n, C] row block (it may be a column block
+    of a wider buffer) that receives db; None: a tensor of its own."""
+    _gmm_graph(g)
+    n = g.n_rows
+    first = next((t for t in (ds, dmx, dmn) if t is not None), None)
+    if (first is None or (dmx is None) != (argmx is None) or (dmn is None) != (argmn is None) or (ds is None and (dq is not None or
+            invdeg is not None)) or (dq is None) != (b is None)):
+        raise DdmpError("gather_moments_bwd: at least one of ds, dmx, dmn; dmx comes with argmx, dmn with argmn; dq comes with b and "
+                        "needs ds; invdeg needs ds")
+    C = first.shape[1] if isinstance(first, torch.Tensor) and first.dim() == 2 else 0
+    op = {}
+    for name, t in (("ds", ds), ("dq", dq), ("b", b), ("dmx", dmx), ("dmn", dmn)):
+        op[name] = (None, 0) if t is None else _rows(t, name, n, C)
+    for name, t in (("argmx", argmx), ("argmn", argmn)):
+        op[name] = (None, 0) if t is None else _gmax_arg(t, n, C)
+    if invdeg is not None:
+        invdeg = _gat_arr(invdeg, (n,), "invdeg")
+    db, lddb = _out(out, "out", n, C, first.device)
+    if db.shape[0] != n:
+        raise DdmpError("gather_moments_bwd: out must be [%d, %d], got %s" % (n, C, tuple(db.shape)))
+    ns = sum(t is not None for t in (ds, dq, dmx, dmn))
+    # algorithmic bytes: every requested gradient stream (and each arg) read once, the row's own b read, db written, invdeg, col +
+    # mirror + multiplicity, rowptr
+    alg = (4.0 * n * C * (ns + (argmx is not None) + (argmn is not None) + (b is not None) + 1) + 4.0 * n * (invdeg is not None)
+           + 12.0 * g.nnz + 4.0 * (n + 1))
+    with _timed("gather_moments_bwd", (C, ns, int(round(g.nnz / max(n, 1)))), alg, 1.0 * g.nnz * C * ns):
+        st = _lib.lib().ddmp_gather_moments_bwd_f32(g.handle, C, _p(op["ds"][0]), op["ds"][1], _p(op["dq"][0]), op["dq"][1],
+                                                    _p(op["b"][0]), op["b"][1], _p(invdeg), _p(op["dmx"][0]), op["dmx"][1],
+                                                    _p(op["argmx"][0]), op["argmx"][1], _p(op["dmn"][0]), op["dmn"][1],
+                                                    _p(op["argmn"][0]), op["argmn"][1], _p(db), lddb, _stream())
+    check(st, "ddmp_gather_moments_bwd_f32")
+    return db
+
+
 def spmm_axpby(g: Graph, x, out=None, z=None, z2=None, a=1.0, b=0.0, c=0.0, d=0.0):
     """out[i] = a * (dinv_i * sum_j dinv_j x[j]) + b * x[i] + c * z[i] + d * z2[i], float32 (ddmp_spmm_axpby_f32): one step of a
     three-term recurrence per launch.  ``z`` / ``z2`` optional (their coefficient is then ignored); ``out`` may be ``z`` or ``z2``,

@@ -460,6 +460,46 @@ int ddmp_gather_stats_bwd_f32(const ddmp_graph* g, int C, const float* dS /*null
                               const int32_t* argmn /*nullable*/, int64_t ldamn, const float* dX0 /*nullable*/, int64_t lddx0,
                               float* dX, int64_t lddx, float* dR /*nullable*/, int64_t lddr, ddmp_stream stream);
 
+/* ------------------------------------------------------------------ neighbour moments (PNAConv): mean-or-sum,
+ * max, min and std-or-var of the neighbours' rows in one sweep, on the graph and with the rules of the neighbour statistics above
+ * (same fma order, ONE multiplication for the mean, strict comparisons from the row's first entry: the smallest source id wins a
+ * tie).  No atomics, fixed orders, every output written completely; a block of a fused call has the bits of the same block
+ * requested alone, and without R and with tw == C the S, Mx, Mn blocks and the args have the bits of ddmp_gather_stats_f32.
+ *
+ * forward:   every neighbour row B[col e, :] is loaded once and feeds any non-empty subset of four blocks (a null pointer: not
+ *            requested; none at all is DDMP_EINVAL):
+ *            S       = w_i sum_e a_e B[col e, c], w_i = 1 / deg_i (mean != 0) or 1;
+ *            Mx, argmx (nullable), Mn, argmn (nullable): as in ddmp_gather_stats_f32;
+ *            V       = the second central moment of the row's entries, from sums SHIFTED by the row's first entry K = B[col rbase, c]:
+ *                      d_e = B[col e, c] - K, m1 = sum a_e d_e, m2 = sum a_e d_e d_e, mu = K + m1 w, var = max(m2 w - (m1 w)^2, 0),
+ *                      w = 1 / deg_i; V = var, or (as_std != 0) var > 1e-5 ? sqrt(var) : 0 (PyG 2.2.0's StdAggregation).  V comes
+ *                      with mu [n, C] (the neighbour mean, saved for the backward; DDMP_EINVAL without it, or mu without V).
+ *            R (nullable, [n, C]): on a row WITH entries R[i,c] is added to the mean, to Mx and to Mn (one unfused addition each)
+ *                      and deg_i R[i,c] to the sum; never to V.  A row without entries gets 0 in every block whatever R is, -1
+ *                      in the args, 0 in mu and invdeg.
+ *            tw, tstride: column c of S, Mx, Mn, V lands at base + row * ld + (c / tw) * tstride + c % tw (tower-major: the row
+ *                      buffer can be [tower][aggregator][tw]); tw must divide C; tw == C is the plain layout (tstride ignored).
+ *                      The args, mu and invdeg (nullable, [n]: 1 / deg_i) are always plain.  The vector kernels need C, tw, tstride
+ *                      and every leading dimension % 4 == 0 and 16-byte aligned matrices; anything else takes scalar kernels.
+ *            No output may alias B, R or another output.  One launch. */
+int ddmp_gather_moments_f32(const ddmp_graph* g, const float* B, int64_t ldb, int C, int mean, int as_std, const float* R /*nullable*/,
+                            int64_t ldr, int tw, int64_t tstride, float* S /*nullable*/, int64_t lds, float* Mx /*nullable*/,
+                            int64_t ldmx, int32_t* argmx /*nullable*/, int64_t ldamx, float* Mn /*nullable*/, int64_t ldmn,
+                            int32_t* argmn /*nullable*/, int64_t ldamn, float* V /*nullable*/, int64_t ldv, float* mu /*nullable*/,
+                            int64_t ldmu, float* invdeg /*nullable*/, ddmp_stream stream);
+/* backward, node side (symmetric structure, as ddmp_gather_stats_bwd_f32):
+ *            dB[j,c] = sum_{e' in row j} ( a w_i dS[i,c] + (argmx[i,c] == j ? dMx[i,c] : 0) + (argmn[i,c] == j ? dMn[i,c] : 0) )
+ *                      + B[j,c] sum_{e' in row j} a w_i dQ[i,c],   i = col e', a = a_{mirror e'},
+ *            w_i = invdeg[i], or 1 with invdeg null.  dQ (nullable; needs dS and B) is the second stream of the std / var chain
+ *            rule: with G = dStd / std where std > 0 (else 0), or 2 dVar, the caller passes dQ = G and adds -G mu to dS.
+ *            dB is written completely: a row without entries gets zeros.
+ *            One launch. */
+int ddmp_gather_moments_bwd_f32(const ddmp_graph* g, int C, const float* dS /*nullable*/, int64_t ldds, const float* dQ /*nullable*/,
+                                int64_t lddq, const float* B /*nullable*/, int64_t ldb,
+                                const float* invdeg /*nullable*/, const float* dMx /*nullable*/, int64_t lddmx,
+                                const int32_t* argmx /*nullable*/, int64_t ldamx, const float* dMn /*nullable*/, int64_t lddmn,
+                                const int32_t* argmn /*nullable*/, int64_t ldamn, float* dB, int64_t lddb, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ dense steps (MFMA; float32 operands and results, the
  * arithmetic is ddmp_set_gemm_mode's: by default SPLIT-precision 16-bit MFMA products with f32 accumulation -- f32-class
  * accuracy, not bit-exact f32; mode 0 = f32-input MFMA, the strict one)

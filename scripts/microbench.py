@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|spline|sage|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|spline|sage|pna|all] [--rows N] [--iters K]
+pna (not part of all): the neighbour-moments launches (ops.gather_moments, ops.gather_moments_bwd) at C = 64, 128, 256
+on the same graph as sage, alternating in one loop: the fused mean + min + max + std forward (plain and tower-major) against
+ops.gather_stats(mean + max + min) plus the two-launch composition of the variance from the gather_stats means of x and of x * x, and
+the backward launch against ops.gather_stats_bwd; the figures and the algorithmic byte counts go to --out
+(profiles/pna_microbench.txt).
 sage (not part of all): the neighbour-statistics launches (ops.gather_stats, ops.gather_stats_bwd) at C = 64, 128,
 256 on the vertex graph of a torus with --rows vertices in RCB order, without loops, alternating in one loop: the fused mean + max
 and mean + max + min forward against the composition of ops.gather_max and one single-statistic launch per remaining aggregator,
@@ -65,7 +70,7 @@ ap.add_argument("--widths", default="512,256,128,64,32")
 ap.add_argument("--rotate", type=int, default=1, help="spmm: cycle through this many (input, output) buffer sets so that narrow "
                 "widths are not served from the 256 MB MALL (a 1M x 32 float tensor is 128 MB)")
 ap.add_argument("--weighted", action="store_true", help="spmm: valued graph against the unvalued graph of the same mesh")
-ap.add_argument("--out", default=None, help="gat / gatv2 / transformer / resgated / feast / edge / gmm / spline / sage: the file the figures are written to (default profiles/<what>_microbench.txt)")
+ap.add_argument("--out", default=None, help="gat / gatv2 / transformer / resgated / feast / edge / gmm / spline / sage / pna: the file the figures are written to (default profiles/<what>_microbench.txt)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 n = a.rows
@@ -879,5 +884,64 @@ if a.what == "sage":
         print("\n".join(lines[-(len(alg) + 2):]), flush=True)
         del Bs, Xs, Rs, Ds, O1, O2, O3, Oa, Ob, G2, saved, amx, inv, amx_e
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "sage_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.what == "pna":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    g = ops.graph_for(ei, nn_, norm="gat", add_self_loops=False)
+    reps = max(a.iters, 20)
+    lines = ["neighbour moments (PNAConv) on the vertex graph of torus(%d, %d) in RCB order: N=%d, entries=%d (no loops), float32; "
+             "median of %d launches [min q1 q3 max], one HIP-event pair per launch, forms alternating in one loop, rotating buffer "
+             "sets; fused = ONE ops.gather_moments launch (mean + min + max + std, root A, mu and both args stored); composed = "
+             "ops.gather_stats(mean + max + min) + the variance from two more ops.gather_stats means, of x and of x * x (the sum of "
+             "the three medians; the x * x product, the subtraction and the root additions are not counted); bytes = the "
+             "algorithmic counts of ops.py and DESIGN.md 4.17 (MB)" % (nu_, nv_, nn_, g.nnz, reps)]
+    print(lines[0], flush=True)
+    for C in (64, 128, 256):
+        R = 2 if nn_ * C * 4 >= (1 << 29) else 4
+        Bs = [torch.randn(nn_, 2 * C, device=dev) for _ in range(R)]           # [A | B]
+        As, Xs = [b[:, :C] for b in Bs], [b[:, C:] for b in Bs]
+        X2 = [(x * x).contiguous() for x in Xs]
+        Ds = [torch.randn(nn_, 4 * C, device=dev) for _ in range(R)]           # [dS | dQ | dMx | dMn]
+        O4, O3 = torch.empty(nn_, 4 * C, device=dev), torch.empty(nn_, 3 * C, device=dev)
+        Oa, Ob = torch.empty(nn_, C, device=dev), torch.empty(nn_, C, device=dev)
+        saved = [ops.gather_moments(g, Xs[i], want=("mean", "min", "max", "std"), root=As[i]) for i in range(R)]
+        amn, amx, inv = [s[1][1] for s in saved], [s[1][2] for s in saved], [s[2] for s in saved]
+        tw = C // 4
+        q = alternate({
+            "moments 4": lambda i: ops.gather_moments(g, Xs[i], want=("mean", "min", "max", "std"), root=As[i], out=O4),
+            "moments 4 towers": lambda i: ops.gather_moments(g, Xs[i], want=("mean", "min", "max", "std"), root=As[i], tower_width=tw, out=O4),
+            "moments std": lambda i: ops.gather_moments(g, Xs[i], want=("std",), out=Oa),
+            "stats mean+max+min": lambda i: ops.gather_stats(g, Xs[i], want=("mean", "max", "min"), out=O3),
+            "stats mean x": lambda i: ops.gather_stats(g, Xs[i], want=("mean",), out=Oa),
+            "stats mean x*x": lambda i: ops.gather_stats(g, X2[i], want=("mean",), out=Ob),
+            "moments bwd": lambda i: ops.gather_moments_bwd(g, ds=Ds[i][:, :C], dq=Ds[i][:, C:2 * C], b=Xs[i], invdeg=inv[i],
+                                                            dmx=Ds[i][:, 2 * C:3 * C], argmx=amx[i], dmn=Ds[i][:, 3 * C:], argmn=amn[i], out=Oa),
+            "stats bwd": lambda i: ops.gather_stats_bwd(g, ds=Ds[i][:, :C], invdeg=inv[i], dmx=Ds[i][:, 2 * C:3 * C], argmx=amx[i],
+                                                        dmn=Ds[i][:, 3 * C:], argmn=amn[i], out=Ob)}, reps, R)
+        feat, ent, node = 4.0 * nn_ * C, 4.0 * g.nnz, 4.0 * nn_
+        alg = {"moments 4": 9 * feat + 2 * ent + 2 * node, "moments 4 towers": 9 * feat + 2 * ent + 2 * node,
+               "moments std": 3 * feat + 2 * ent + 2 * node, "stats mean+max+min": 6 * feat + 2 * ent + 2 * node,
+               "stats mean x": 2 * feat + 2 * ent + 2 * node, "stats mean x*x": 2 * feat + 2 * ent + 2 * node,
+               "moments bwd": 8 * feat + 3 * ent + 2 * node, "stats bwd": 6 * feat + 3 * ent + 2 * node}
+        lines.append("C=%d (%d buffer sets; towers of %d):" % (C, R, tw))
+        for k in alg:
+            lines.append("  %-19s %s  %7.0f MB  %.2f TB/s alg" % (k, fmt(q[k]), alg[k] / 1e6, alg[k] / q[k][2] / 1e6))
+        c3 = q["stats mean+max+min"][2] + q["stats mean x"][2] + q["stats mean x*x"][2]
+        lines.append("  fused mean+min+max+std %.0f us vs composed (three sweeps) %.0f us: x%.2f;  tower-major x%.2f of plain;  "
+                     "moments bwd (4 streams + B) x%.2f of stats bwd (3 streams)"
+                     % (q["moments 4"][2], c3, q["moments 4"][2] / c3, q["moments 4 towers"][2] / q["moments 4"][2],
+                        q["moments bwd"][2] / q["stats bwd"][2]))
+        print("\n".join(lines[-(len(alg) + 2):]), flush=True)
+        del Bs, As, Xs, X2, Ds, O4, O3, Oa, Ob, saved, amn, amx, inv
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "pna_microbench.txt")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
