@@ -611,18 +611,22 @@ static RowRoute row_route(int64_t n_rows, int KD, int MD, bool has_pro, int mode
 }
 // What only a call knows: the f16x3 kernels read A (and A2) as float4, the tiled kernel writes Y as float4.
 // (ddmp_gemm_prepare_weights sees no call and assumes both hold: planes it makes for a call where they do not are re-made.)
-static inline bool route_fits_call(const RowRoute& r, const float* Y, int64_t ldy, int64_t lda, int64_t lda2) {
+static inline bool route_fits_call(const RowRoute& r, bool y_aligned, int64_t ldy, int64_t lda, int64_t lda2) {
     if (r.family == kRowPanelF16) return lda % 4 == 0 && lda2 % 4 == 0;
-    if (r.family == kRowTiled) return ldy % 4 == 0 && aligned16(Y);
+    if (r.family == kRowTiled) return ldy % 4 == 0 && y_aligned;
     return true;
+}
+// planes_ok: planes_fit() of the call's workspace; y_aligned: aligned16(Y)
+static RowRoute row_route_fit(int64_t n_rows, int KD, int MD, bool has_pro, bool planes_ok, bool y_aligned, int64_t ldy, int64_t lda,
+                              int64_t lda2) {
+    RowRoute r = row_route(n_rows, KD, MD, has_pro, gemm_mode(), gemm_f16() != 0, planes_ok);
+    while (!route_fits_call(r, y_aligned, ldy, lda, lda2))
+        r = row_route(n_rows, KD, MD, has_pro, gemm_mode(), gemm_f16() != 0, planes_ok, r.family);
+    return r;
 }
 static RowRoute row_route_call(int64_t n_rows, int KD, int MD, bool has_pro, const void* ws, size_t ws_bytes, const float* Y,
                                int64_t ldy, int64_t lda, int64_t lda2) {
-    const bool planes_ok = planes_fit(ws, ws_bytes, KD, MD);
-    RowRoute r = row_route(n_rows, KD, MD, has_pro, gemm_mode(), gemm_f16() != 0, planes_ok);
-    while (!route_fits_call(r, Y, ldy, lda, lda2))
-        r = row_route(n_rows, KD, MD, has_pro, gemm_mode(), gemm_f16() != 0, planes_ok, r.family);
-    return r;
+    return row_route_fit(n_rows, KD, MD, has_pro, planes_fit(ws, ws_bytes, KD, MD), aligned16(Y), ldy, lda, lda2);
 }
 // Within kRowPanelF16: the row-register kernel (gemm_rr.inc) or the row-panel kernel?  dual = the (dZ, Yb) operand pair with
 // two column halves (512 <- 512 dgrad): the halves are separate, freely drifting workgroups and BOTH stream (dZ, Y) -- PMC: the
@@ -631,6 +635,16 @@ static RowRoute row_route_call(int64_t n_rows, int KD, int MD, bool has_pro, con
 static inline bool rr_kernel_ok(const RowRoute& r, bool dual, int64_t n_rows, int64_t lda, int64_t lda2) {
     return r.rr && !(dual && r.MP > kRRCols) && n_rows * lda * 4 < ((int64_t)1 << 32) &&
            n_rows * lda2 * 4 < ((int64_t)1 << 32);              // (32-bit lane offsets)
+}
+
+// For tests that name a route: the family (kRow*: 1 f16x3 row panel, 2 bf16 row panel, 3 tiled, 4 presplit, 5 plain) a row entry
+// point takes for these operands with a fitting workspace in the current mode, + 256 where the row-register kernel runs it.
+// lda2 > 0: the (dZ, Yb) operand pair of ddmp_gemm_nn_bnbwd_f32; y_misaligned: Y is not on 16 bytes.  Host only.
+extern "C" int ddmp_gemm_row_route(int64_t n_rows, int KD, int MD, int has_pro, int64_t lda, int64_t lda2, int64_t ldy,
+                                   int y_misaligned) {
+    if (n_rows <= 0 || KD <= 0 || MD <= 0) return DDMP_EINVAL;
+    const RowRoute r = row_route_fit(n_rows, KD, MD, has_pro != 0, true, !y_misaligned, ldy, lda, lda2);
+    return r.family + (rr_kernel_ok(r, lda2 > 0, n_rows, lda, lda2) ? 256 : 0);
 }
 
 // The plane layout the entry points below will want for W [M,K] in the forward (form 0: Y[n,M] = f(A[n,K]) . W^T) or dgrad
@@ -1083,6 +1097,33 @@ extern "C" size_t ddmp_gemm_tn_workspace_bytes(int64_t n_rows, int M, int K) {
     return (size_t)std::max(p.n_splits, q.n_splits) * (size_t)M * (size_t)K * sizeof(float) + 64;    // + two scale slots (f16 modes)
 }
 
+// Which of the four wgrad kernels runs, and on what plan.  ld_ok: the float4 loads of the f16x3 route reach the operands (leading
+// dimensions multiples of 4, bases on 16 bytes).
+enum { kTnF16RowMajor = 1, kTnPanelB16, kTnTiledB16, kTnTiledF32 };
+struct TnRoute {
+    TnPlan p;
+    int kernel;
+};
+static TnRoute tn_route(int64_t n_rows, int M, int K, bool dual, bool ld_ok, int64_t ldg, int64_t ldg2, int64_t ldz) {
+    const int mode = gemm_mode();
+    const bool f16_ok = mode == 6 && gemm_f16() && ld_ok;
+    TnRoute rt;
+    rt.p = tn_plan(n_rows, M, K, f16_ok);
+    if (rt.p.T == 4 && rt.p.tm + rt.p.tk < 512 && !tn_wide_ok(rt.p.rows_per_split, ldg, ldg2, ldz)) rt.p = tn_plan(n_rows, M, K);
+    if (rt.p.T == 4) rt.kernel = (f16_ok && tn_wide_ok(rt.p.rows_per_split, ldg, ldg2, ldz)) ? kTnF16RowMajor : kTnPanelB16;
+    else rt.kernel = (mode == 0 && !dual) ? kTnTiledF32 : kTnTiledB16;
+    return rt;
+}
+// For tests that name a route: the kernel (kTn*: 1 f16x3 row-major, 2 bf16 panel, 3 bf16 tiled, 4 f32 tiled) a wgrad over n_rows
+// rows launches in the current mode for operands with leading dimensions near M and K (far inside tn_wide_ok), and
+// plan4 (may be null) = T, tm, tk, n_splits.  dual: the ddmp_gemm_tn_bnbwd_f32 form.  Host only.
+extern "C" int ddmp_gemm_tn_route(int64_t n_rows, int M, int K, int dual, int ld_ok, int* plan4) {
+    if (n_rows <= 0 || M <= 0 || K <= 0) return DDMP_EINVAL;
+    const TnRoute rt = tn_route(n_rows, M, K, dual != 0, ld_ok != 0, M, dual ? M : 0, K);
+    if (plan4) plan4[0] = rt.p.T, plan4[1] = rt.p.tm, plan4[2] = rt.p.tk, plan4[3] = rt.p.n_splits;
+    return rt.kernel;
+}
+
 // Both wgrad entry points, after their own argument checks.  DUAL: G is the BatchNorm+LeakyReLU backward of (G = dZ, G2 = Yb),
 //   dY = a * dZ * lrelu'(a * Yb + b) + c1 * Yb + c0  per column of M, rebuilt on the load; otherwise G2 and the coefficients are
 // null.  f = optional BatchNorm+LeakyReLU prologue on Z (columns of K).  Operands the float4 loads of the f16x3 route cannot
@@ -1093,10 +1134,9 @@ static int gemm_tn(const float* G, int64_t ldg, const float* G2, int64_t ldg2, c
                    const float* pro_scale, const float* pro_shift, float slope, void* workspace, size_t workspace_bytes,
                    hipStream_t st, ddmp::CallCtx& ctx) {
     const int mode = gemm_mode();
-    const bool f16_ok = mode == 6 && gemm_f16() && ldg % 4 == 0 && ldg2 % 4 == 0 && ldz % 4 == 0 && aligned16(G) && aligned16(G2) &&
-                        aligned16(Z);
-    TnPlan p = tn_plan(n_rows, M, K, f16_ok);
-    if (p.T == 4 && p.tm + p.tk < 512 && !tn_wide_ok(p.rows_per_split, ldg, ldg2, ldz)) p = tn_plan(n_rows, M, K);
+    const bool ld_ok = ldg % 4 == 0 && ldg2 % 4 == 0 && ldz % 4 == 0 && aligned16(G) && aligned16(G2) && aligned16(Z);
+    const TnRoute rt = tn_route(n_rows, M, K, DUAL, ld_ok, ldg, ldg2, ldz);
+    const TnPlan& p = rt.p;
     const size_t need = (size_t)p.n_splits * (size_t)M * (size_t)K * sizeof(float) + 64;
     if (!workspace || workspace_bytes < need) return DDMP_EWORKSPACE;
     float* part = (float*)workspace;
@@ -1104,7 +1144,7 @@ static int gemm_tn(const float* G, int64_t ldg, const float* G2, int64_t ldg2, c
     const int n_tiles = p.n_tiles_m * p.n_tiles_k;
     dim3 grid((unsigned)(cdiv(p.n_splits, kXcd) * kXcd * n_tiles)), block(p.T == 4 ? 512 : 256);
     const int pro = pro_scale != nullptr;
-    if (p.T == 4 && f16_ok && tn_wide_ok(p.rows_per_split, ldg, ldg2, ldz)) {
+    if (rt.kernel == kTnF16RowMajor) {
         float* tail = (float*)((char*)workspace + need - 64);
         const bool own = !(ctx.slot_a && ctx.slot_b);
         float* gslot = own ? tail : ctx.slot_a;
@@ -1119,7 +1159,7 @@ static int gemm_tn(const float* G, int64_t ldg, const float* G2, int64_t ldg2, c
         for (int heal = 0; heal <= (prime ? 0 : 1); ++heal)           // second launch: redo on overflow (gemm_f16s.inc)
             launch_tn_wide(G, ldg, G2, ldg2, Z, ldz, part, sstride, n_rows, M, K, p, pro_scale, pro_shift, a, b, c1, c0, slope, gslot,
                            zslot, target, heal, st);
-    } else if (p.T == 4) {                                       // 256 x 256 panels, bf16 split terms
+    } else if (rt.kernel == kTnPanelB16) {                       // 256 x 256 panels, bf16 split terms
         pick<2, 3>(mode == 6 ? 3 : 2, [&](auto nt) {
             pick<0, 1>(pro, [&](auto pr) {
                 hipLaunchKernelGGL((gemm_tn_panel_kernel<decltype(nt)::value, decltype(pr)::value != 0, DUAL>), grid, block, 0, st, G,

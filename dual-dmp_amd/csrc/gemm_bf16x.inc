@@ -387,7 +387,8 @@ __global__ __launch_bounds__(256) void gemm_rows_bf16_kernel(
             const int q = tid % QPR, r0 = tid / QPR;
             const int c = col0 + q * 4;
             float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (bias && c + 3 < MD) bv = *reinterpret_cast<const float4*>(bias + c);
+            // (element loads: no entry point asks for a 16-byte aligned bias, and a view into a longer vector is not)
+            if (bias && c + 3 < MD) bv = make_float4(bias[c], bias[c + 1], bias[c + 2], bias[c + 3]);
             const bool vec_ok = (c + 3 < MD) && ((ldy & 3) == 0) && ((reinterpret_cast<uintptr_t>(Y) & 15) == 0);
 #pragma unroll 4
             for (int row = r0; row < kBM; row += 256 / QPR) {

@@ -1863,6 +1863,29 @@ def gemm_tn_bnbwd_supported(cout, cin, n_rows, dtype=torch.float32):
     return dtype == torch.float32 and bool(_lib.lib().ddmp_gemm_tn_bnbwd_supported(int(cout), int(cin), int(n_rows)))
 
 
+ROW_FAMILIES = {1: "f16x3-panel", 2: "bf16-panel", 3: "tiled", 4: "presplit", 5: "plain"}
+TN_KERNELS = {1: "f16x3-rowmajor", 2: "bf16-panel", 3: "bf16-tiled", 4: "f32-tiled"}
+
+
+def gemm_row_route(n_rows, KD, MD, has_pro=False, lda=None, lda2=0, ldy=None, y_misaligned=False):
+    """-> (family name, row-register kernel?) of a row product out[n, MD] = f(a[n, KD]) . B in the current GEMM mode
+    (ddmp_gemm_row_route; host only).  lda2 > 0: the (dz, yb) operand pair of gemm_nn_bnbwd."""
+    r = int(_lib.lib().ddmp_gemm_row_route(int(n_rows), int(KD), int(MD), int(bool(has_pro)), int(KD if lda is None else lda),
+                                           int(lda2), int(MD if ldy is None else ldy), int(bool(y_misaligned))))
+    check(min(r, 0), "ddmp_gemm_row_route")
+    return ROW_FAMILIES[r & 255], bool(r & 256)
+
+
+def gemm_tn_route(n_rows, M, K, dual=False, ld_ok=True):
+    """-> (kernel name, T, tm, tk, n_splits) of a weight gradient out[M, K] over n_rows rows in the current GEMM mode
+    (ddmp_gemm_tn_route; host only).  dual: the gemm_tn_bnbwd form; ld_ok: leading dimensions % 4 == 0 and bases on 16 bytes."""
+    plan = (ctypes.c_int * 4)()
+    r = int(_lib.lib().ddmp_gemm_tn_route(int(n_rows), int(M), int(K), int(bool(dual)), int(bool(ld_ok)),
+                                          ctypes.cast(plan, ctypes.c_void_p)))
+    check(min(r, 0), "ddmp_gemm_tn_route")
+    return (TN_KERNELS[r],) + tuple(plan)
+
+
 def rows_gather(src, idx, out=None, n_rows=None):
     """out[r] = src[idx[r]] (halo packing on the library's kernel; float32 / bfloat16 rows of 16-byte multiples)."""
     src, lds = _mat(src, "src")

@@ -727,6 +727,15 @@ int ddmp_gemm_tn_bnbwd_f32(const float* dZ, int64_t lddz, const float* Yb, int64
                            const float* c1, const float* c0, const float* pro_scale /*nullable*/,
                            const float* pro_shift /*nullable*/, float slope, void* workspace, size_t workspace_bytes,
                            ddmp_stream stream);
+/* For tests that name a route (host only, nothing is launched; the current GEMM mode and the DDMP_* switches apply).
+ * ddmp_gemm_row_route: the kernel family of a row product Y[n, MD] = f(A[n, KD]) . B with a fitting workspace -- 1 f16x3 row panel,
+ *   2 bf16 row panel, 3 tiled, 4 presplit, 5 plain -- + 256 where the row-register kernel runs the f16x3 family.  lda2 > 0: the
+ *   (dZ, Yb) operand pair of ddmp_gemm_nn_bnbwd_f32 (0 otherwise); y_misaligned != 0: Y is not on 16 bytes.
+ * ddmp_gemm_tn_route: the wgrad kernel -- 1 f16x3 row-major, 2 bf16 panel, 3 bf16 tiled, 4 f32 tiled -- for operands of small
+ *   leading dimensions; ld_ok: every leading dimension a multiple of 4 and every base on 16 bytes; dual: the _bnbwd form;
+ *   plan4: T (1 | 2 tiles of 64 T, 4 = panels), tm, tk (panel edges, 0 for tiles), n_splits */
+int ddmp_gemm_row_route(int64_t n_rows, int KD, int MD, int has_pro, int64_t lda, int64_t lda2, int64_t ldy, int y_misaligned);
+int ddmp_gemm_tn_route(int64_t n_rows, int M, int K, int dual, int ld_ok, int* plan4 /*[4], nullable*/);
 
 /* graph-replay form: the step count lives on the device.  ddmp_adam_prepare does ++(*step_counter) and writes
  * coef = { lr / (1 - beta1^t), sqrt(1 - beta2^t) }; ddmp_adam_step_dev_f32 reads coef instead of host values. */
