@@ -32,7 +32,9 @@ Two interchangeable forms, both taking the reference's ``Dataset`` object (field
     edge plus the ``lin_skip`` root term; parameters ``convN.lin_key.weight``, ``convN.lin_skip.weight``, ``convN.bias`` ...);
     ``conv="spline", K=2`` builds them from :class:`nn_ops.SplineConv` with ``dim=3`` and ``kernel_size=K`` (SplineCNN: every edge
     mixes the 8 of K^3 weight matrices its pseudo-coordinates select by a linear B-spline basis; parameters ``convN.weight``,
-    ``convN.lin.weight``, ``convN.bias``).
+    ``convN.lin.weight``, ``convN.bias``); ``conv="gen"`` builds them from :class:`nn_ops.GENConv` with its defaults (DeeperGCN's
+    layer: a per-channel softmax aggregation of ``relu(x_j) + eps``, a residual root term and a two-layer MLP; parameters
+    ``convN.lin_src.weight``, ``convN.lin_dst.weight``, ``convN.mlp.0.weight``, ``convN.msg_norm.scale`` ...).
     The GMM and spline operators' pseudo-coordinates are the dataset's ``edge_attr`` (vertex graph) / ``face_attr`` (face graph) if any, else
     ``nn_ops.cartesian_pseudo`` of the smoothed vertex positions / the noisy face centroids, computed once and cached on the
     dataset.  The fused engine, the trainer, the CLI,
@@ -52,7 +54,7 @@ import torch.nn as nn
 
 from . import ops
 from .engine import ArenaLayout, GcnEngine, NORM_WIDTHS, POS_WIDTHS
-from .nn_ops import (ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv, GMMConv, ResGatedGraphConv, SplineConv, TransformerConv,
+from .nn_ops import (ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv, GENConv, GMMConv, ResGatedGraphConv, SplineConv, TransformerConv,
                      cartesian_pseudo)
 
 
@@ -275,8 +277,8 @@ class NormalNetFused(_FusedNet):
 
 
 # -------------------------------------------------------------------------------- operator-level form
-_CONVS = ("gcn", "cheb", "gat", "feast", "edge", "gmm", "transformer", "resgated", "spline")
-_CONV_MSG = "conv must be 'gcn', 'cheb', 'gat', 'feast', 'edge', 'gmm', 'transformer', 'resgated' or 'spline', got %r"
+_CONVS = ("gcn", "cheb", "gat", "feast", "edge", "gmm", "transformer", "resgated", "spline", "gen")
+_CONV_MSG = "conv must be 'gcn', 'cheb', 'gat', 'feast', 'edge', 'gmm', 'transformer', 'resgated', 'spline' or 'gen', got %r"
 
 
 class _ModularNet(nn.Module):
@@ -307,6 +309,8 @@ class _ModularNet(nn.Module):
                 layer = GMMConv(h[i], h[i + 1], dim=3, kernel_size=K)
             elif conv == "spline":
                 layer = SplineConv(h[i], h[i + 1], dim=3, kernel_size=K)
+            elif conv == "gen":
+                layer = GENConv(h[i], h[i + 1])
             else:
                 layer = GCNConv(h[i], h[i + 1]) if conv == "gcn" else ChebConv(h[i], h[i + 1], K)
             setattr(self, "conv%d" % (i + 1), layer)

@@ -1,8 +1,8 @@
-"""Drop-ins for twelve ``torch_geometric.nn`` 2.2.0 operators on the HIP kernels: same constructor / call signature, parameter names
+"""Drop-ins for thirteen ``torch_geometric.nn`` 2.2.0 operators on the HIP kernels: same constructor / call signature, parameter names
 and initialisation; the dense part goes through the GEMMs, the graph part through one fused gather launch per direction, and no
 per-edge feature tensor exists at any point.  Each operator is documented once, at its class: ``GCNConv``, ``ChebConv``,
 ``GATConv``, ``GATv2Conv``, ``TransformerConv``, ``ResGatedGraphConv``, ``FeaStConv``, ``GMMConv`` (with ``cartesian_pseudo``),
-``SplineConv``, ``EdgeConv``, ``SAGEConv``, ``PNAConv`` (with ``degree_histogram``).
+``SplineConv``, ``EdgeConv``, ``SAGEConv``, ``PNAConv`` (with ``degree_histogram``), ``GENConv``.
 
 ``edge_weight`` (``GCNConv`` and ``ChebConv``; restated from the published PyG 2.2.0 source from memory -- PyG cannot be installed
 here, so this could not be checked against it; the pin is the dense float64 restatement ``tests/gcnw_ref.py``):
@@ -25,6 +25,7 @@ here, so this could not be checked against it; the pin is the dense float64 rest
 """
 from __future__ import annotations
 
+import contextlib
 import math
 
 import torch
@@ -1845,3 +1846,291 @@ class PNAConv(nn.Module):
     def extra_repr(self):
         return "%d, %d, towers=%d, aggregators=%s, scalers=%s" % (self.in_channels, self.out_channels, self.towers, self.aggregators,
                                                                 self.scalers)
+
+
+class _LinearFn(_Fn):
+    """``x @ w^T + b`` on the project's GEMMs (GENConv's MLP): ``ops.gemm_nt`` forward, ``ops.gemm_tn`` (wgrad) and ``ops.gemm_nn``
+    (dgrad) backward, the operands zero-padded to multiples of 4 columns / rows.  ``strict``: the three run with float32-input
+    MFMA (GEMM mode 0) instead of the split-precision default, whose f32-class error has a part that is the same in every row."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, strict=False):
+        ctx.strict = bool(strict)
+        with (ops.gemm_mode(0) if strict else contextlib.nullcontext()):
+            return _LinearFn._forward(ctx, x, w, b)
+
+    @staticmethod
+    def _forward(ctx, x, w, b):
+        dt, cin, cout = x.dtype, w.shape[1], w.shape[0]
+        xp = _pad_cols(x.detach())
+        wp = _packed_rows([w.detach()], xp.shape[1], x.device, dtype=dt)
+        lb = None
+        if b is not None:
+            lb = torch.zeros(wp.shape[0], dtype=dt, device=x.device)
+            lb[:cout] = b.detach()
+        ctx.save_for_backward(xp, wp)
+        ctx.dims = (cin, cout)
+        return ops.gemm_nt(xp, wp, bias=lb)[:, :cout]
+
+    @staticmethod
+    def _backward(ctx, dy):
+        xp, wp = ctx.saved_tensors
+        (cin, cout), need = ctx.dims, ctx.needs_input_grad
+        dyp = torch.zeros((dy.shape[0], wp.shape[0]), dtype=xp.dtype, device=dy.device)
+        dyp[:, :cout] = dy
+        with (ops.gemm_mode(0) if ctx.strict else contextlib.nullcontext()):
+            dw = ops.gemm_tn(dyp, xp)[:cout, :cin] if need[1] else None
+            dx = ops.gemm_nn(dyp, wp)[:, :cin] if need[0] else None
+        db = _bias_grad(dyp)[:cout] if need[2] else None
+        return dx, dw, db, None
+
+
+class _BatchNorm1d64(nn.BatchNorm1d):
+    """``nn.BatchNorm1d`` (same parameters, buffers and ``state_dict``) that normalises float32 input in float64 and rounds the
+    result once, as the project's own BatchNorm kernels take their column statistics in float64.  In float32 the column means of
+    the backward carry an error that is the SAME for every row; a gradient that sums over all rows against weights of one sign
+    (``msg_norm.scale``'s, whose terms otherwise cancel a thousand to one) collects it N times over."""
+
+    def forward(self, x):
+        if x.dtype != torch.float32:
+            return super().forward(x)
+        self._check_input_dim(x)
+        momentum = 0.0 if self.momentum is None else self.momentum
+        if self.training and self.track_running_stats and self.num_batches_tracked is not None:
+            self.num_batches_tracked.add_(1)
+            if self.momentum is None:
+                momentum = 1.0 / float(self.num_batches_tracked)
+        training = self.training or self.running_mean is None
+        stats = self.running_mean is not None and (not self.training or self.track_running_stats)
+        rm, rv = (self.running_mean.double(), self.running_var.double()) if stats else (None, None)
+        w, b = (self.weight.double(), self.bias.double()) if self.affine else (None, None)
+        y = torch.nn.functional.batch_norm(x.double(), rm, rv, w, b, training, momentum, self.eps)
+        if training and stats:
+            self.running_mean.copy_(rm)
+            self.running_var.copy_(rv)
+        return y.to(x.dtype)
+
+
+class _GENLinear(_LinB):
+    """A ``Linear`` of GENConv's MLP: PyG's parameter names, ``_LinearFn``'s GEMMs (``strict``: see there)."""
+    strict = False
+
+    def forward(self, x):
+        return _LinearFn.apply(x, self.weight, self.bias, self.strict)
+
+
+class _GENConvFn(_Fn):
+    """The graph part of ``GENConv``, ONE launch per direction (``ops.gather_softmax`` / ``ops.gather_softmax_bwd``).  Inputs: x,
+    ``lin_src`` / ``lin_dst`` weights and biases (None with in == out), the temperature parameter (None unless learnt), the graph, the
+    temperature's value, the message eps, ``fuse_root`` (False with ``msg_norm``: the root add is torch work around the launch) and
+    ``want`` (whether a backward can follow).
+
+    * in != out: ONE GEMM against ``[lin_src.weight ; lin_dst.weight]`` gives the row buffer ``[H | D]``; the launch gives
+      ``D + agg`` (``fuse_root``) or ``agg`` -- then the function returns ``(agg, D)``.  Backward: the launch writes ``[dH | dD]`` into
+      one gradient row buffer (without ``fuse_root`` the ``dD`` block is a copy of the second output's gradient), then ONE wgrad and
+      ONE dgrad GEMM.
+    * in == out: no GEMM; the launch runs on x with ``root = x``, and ``dx = dOut + scatter`` comes from the one backward launch.
+
+    The backward's ``Y'`` (the aggregate without the root) is ``y - root``, one torch elementwise op, where the root was fused.
+    The temperature's gradient is the float64 sum of the launch's per-row partials (they are of both signs), rounded once.
+    Saved: the padded x and packed weight (in != out), H (x itself with in == out), y, lse."""
+
+    @staticmethod
+    def forward(ctx, x, ws, bs, wd, bd, tpar, graph, t, eps, fuse_root, want):
+        dt = x.dtype
+        need = bool(want) and any(ctx.needs_input_grad[:6])
+        ctx.graph, ctx.scal, ctx.fuse, ctx.lin = graph, (t, eps), bool(fuse_root), ws is not None
+        if ctx.lin:
+            xp, wp, buf, spans = _packed_gemm(x, (ws, wd), (bs, bd), dtype=dt)   # buf [N, 2 out rounded up to 4]: H | D | zero padding
+            h, d = _cols(buf, spans[0]), _cols(buf, spans[1])
+            ctx.spans, ctx.cin = spans, x.shape[1]
+        else:
+            h = d = x.detach().contiguous()
+        y, lse = ops.gather_softmax(graph, h, t, msg_eps=eps, root=d if fuse_root else None, want_lse=need)
+        if need:
+            ctx.save_for_backward(*((xp, wp) if ctx.lin else ()), h, d, y, lse)
+        if fuse_root:
+            return y
+        if ctx.lin:
+            return y, d
+        return y
+
+    @staticmethod
+    def _backward(ctx, dy, dd=None):
+        graph, (t, eps), need = ctx.graph, ctx.scal, ctx.needs_input_grad
+        *lin, h, d, y, lse = ctx.saved_tensors
+        dy = dy.contiguous().to(h.dtype)
+        yp = y - d if ctx.fuse else y
+        if not ctx.lin:
+            dx, _, dtr = ops.gather_softmax_bwd(graph, dy, h, yp, lse, t, msg_eps=eps, root="add" if ctx.fuse else False,
+                                                want_dt=need[5])
+            return dx, None, None, None, None, (dtr.double().sum().to(dtr.dtype).view(1) if need[5] else None), None, None, None, None, None
+        xp, wp = lin
+        gb = _grad_rows(dy.shape[0], ctx.spans, wp.shape[0], dy.device, h.dtype)
+        _, _, dtr = ops.gather_softmax_bwd(graph, dy, h, yp, lse, t, msg_eps=eps, root=ctx.fuse, want_dt=need[5], out=gb)   # gb = [dH | dD | 0]
+        if not ctx.fuse:
+            _cols(gb, ctx.spans[1]).copy_(dd)
+        dx, (dws, dwd), (dbs, dbd) = _packed_grads(gb, xp, wp, ctx.spans, ctx.cin, (need[1], need[3]), (need[2], need[4]), need[0])
+        return dx, dws, dbs, dwd, dbd, (dtr.double().sum().to(dtr.dtype).view(1) if need[5] else None), None, None, None, None, None
+
+
+class _SoftmaxAggr(nn.Module):
+    """PyG's ``SoftmaxAggregation(t, learn)`` as a parameter holder: ``t`` is a [1] parameter with ``learn``, else a float."""
+
+    def __init__(self, t, learn):
+        super().__init__()
+        self._init_t, self.learn = float(t), bool(learn)
+        self.t = nn.Parameter(torch.full((1,), float(t))) if learn else float(t)
+
+    def reset_parameters(self):
+        if self.learn:
+            with torch.no_grad():
+                self.t.fill_(self._init_t)
+
+
+class _ScaleFn(torch.autograd.Function):
+    """``u * scale`` with ``scale`` [1].  The gradient of the scale is the sum of N x C signed terms that largely cancel: it is
+    accumulated in float64 (one elementwise pass over [N, C]) and rounded once."""
+
+    @staticmethod
+    def forward(ctx, u, scale):
+        ctx.save_for_backward(u, scale)
+        return u * scale
+
+    @staticmethod
+    def backward(ctx, dy):
+        u, scale = ctx.saved_tensors
+        ds = (dy.double() * u.double()).sum().to(scale.dtype).view(1) if ctx.needs_input_grad[1] else None
+        return (dy * scale if ctx.needs_input_grad[0] else None), ds
+
+
+class _MessageNorm(nn.Module):
+    """PyG's ``MessageNorm(learn_scale)``: ``normalize(msg, p=2, dim=-1) * ||x||_2 * scale``; ``scale`` [1], initialised to 1, always in
+    the ``state_dict``, ``requires_grad = learn_scale``."""
+
+    def __init__(self, learn_scale=False):
+        super().__init__()
+        self.scale = nn.Parameter(torch.ones(1), requires_grad=bool(learn_scale))
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            self.scale.fill_(1.0)
+
+    def forward(self, x, msg):
+        return _ScaleFn.apply(torch.nn.functional.normalize(msg, p=2.0, dim=-1) * x.norm(p=2, dim=-1, keepdim=True), self.scale)
+
+
+class GENConv(nn.Module):
+    """``torch_geometric.nn.GENConv`` 2.2.0 (Li et al., DeeperGCN, 2020) on the HIP kernels,
+    ``GENConv(in_channels, out_channels, aggr="softmax", t=1.0, learn_t=False, p=1.0, learn_p=False, msg_norm=False,
+    learn_msg_scale=False, norm="batch", num_layers=2, expansion=2, eps=1e-7, bias=False, edge_dim=None)``,
+    ``forward(x, edge_index, edge_attr=None, size=None)`` (restated from the published 2.2.0 source from memory -- PyG cannot be
+    installed here, so this could not be checked against it; the pin is the float64 restatement ``tests/gen_ref.py``):
+
+    * ``h = lin_src(x)`` (in != out, else x); ``agg_i = sum_j softmax_j(t m_j) m_j`` per channel over the edges j -> i with the message
+      ``m_j = relu(h_j) + eps`` (PyG's ``SoftmaxAggregation``: the mean at t = 0, the max as t -> inf); with ``msg_norm``
+      ``agg = normalize(agg, p=2, dim=-1) * ||x_i||_2 * msg_norm.scale`` (the RAW x); ``out = agg + lin_dst(x)`` (in != out, else
+      ``+ x``); ``return mlp(out)``.  Parameters: ``lin_src.weight`` / ``lin_dst.weight`` [out, in] (only with in != out; ``.bias``
+      with ``bias=True``), ``aggr_module.t`` [1] (only with ``learn_t``), ``msg_norm.scale`` [1] (only with ``msg_norm``; always in
+      the ``state_dict``, trained with ``learn_msg_scale``), and the MLP, an ``nn.Sequential`` of ``num_layers - 1`` hidden blocks
+      ``Linear(., out * expansion)``, the norm (``BatchNorm1d`` for ``"batch"``, ``LayerNorm`` for ``"layer"``, absent for None),
+      ``ReLU``, ``Dropout(0.)`` and a last ``Linear(., out)``: ``mlp.0``, ``mlp.1``, ``mlp.4`` for two layers.  Every Linear is
+      uniform(+-1/sqrt(fan-in)) and has a bias only with ``bias=True``.
+    * the launches (``_GENConvFn``): in != out -- ONE GEMM against the packed ``[lin_src.weight ; lin_dst.weight]`` gives ``[H | D]``,
+      ONE ``ops.gather_softmax`` launch gives ``D + agg`` (the message is formed in registers), ONE ``ops.gather_softmax_bwd`` launch
+      writes ``[dH | dD]``, then one wgrad and one dgrad GEMM; in == out -- no GEMM in the graph part, the launch runs on x with root x.
+      With ``msg_norm`` the launch runs without root and the normalisation and the root add are torch work on [N, .] around it.  The
+      MLP's Linears go through the project's GEMMs (``_LinearFn``); the norm and the ReLU are torch modules.  With ``msg_norm`` and
+      ``learn_msg_scale`` alone the Linears run in GEMM mode 0 and the BatchNorm normalises in float64 (``_BatchNorm1d64``): the
+      scale's scalar gradient cancels a thousand to one.  ``aggr_module.t``'s
+      gradient is the sum of the backward launch's per-row partials.  No [E, .] tensor and no ``index_add_`` / ``scatter`` exist at
+      any point.  The graph is GATConv's without loops: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``.
+      Symmetric edge STRUCTURE only.  A learnt temperature is read back to the host once per forward (its value is a launch argument).
+    * no self loops are added, an explicit loop is an ordinary edge, a duplicate edge counts twice in the softmax, a node without
+      incoming edges gets ``mlp(lin_dst(x_i))``.  Differentiable w.r.t. x and every parameter; float32, bitwise reproducible; a
+      forward without a gradient stores no ``lse``.
+    * refused with ``ValueError`` before any launch: ``aggr`` other than ``"softmax"`` (``"powermean"`` / ``"power"`` is the named
+      follow-up: a second mode of the same sweep; ``"softmax_sg"`` too), ``edge_dim`` / ``edge_attr`` (the message becomes
+      per-edge), ``learn_p=True``, ``norm="instance"`` or any other name, ``num_layers < 1``, tuple ``in_channels`` or a tuple ``x``
+      (bipartite), ``size``, bf16 features, a CPU ``x``, an ``x`` that is not [N, in]."""
+
+    def __init__(self, in_channels, out_channels: int, aggr="softmax", t: float = 1.0, learn_t: bool = False, p: float = 1.0,
+                 learn_p: bool = False, msg_norm: bool = False, learn_msg_scale: bool = False, norm="batch", num_layers: int = 2,
+                 expansion: int = 2, eps: float = 1e-7, bias: bool = False, edge_dim=None, **kwargs):
+        super().__init__()
+        _no_tuple_channels("GENConv", in_channels)
+        if aggr != "softmax":
+            raise ValueError("GENConv: only aggr='softmax' is implemented on the HIP path ('powermean' is the named follow-up), got %r"
+                             % (aggr,))
+        _not_implemented("GENConv", edge_dim=edge_dim)
+        if learn_p:
+            raise ValueError("GENConv: learn_p=True belongs to the power-mean aggregation, which is not implemented on the HIP path")
+        if norm not in ("batch", "layer", None):
+            raise ValueError("GENConv: norm must be 'batch', 'layer' or None on the HIP path, got %r" % (norm,))
+        _int_ge1("GENConv", "num_layers", num_layers)
+        _int_ge1("GENConv", "expansion", expansion)
+        if not math.isfinite(float(t)) or not math.isfinite(float(eps)) or float(eps) < 0:
+            raise ValueError("GENConv: t must be finite and eps a finite float >= 0, got t=%r, eps=%r" % (t, eps))
+        if kwargs:
+            raise TypeError("GENConv: unexpected keyword arguments %s" % sorted(kwargs))
+        self.in_channels, self.out_channels, self.aggr, self.eps = in_channels, out_channels, aggr, float(eps)
+        self.aggr_module = _SoftmaxAggr(t, learn_t)
+        if in_channels != out_channels:
+            self.lin_src = _LinB(in_channels, out_channels, bias=bias)
+            self.lin_dst = _LinB(in_channels, out_channels, bias=bias)
+        widths = [out_channels] + [out_channels * expansion] * (num_layers - 1) + [out_channels]
+        # msg_norm.scale's gradient is ONE scalar, sum_i,c dOut u with u >= 0, whose terms cancel about a thousand to one: an error of
+        # dOut that is the same in every row (1e-8 of its size is enough) is collected N times over.  Where that scalar exists, the
+        # MLP that produces dOut takes its BatchNorm in float64 and runs its GEMMs in the strict mode (DESIGN.md 4.18, Accuracy).
+        sensitive = bool(msg_norm and learn_msg_scale)
+        layers = []
+        for i in range(1, len(widths)):
+            layers.append(_GENLinear(widths[i - 1], widths[i], bias=bias))
+            if i < len(widths) - 1:
+                if norm == "batch":
+                    layers.append((_BatchNorm1d64 if sensitive else nn.BatchNorm1d)(widths[i], affine=True))
+                elif norm == "layer":
+                    layers.append(nn.LayerNorm(widths[i], elementwise_affine=True))
+                layers += [nn.ReLU(), nn.Dropout(0.0)]
+        self.mlp = nn.Sequential(*layers)
+        if msg_norm:
+            self.msg_norm = _MessageNorm(learn_msg_scale)
+        for m in self.mlp:
+            if isinstance(m, _GENLinear):
+                m.strict = sensitive
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            for m in self.modules():
+                if isinstance(m, _Lin):
+                    _reset_linear(m)
+                elif isinstance(m, (nn.BatchNorm1d, nn.LayerNorm, _SoftmaxAggr, _MessageNorm)):
+                    m.reset_parameters()
+
+    def forward(self, x, edge_index, edge_attr=None, size=None) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present)."""
+        _no_tuple_x("GENConv", x)
+        _not_implemented("GENConv", edge_attr=edge_attr, size=size)
+        _check_x("GENConv", x, self.in_channels)
+        _need_gpu("GENConv", x, exc=ValueError)
+        _need_entries("GENConv", edge_index)
+        return self._core(x, edge_index)
+
+    def _core(self, x, edge_index):
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
+            lin = self.in_channels != self.out_channels
+            ws, bs, wd, bd = (self.lin_src.weight, self.lin_src.bias, self.lin_dst.weight, self.lin_dst.bias) if lin else (None,) * 4
+            tpar = self.aggr_module.t if self.aggr_module.learn else None
+            t = float(tpar.detach()) if tpar is not None else self.aggr_module.t
+            fuse = not hasattr(self, "msg_norm")
+            want = torch.is_grad_enabled() and any(v is not None and v.requires_grad for v in (x, ws, bs, wd, bd, tpar))
+            out = _GENConvFn.apply(x, ws, bs, wd, bd, tpar, graph, t, self.eps, fuse, want)
+            if not fuse:
+                agg, root = out if lin else (out, x)
+                out = self.msg_norm(x, agg) + root
+            return self.mlp(out)
+
+    def extra_repr(self):
+        return "%d, %d, aggr=%s" % (self.in_channels, self.out_channels, self.aggr)

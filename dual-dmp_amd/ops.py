@@ -6,6 +6,7 @@ No wrapper has a CPU path: a non-CUDA tensor raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import os
@@ -125,6 +126,21 @@ def set_gemm_mode(mode: int):
 
 def get_gemm_mode() -> int:
     return int(_lib.lib().ddmp_get_gemm_mode())
+
+
+@contextlib.contextmanager
+def gemm_mode(mode: int):
+    """The GEMM calls made inside run in ``mode`` (``set_gemm_mode``); the mode that was set before is restored on the way out.  The
+    mode is read on the host when a GEMM is dispatched, so this covers exactly the launches enqueued inside the block.  The mode
+    is process-wide: a GEMM that ANOTHER host thread dispatches while the block is open runs in ``mode`` too."""
+    old = get_gemm_mode()
+    if old != mode:
+        set_gemm_mode(mode)
+    try:
+        yield
+    finally:
+        if old != mode:
+            set_gemm_mode(old)
 
 
 def unfused(name: str) -> bool:
@@ -1552,6 +1568,84 @@ def gather_moments_bwd(g: Graph, ds=None, dq=None, b=None, invdeg=None, dmx=None
                                                     _p(op["argmn"][0]), op["argmn"][1], _p(db), lddb, _stream())
     check(st, "ddmp_gather_moments_bwd_f32")
     return db
+
+
+# ---------------------------------------------------------------------------------------- softmax aggregation
+def _smax_scalars(who, t, msg_eps):
+    """-> (t, has_eps, eps) as Python numbers: ``t`` any finite float, ``msg_eps`` None or a finite float >= 0."""
+    t = float(t)
+    if not math.isfinite(t):
+        raise DdmpError("%s: the temperature t must be finite, got %r" % (who, t))
+    if msg_eps is None:
+        return t, 0, 0.0
+    eps = float(msg_eps)
+    if not math.isfinite(eps) or eps < 0.0:
+        raise DdmpError("%s: msg_eps must be None or a finite float >= 0, got %r" % (who, msg_eps))
+    return t, 1, eps
+
+
+def gather_softmax(g: Graph, h, t, msg_eps=None, root=None, out=None, want_lse=True):
+    """Per-channel softmax aggregation of the neighbours' rows in ONE launch (``ddmp_gather_softmax_f32``) -> (y [n, C], lse [n, C] |
+    None): with the message ``m_j = relu(h[j]) + msg_eps`` (``msg_eps=None``: ``m_j = h[j]``, a plain ``SoftmaxAggregation``) and the
+    temperature ``t`` (any finite float), per row i and channel c ``y = root[i] + sum_e p_e m_e`` with ``p_e = a_e exp(t m_e) /
+    sum_e a_e exp(t m_e)`` over the row's entries (``a_e``: the entry's multiplicity) and ``lse = log sum_e a_e exp(t m_e)``, both
+    evaluated against the running maximum.  ``h`` [n, C]; ``root`` [n, C] optional (it may be a column block of the buffer ``h`` is a
+    block of); a row without entries gets its root row bit for bit (0 without root) and lse = 0.  ``out``: a float32 [n, C] row block
+    (it may be a column block of a wider buffer) that receives y; None: a tensor of its own.  ``want_lse=False`` skips the store of
+    ``lse`` (a forward without a backward)."""
+    _gmm_graph(g)
+    t, has_eps, eps = _smax_scalars("gather_softmax", t, msg_eps)
+    n = g.n_rows
+    h, ldh = _rows(h, "h", n)
+    C = h.shape[1]
+    ldr = 0
+    if root is not None:
+        root, ldr = _rows(root, "root", n, C)
+    y, ldy = _out(out, "out", n, C, h.device)
+    if y.shape[0] != n:
+        raise DdmpError("gather_softmax: out must be [%d, %d], got %s" % (n, C, tuple(y.shape)))
+    lse = torch.empty((n, C), dtype=torch.float32, device=h.device) if want_lse else None
+    # algorithmic bytes: every gathered row read ONCE, y (and lse) written, the root block read, col + multiplicity, rowptr
+    alg = 4.0 * n * C * (2 + bool(want_lse) + (root is not None)) + 8.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("gather_softmax", (C, has_eps, int(round(g.nnz / max(n, 1)))), alg, 8.0 * g.nnz * C,
+                survey=8.0 * n * C + 4.0 * g.nnz + 4.0 * (n + 1)):
+        st = _lib.lib().ddmp_gather_softmax_f32(g.handle, _p(h), ldh, C, t, has_eps, eps, _p(root), ldr, _p(y), ldy, _p(lse), C,
+                                                _stream())
+    check(st, "ddmp_gather_softmax_f32")
+    return y, lse
+
+
+def gather_softmax_bwd(g: Graph, dout, h, y, lse, t, msg_eps=None, root=False, want_dt=False, out=None):
+    """Backward of ``gather_softmax`` in one launch (``ddmp_gather_softmax_bwd_f32``) -> (dh [n, C] written completely, droot [n, C] |
+    None, dt_rows [n] | None).  ``y`` is the forward's aggregate WITHOUT the root term (a caller whose forward fused a root passes
+    ``y - root``), ``lse`` the forward's.  With ``i = col e'``, ``w`` the mirrored multiplicity and ``p = exp(t m_j - lse[i])``:
+    ``s[j] = sum_{e' in row j} w p dout[i]``, ``r[j] = sum_{e' in row j} w p dout[i] (m_j - y[i])``, ``dh[j] = (s + t r)`` times
+    ``[h[j] > 0]`` when ``msg_eps`` is given, ``droot[j] = dout[j]`` (``root=True``), ``dt_rows[j] = sum_c m_j[c] r[j, c]``
+    (``want_dt``; the temperature's gradient is ``dt_rows.sum()``).  ``root="add"``: the forward's root WAS ``h``, so ``dout[j]`` is
+    added to ``dh[j]`` (after the mask) and there is no droot block.  ``out``: a float32 [n, >= C (+ C)] row buffer that receives
+    [dh | droot] in its leading columns (the results are then views of it; further columns are left untouched); None: a buffer of its
+    own."""
+    _gmm_graph(g)
+    t, has_eps, eps = _smax_scalars("gather_softmax_bwd", t, msg_eps)
+    n = g.n_rows
+    dout, lddo = _rows(dout, "dout", n)
+    C = dout.shape[1]
+    h, ldh = _rows(h, "h", n, C)
+    y, ldy = _rows(y, "y", n, C)
+    lse, ldl = _rows(lse, "lse", n, C)
+    if root not in (False, True, "add"):
+        raise DdmpError("gather_softmax_bwd: root must be False, True or 'add', got %r" % (root,))
+    add, root = int(root == "add"), root is True
+    (dh, lddh), (dr, lddr) = _out_with_root(out, "gather_softmax_bwd", n, C, C, root, dout.device)
+    dt = torch.empty(n, dtype=torch.float32, device=dout.device) if want_dt else None
+    # algorithmic bytes: the three neighbour streams (dout, y, lse) read once each, the row's own h read, dh written (and the root
+    # block, with dout once more), dt_rows, col + mirror + multiplicity, rowptr
+    alg = 4.0 * n * C * (5 + 2 * root + add) + 4.0 * n * bool(want_dt) + 12.0 * g.nnz + 4.0 * (n + 1)
+    with _timed("gather_softmax_bwd", (C, has_eps, int(round(g.nnz / max(n, 1)))), alg, 9.0 * g.nnz * C):
+        st = _lib.lib().ddmp_gather_softmax_bwd_f32(g.handle, C, _p(dout), lddo, _p(h), ldh, _p(y), ldy, _p(lse), ldl, t, has_eps, eps,
+                                                    add, _p(dh), lddh, _p(dr), lddr, _p(dt), _stream())
+    check(st, "ddmp_gather_softmax_bwd_f32")
+    return dh, dr, dt
 
 
 def spmm_axpby(g: Graph, x, out=None, z=None, z2=None, a=1.0, b=0.0, c=0.0, d=0.0):

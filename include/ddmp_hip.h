@@ -500,6 +500,37 @@ int ddmp_gather_moments_bwd_f32(const ddmp_graph* g, int C, const float* dS /*nu
                                 const int32_t* argmx /*nullable*/, int64_t ldamx, const float* dMn /*nullable*/, int64_t lddmn,
                                 const int32_t* argmn /*nullable*/, int64_t ldamn, float* dB, int64_t lddb, ddmp_stream stream);
 
+/* ------------------------------------------------------------------ per-channel softmax aggregation (GENConv / PyG's
+ * SoftmaxAggregation) on the graph of the neighbour statistics above.  The message is m_j[c] = max(H[j,c], 0) +
+ * msg_eps with has_eps != 0 (msg_eps >= 0), else m_j[c] = H[j,c]; it is formed in registers and never written.  t: any finite float.
+ *
+ * forward:   per row i and channel c, over the row's entries e (a_e their multiplicities):
+ *            p_e = a_e exp(t m_e - mx) / sum_e a_e exp(t m_e - mx), mx = max_e t m_e;
+ *            Y[i,c] = R[i,c] + sum_e p_e m_e;   lse[i,c] = mx + log sum_e a_e exp(t m_e - mx).
+ *            Every neighbour row is loaded once per sweep (the row's first one a second time ahead of it, for the shift; an L1
+ *            hit); the running maximum, denominator and numerator of a channel stay in registers over
+ *            all entries and are rescaled once per batch of 8 entries.  The sums run over m_e - (the row's first message), so a
+ *            column with a large offset keeps Y to float32 rounding.  R (nullable, [n, C]; it may be a column block of the buffer H
+ *            is a block of): one unfused addition.  A row without entries gets R's row bit for bit (0 without R) and lse = 0.
+ *            lse (nullable): not stored when null (a forward without a backward).  No output may alias H, R or the other output.
+ *            The vector kernels need C and every leading dimension % 4 == 0 and 16-byte aligned matrices; anything else takes
+ *            scalar kernels.  One launch. */
+int ddmp_gather_softmax_f32(const ddmp_graph* g, const float* H, int64_t ldh, int C, float t, int has_eps, float msg_eps,
+                            const float* R /*nullable*/, int64_t ldr, float* Y, int64_t ldy, float* lse /*nullable*/, int64_t ldl,
+                            ddmp_stream stream);
+/* backward, node side (symmetric structure, as ddmp_gather_stats_bwd_f32), with i = col e', w = a_{mirror e'},
+ *            p = exp(t m_j[c] - lse[i,c]) and Yp = Y without the R term (the caller passes it):
+ *            s[j,c] = sum_{e' in row j} w p dOut[i,c],   r[j,c] = sum_{e' in row j} w p dOut[i,c] (m_j[c] - Yp[i,c]),
+ *            dH[j,c] = (s + t r) (has_eps: times [H[j,c] > 0]),   dR[j,:] = dOut[j,:] (nullable: the root block of the same gradient
+ *            row buffer),   dt_rows[j] = sum_c m_j[c] r[j,c] (nullable, [n]: the temperature's gradient is its sum).
+ *            add_dout != 0: dH[j,c] += dOut[j,c], one unfused addition after the mask (a layer whose root term is H itself).
+ *            dH is written completely: a row without entries gets zeros (dOut's row with add_dout).  No output may alias an input
+ *            or another output.  One launch. */
+int ddmp_gather_softmax_bwd_f32(const ddmp_graph* g, int C, const float* dOut, int64_t lddo, const float* H, int64_t ldh,
+                                const float* Yp, int64_t ldyp, const float* lse, int64_t ldl, float t, int has_eps, float msg_eps,
+                                int add_dout, float* dH, int64_t lddh, float* dR /*nullable*/, int64_t lddr,
+                                float* dt_rows /*nullable*/, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ dense steps (MFMA; float32 operands and results, the
  * arithmetic is ddmp_set_gemm_mode's: by default SPLIT-precision 16-bit MFMA products with f32 accumulation -- f32-class
  * accuracy, not bit-exact f32; mode 0 = f32-input MFMA, the strict one)

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|spline|sage|pna|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|spline|sage|pna|gen|all] [--rows N] [--iters K]
+gen (not part of all): the softmax-aggregation launches (ops.gather_softmax, ops.gather_softmax_bwd) at C = 32, 64, 128,
+256 on the same graph as sage, alternating in one loop: the forward (with and without the lse store) against the single-mean
+ops.gather_stats with root at the same width, and the backward launch against ops.gather_stats_bwd; the figures and the algorithmic
+byte counts go to --out (profiles/gen_microbench.txt).
 pna (not part of all): the neighbour-moments launches (ops.gather_moments, ops.gather_moments_bwd) at C = 64, 128, 256
 on the same graph as sage, alternating in one loop: the fused mean + min + max + std forward (plain and tower-major) against
 ops.gather_stats(mean + max + min) plus the two-launch composition of the variance from the gather_stats means of x and of x * x, and
@@ -70,7 +74,7 @@ ap.add_argument("--widths", default="512,256,128,64,32")
 ap.add_argument("--rotate", type=int, default=1, help="spmm: cycle through this many (input, output) buffer sets so that narrow "
                 "widths are not served from the 256 MB MALL (a 1M x 32 float tensor is 128 MB)")
 ap.add_argument("--weighted", action="store_true", help="spmm: valued graph against the unvalued graph of the same mesh")
-ap.add_argument("--out", default=None, help="gat / gatv2 / transformer / resgated / feast / edge / gmm / spline / sage / pna: the file the figures are written to (default profiles/<what>_microbench.txt)")
+ap.add_argument("--out", default=None, help="gat / gatv2 / transformer / resgated / feast / edge / gmm / spline / sage / pna / gen: the file the figures are written to (default profiles/<what>_microbench.txt)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 n = a.rows
@@ -943,5 +947,56 @@ if a.what == "pna":
         print("\n".join(lines[-(len(alg) + 2):]), flush=True)
         del Bs, As, Xs, X2, Ds, O4, O3, Oa, Ob, saved, amn, amx, inv
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "pna_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.what == "gen":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    g = ops.graph_for(ei, nn_, norm="gat", add_self_loops=False)
+    reps = max(a.iters, 20)
+    lines = ["softmax aggregation (GENConv) on the vertex graph of torus(%d, %d) in RCB order: N=%d, entries=%d (no loops), float32; "
+             "median of %d launches [min q1 q3 max], one HIP-event pair per launch, forms alternating in one loop, rotating buffer "
+             "sets; softmax = ONE ops.gather_softmax launch (message relu + eps, t = 1, root, lse stored; 'no lse': a forward without "
+             "a backward), mean = ops.gather_stats(mean) with root at the same width; softmax bwd = ONE ops.gather_softmax_bwd launch "
+             "(dH and the root block, dt_rows), mean bwd = ops.gather_stats_bwd (dX and the root block); bytes = the algorithmic counts "
+             "of ops.py and DESIGN.md 4.18 (MB)" % (nu_, nv_, nn_, g.nnz, reps)]
+    print(lines[0], flush=True)
+    for C in (32, 64, 128, 256):
+        R = 2 if nn_ * C * 4 >= (1 << 29) else 4
+        Bs = [torch.randn(nn_, 2 * C, device=dev) for _ in range(R)]           # [H | D]
+        Hs, Rs = [b[:, :C] for b in Bs], [b[:, C:] for b in Bs]
+        Ds = [torch.randn(nn_, C, device=dev) for _ in range(R)]
+        Oy, Om = torch.empty(nn_, C, device=dev), torch.empty(nn_, C, device=dev)
+        G2, G3 = torch.empty(nn_, 2 * C, device=dev), torch.empty(nn_, 2 * C, device=dev)
+        saved = [ops.gather_softmax(g, Hs[i], 1.0, msg_eps=1e-7, root=Rs[i]) for i in range(R)]
+        Yp, Ls = [s[0] - Rs[i] for i, s in enumerate(saved)], [s[1] for s in saved]
+        inv = ops.gather_stats(g, Hs[0], want=("mean",))[2]
+        q = alternate({
+            "softmax": lambda i: ops.gather_softmax(g, Hs[i], 1.0, msg_eps=1e-7, root=Rs[i], out=Oy),
+            "softmax no lse": lambda i: ops.gather_softmax(g, Hs[i], 1.0, msg_eps=1e-7, root=Rs[i], out=Oy, want_lse=False),
+            "mean": lambda i: ops.gather_stats(g, Hs[i], want=("mean",), root=Rs[i], out=Om),
+            "softmax bwd": lambda i: ops.gather_softmax_bwd(g, Ds[i], Hs[i], Yp[i], Ls[i], 1.0, msg_eps=1e-7, root=True, want_dt=True, out=G2),
+            "mean bwd": lambda i: ops.gather_stats_bwd(g, ds=Ds[i], invdeg=inv, root=True, out=G3)}, reps, R)
+        feat, ent, node = 4.0 * nn_ * C, 4.0 * g.nnz, 4.0 * nn_
+        alg = {"softmax": 4 * feat + 2 * ent + node, "softmax no lse": 3 * feat + 2 * ent + node, "mean": 3 * feat + 2 * ent + 2 * node,
+               "softmax bwd": 7 * feat + 3 * ent + 2 * node, "mean bwd": 4 * feat + 3 * ent + 2 * node}
+        lines.append("C=%d (%d buffer sets):" % (C, R))
+        for k in alg:
+            lines.append("  %-15s %s  %7.0f MB  %.2f TB/s alg" % (k, fmt(q[k]), alg[k] / 1e6, alg[k] / q[k][2] / 1e6))
+        rate = lambda k: alg[k] / q[k][2]
+        lines.append("  softmax x%.2f of mean in time (x%.2f per byte); without lse x%.2f (x%.2f per byte);  softmax bwd x%.2f of mean bwd "
+                     "in time (x%.2f per byte)"
+                     % (q["softmax"][2] / q["mean"][2], rate("mean") / rate("softmax"), q["softmax no lse"][2] / q["mean"][2],
+                        rate("mean") / rate("softmax no lse"), q["softmax bwd"][2] / q["mean bwd"][2], rate("mean bwd") / rate("softmax bwd")))
+        print("\n".join(lines[-(len(alg) + 2):]), flush=True)
+        del Bs, Hs, Rs, Ds, Oy, Om, G2, G3, saved, Yp, Ls, inv
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "gen_microbench.txt")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
