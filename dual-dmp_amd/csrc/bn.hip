@@ -269,6 +269,76 @@ int run_colreduce(const F& f, int64_t n_rows, int C, int width, double* out, voi
     return DDMP_OK;
 }
 
+// Any width, leading dimension and alignment: the first stage for the operands colreduce_kernel cannot take (C not a power of two
+// or below 8, ld % 4 != 0, a block that does not start on 16 bytes) -- what the composed routes of the gather hand on
+// (ddmp_spmm_stats_f32 / ddmp_spmm_bnred_f32 where their fused kernel does not apply).  One thread per column of a 32-column tile
+// and row slice (8 slices per workgroup, gridDim.y workgroups over the rows), scalar loads, float64 sums in a fixed order; the
+// records have colreduce_kernel's layout, so reduce_partials_kernel (and the coefficients riding on it) is shared.
+// G::operator()(row, c, s0, s1): the element's two contributions, the same expressions as the vector functors'.
+struct StatsS {
+    const float* Y;
+    int64_t ldy;
+    __device__ __forceinline__ void operator()(int row, int c, double& s0, double& s1) const {
+        const double a = Y[(int64_t)row * ldy + c];
+        s0 += a;
+        s1 = fma(a, a, s1);
+    }
+};
+
+struct BwdReduceS {
+    const float *dZ, *Y;
+    const float *scale, *shift, *mean, *rstd;
+    int64_t lddz, ldy;
+    float slope;
+    __device__ __forceinline__ void operator()(int row, int c, double& s0, double& s1) const {
+        const float y = Y[(int64_t)row * ldy + c];
+        const float g = dZ[(int64_t)row * lddz + c] * lrelu_grad(fmaf(y, scale[c], shift[c]), slope);
+        s0 += g;
+        s1 = fma((double)g, (double)((y - mean[c]) * rstd[c]), s1);
+    }
+};
+
+template <class G>
+__global__ __launch_bounds__(256) void colreduce_scalar_kernel(G f, int n_rows, int C, double* __restrict__ partial) {
+    __shared__ double sm[2][256];
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31), sl = threadIdx.x >> 5;
+    double s0 = 0.0, s1 = 0.0;
+    if (c < C)
+        for (int row = blockIdx.y * 8 + sl; row < n_rows; row += gridDim.y * 8) f(row, c, s0, s1);
+    sm[0][threadIdx.x] = s0;
+    sm[1][threadIdx.x] = s1;
+    __syncthreads();
+    if (sl == 0 && c < C) {
+        double r0 = 0.0, r1 = 0.0;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            r0 += sm[0][threadIdx.x + 32 * u];
+            r1 += sm[1][threadIdx.x + 32 * u];
+        }
+        partial[(int64_t)blockIdx.y * 2 * C + c] = r0;
+        partial[(int64_t)blockIdx.y * 2 * C + C + c] = r1;
+    }
+}
+
+int colreduce_scalar_blocks(int64_t n_rows) {                    // >= 32 rows per slice where the input allows
+    return (int)std::max<int64_t>(1, std::min<int64_t>(kMaxBlocks, cdiv(n_rows, (int64_t)8 * 32)));
+}
+
+template <class G>
+int run_colreduce_scalar(const G& f, int64_t n_rows, int C, double* out, void* ws, size_t ws_bytes, hipStream_t st,
+                         const FinalizeArgs& fin) {
+    const int nblk = colreduce_scalar_blocks(n_rows);
+    if (!ws || ws_bytes < (size_t)nblk * 2 * C * sizeof(double)) return DDMP_EWORKSPACE;
+    double* partial = (double*)ws;
+    hipLaunchKernelGGL((colreduce_scalar_kernel<G>), dim3((unsigned)cdiv(C, 32), nblk), dim3(256), 0, st, f, (int)n_rows, C, partial);
+    LAUNCH_TRY();
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)cdiv(C, 32)), dim3(256), 0, st, partial, nblk, C, out, fin);
+    LAUNCH_TRY();
+    return DDMP_OK;
+}
+
+bool vec16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 }  // namespace
 
 extern "C" size_t ddmp_colreduce_workspace_bytes(int64_t n_rows, int C) {
@@ -287,6 +357,33 @@ extern "C" int ddmp_bn_stats_f32(const float* Y, int64_t ldy, int64_t n_rows, in
                                  void* ws, size_t ws_bytes, ddmp_stream stream) {
     CallCtx ctx;
     return ddmp_bn_stats_f32(Y, ldy, n_rows, C, sums, ws, ws_bytes, stream, ctx);
+}
+
+// The two reductions for the composed routes of the gather: colreduce_kernel where it applies (the exported entry points' own
+// conditions, which they go on refusing), else the scalar first stage -- a composed route must not refuse AFTER its gather has
+// written the output.
+size_t ddmp_colreduce_any_workspace_bytes(int64_t n_rows, int C) {
+    if (n_rows <= 0 || C <= 0) return 0;
+    return std::max(ddmp_colreduce_workspace_bytes(n_rows, C), (size_t)colreduce_scalar_blocks(n_rows) * 2 * (size_t)C * sizeof(double));
+}
+
+int ddmp_bn_stats_any_f32(const float* Y, int64_t ldy, int64_t n_rows, int C, double* sums, void* ws, size_t ws_bytes,
+                          ddmp_stream stream, CallCtx& ctx) {
+    ARG_TRY(Y && sums && n_rows > 0 && n_rows < INT32_MAX && C > 0 && ldy >= C);
+    if (width_ok(C) && ldy % 4 == 0 && vec16(Y)) return ddmp_bn_stats_f32(Y, ldy, n_rows, C, sums, ws, ws_bytes, stream, ctx);
+    StatsS f{Y, ldy};
+    return run_colreduce_scalar(f, n_rows, C, sums, ws, ws_bytes, (hipStream_t)stream, ctx.take_fin(C));
+}
+
+int ddmp_bn_bwd_reduce_any_f32(const float* dZ, int64_t lddz, const float* Y, int64_t ldy, int64_t n_rows, int C, const float* scale,
+                               const float* shift, const float* mean, const float* rstd, float slope, double* sums2, void* ws,
+                               size_t ws_bytes, ddmp_stream stream, CallCtx& ctx) {
+    ARG_TRY(dZ && Y && scale && shift && mean && rstd && sums2);
+    ARG_TRY(n_rows > 0 && n_rows < INT32_MAX && C > 0 && ldy >= C && lddz >= C);
+    if (width_ok(C) && ldy % 4 == 0 && lddz % 4 == 0 && vec16(dZ) && vec16(Y) && vec16(scale) && vec16(shift) && vec16(mean) && vec16(rstd))
+        return ddmp_bn_bwd_reduce_f32(dZ, lddz, Y, ldy, n_rows, C, scale, shift, mean, rstd, slope, sums2, ws, ws_bytes, stream, ctx);
+    BwdReduceS f{dZ, Y, scale, shift, mean, rstd, lddz, ldy, slope};
+    return run_colreduce_scalar(f, n_rows, C, sums2, ws, ws_bytes, (hipStream_t)stream, ctx.take_fin(C));
 }
 
 extern "C" int ddmp_bn_prepare_f32(const double* sums, double n_total, int C, const float* gamma,

@@ -58,6 +58,13 @@ int ddmp_bn_stats_f32(const float* Y, int64_t ldy, int64_t n_rows, int C, double
                       ddmp_stream stream, ddmp::CallCtx& ctx);
 int ddmp_bn_stats_bf16(const uint16_t* Y, int64_t ldy, int64_t n_rows, int C, double* sums, void* workspace,
                        size_t workspace_bytes, ddmp_stream stream, ddmp::CallCtx& ctx);
+// (the composed routes of the gather: any width, leading dimension and alignment -- bn.hip)
+size_t ddmp_colreduce_any_workspace_bytes(int64_t n_rows, int C);
+int ddmp_bn_stats_any_f32(const float* Y, int64_t ldy, int64_t n_rows, int C, double* sums, void* workspace, size_t workspace_bytes,
+                          ddmp_stream stream, ddmp::CallCtx& ctx);
+int ddmp_bn_bwd_reduce_any_f32(const float* dZ, int64_t lddz, const float* Y, int64_t ldy, int64_t n_rows, int C, const float* scale,
+                               const float* shift, const float* mean, const float* rstd, float slope, double* sums2 /*[2C]*/,
+                               void* workspace, size_t workspace_bytes, ddmp_stream stream, ddmp::CallCtx& ctx);
 int ddmp_bn_bwd_reduce(const void* dZ, int64_t lddz, const void* Y, int64_t ldy, int64_t n_rows, int C, int dtype,
                        const float* scale, const float* shift, const float* mean, const float* rstd, float slope, double* sums2,
                        void* workspace, size_t workspace_bytes, ddmp_stream stream, ddmp::CallCtx& ctx);

@@ -638,7 +638,7 @@ extern "C" int ddmp_spmm_axpby_f32(const ddmp_graph* g, const float* X, int64_t 
 extern "C" size_t ddmp_spmm_bnred_workspace_bytes(int64_t n_rows, int C) {
     if (n_rows <= 0 || C <= 0) return 0;
     const size_t fused = (size_t)ddmp::cdiv(n_rows, kRB) * 4 * 2 * (size_t)C * sizeof(float) + 256 + fpartials_mid_bytes(C);
-    return std::max(fused, ddmp_colreduce_workspace_bytes(n_rows, C));
+    return std::max(fused, ddmp_colreduce_any_workspace_bytes(n_rows, C));   // (the composed route: any width, bn.hip)
 }
 
 int ddmp_spmm_bnred_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, int C, const float* Yp,
@@ -655,8 +655,8 @@ int ddmp_spmm_bnred_f32(const ddmp_graph* g, const float* X, int64_t ldx, float*
     if (!fused) {
         int rc = ddmp_spmm_f32(g, X, ldx, Y, ldy, C, nullptr, nullptr, nullptr, slope, stream);
         if (rc != DDMP_OK) return rc;
-        return ddmp_bn_bwd_reduce_f32(Y, ldy, Yp, ldyp, g->n_rows, C, scale, shift, mean, rstd, slope, sums2, ws, ws_bytes,
-                                      stream, ctx);
+        return ddmp_bn_bwd_reduce_any_f32(Y, ldy, Yp, ldyp, g->n_rows, C, scale, shift, mean, rstd, slope, sums2, ws, ws_bytes,
+                                          stream, ctx);
     }
     const int n = (int)g->n_rows;
     const int n_chunks = (int)cdiv(n, kRB);
@@ -713,7 +713,7 @@ int ddmp_spmm_stats_f32(const ddmp_graph* g, const float* X, int64_t ldx, float*
     if (!fused) {
         int rc = ddmp_spmm_f32(g, X, ldx, Y, ldy, C, bias, pro_scale, pro_shift, slope, stream);
         if (rc != DDMP_OK) return rc;
-        return ddmp_bn_stats_f32(Y, ldy, g->n_rows, C, sums2, ws, ws_bytes, stream, ctx);
+        return ddmp_bn_stats_any_f32(Y, ldy, g->n_rows, C, sums2, ws, ws_bytes, stream, ctx);
     }
     BnRed red{nullptr, 0, nullptr, nullptr, ref, nullptr, (float*)ws};
     // LDS-patch kernel where selected (one record per chunk, like the lean gather; its heavy chunks: the lean gather's list)

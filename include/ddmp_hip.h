@@ -688,7 +688,8 @@ int ddmp_adam_step_f32(float* p, const float* g, float* m, float* v, int64_t n, 
  * sums (y - ref) and (y - ref)^2 in float32 over 16 rows at a time and in float64 from there on, and the shift is undone
  * exactly -- around ref those partial sums are well conditioned whatever mean / std is (float32-class statistics, as
  * nn.BatchNorm1d computes them).  Workspace: ddmp_spmm_bnred_ws_bytes(n_rows, C, DDMP_F32).  Where the fused kernel does not
- * apply (C % 32, misaligned, ref NULL) it runs ddmp_spmm_f32 + ddmp_bn_stats_f32. */
+ * apply (C % 32, misaligned, ref NULL) it runs ddmp_spmm_f32 + the column reduction of ddmp_bn_stats_f32, at any width, leading
+ * dimension and alignment (a scalar first stage where that entry point's own kernel does not apply); ddmp_spmm_bnred likewise. */
 int ddmp_spmm_stats_supported(int C);
 int ddmp_spmm_stats_f32(const ddmp_graph* g, const float* X, int64_t ldx, float* Y, int64_t ldy, int C,
                         const float* bias /*nullable*/, const float* pro_scale /*nullable*/,

@@ -27,6 +27,8 @@ import numpy as np
 import pytest
 import torch
 
+from gather_layout_cases import split70k_csr, star_csr
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -90,16 +92,8 @@ def small(dev):
         out[name] = G(dev, rowptr, col, dinv, len(vv), handle=ops.graph_for(ei.to(dev), len(vv)))
         out[name]._keep = ei
     # hand-made CSR: 200 rows over 260 columns; rows 0..69 empty (an empty first chunk), row 100 has 1500 entries (repeats
-    # allowed: multi-edges), rows 150..155 empty, the rest 1..9 entries; arbitrary positive "dinv"
-    rng = np.random.default_rng(7)
-    n, nc = 200, 260
-    lens = rng.integers(1, 10, size=n)
-    lens[:70] = 0
-    lens[150:156] = 0
-    lens[100] = 1500
-    rowptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    col = rng.integers(0, nc, size=int(rowptr[-1])).astype(np.int32)
-    dinv = (rng.random(nc) * 0.9 + 0.1).astype(np.float32)
+    # allowed: multi-edges), rows 150..155 empty, the rest 1..9 entries; arbitrary positive "dinv" (gather_layout_cases.star_csr)
+    rowptr, col, dinv, nc = star_csr()
     out["star"] = G(dev, rowptr, col, dinv, nc)
     return out
 
@@ -280,22 +274,7 @@ def test_oversized_chunks_are_split_into_halves_or_quarters(dev, C):
     from dual_dmp_amd import _lib
     if os.environ.get("DDMP_SPMM_PATCH") == "0":
         pytest.skip("LDS-patch gather switched off")
-    n = 70400
-    rng = np.random.default_rng(5)
-    rows_cols = []
-    special = {100: 2, 500: 5, 900: 8}                            # chunk -> distinct far columns per row
-    for c in range(n // 64):
-        r = np.arange(64 * c, 64 * c + 64)
-        k = special.get(c)
-        if k is None:
-            cols = np.stack([r, np.clip(r + 1, 0, n - 1), np.clip(r - 1, 0, n - 1), np.clip(r + 3, 0, n - 1)], 1)
-        else:                                                     # row i of the chunk: k columns nobody else in the chunk references
-            cols = (np.arange(64 * k).reshape(64, k) * 97 + 1000 * c) % n
-        rows_cols.append(cols)
-    lens = np.array([len(x) for cc in rows_cols for x in cc])
-    rowptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-    col = np.concatenate([np.asarray(x) for cc in rows_cols for x in cc]).astype(np.int32)
-    dinv = (rng.random(n) * 0.9 + 0.1).astype(np.float32)
+    rowptr, col, dinv, n = split70k_csr()                       # (the builder: gather_layout_cases.py)
     gr = G(dev, rowptr, col, dinv, n)
     if os.environ.get("DDMP_SPMM_PATCH") is None:
         kd, nh, ns = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
