@@ -16,12 +16,6 @@
 
 namespace {
 
-__device__ __forceinline__ void take(float& m, int& id, float v, int j) {
-    const bool w = v > m;
-    m = w ? v : m;
-    id = w ? j : id;
-}
-
 // ------------------------------------------------------------------------------------------------ forward
 __global__ __launch_bounds__(256) void gather_max_kernel(const int* __restrict__ rowptr, const int* __restrict__ col,
                                                          const float* __restrict__ B, int64_t ldb, const float* __restrict__ A,
@@ -55,10 +49,10 @@ __global__ __launch_bounds__(256) void gather_max_kernel(const int* __restrict__
                     for (int k = 0; k < NE; ++k) x[k] = ld4(B + (int64_t)j[k] * ldb + q * 4);
 #pragma unroll
                     for (int k = 0; k < NE; ++k) {
-                        take(m.x, id.x, x[k].x, j[k]);
-                        take(m.y, id.y, x[k].y, j[k]);
-                        take(m.z, id.z, x[k].z, j[k]);
-                        take(m.w, id.w, x[k].w, j[k]);
+                        take_gt(m.x, id.x, x[k].x, j[k]);
+                        take_gt(m.y, id.y, x[k].y, j[k]);
+                        take_gt(m.z, id.z, x[k].z, j[k]);
+                        take_gt(m.w, id.w, x[k].w, j[k]);
                     }
                 };
                 ROW_BATCH_SWITCH(b0, nn, batch)
@@ -91,7 +85,7 @@ __global__ __launch_bounds__(256) void gather_max_scalar_kernel(const int* __res
             m = B[(int64_t)id * ldb + c];
             for (int e = e0 + 1; e < e1; ++e) {
                 const int j = col[e];
-                take(m, id, B[(int64_t)j * ldb + c], j);
+                take_gt(m, id, B[(int64_t)j * ldb + c], j);
             }
             if (A) m = A[(int64_t)row * lda + c] + m;
         }

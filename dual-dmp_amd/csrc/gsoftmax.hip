@@ -305,9 +305,6 @@ __global__ __launch_bounds__(256) void gather_softmax_bwd_scalar_kernel(const in
 
 // the attention graph WITHOUT loop handling: a_e counts the input edges of entry e
 inline bool smax_graph_ok(const ddmp_graph* g) { return attn_graph_ok(g) && g->valued == DDMP_GV_VALUED; }
-// a float32 [n, C] operand: present -> wide enough; `vec`: leading dimension % 4 == 0 and 16-byte aligned
-inline bool wide(const void* m, int64_t ld, int C) { return !m || ld >= C; }
-inline bool vec_ok(const void* m, int64_t ld) { return !m || (ld % 4 == 0 && al16(m)); }
 inline bool finite_f(float v) { return v == v && v - v == 0.f; }
 
 template <bool kMsg>

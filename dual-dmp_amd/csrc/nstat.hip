@@ -73,16 +73,6 @@ struct StatsBwd {
     int64_t lddr;
 };
 
-__device__ __forceinline__ void take_gt(float& m, int& id, float v, int j) {
-    const bool w = v > m;
-    m = w ? v : m;
-    id = w ? j : id;
-}
-__device__ __forceinline__ void take_lt(float& m, int& id, float v, int j) {
-    const bool w = v < m;
-    m = w ? v : m;
-    id = w ? j : id;
-}
 // the epilogue of S: (mean: one multiplication) + root + bias, never contracted into an fma
 __device__ __forceinline__ float finish(float acc, float w, bool mean, bool has_r, float r, bool has_b, float b) {
     float v = mean ? __fmul_rn(acc, w) : acc;
@@ -309,9 +299,6 @@ __global__ __launch_bounds__(256) void gather_stats_bwd_scalar_kernel(const int*
 
 // the attention graph WITHOUT loop handling: a_e counts the input edges of entry e, so sum_e a_e is the in-degree
 inline bool stats_graph_ok(const ddmp_graph* g) { return attn_graph_ok(g) && g->valued == DDMP_GV_VALUED; }
-// a float32 / int32 [n, C] operand: present -> wide enough; `vec`: leading dimension % 4 == 0 and 16-byte aligned
-inline bool wide(const void* m, int64_t ld, int C) { return !m || ld >= C; }
-inline bool vec_ok(const void* m, int64_t ld) { return !m || (ld % 4 == 0 && al16(m)); }
 
 template <int kW>
 int launch_fwd(hipStream_t st, const ddmp_graph* g, bool vec, const StatsFwd& p, int C) {
@@ -324,16 +311,7 @@ int launch_bwd(hipStream_t st, const ddmp_graph* g, bool vec, const StatsBwd& p,
                        g->mirror, g->a, p, (int)g->n_rows, C);
 }
 
-#define STATS_SWITCH(what, launch, ...)                  \
-    switch (what) {                                      \
-        case 1: return launch<1>(__VA_ARGS__);           \
-        case 2: return launch<2>(__VA_ARGS__);           \
-        case 3: return launch<3>(__VA_ARGS__);           \
-        case 4: return launch<4>(__VA_ARGS__);           \
-        case 5: return launch<5>(__VA_ARGS__);           \
-        case 6: return launch<6>(__VA_ARGS__);           \
-        default: return launch<7>(__VA_ARGS__);          \
-    }
+using StatsSubsets = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7>;        // every non-empty subset of sum, max, min
 
 }  // namespace
 
@@ -351,7 +329,7 @@ extern "C" int ddmp_gather_stats_f32(const ddmp_graph* g, const float* X, int64_
                      vec_ok(argmx, ldamx) && vec_ok(Mn, ldmn) && vec_ok(argmn, ldamn) && vec_ok(Xcopy, ldxc);
     const StatsFwd p{X, ldx, R, ldr, bias, mean, S, lds, Mx, ldmx, argmx, ldamx, Mn, ldmn, argmn, ldamn, invdeg, Xcopy, ldxc};
     const int what = (S ? kSum : 0) | (Mx ? kMax : 0) | (Mn ? kMin : 0);
-    STATS_SWITCH(what, launch_fwd, (hipStream_t)stream, g, vec, p, C)
+    return for_subset(StatsSubsets(), what, [&](auto kw) { return launch_fwd<kw()>((hipStream_t)stream, g, vec, p, C); });
 }
 
 extern "C" int ddmp_gather_stats_bwd_f32(const ddmp_graph* g, int C, const float* dS, int64_t ldds, const float* invdeg,
@@ -367,5 +345,5 @@ extern "C" int ddmp_gather_stats_bwd_f32(const ddmp_graph* g, int C, const float
                      vec_ok(argmn, ldamn) && vec_ok(dX0, lddx0) && vec_ok(dX, lddx) && vec_ok(dR, lddr);
     const StatsBwd p{dS, ldds, invdeg, dMx, lddmx, argmx, ldamx, dMn, lddmn, argmn, ldamn, dX0, lddx0, dX, lddx, dR, lddr};
     const int what = (dS ? kSum : 0) | (dMx ? kMax : 0) | (dMn ? kMin : 0);
-    STATS_SWITCH(what, launch_bwd, (hipStream_t)stream, g, vec, p, C)
+    return for_subset(StatsSubsets(), what, [&](auto kw) { return launch_bwd<kw()>((hipStream_t)stream, g, vec, p, C); });
 }

@@ -81,16 +81,6 @@ struct MomBwd {
     int64_t lddb;
 };
 
-__device__ __forceinline__ void take_gt(float& m, int& id, float v, int j) {
-    const bool w = v > m;
-    m = w ? v : m;
-    id = w ? j : id;
-}
-__device__ __forceinline__ void take_lt(float& m, int& id, float v, int j) {
-    const bool w = v < m;
-    m = w ? v : m;
-    id = w ? j : id;
-}
 // one entry of the shifted moments: d = x - K, m1 += a d, m2 += (a d) d
 __device__ __forceinline__ void moment(float& m1, float& m2, float a, float x, float k) {
     const float d = __fsub_rn(x, k);
@@ -356,9 +346,6 @@ __global__ __launch_bounds__(256) void gather_moments_bwd_scalar_kernel(const in
 
 // the attention graph WITHOUT loop handling: a_e counts the input edges of entry e, so sum_e a_e is the in-degree
 inline bool moments_graph_ok(const ddmp_graph* g) { return attn_graph_ok(g) && g->valued == DDMP_GV_VALUED; }
-// a float32 / int32 [n, C] operand: present -> wide enough; `vec`: leading dimension % 4 == 0 and 16-byte aligned
-inline bool wide(const void* m, int64_t ld, int64_t C) { return !m || ld >= C; }
-inline bool vec_ok(const void* m, int64_t ld) { return !m || (ld % 4 == 0 && al16(m)); }
 // no two of the present pointers are equal
 template <size_t N>
 inline bool distinct(const void* const (&ptr)[N]) {
@@ -379,40 +366,8 @@ int launch_bwd(hipStream_t st, const ddmp_graph* g, bool vec, const MomBwd& p, i
                        g->mirror, g->a, p, (int)g->n_rows, C);
 }
 
-// every non-empty subset of the four forward blocks
-#define MOMENTS_SWITCH(what, launch, ...)                                                                         \
-    switch (what) {                                                                                               \
-        case 1: return launch<1>(__VA_ARGS__);                                                                    \
-        case 2: return launch<2>(__VA_ARGS__);                                                                    \
-        case 3: return launch<3>(__VA_ARGS__);                                                                    \
-        case 4: return launch<4>(__VA_ARGS__);                                                                    \
-        case 5: return launch<5>(__VA_ARGS__);                                                                    \
-        case 6: return launch<6>(__VA_ARGS__);                                                                    \
-        case 7: return launch<7>(__VA_ARGS__);                                                                    \
-        case 8: return launch<8>(__VA_ARGS__);                                                                    \
-        case 9: return launch<9>(__VA_ARGS__);                                                                    \
-        case 10: return launch<10>(__VA_ARGS__);                                                                  \
-        case 11: return launch<11>(__VA_ARGS__);                                                                  \
-        case 12: return launch<12>(__VA_ARGS__);                                                                  \
-        case 13: return launch<13>(__VA_ARGS__);                                                                  \
-        case 14: return launch<14>(__VA_ARGS__);                                                                  \
-        default: return launch<15>(__VA_ARGS__);                                                                  \
-    }
-// the backward's: the dQ stream comes with dS
-#define MOMENTS_BWD_SWITCH(what, launch, ...)                                                                     \
-    switch (what) {                                                                                               \
-        case 1: return launch<1>(__VA_ARGS__);                                                                    \
-        case 2: return launch<2>(__VA_ARGS__);                                                                    \
-        case 3: return launch<3>(__VA_ARGS__);                                                                    \
-        case 4: return launch<4>(__VA_ARGS__);                                                                    \
-        case 5: return launch<5>(__VA_ARGS__);                                                                    \
-        case 6: return launch<6>(__VA_ARGS__);                                                                    \
-        case 7: return launch<7>(__VA_ARGS__);                                                                    \
-        case 9: return launch<9>(__VA_ARGS__);                                                                    \
-        case 11: return launch<11>(__VA_ARGS__);                                                                  \
-        case 13: return launch<13>(__VA_ARGS__);                                                                  \
-        default: return launch<15>(__VA_ARGS__);                                                                  \
-    }
+using MomentSubsets = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>;        // every non-empty subset
+using MomentBwdSubsets = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 9, 11, 13, 15>;        // the dQ stream comes with dS
 
 }  // namespace
 
@@ -433,7 +388,7 @@ extern "C" int ddmp_gather_moments_f32(const ddmp_graph* g, const float* B, int6
     const MomFwd p{B, ldb, R, ldr, mean, as_std, tw, tw == C ? 0 : tstride, S, lds, Mx, ldmx, argmx, ldamx, Mn, ldmn, argmn, ldamn,
                    V, ldv, mu, ldmu, invdeg};
     const int what = (S ? kSum : 0) | (Mx ? kMax : 0) | (Mn ? kMin : 0) | (V ? kVar : 0);
-    MOMENTS_SWITCH(what, launch_fwd, (hipStream_t)stream, g, vec, p, C)
+    return for_subset(MomentSubsets(), what, [&](auto kw) { return launch_fwd<kw()>((hipStream_t)stream, g, vec, p, C); });
 }
 
 extern "C" int ddmp_gather_moments_bwd_f32(const ddmp_graph* g, int C, const float* dS, int64_t ldds, const float* dQ, int64_t lddq,
@@ -450,5 +405,5 @@ extern "C" int ddmp_gather_moments_bwd_f32(const ddmp_graph* g, int C, const flo
                      vec_ok(dMx, lddmx) && vec_ok(argmx, ldamx) && vec_ok(dMn, lddmn) && vec_ok(argmn, ldamn) && vec_ok(dB, lddb);
     const MomBwd p{dS, ldds, dQ, lddq, B, ldb, invdeg, dMx, lddmx, argmx, ldamx, dMn, lddmn, argmn, ldamn, dB, lddb};
     const int what = (dS ? kSum : 0) | (dMx ? kMax : 0) | (dMn ? kMin : 0) | (dQ ? kVar : 0);
-    MOMENTS_BWD_SWITCH(what, launch_bwd, (hipStream_t)stream, g, vec, p, C)
+    return for_subset(MomentBwdSubsets(), what, [&](auto kw) { return launch_bwd<kw()>((hipStream_t)stream, g, vec, p, C); });
 }

@@ -1,5 +1,5 @@
 // The row-gather work layout of the graph-operator kernels (sddmm.hip, gat.hip, gatv2.hip, tconv.hip, rgate.hip, feast.hip,
-// gmm.hip, gmax.hip, spline.hip; gather_mix.h, colsum_final.h):
+// gmm.hip, gmax.hip, spline.hip, nstat.hip, pna.hip, gsoftmax.hip; gather_mix.h, colsum_final.h):
 // the one place that fixes it.  (The SpMM files have their own variants of it; they do not include this header.)
 //   * a workgroup (4 waves) owns a chunk of kRB = 64 consecutive rows; blockIdx -> chunk is XCD-aware (block b runs on XCD b % 8,
 //     so XCD x takes the chunks x * chunks_per_xcd ..: the ~deg re-reads of a neighbour row by neighbouring output rows hit that
@@ -24,6 +24,7 @@
 #include "ddmp_common.h"
 
 #include <type_traits>
+#include <utility>
 
 namespace {
 
@@ -62,6 +63,17 @@ __device__ __forceinline__ float red_heads(float t, int lw) {
     if (lw < 4) t += __shfl_xor(t, 2, 64);
     if (lw < 8) t += __shfl_xor(t, 4, 64);
     return t;
+}
+// the running extremum and its entry's id: replaced on a strict > (<) only, so the first entry in CSR order wins a tie
+__device__ __forceinline__ void take_gt(float& m, int& id, float v, int j) {
+    const bool w = v > m;
+    m = w ? v : m;
+    id = w ? j : id;
+}
+__device__ __forceinline__ void take_lt(float& m, int& id, float v, int j) {
+    const bool w = v < m;
+    m = w ? v : m;
+    id = w ? j : id;
 }
 inline int lanes_per_head(int C) {
     const int W = C / 4;
@@ -163,6 +175,9 @@ __device__ __forceinline__ void gather_pass(const int* __restrict__ col, const i
 
 // ------------------------------------------------------------------------------------------------ host side
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// an OPTIONAL float32 / int32 [n, C] operand: present -> wide enough; `vec`: leading dimension % 4 == 0 and 16-byte aligned
+inline bool wide(const void* m, int64_t ld, int64_t C) { return !m || ld >= C; }
+inline bool vec_ok(const void* m, int64_t ld) { return !m || (ld % 4 == 0 && al16(m)); }
 
 // The attention graph: the coalesced square structure of a valued graph.  `values`: the kernels also read the entries'
 // multiplicities (g->a) and the mirror map; the arg-max gather reads neither.
@@ -206,6 +221,15 @@ inline int launch_head_rows(hipStream_t st, int n, bool vec, int lw, VK vk, SK s
     }
     LAUNCH_TRY();
     return DDMP_OK;
+}
+
+// The subset dispatch of the kernels compiled per subset of their outputs: launch(std::integral_constant<int, kW>()) for the kW of
+// the allowed subsets that equals `what`, so only the listed subsets are instantiated.  (The entry points' checks admit no other.)
+template <int... kWs, class Launch>
+inline int for_subset(std::integer_sequence<int, kWs...>, int what, Launch launch) {
+    int st = DDMP_EINVAL;
+    (void)((what == kWs && ((st = launch(std::integral_constant<int, kWs>())), true)) || ...);
+    return st;
 }
 
 }  // namespace

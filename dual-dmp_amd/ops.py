@@ -1338,17 +1338,68 @@ def gather_max_bwd(g: Graph, dg, arg, out=None):
     return da, db
 
 
-# ---------------------------------------------------------------------------------------- neighbour statistics
+# ---------------------------------------------------------------------------------------- neighbour statistics and moments
+#   Written once for both operators: the ``want`` validation, the (pointer, leading dimension) table of
+# the forward's blocks and args, and the backward's operand table with its refusals.
 STATS = ("mean", "add", "max", "min")
+MOMENTS = ("mean", "sum", "max", "min", "std", "var")
+_NBR_BLOCK = {"mean": "sum", "add": "sum", "sum": "sum", "max": "max", "min": "min", "std": "var", "var": "var"}
+
+
+def _nbr_want(want, names, pairs):
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if (not want or any(w not in names for w in want) or len(set(want)) != len(want)
+            or any(u in want and v in want for u, v in pairs)):
+        raise DdmpError("want must be a non-empty sequence of distinct names out of %r with %s, got %r"
+                        % (names, " and ".join("at most one of %r / %r" % uv for uv in pairs), want))
+    return want
+
+
+def _nbr_out(who, out, n, width, device):
+    if out is None:
+        out = torch.empty((n, width), dtype=torch.float32, device=device)
+    out, ldo = _mat(_chk(out, torch.float32, "out"), "out")
+    if out.shape[0] != n or out.shape[1] < width:
+        raise DdmpError("%s: out must be [%d, >= %d], got %s" % (who, n, width, tuple(out.shape)))
+    return out, ldo
+
+
+def _nbr_table(want, firsts, want_arg, n, C, device):
+    """-> (ptr, args, flat): ``ptr[block]`` = (tensor, leading dimension) of the sum / max / min / var block from ``firsts`` (parallel
+    to ``want``) and of the args ``amax`` / ``amin`` allocated here (``want_arg``), (None, 0) where absent; ``args`` parallel to
+    ``want``; ``flat``: S, lds, Mx, ldmx, argmx, ldamx, Mn, ldmn, argmn, ldamn as both entry points take them."""
+    ptr = {k: (None, 0) for k in ("sum", "max", "amax", "min", "amin", "var")}
+    args = [None] * len(want)
+    for k, w in enumerate(want):
+        ptr[_NBR_BLOCK[w]] = firsts[k]
+        if w in ("max", "min") and want_arg:
+            args[k] = torch.empty((n, C), dtype=torch.int32, device=device)
+            ptr["a" + w] = _gmax_arg(args[k], n, C)
+    flat = [v for k in ("sum", "max", "amax", "min", "amin") for v in (_p(ptr[k][0]), ptr[k][1])]
+    return ptr, args, flat
+
+
+def _nbr_bwd_operands(who, n, rows, argmx, argmn, invdeg, bad, rule):
+    """The backward's operands.  ``rows``: name -> float32 [n, C] tensor or None, with ds, dmx and dmn among them; ``bad``: the
+    operator's own refusal, ``rule`` its wording.  -> (first, C, op, invdeg): the first gradient present, ``op[name]`` = the
+    (pointer, leading dimension) arguments of every row operand and arg ((None, 0) where absent), invdeg checked."""
+    ds, dmx, dmn = rows["ds"], rows["dmx"], rows["dmn"]
+    first = next((t for t in (ds, dmx, dmn) if t is not None), None)
+    if (first is None or (dmx is None) != (argmx is None) or (dmn is None) != (argmn is None) or (ds is None and invdeg is not None)
+            or bad):
+        raise DdmpError("%s: at least one of ds, dmx, dmn; dmx comes with argmx, dmn with argmn; %s" % (who, rule))
+    C = first.shape[1] if isinstance(first, torch.Tensor) and first.dim() == 2 else 0
+    op = {name: (None, 0) if t is None else _rows(t, name, n, C) for name, t in rows.items()}
+    for name, t in (("argmx", argmx), ("argmn", argmn)):
+        op[name] = (None, 0) if t is None else _gmax_arg(t, n, C)
+    if invdeg is not None:
+        invdeg = _gat_arr(invdeg, (n,), "invdeg")
+    return first, C, {name: (_p(t), ld) for name, (t, ld) in op.items()}, invdeg
 
 
 def _stats_want(want):
     """``want`` as a tuple of distinct names out of ``STATS`` with at most one of mean / add, or ``DdmpError``."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(w not in STATS for w in want) or len(set(want)) != len(want) or ("mean" in want and "add" in want):
-        raise DdmpError("want must be a non-empty sequence of distinct names out of %r with at most one of 'mean' / 'add', got %r"
-                        % (STATS, want))
-    return want
+    return _nbr_want(want, STATS, (("mean", "add"),))
 
 
 def gather_stats(g: Graph, x, want=("mean",), root=None, bias=None, copy_x=False, want_arg=True, out=None):
@@ -1379,21 +1430,10 @@ def gather_stats(g: Graph, x, want=("mean",), root=None, bias=None, copy_x=False
     if bias is not None:
         bias = _gat_arr(bias, (C,), "bias")
     nb = len(want) + bool(copy_x)
-    if out is None:
-        out = torch.empty((n, nb * C), dtype=torch.float32, device=x.device)
-    out, _ = _mat(_chk(out, torch.float32, "out"), "out")
-    if out.shape[0] != n or out.shape[1] < nb * C:
-        raise DdmpError("gather_stats: out must be [%d, >= %d], got %s" % (n, nb * C, tuple(out.shape)))
+    out, _ = _nbr_out("gather_stats", out, n, nb * C, x.device)
     blocks = [out[:, k * C:(k + 1) * C] for k in range(nb)]
-    ptr = {k: (None, 0) for k in ("sum", "max", "min", "amax", "amin", "copy")}
-    args = [None] * len(want)
-    for k, w in enumerate(want):
-        ptr["sum" if w in ("mean", "add") else w] = _mat(blocks[k], w)
-        if w in ("max", "min") and want_arg:
-            args[k] = torch.empty((n, C), dtype=torch.int32, device=x.device)
-            ptr["a" + w] = _gmax_arg(args[k], n, C)
-    if copy_x:
-        ptr["copy"] = _mat(blocks[-1], "copy")
+    _, args, flat = _nbr_table(want, [_mat(blk, w) for blk, w in zip(blocks, want)], want_arg, n, C, x.device)
+    xc, ldxc = _mat(blocks[-1], "copy") if copy_x else (None, 0)
     invdeg = torch.empty(n, dtype=torch.float32, device=x.device) if "mean" in want else None
     # algorithmic bytes: every gathered row read ONCE whatever the number of statistics, one row written per block and per arg, the
     # root block and the row's own features (copy_x) read, invdeg written, col + multiplicity, rowptr
@@ -1401,11 +1441,8 @@ def gather_stats(g: Graph, x, want=("mean",), root=None, bias=None, copy_x=False
     alg = 4.0 * n * C * (1 + nb + n_arg + (root is not None) + bool(copy_x)) + 4.0 * n * (invdeg is not None) + 8.0 * g.nnz + 4.0 * (n + 1)
     with _timed("gather_stats", (C, "+".join(want), int(round(g.nnz / max(n, 1)))), alg, 1.0 * g.nnz * C * len(want),
                 survey=8.0 * n * C + 4.0 * g.nnz + 4.0 * (n + 1)):
-        st = _lib.lib().ddmp_gather_stats_f32(g.handle, _p(x), ldx, C, int("mean" in want), _p(root), ldr, _p(bias),
-                                              _p(ptr["sum"][0]), ptr["sum"][1], _p(ptr["max"][0]), ptr["max"][1],
-                                              _p(ptr["amax"][0]), ptr["amax"][1], _p(ptr["min"][0]), ptr["min"][1],
-                                              _p(ptr["amin"][0]), ptr["amin"][1], _p(invdeg), _p(ptr["copy"][0]), ptr["copy"][1],
-                                              _stream())
+        st = _lib.lib().ddmp_gather_stats_f32(g.handle, _p(x), ldx, C, int("mean" in want), _p(root), ldr, _p(bias), *flat,
+                                              _p(invdeg), _p(xc), ldxc, _stream())
     check(st, "ddmp_gather_stats_f32")
     return tuple(blocks), tuple(args), invdeg
 
@@ -1420,17 +1457,8 @@ def gather_stats_bwd(g: Graph, ds=None, invdeg=None, dmx=None, argmx=None, dmn=N
     views of it; further columns are left untouched); None: a buffer of its own."""
     _gmm_graph(g)
     n = g.n_rows
-    first = next((t for t in (ds, dmx, dmn) if t is not None), None)
-    if first is None or (dmx is None) != (argmx is None) or (dmn is None) != (argmn is None) or (ds is None and (root or invdeg is not None)):
-        raise DdmpError("gather_stats_bwd: at least one of ds, dmx, dmn; dmx comes with argmx, dmn with argmn; invdeg and root need ds")
-    C = first.shape[1] if isinstance(first, torch.Tensor) and first.dim() == 2 else 0
-    op = {}
-    for name, t in (("ds", ds), ("dmx", dmx), ("dmn", dmn), ("dx0", dx0)):
-        op[name] = (None, 0) if t is None else _rows(t, name, n, C)
-    for name, t in (("argmx", argmx), ("argmn", argmn)):
-        op[name] = (None, 0) if t is None else _gmax_arg(t, n, C)
-    if invdeg is not None:
-        invdeg = _gat_arr(invdeg, (n,), "invdeg")
+    first, C, op, invdeg = _nbr_bwd_operands("gather_stats_bwd", n, dict(ds=ds, dmx=dmx, dmn=dmn, dx0=dx0), argmx, argmn, invdeg,
+                                             ds is None and root, "invdeg and root need ds")
     (dx, lddx), (dr, lddr) = _out_with_root(out, "gather_stats_bwd", n, C, C, root, first.device)
     ns = sum(t is not None for t in (ds, dmx, dmn, dx0))
     # algorithmic bytes: every requested gradient stream (and each arg) read once, dx (and the root block, with ds once more)
@@ -1438,27 +1466,16 @@ def gather_stats_bwd(g: Graph, ds=None, invdeg=None, dmx=None, argmx=None, dmn=N
     alg = (4.0 * n * C * (ns + (argmx is not None) + (argmn is not None) + 1 + 2 * bool(root)) + 4.0 * n * (invdeg is not None)
            + 12.0 * g.nnz + 4.0 * (n + 1))
     with _timed("gather_stats_bwd", (C, ns, int(round(g.nnz / max(n, 1)))), alg, 1.0 * g.nnz * C * ns):
-        st = _lib.lib().ddmp_gather_stats_bwd_f32(g.handle, C, _p(op["ds"][0]), op["ds"][1], _p(invdeg), _p(op["dmx"][0]), op["dmx"][1],
-                                                  _p(op["argmx"][0]), op["argmx"][1], _p(op["dmn"][0]), op["dmn"][1],
-                                                  _p(op["argmn"][0]), op["argmn"][1], _p(op["dx0"][0]), op["dx0"][1], _p(dx), lddx,
-                                                  _p(dr), lddr, _stream())
+        st = _lib.lib().ddmp_gather_stats_bwd_f32(g.handle, C, *op["ds"], _p(invdeg), *op["dmx"], *op["argmx"], *op["dmn"],
+                                                  *op["argmn"], *op["dx0"], _p(dx), lddx, _p(dr), lddr, _stream())
     check(st, "ddmp_gather_stats_bwd_f32")
     return dx, dr
-
-
-# ---------------------------------------------------------------------------------------- neighbour moments
-MOMENTS = ("mean", "sum", "max", "min", "std", "var")
 
 
 def _moments_want(want):
     """``want`` as a tuple of distinct names out of ``MOMENTS`` with at most one of mean / sum and at most one of std / var, or
     ``DdmpError``."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    if (not want or any(w not in MOMENTS for w in want) or len(set(want)) != len(want) or ("mean" in want and "sum" in want)
-            or ("std" in want and "var" in want)):
-        raise DdmpError("want must be a non-empty sequence of distinct names out of %r with at most one of 'mean' / 'sum' and at most "
-                        "one of 'std' / 'var', got %r" % (MOMENTS, want))
-    return want
+    return _nbr_want(want, MOMENTS, (("mean", "sum"), ("std", "var")))
 
 
 def gather_moments(g: Graph, b, want=("mean",), root=None, tower_width=None, want_arg=True, out=None):
@@ -1493,24 +1510,14 @@ def gather_moments(g: Graph, b, want=("mean",), root=None, tower_width=None, wan
     if root is not None:
         root, ldr = _rows(root, "root", n, C)
     nb, T = len(want), C // tw
-    if out is None:
-        out = torch.empty((n, nb * C), dtype=torch.float32, device=b.device)
-    out, ldo = _mat(_chk(out, torch.float32, "out"), "out")
-    if out.shape[0] != n or out.shape[1] < nb * C:
-        raise DdmpError("gather_moments: out must be [%d, >= %d], got %s" % (n, nb * C, tuple(out.shape)))
+    out, ldo = _nbr_out("gather_moments", out, n, nb * C, b.device)
     if T == 1:
         blocks = [out[:, k * C:(k + 1) * C] for k in range(nb)]
     else:
         towers = out[:, :nb * C].unflatten(1, (T, nb, tw))
         blocks = [towers[:, :, k] for k in range(nb)]
-    ptr = {k: (None, 0) for k in ("sum", "max", "min", "var", "amax", "amin")}
-    args = [None] * nb
-    for k, w in enumerate(want):
-        key = "sum" if w in ("mean", "sum") else "var" if w in ("std", "var") else w
-        ptr[key] = (out[:, k * tw:], ldo)                        # (the block's first column; the kernel places the towers)
-        if w in ("max", "min") and want_arg:
-            args[k] = torch.empty((n, C), dtype=torch.int32, device=b.device)
-            ptr["a" + w] = _gmax_arg(args[k], n, C)
+    # (a block's first column; the kernel places the towers)
+    ptr, args, flat = _nbr_table(want, [(out[:, k * tw:], ldo) for k in range(nb)], want_arg, n, C, b.device)
     has_var = ptr["var"][0] is not None
     mu = torch.empty((n, C), dtype=torch.float32, device=b.device) if has_var else None
     invdeg = torch.empty(n, dtype=torch.float32, device=b.device)
@@ -1521,10 +1528,7 @@ def gather_moments(g: Graph, b, want=("mean",), root=None, tower_width=None, wan
     with _timed("gather_moments", (C, "+".join(want), tw, int(round(g.nnz / max(n, 1)))), alg, 1.0 * g.nnz * C * (nb + has_var),
                 survey=8.0 * n * C + 4.0 * g.nnz + 4.0 * (n + 1)):
         st = _lib.lib().ddmp_gather_moments_f32(g.handle, _p(b), ldb, C, int("mean" in want), int("std" in want), _p(root), ldr, tw,
-                                                nb * tw, _p(ptr["sum"][0]), ptr["sum"][1], _p(ptr["max"][0]), ptr["max"][1],
-                                                _p(ptr["amax"][0]), ptr["amax"][1], _p(ptr["min"][0]), ptr["min"][1],
-                                                _p(ptr["amin"][0]), ptr["amin"][1], _p(ptr["var"][0]), ptr["var"][1], _p(mu), C,
-                                                _p(invdeg), _stream())
+                                                nb * tw, *flat, _p(ptr["var"][0]), ptr["var"][1], _p(mu), C, _p(invdeg), _stream())
     check(st, "ddmp_gather_moments_f32")
     return tuple(blocks), tuple(args), invdeg, mu
 
@@ -1540,19 +1544,9 @@ def gather_moments_bwd(g: Graph, ds=None, dq=None, b=None, invdeg=None, dmx=None
     of a wider buffer) that receives db; None: a tensor of its own."""
     _gmm_graph(g)
     n = g.n_rows
-    first = next((t for t in (ds, dmx, dmn) if t is not None), None)
-    if (first is None or (dmx is None) != (argmx is None) or (dmn is None) != (argmn is None) or (ds is None and (dq is not None or
-            invdeg is not None)) or (dq is None) != (b is None)):
-        raise DdmpError("gather_moments_bwd: at least one of ds, dmx, dmn; dmx comes with argmx, dmn with argmn; dq comes with b and "
-                        "needs ds; invdeg needs ds")
-    C = first.shape[1] if isinstance(first, torch.Tensor) and first.dim() == 2 else 0
-    op = {}
-    for name, t in (("ds", ds), ("dq", dq), ("b", b), ("dmx", dmx), ("dmn", dmn)):
-        op[name] = (None, 0) if t is None else _rows(t, name, n, C)
-    for name, t in (("argmx", argmx), ("argmn", argmn)):
-        op[name] = (None, 0) if t is None else _gmax_arg(t, n, C)
-    if invdeg is not None:
-        invdeg = _gat_arr(invdeg, (n,), "invdeg")
+    first, C, op, invdeg = _nbr_bwd_operands("gather_moments_bwd", n, dict(ds=ds, dq=dq, b=b, dmx=dmx, dmn=dmn), argmx, argmn, invdeg,
+                                             (ds is None and dq is not None) or (dq is None) != (b is None),
+                                             "dq comes with b and needs ds; invdeg needs ds")
     db, lddb = _out(out, "out", n, C, first.device)
     if db.shape[0] != n:
         raise DdmpError("gather_moments_bwd: out must be [%d, %d], got %s" % (n, C, tuple(db.shape)))
@@ -1562,10 +1556,8 @@ def gather_moments_bwd(g: Graph, ds=None, dq=None, b=None, invdeg=None, dmx=None
     alg = (4.0 * n * C * (ns + (argmx is not None) + (argmn is not None) + (b is not None) + 1) + 4.0 * n * (invdeg is not None)
            + 12.0 * g.nnz + 4.0 * (n + 1))
     with _timed("gather_moments_bwd", (C, ns, int(round(g.nnz / max(n, 1)))), alg, 1.0 * g.nnz * C * ns):
-        st = _lib.lib().ddmp_gather_moments_bwd_f32(g.handle, C, _p(op["ds"][0]), op["ds"][1], _p(op["dq"][0]), op["dq"][1],
-                                                    _p(op["b"][0]), op["b"][1], _p(invdeg), _p(op["dmx"][0]), op["dmx"][1],
-                                                    _p(op["argmx"][0]), op["argmx"][1], _p(op["dmn"][0]), op["dmn"][1],
-                                                    _p(op["argmn"][0]), op["argmn"][1], _p(db), lddb, _stream())
+        st = _lib.lib().ddmp_gather_moments_bwd_f32(g.handle, C, *op["ds"], *op["dq"], *op["b"], _p(invdeg), *op["dmx"], *op["argmx"],
+                                                    *op["dmn"], *op["argmn"], _p(db), lddb, _stream())
     check(st, "ddmp_gather_moments_bwd_f32")
     return db
 

@@ -274,6 +274,23 @@ def test_backward_kernel(dev, graphs, host, name, C):
             assert bool((db.cpu()[empty] == 0).all())            # a row without entries gets zeros
 
 
+@pytest.mark.parametrize("name", ["hub", "ico"])                 # the long row; the pendant, one-source and edgeless rows
+@pytest.mark.parametrize("C", [3, 4, 40])                        # the scalar path, one float4, a ragged width
+def test_backward_has_the_bits_of_gather_stats_bwd(dev, graphs, name, C):
+    """For the streams that both backward entry points know (dS with and without invdeg, the maximum's, the minimum's) nstat.hip and
+    pna.hip perform the same operations in the same order, so the bits are equal -- the backward's counterpart of the forward
+    equality that ``test_kernels_match_torch`` asserts, and the guard that a fix to one copy reaches the other."""
+    from dual_dmp_amd import ops
+    ei, n = graphs[name]
+    gen = torch.Generator().manual_seed(n + C)
+    b, ds, dmx, dmn = (torch.randn(n, C, generator=gen).to(dev) for _ in range(4))
+    g = ops.graph_for(ei.to(dev), n, norm="gat", add_self_loops=False)
+    _, (_, amx, amn), invdeg, _ = ops.gather_moments(g, b, want=("mean", "max", "min"))
+    for streams in (dict(ds=ds, invdeg=invdeg), dict(ds=ds), dict(dmx=dmx, argmx=amx), dict(dmn=dmn, argmn=amn),
+                    dict(ds=ds, invdeg=invdeg, dmx=dmx, argmx=amx, dmn=dmn, argmn=amn)):
+        assert torch.equal(ops.gather_stats_bwd(g, **streams)[0], ops.gather_moments_bwd(g, **streams)), sorted(streams)
+
+
 # ------------------------------------------------------------------------------------------------ 5. the operator
 def _record(monkeypatch, masks):
     """Every ``ops.gather_moments`` result from here on, in call order; and the gradients reaching the ambiguous outputs of the
