@@ -1,8 +1,8 @@
-"""Drop-ins for thirteen ``torch_geometric.nn`` 2.2.0 operators on the HIP kernels: same constructor / call signature, parameter names
+"""Drop-ins for fourteen ``torch_geometric.nn`` 2.2.0 operators on the HIP kernels: same constructor / call signature, parameter names
 and initialisation; the dense part goes through the GEMMs, the graph part through one fused gather launch per direction, and no
 per-edge feature tensor exists at any point.  Each operator is documented once, at its class: ``GCNConv``, ``ChebConv``,
 ``GATConv``, ``GATv2Conv``, ``TransformerConv``, ``ResGatedGraphConv``, ``FeaStConv``, ``GMMConv`` (with ``cartesian_pseudo``),
-``SplineConv``, ``EdgeConv``, ``SAGEConv``, ``PNAConv`` (with ``degree_histogram``), ``GENConv``.
+``SplineConv``, ``EdgeConv``, ``SAGEConv``, ``PNAConv`` (with ``degree_histogram``), ``GENConv``, ``CGConv``.
 
 ``edge_weight`` (``GCNConv`` and ``ChebConv``; restated from the published PyG 2.2.0 source from memory -- PyG cannot be installed
 here, so this could not be checked against it; the pin is the dense float64 restatement ``tests/gcnw_ref.py``):
@@ -2134,3 +2134,136 @@ class GENConv(nn.Module):
 
     def extra_repr(self):
         return "%d, %d, aggr=%s" % (self.in_channels, self.out_channels, self.aggr)
+
+
+class _CGConvFn(_Fn):
+    """With ``lin_f.weight = [Wf_i | Wf_j | Ef]`` and ``lin_s.weight = [Ws_i | Ws_j | Es]`` (columns ``x_i | x_j | edge_attr``) the
+    linear layers on ``cat[x_i, x_j, e_ij]`` split by columns: ONE GEMM against the packed weight [Wf_i ; Ws_i ; Wf_j ; Ws_j] with
+    the lin biases on the first two blocks gives the row buffer [Af | As | Bf | Bs], then ONE launch forms both gates of every edge
+    in registers -- ``sigmoid(Af[i] + Bf[j] + Ef e_ij) * softplus(As[i] + Bs[j] + Es e_ij)`` -- and gathers (``ops.cgate_fwd``;
+    ``root``: the residual x_i rides in as the start of the sums).  Saved: the padded x, the packed weight, the row buffer, the
+    float32 attributes and the two transposed [dim, C] edge blocks -- nothing per edge.  Backward: the row-side launch (dAf, dAs and
+    the rows' shares of dEf / dEs) and the node-side launch (dBf, dBs), both recomputing the gates, into ONE row buffer
+    [dAf | dAs | dBf | dBs]; the lin bias gradients are column sums of its first two blocks, dEf / dEs the column sum of the shares,
+    then ONE wgrad and ONE dgrad GEMM on it; the residual's gradient is added to dx."""
+
+    @staticmethod
+    def forward(ctx, x, wf, bf, ws, bs, attr, graph, dim, mean, root):
+        C = x.shape[1]
+        blocks = (wf[:, :C], ws[:, :C], wf[:, C:2 * C], ws[:, C:2 * C])
+        xp, wp, buf, spans = _packed_gemm(x, blocks, (bf, bs, None, None))    # buf: Af | As | Bf | Bs | zero padding
+        a32 = eft = est = None
+        if dim > 0:
+            a32 = attr.detach().to(torch.float32).contiguous()    # (float64 attributes are rounded once)
+            eft = wf.detach()[:, 2 * C:].t().to(torch.float32).contiguous()
+            est = ws.detach()[:, 2 * C:].t().to(torch.float32).contiguous()
+        y = ops.cgate_fwd(graph, *(_cols(buf, sp) for sp in spans), attr=a32, ef=eft, es=est, root=xp[:, :C] if root else None,
+                          mean=mean)
+        ctx.save_for_backward(xp, wp, buf, a32, eft, est)
+        ctx.graph, ctx.spans, ctx.opts = graph, spans, (C, dim, mean, root)
+        return y
+
+    @staticmethod
+    def _backward(ctx, dy):
+        xp, wp, buf, a32, eft, est = ctx.saved_tensors
+        graph, spans, (C, dim, mean, root), need = ctx.graph, ctx.spans, ctx.opts, ctx.needs_input_grad
+        dy = dy.contiguous().to(torch.float32)
+        blocks = tuple(_cols(buf, sp) for sp in spans)
+        g = _grad_rows(dy.shape[0], spans, wp.shape[0], dy.device)             # [dAf | dAs | dBf | dBs | 0]
+        gaf, gas, gbf, gbs = (_cols(g, sp) for sp in spans)
+        want_e = dim > 0 and (need[1] or need[3])
+        _, _, parts = ops.cgate_bwd_row(graph, dy, *blocks, attr=a32, ef=eft, es=est, mean=mean, out_f=gaf, out_s=gas,
+                                        want_parts=want_e)
+        ops.cgate_bwd_node(graph, dy, *blocks, attr=a32, ef=eft, es=est, mean=mean, out_f=gbf, out_s=gbs)
+        dbf = _bias_grad(gaf) if need[2] else None
+        dbs = _bias_grad(gas) if need[4] else None
+        de = ops.gatv2_datt(parts, 2 * dim) if want_e else None                # [dEf^T ; dEs^T], [dim, C] each
+        dx, (dfi, dsi, dfj, dsj), _ = _packed_grads(g, xp, wp, spans, C, (need[1], need[3], need[1], need[3]), None, need[0])
+        dwf = dws = None
+        if need[1]:
+            dwf = torch.cat([dfi, dfj] + ([de[:dim].t()] if dim > 0 else []), 1)
+        if need[3]:
+            dws = torch.cat([dsi, dsj] + ([de[dim:].t()] if dim > 0 else []), 1)
+        if dx is not None and root:
+            dx = dx + dy
+        return dx, dwf, dbf, dws, dbs, None, None, None, None, None
+
+
+class CGConv(nn.Module):
+    """``torch_geometric.nn.CGConv`` 2.2.0 (Xie & Grossman, "Crystal Graph Convolutional Neural Networks", PRL 2018) on the HIP
+    kernels (restated from the published source from memory -- PyG cannot be installed here, so this could not be
+    checked against it; the pin is the float64 restatement ``tests/cg_ref.py``),
+    ``CGConv(channels, dim=0, aggr="add", batch_norm=False, bias=True)``, ``forward(x, edge_index, edge_attr=None)``.  It is the
+    one operator here in which a learned function of the edge attribute enters a per-channel nonlinearity, and it is
+    width-preserving and residual.
+
+    * parameters ``lin_f`` / ``lin_s``: ``weight`` [C, 2 C + dim] with the columns ``x_i | x_j | edge_attr`` and ``bias`` [C]
+      (registered as None with ``bias=False``), uniform(+-1/sqrt(2 C + dim)); ``bn``: a ``torch.nn.BatchNorm1d(C)`` with
+      ``batch_norm`` (same parameters, buffers and ``state_dict``; it normalises in float64 and rounds once), else None.
+    * for an edge j -> i with ``z = cat[x_i, x_j, e_ij]``: ``out_i = x_i + sum_{j -> i} sigmoid(lin_f(z)) * softplus(lin_s(z))``
+      (``aggr="mean"``: the sum divided by the number of edges into i); with ``batch_norm`` the sum goes through ``bn`` before
+      ``x_i`` is added, in PyG's order.  No self loops are added, an explicit loop is an ordinary edge, duplicate edges each count
+      with their own attributes, a node without incoming edges returns ``x_i`` (``bn`` of a zero row with ``batch_norm``).
+    * the launches: ``_CGConvFn``.  No [E, 2 C + dim] concatenation, no [E, C] pre-activation, gate or message and no
+      ``index_add_`` exist at any point, in the backward either: it recomputes both gates.  The graph is
+      ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=False)``, same handle and cache key as the other operators on it.
+      Symmetric edge STRUCTURE only.
+    * differentiable w.r.t. x and every parameter; float32, bitwise reproducible.
+    * refused with ``ValueError`` before any launch: tuple ``channels`` or a tuple ``x`` (bipartite), ``dim`` that is not an integer
+      in [0, ``ops.CG_MAX_DIM``], ``aggr`` other than ``"add"`` / ``"sum"`` / ``"mean"``, ``edge_attr`` missing with ``dim > 0``,
+      given with ``dim == 0``, not [E, dim], not float32 / float64 (float64 is rounded to float32 once) or requiring grad (the
+      gradient w.r.t. ``edge_attr`` is not implemented), bf16 features, CPU tensors, an ``x`` that is not [N, channels]."""
+
+    def __init__(self, channels, dim: int = 0, aggr: str = "add", batch_norm: bool = False, bias: bool = True, **kwargs):
+        super().__init__()
+        if isinstance(channels, (tuple, list)):
+            raise ValueError("CGConv: tuple channels (bipartite graphs) are not implemented on the HIP path")
+        _int_ge1("CGConv", "channels", channels)
+        if not isinstance(dim, int) or isinstance(dim, bool) or not 0 <= dim <= ops.CG_MAX_DIM:
+            raise ValueError("CGConv: dim must be an integer in [0, %d] on the HIP path, got %r" % (ops.CG_MAX_DIM, dim))
+        _check_aggr("CGConv", aggr, ("add", "sum", "mean"), kwargs)
+        self.channels, self.dim, self.aggr, self.batch_norm = channels, dim, aggr, bool(batch_norm)
+        self.lin_f = _LinB(2 * channels + dim, channels, bias=bias)
+        self.lin_s = _LinB(2 * channels + dim, channels, bias=bias)
+        # The lin biases' gradients sum dOut over ALL rows against weights of one sign (f (1 - f) s and f sigmoid(S) are positive),
+        # and a BatchNorm backward gives dOut a zero column sum: the terms cancel a hundred to one and more, and the float32
+        # BatchNorm's column means carry an error that is the same in every row and is collected N times over (measured: 1.6e-5 of
+        # lin_s.bias's gradient on a 1800-node graph).  So ``bn`` takes its statistics in float64, as GENConv's does (DESIGN.md 4.19).
+        self.bn = _BatchNorm1d64(channels) if batch_norm else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            _reset_linear(self.lin_f)
+            _reset_linear(self.lin_s)
+        if self.bn is not None:
+            self.bn.reset_parameters()
+
+    def forward(self, x, edge_index, edge_attr=None) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present); ``edge_attr``: [E, dim], float32
+        or float64 (rounded to float32 once), not requiring grad -- None with ``dim == 0``."""
+        _no_tuple_x("CGConv", x)
+        _check_x("CGConv", x, self.channels)
+        if self.dim == 0:
+            if edge_attr is not None:
+                raise ValueError("CGConv: edge_attr given but the layer was built with dim=0")
+        else:
+            if not isinstance(edge_attr, torch.Tensor):
+                raise ValueError("CGConv: edge_attr ([E, %d]) is required" % self.dim)
+            if edge_attr.dim() != 2 or tuple(edge_attr.shape) != (edge_index.shape[1], self.dim):
+                raise ValueError("CGConv: edge_attr must be [%d, %d], got %s" % (edge_index.shape[1], self.dim, tuple(edge_attr.shape)))
+            if edge_attr.dtype not in (torch.float32, torch.float64):
+                raise ValueError("CGConv: edge_attr must be float32 or float64, got %s" % edge_attr.dtype)
+            if edge_attr.requires_grad:
+                raise ValueError("CGConv: the gradient with respect to edge_attr is not implemented on the HIP path: pass "
+                                 "edge_attr.detach()")
+        _need_gpu("CGConv", x, edge_attr, exc=ValueError)
+        _need_entries("CGConv", edge_index)
+        with ops.on_device(x):
+            graph = ops.graph_for(edge_index, x.shape[0], norm="gat", add_self_loops=False)
+            out = _CGConvFn.apply(x, self.lin_f.weight, self.lin_f.bias, self.lin_s.weight, self.lin_s.bias, edge_attr, graph,
+                                  self.dim, self.aggr == "mean", self.bn is None)
+        return out if self.bn is None else self.bn(out) + x
+
+    def extra_repr(self):
+        return "%d, dim=%d, aggr=%s, batch_norm=%s" % (self.channels, self.dim, self.aggr, self.bn is not None)

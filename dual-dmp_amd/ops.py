@@ -1280,6 +1280,101 @@ def spline_bwd_node(g: Graph, dout, attr, kernel_size, is_open, C, mean=True, ou
     return dhf, dr
 
 
+# ---------------------------------------------------------------------------------------- crystal graph convolution
+CG_MAX_DIM = 8              # attribute coordinates per edge: the 2 dim float4 of Ef / Es of a column slab stay in registers
+
+
+def _cgate_operands(g, who, attr, ef, es, **mats):
+    """The operands every crystal-gate call shares -> (n, C, {name: (tensor, ld)}, attr, ef, es, dim): the [n, C] row blocks by
+    name (column blocks of one row buffer are fine), ``attr`` contiguous float32 [g.nnz_in, dim] and ``ef`` / ``es`` contiguous
+    float32 [dim, C] (the edge weights TRANSPOSED) -- or all three None: dim = 0, the entries count with their multiplicities."""
+    n, C, m = _head_mats(g, 1, who, **mats)
+    if attr is None:
+        if ef is not None or es is not None:
+            raise DdmpError("%s: ef / es without attr (dim == 0 takes neither)" % who)
+        return n, C, m, None, None, None, 0
+    _gmm_graph(g)
+    _chk(attr, torch.float32, "attr")
+    if attr.dim() != 2 or attr.shape[0] != g.nnz_in or not attr.is_contiguous() or not 1 <= attr.shape[1] <= CG_MAX_DIM:
+        raise DdmpError("attr must be a contiguous float32 [%d, dim] (one row per input edge) with dim in [1, %d], got %s"
+                        % (g.nnz_in, CG_MAX_DIM, tuple(attr.shape)))
+    dim = attr.shape[1]
+    return n, C, m, attr, _gat_arr(ef, (dim, C), "ef"), _gat_arr(es, (dim, C), "es"), dim
+
+
+def _cgate_key(g, C, dim):
+    return (C, dim, int(round(g.nnz / max(g.n_rows, 1))))
+
+
+def _cgate_graph_bytes(g, n, C, dim, mirror=False):
+    """col (+ mirror), rowptr and: the multiplicities (dim == 0) | ee_ptr, ee_idx, the attribute rows and Ef / Es (dim > 0)."""
+    b = (8.0 if mirror else 4.0) * g.nnz + 4.0 * (n + 1)
+    return b + (4.0 * g.nnz if dim == 0 else 4.0 * g.nnz + 4.0 * g.nnz_in * (dim + 1) + 8.0 * dim * C)
+
+
+def cgate_fwd(g: Graph, af, as_, bf, bs, attr=None, ef=None, es=None, root=None, mean=False, out=None):
+    """Two per-channel gates + gather in one launch (``ddmp_cgate_fwd_f32``) -> y [n, C]:
+    ``y[i] = root[i] + w_i sum_{t: j -> i} sigmoid(af[i] + bf[j] + ef^T a_t) * softplus(as_[i] + bs[j] + es^T a_t)``, ``w_i`` = 1 or
+    (``mean``) 1 / the number of input edges into i.  ``af`` / ``as_`` / ``bf`` / ``bs``: [n, C] (column blocks of one row buffer
+    are fine); ``attr``: contiguous float32 [g.nnz_in, dim] with ``ef`` / ``es`` [dim, C], or all None (dim = 0); ``root``: [n, C]
+    added per row, or None.  Nothing is kept per edge."""
+    mats = dict(af=af, as_=as_, bf=bf, bs=bs) if root is None else dict(af=af, as_=as_, bf=bf, bs=bs, root=root)
+    n, C, m, attr, ef, es, dim = _cgate_operands(g, "cgate_fwd", attr, ef, es, **mats)
+    (af, ldaf), (as_, ldas), (bf, ldbf), (bs, ldbs) = m["af"], m["as_"], m["bf"], m["bs"]
+    root, ldr = m.get("root", (None, 0))
+    out, ldy = _out(out, "out", n, C, af.device)
+    # algorithmic bytes: the four blocks (and the root) read once each, y written, the graph and the attributes
+    alg = (20.0 if root is None else 24.0) * n * C + _cgate_graph_bytes(g, n, C, dim)
+    with _timed("cgate_fwd", _cgate_key(g, C, dim), alg, (4.0 * dim + 30.0) * max(g.nnz, g.nnz_in) * C):
+        st = _lib.lib().ddmp_cgate_fwd_f32(g.handle, _p(af), ldaf, _p(as_), ldas, _p(bf), ldbf, _p(bs), ldbs, C, _p(attr), dim,
+                                           _p(ef), _p(es), _p(root), ldr, int(bool(mean)), _p(out), ldy, _stream())
+    check(st, "ddmp_cgate_fwd_f32")
+    return out
+
+
+def cgate_bwd_row(g: Graph, dout, af, as_, bf, bs, attr=None, ef=None, es=None, mean=False, out_f=None, out_s=None, want_parts=True):
+    """Row i's side of the backward (``ddmp_cgate_bwd_row_f32``) -> (daf, das [n, C] each, written completely, parts | None);
+    both gates are recomputed.  ``parts`` (dim > 0 and ``want_parts``): the rows' shares of the edge weights' gradient,
+    [n, 2 * dim * C]; their column sum (``gatv2_datt(parts, 2 * dim)``) is [def ; des], [dim, C] each.  ``out_f`` / ``out_s``: where
+    daf / das go (column blocks of a row buffer are fine)."""
+    n, C, m, attr, ef, es, dim = _cgate_operands(g, "cgate_bwd_row", attr, ef, es, dout=dout, af=af, as_=as_, bf=bf, bs=bs)
+    (dout, lddo), (af, ldaf), (as_, ldas), (bf, ldbf), (bs, ldbs) = m["dout"], m["af"], m["as_"], m["bf"], m["bs"]
+    out_f, lddaf = _out(out_f, "out_f", n, C, af.device)
+    out_s, lddas = _out(out_s, "out_s", n, C, af.device)
+    parts = torch.empty((n, 2 * dim * C), dtype=torch.float32, device=af.device) if dim > 0 and want_parts else None
+    # algorithmic bytes: dout and the four blocks read once each, daf and das (and the partials) written, the graph and the attributes
+    alg = 28.0 * n * C + (0.0 if parts is None else 8.0 * n * dim * C) + _cgate_graph_bytes(g, n, C, dim)
+    with _timed("cgate_bwd_row", _cgate_key(g, C, dim), alg, (8.0 * dim + 40.0) * max(g.nnz, g.nnz_in) * C):
+        st = _lib.lib().ddmp_cgate_bwd_row_f32(g.handle, _p(dout), lddo, _p(af), ldaf, _p(as_), ldas, _p(bf), ldbf, _p(bs), ldbs, C,
+                                               _p(attr), dim, _p(ef), _p(es), int(bool(mean)), _p(out_f), lddaf, _p(out_s), lddas,
+                                               _p(parts), _stream())
+    check(st, "ddmp_cgate_bwd_row_f32")
+    return out_f, out_s, parts
+
+
+def cgate_bwd_node(g: Graph, dout, af, as_, bf, bs, attr=None, ef=None, es=None, mean=False, out_f=None, out_s=None, out_r=None):
+    """Node j's side of the backward (``ddmp_cgate_bwd_node_f32``) -> (dbf, dbs) [n, C] each, written completely; both gates are
+    recomputed and the edges j -> i (or their count) are read through the mirror map.  ``out_f`` / ``out_s``: where they go;
+    ``out_r``: a [n, C] block that also receives a copy of ``dout`` (the root term's gradient), or None.  Column blocks of one row
+    buffer are fine."""
+    n, C, m, attr, ef, es, dim = _cgate_operands(g, "cgate_bwd_node", attr, ef, es, dout=dout, af=af, as_=as_, bf=bf, bs=bs)
+    (dout, lddo), (af, ldaf), (as_, ldas), (bf, ldbf), (bs, ldbs) = m["dout"], m["af"], m["as_"], m["bf"], m["bs"]
+    out_f, lddbf = _out(out_f, "out_f", n, C, af.device)
+    out_s, lddbs = _out(out_s, "out_s", n, C, af.device)
+    ldds = 0
+    if out_r is not None:
+        out_r, ldds = _out(out_r, "out_r", n, C, af.device)
+    # algorithmic bytes: dout and the four blocks read once each, dbf and dbs (and the root block) written, the graph (col + mirror)
+    # and the attributes
+    alg = (28.0 if out_r is None else 32.0) * n * C + _cgate_graph_bytes(g, n, C, dim, mirror=True)
+    with _timed("cgate_bwd_node", _cgate_key(g, C, dim), alg, (4.0 * dim + 40.0) * max(g.nnz, g.nnz_in) * C):
+        st = _lib.lib().ddmp_cgate_bwd_node_f32(g.handle, _p(dout), lddo, _p(af), ldaf, _p(as_), ldas, _p(bf), ldbf, _p(bs), ldbs, C,
+                                                _p(attr), dim, _p(ef), _p(es), int(bool(mean)), _p(out_f), lddbf, _p(out_s), lddbs,
+                                                _p(out_r), ldds, _stream())
+    check(st, "ddmp_cgate_bwd_node_f32")
+    return out_f, out_s
+
+
 # ---------------------------------------------------------------------------------------- max aggregation (DESIGN.md 4.10)
 def _gmax_arg(arg, n, C):
     _chk(arg, torch.int32, "arg")

@@ -531,6 +531,42 @@ int ddmp_gather_softmax_bwd_f32(const ddmp_graph* g, int C, const float* dOut, i
                                 int add_dout, float* dH, int64_t lddh, float* dR /*nullable*/, int64_t lddr,
                                 float* dt_rows /*nullable*/, ddmp_stream stream);
 
+/* ------------------------------------------------------------------ crystal graph convolution (torch_geometric CGConv; DESIGN.md
+ * 4.19): two per-channel gates on every input edge t: j -> i, each with a learned term in the edge's attributes a_t [dim]:
+ *   F_t = Af[i,:] + Bf[j,:] + Ef a_t,   S_t = As[i,:] + Bs[j,:] + Es a_t,   f = sigmoid(F_t),   s = softplus(S_t).
+ * float32.  Af, As, Bf, Bs: [n, C] with their own leading dimensions (column blocks of one row buffer).  dim in [0, 8].
+ * dim > 0: the graph of ddmp_graph_create_valued(flags = 0) left at all-ones values (an entry's input edges are its ee span, in
+ * input order: duplicate edges with different attributes are exact); attr: contiguous [input edges, dim] in the order of the edge
+ * list the graph was created from; EfT, EsT: the edge weights TRANSPOSED, contiguous [dim, C].  dim == 0: any attention graph; attr,
+ * EfT and EsT are null, an entry counts with its multiplicity and the ee tables are not read.  mean != 0: w_i = 1 / (the number
+ * of input edges into i) (1 for a row without any), else w_i = 1.  Nothing is stored per edge: the backward launches recompute
+ * both gates.  softplus keeps its relative accuracy for S -> -inf; no NaN and no Inf for any finite operand.  No output may alias an
+ * input or another output.  The vector kernels need C and every leading dimension % 4 == 0 and 16-byte aligned operands; anything
+ * else takes scalar kernels.  No atomics, fixed order: bitwise reproducible.
+ *
+ * forward:   Y[i,:] = root[i,:] + w_i sum_{t -> i} f (.) s  (root [n, C] nullable: zeros).  A row without entries gets root[i,:]
+ *            bit for bit.  One launch. */
+int ddmp_cgate_fwd_f32(const ddmp_graph* g, const float* Af, int64_t ldaf, const float* As, int64_t ldas, const float* Bf,
+                       int64_t ldbf, const float* Bs, int64_t ldbs, int C, const float* attr /*null iff dim == 0*/, int dim,
+                       const float* EfT /*null iff dim == 0*/, const float* EsT /*null iff dim == 0*/, const float* root /*nullable*/,
+                       int64_t ldr, int mean, float* Y, int64_t ldy, ddmp_stream stream);
+/* backward, row side, with dF_t = dOut[i,:] (.) s (.) f (1 - f) and dS_t = dOut[i,:] (.) f (.) sigmoid(S_t):
+ *            dAf[i,:] = w_i sum_{t -> i} dF_t,   dAs[i,:] = w_i sum_{t -> i} dS_t  (written completely) and, dim > 0 and P non-null,
+ *            the per-row partials P[i] = w_i [sum_t dF_t (x) a_t | sum_t dS_t (x) a_t], contiguous [n, 2, dim, C]: their column sum
+ *            is [dEfT | dEsT].  One launch. */
+int ddmp_cgate_bwd_row_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Af, int64_t ldaf, const float* As,
+                           int64_t ldas, const float* Bf, int64_t ldbf, const float* Bs, int64_t ldbs, int C,
+                           const float* attr /*null iff dim == 0*/, int dim, const float* EfT, const float* EsT, int mean, float* dAf,
+                           int64_t lddaf, float* dAs, int64_t lddas, float* P /*nullable*/, ddmp_stream stream);
+/* backward, node side (row j's own entries e' enumerate the targets i = col e' that j feeds -- the structure is symmetric -- and
+ *            the edges j -> i, or their count, are those of the mirrored entry):
+ *            dBf[j,:] = sum_{t: j -> i} w_i dF_t,   dBs[j,:] = sum_{t: j -> i} w_i dS_t  (written completely) and, dS non-null, the
+ *            root block's gradient dS[j,:] = dOut[j,:].  One launch. */
+int ddmp_cgate_bwd_node_f32(const ddmp_graph* g, const float* dOut, int64_t lddo, const float* Af, int64_t ldaf, const float* As,
+                            int64_t ldas, const float* Bf, int64_t ldbf, const float* Bs, int64_t ldbs, int C,
+                            const float* attr /*null iff dim == 0*/, int dim, const float* EfT, const float* EsT, int mean, float* dBf,
+                            int64_t lddbf, float* dBs, int64_t lddbs, float* dS /*nullable*/, int64_t ldds, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ dense steps (MFMA; float32 operands and results, the
  * arithmetic is ddmp_set_gemm_mode's: by default SPLIT-precision 16-bit MFMA products with f32 accumulation -- f32-class
  * accuracy, not bit-exact f32; mode 0 = f32-input MFMA, the strict one)

@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|spline|sage|pna|gen|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|spline|sage|pna|gen|cg|all] [--rows N] [--iters K]
+cg (not part of all): the crystal-gate launches (ops.cgate_fwd with the root block, cgate_bwd_row with and without the partials,
+cgate_bwd_node with the root block's gradient) at C = 64, 128 and dim = 0, 3 on the vertex graph of a torus with --rows
+vertices in RCB order, without loops, each alternating in one loop with the rgate_* launch of the same role at the same width; then
+the torch edge-list composition on the same inputs and its autograd backward; the figures, the algorithmic byte counts and each
+launch's achieved rate on them go to --out (profiles/cg_microbench.txt).
 gen (not part of all): the softmax-aggregation launches (ops.gather_softmax, ops.gather_softmax_bwd) at C = 32, 64, 128,
 256 on the same graph as sage, alternating in one loop: the forward (with and without the lse store) against the single-mean
 ops.gather_stats with root at the same width, and the backward launch against ops.gather_stats_bwd; the figures and the algorithmic
@@ -574,6 +579,84 @@ if a.what == "resgated":
         print("\n".join(lines[-(len(q) + 2):]), flush=True)
         del Ks, Qs, Vs, Ss, Ds, Out, Out2, Out3, st, kk, qq_, vv_, yt
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "resgated_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.what == "cg":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    g = ops.graph_for(ei, nn_, norm="gat", add_self_loops=False)
+    src, dst = ei[0], ei[1]
+    reps = max(a.iters, 20)
+    lines = ["crystal graph convolution (CGConv) on the vertex graph of torus(%d, %d) in RCB order: N=%d, entries=%d = input edges "
+             "(no loops, no duplicates), float32, aggr=add; median of %d launches [min q1 q3 max], one HIP-event pair per launch, forms "
+             "alternating in one loop, rotating buffer sets; bytes = the algorithmic counts of ops.py (MB); rgate_* = the residual-gate "
+             "launches at the same width on the same graph (two gathered streams, one gate: the in-tree yardstick); bwd_row-P = the "
+             "row side without the partials; torch = index_select x4, the attribute products, sigmoid, softplus, multiply, "
+             "index_add_ on the same inputs (forward) and its autograd backward, mean of 3 runs" % (nu_, nv_, nn_, g.nnz, reps)]
+    print(lines[0], flush=True)
+    for C in (64, 128):
+        for dim in (0, 3):
+            R = 2 if nn_ * C * 4 >= (1 << 29) else 4
+            Af, As, Bf, Bs, Rs, Ds = ([torch.randn(nn_, C, device=dev) for _ in range(R)] for _ in range(6))
+            bias = torch.randn(C, device=dev)
+            Out, Out2, Out3 = (torch.empty(nn_, C, device=dev) for _ in range(3))
+            attr = torch.randn(ei.shape[1], dim, device=dev) if dim else None
+            ef, es = (torch.randn(dim, C, device=dev) * 0.5 for _ in range(2)) if dim else (None, None)
+            kw = dict(attr=attr, ef=ef, es=es)
+            fns = {
+                "rgate_fwd": lambda i: ops.rgate_fwd(g, Af[i], Bf[i], Bs[i], skip=Rs[i], bias=bias, out=Out),
+                "fwd": lambda i: ops.cgate_fwd(g, Af[i], As[i], Bf[i], Bs[i], root=Rs[i], out=Out, **kw),
+                "rgate_bwd_row": lambda i: ops.rgate_bwd_row(g, Ds[i], Af[i], Bf[i], Bs[i], out=Out),
+                "bwd_row": lambda i: ops.cgate_bwd_row(g, Ds[i], Af[i], As[i], Bf[i], Bs[i], out_f=Out, out_s=Out2, **kw),
+                "rgate_bwd_node": lambda i: ops.rgate_bwd_node(g, Ds[i], Af[i], Bf[i], Bs[i], out_q=Out, out_v=Out2, out_s=Out3),
+                "bwd_node": lambda i: ops.cgate_bwd_node(g, Ds[i], Af[i], As[i], Bf[i], Bs[i], out_f=Out, out_s=Out2, out_r=Out3, **kw)}
+            if dim:
+                fns["bwd_row-P"] = lambda i: ops.cgate_bwd_row(g, Ds[i], Af[i], As[i], Bf[i], Bs[i], out_f=Out, out_s=Out2,
+                                                               want_parts=False, **kw)
+            q = alternate(fns, reps, R)
+            feat, ent, node = 4.0 * nn_ * C, 4.0 * g.nnz, 4.0 * nn_
+            gb = ent + node + (ent if dim == 0 else ent + ent * (dim + 1) + 8.0 * dim * C)    # ops._cgate_graph_bytes
+            alg = {"rgate_fwd": 5 * feat + 2 * ent + node, "fwd": 6 * feat + gb,
+                   "rgate_bwd_row": 5 * feat + 2 * ent + node, "bwd_row": (7 + 2 * dim) * feat + gb, "bwd_row-P": 7 * feat + gb,
+                   "rgate_bwd_node": 7 * feat + 3 * ent + node, "bwd_node": 8 * feat + gb + ent}
+            base = {"fwd": "rgate_fwd", "bwd_row": "rgate_bwd_row", "bwd_row-P": "rgate_bwd_row", "bwd_node": "rgate_bwd_node"}
+            lines.append("C=%d dim=%d (%d buffer sets):" % (C, dim, R))
+            for k in q:
+                tail = "  x%.2f of %s" % (q[k][2] / q[base[k]][2], base[k]) if k in base else ""
+                lines.append("  %-15s %s  %7.0f MB  %.2f TB/s alg = %4.1f%% of 8 TB/s%s" % (
+                    k, fmt(q[k]), alg[k] / 1e6, alg[k] / q[k][2] / 1e6, alg[k] / q[k][2] / 1e6 / 8.0 * 100.0, tail))
+            if dim:
+                lines.append("  the partials: %.0f us = %.0f%% of bwd_row for %.0f MB more" % (
+                    q["bwd_row"][2] - q["bwd_row-P"][2], 100.0 * (q["bwd_row"][2] - q["bwd_row-P"][2]) / q["bwd_row"][2],
+                    2 * dim * feat / 1e6))
+            # the torch edge-list composition on the same inputs, and its autograd backward
+            leaves = [t.clone().requires_grad_(True) for t in (Af[0], As[0], Bf[0], Bs[0])]
+
+            def torch_fwd():
+                pf = leaves[0].index_select(0, dst) + leaves[2].index_select(0, src)
+                ps = leaves[1].index_select(0, dst) + leaves[3].index_select(0, src)
+                if dim:
+                    pf, ps = pf + attr @ ef, ps + attr @ es
+                msg = torch.sigmoid(pf) * torch.nn.functional.softplus(ps)
+                return torch.zeros_like(leaves[0]).index_add_(0, dst, msg) + Rs[0]
+
+            t_f = timeit(lambda: torch_fwd().detach(), 3)
+            yt = torch_fwd()
+            t_b = timeit(lambda: torch.autograd.grad(yt, leaves, Ds[0], retain_graph=True), 3)
+            ours_b = q["bwd_row"][2] + q["bwd_node"][2]
+            err = float((ops.cgate_fwd(g, Af[0], As[0], Bf[0], Bs[0], root=Rs[0], **kw) - yt.detach()).norm() / yt.detach().norm())
+            lines.append("  torch forward %8.0f us = x%.1f of fwd;  torch backward %8.0f us = x%.1f of bwd_row + bwd_node (%.0f us);  "
+                         "rel-L2 fwd vs torch %.1e" % (t_f, t_f / q["fwd"][2], t_b, t_b / ours_b, ours_b, err))
+            print("\n".join(lines[-(len(q) + 2 + (1 if dim else 0)):]), flush=True)
+            del Af, As, Bf, Bs, Rs, Ds, Out, Out2, Out3, leaves, yt, attr, ef, es, kw, fns
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "cg_microbench.txt")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
 
