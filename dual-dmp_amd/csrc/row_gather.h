@@ -1,5 +1,5 @@
 // The row-gather work layout of the graph-operator kernels (sddmm.hip, gat.hip, gatv2.hip, tconv.hip, rgate.hip, feast.hip,
-// gmm.hip, gmax.hip, spline.hip, nstat.hip, pna.hip, gsoftmax.hip, cgate.hip; gather_mix.h, colsum_final.h):
+// gmm.hip, gmax.hip, spline.hip, nstat.hip, pna.hip, gsoftmax.hip, cgate.hip, ppf.hip; gather_mix.h, colsum_final.h):
 // the one place that fixes it.  (The SpMM files have their own variants of it; they do not include this header.)
 //   * a workgroup (4 waves) owns a chunk of kRB = 64 consecutive rows; blockIdx -> chunk is XCD-aware (block b runs on XCD b % 8,
 //     so XCD x takes the chunks x * chunks_per_xcd ..: the ~deg re-reads of a neighbour row by neighbouring output rows hit that

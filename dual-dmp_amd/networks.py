@@ -34,7 +34,11 @@ Two interchangeable forms, both taking the reference's ``Dataset`` object (field
     mixes the 8 of K^3 weight matrices its pseudo-coordinates select by a linear B-spline basis; parameters ``convN.weight``,
     ``convN.lin.weight``, ``convN.bias``); ``conv="gen"`` builds them from :class:`nn_ops.GENConv` with its defaults (DeeperGCN's
     layer: a per-channel softmax aggregation of ``relu(x_j) + eps``, a residual root term and a two-layer MLP; parameters
-    ``convN.lin_src.weight``, ``convN.lin_dst.weight``, ``convN.mlp.0.weight``, ``convN.msg_norm.scale`` ...).
+    ``convN.lin_src.weight``, ``convN.lin_dst.weight``, ``convN.mlp.0.weight``, ``convN.msg_norm.scale`` ...);
+    ``conv="ppf"`` (``NormalNet`` only: the vertex dataset carries no normals, ``PosNet`` raises) builds them from
+    :class:`nn_ops.PPFConv` over ``nn.Linear(in + 4, out)`` (PPFNet's layer: the maximum over the neighbourhood of a linear
+    function of the neighbour's features and the four point-pair features of the two oriented faces -- centroid ``z2[:, :3]``,
+    unit normal ``z2[:, 3:6]``; parameters ``convN.local_nn.weight``, ``convN.local_nn.bias``).
     The GMM and spline operators' pseudo-coordinates are the dataset's ``edge_attr`` (vertex graph) / ``face_attr`` (face graph) if any, else
     ``nn_ops.cartesian_pseudo`` of the smoothed vertex positions / the noisy face centroids, computed once and cached on the
     dataset.  The fused engine, the trainer, the CLI,
@@ -54,8 +58,8 @@ import torch.nn as nn
 
 from . import ops
 from .engine import ArenaLayout, GcnEngine, NORM_WIDTHS, POS_WIDTHS
-from .nn_ops import (ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv, GENConv, GMMConv, ResGatedGraphConv, SplineConv, TransformerConv,
-                     cartesian_pseudo)
+from .nn_ops import (ChebConv, EdgeConv, FeaStConv, GATConv, GCNConv, GENConv, GMMConv, PPFConv, ResGatedGraphConv, SplineConv,
+                     TransformerConv, cartesian_pseudo)
 
 
 class _EngineFn(torch.autograd.Function):
@@ -277,12 +281,13 @@ class NormalNetFused(_FusedNet):
 
 
 # -------------------------------------------------------------------------------- operator-level form
-_CONVS = ("gcn", "cheb", "gat", "feast", "edge", "gmm", "transformer", "resgated", "spline", "gen")
-_CONV_MSG = "conv must be 'gcn', 'cheb', 'gat', 'feast', 'edge', 'gmm', 'transformer', 'resgated', 'spline' or 'gen', got %r"
+_CONVS = ("gcn", "cheb", "gat", "feast", "edge", "gmm", "transformer", "resgated", "spline", "gen", "ppf")
+_CONV_MSG = "conv must be 'gcn', 'cheb', 'gat', 'feast', 'edge', 'gmm', 'transformer', 'resgated', 'spline', 'gen' or 'ppf', got %r"
 
 
 class _ModularNet(nn.Module):
     _widths = None
+    _oriented = False                                            # the net's dataset carries a unit normal per node
 
     def __init__(self, device, conv="gcn", K=3, heads=1):
         super().__init__()
@@ -290,6 +295,9 @@ class _ModularNet(nn.Module):
         h = self._widths
         if conv not in _CONVS:
             raise ValueError(_CONV_MSG % (conv,))
+        if conv == "ppf" and not self._oriented:
+            raise ValueError("conv='ppf' needs oriented points (a position and a unit normal per node): the vertex dataset carries "
+                             "no vertex normals -- PPFConv is available in NormalNet, on the face graph")
         if conv in ("gat", "transformer"):
             bad = [w for w in h[1:13] if not isinstance(heads, int) or heads < 1 or w % heads]
             if bad:
@@ -311,6 +319,8 @@ class _ModularNet(nn.Module):
                 layer = SplineConv(h[i], h[i + 1], dim=3, kernel_size=K)
             elif conv == "gen":
                 layer = GENConv(h[i], h[i + 1])
+            elif conv == "ppf":
+                layer = PPFConv(nn.Linear(h[i] + 4, h[i + 1]))
             else:
                 layer = GCNConv(h[i], h[i + 1]) if conv == "gcn" else ChebConv(h[i], h[i + 1], K)
             setattr(self, "conv%d" % (i + 1), layer)
@@ -335,10 +345,12 @@ class _ModularNet(nn.Module):
             cache[(name, str(self.device))] = hit
         return hit[2]
 
-    def _trunk(self, x, edge_index, edge_weight=None, pseudo=None):
+    def _trunk(self, x, edge_index, edge_weight=None, pseudo=None, oriented=None):
         for i in range(1, 13):
             conv = getattr(self, "conv%d" % i)
-            if pseudo is not None:
+            if oriented is not None:
+                y = conv(x, oriented[0], oriented[1], edge_index)
+            elif pseudo is not None:
                 y = conv(x, edge_index, pseudo)
             else:
                 y = conv(x, edge_index) if edge_weight is None else conv(x, edge_index, edge_weight)
@@ -374,6 +386,22 @@ class _ModularNet(nn.Module):
         return hit[3]
 
 
+    def _oriented_points(self, data, z2):
+        """``conv="ppf"`` (None for every other operator): the face centroids and unit normals ``z2[:, :3]``, ``z2[:, 3:6]`` as STABLE
+        detached views kept on the dataset like ``_dev``'s copies (they share ``z2``'s version counter): ``ops.ppf_entries`` caches
+        the features on the identity and version of the two tensors, so the twelve layers and every step share one evaluation."""
+        if self.conv_kind != "ppf":
+            return None
+        cache = data.__dict__.setdefault("_ddmp_dev", {})
+        key = ("oriented:z2", str(self.device))
+        hit = cache.get(key)
+        if hit is None or hit[0] is not z2:
+            base = z2.detach()
+            hit = (z2, base[:, :3], base[:, 3:6])
+            cache[key] = hit
+        return hit[1], hit[2]
+
+
 class PosNetModular(_ModularNet):
     _widths = POS_WIDTHS
 
@@ -386,10 +414,12 @@ class PosNetModular(_ModularNet):
 
 class NormalNetModular(_ModularNet):
     _widths = NORM_WIDTHS
+    _oriented = True                                             # z2 = [fc, fn, fa]
 
     def forward(self, data):
         z2, edge_index = self._dev(data, "z2"), self._dev(data, "face_index")
-        dx = self._trunk(z2, edge_index, self._weight(data, "face_weight"), self._pseudo(data, "face_attr", z2, edge_index, cols=3))
+        dx = self._trunk(z2, edge_index, self._weight(data, "face_weight"), self._pseudo(data, "face_attr", z2, edge_index, cols=3),
+                         self._oriented_points(data, z2))
         dx = torch.tanh(self.linear2(self.l_relu(self.linear1(dx))))
         dx_norm = torch.reciprocal(torch.norm(dx, dim=1, keepdim=True).expand(-1, 3) + 1.0e-12)
         return torch.mul(dx, dx_norm)

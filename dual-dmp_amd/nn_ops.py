@@ -1,8 +1,9 @@
-"""Drop-ins for fourteen ``torch_geometric.nn`` 2.2.0 operators on the HIP kernels: same constructor / call signature, parameter names
+"""Drop-ins for fifteen ``torch_geometric.nn`` 2.2.0 operators on the HIP kernels: same constructor / call signature, parameter names
 and initialisation; the dense part goes through the GEMMs, the graph part through one fused gather launch per direction, and no
 per-edge feature tensor exists at any point.  Each operator is documented once, at its class: ``GCNConv``, ``ChebConv``,
 ``GATConv``, ``GATv2Conv``, ``TransformerConv``, ``ResGatedGraphConv``, ``FeaStConv``, ``GMMConv`` (with ``cartesian_pseudo``),
-``SplineConv``, ``EdgeConv``, ``SAGEConv``, ``PNAConv`` (with ``degree_histogram``), ``GENConv``, ``CGConv``.
+``SplineConv``, ``EdgeConv``, ``PPFConv`` (with ``point_pair_features``), ``SAGEConv``, ``PNAConv`` (with ``degree_histogram``),
+``GENConv``, ``CGConv``.
 
 ``edge_weight`` (``GCNConv`` and ``ChebConv``; restated from the published PyG 2.2.0 source from memory -- PyG cannot be installed
 here, so this could not be checked against it; the pin is the dense float64 restatement ``tests/gcnw_ref.py``):
@@ -1345,23 +1346,27 @@ def _edge_conv(x, weight, bias, graph):
     return _EdgeConvFn.apply(x, weight, bias, graph, want)
 
 
-_EDGE_NN_MSG = ("EdgeConv: on the HIP path nn must be a torch.nn.Linear(2 * in, out), or a torch.nn.Sequential of one followed by ReLU, "
+_EDGE_NN_MSG = ("%s: on the HIP path %s must be a torch.nn.Linear(%s, out), or a torch.nn.Sequential of one followed by ReLU, "
                 "LeakyReLU(negative_slope >= 0) or Identity modules only (elementwise, non-decreasing, 0 -> 0: they commute with the "
                 "maximum); got %s")
 
 
-def _edge_nn(module):
-    """-> (the ``Linear`` of an accepted edge function, the elementwise modules behind it), or ``ValueError``."""
+def _edge_nn(module, who=("EdgeConv", "nn", "2 * in")):
+    """-> (the ``Linear`` of an accepted edge function, the elementwise modules behind it), or ``ValueError``.  ``who``: the
+    operator, its argument and the ``Linear``'s input width, for the message (EdgeConv: an even width; PPFConv: at least 4)."""
     lin, rest = module, []
     if isinstance(module, nn.Sequential) and len(module) > 0:
         lin, rest = module[0], list(module)[1:]
     if type(lin) is not nn.Linear or lin.weight.dtype != torch.float32:
-        raise ValueError(_EDGE_NN_MSG % (module,))
-    if lin.in_features % 2:
+        raise ValueError(_EDGE_NN_MSG % (who + (module,)))
+    if who[0] == "EdgeConv" and lin.in_features % 2:
         raise ValueError("EdgeConv: the Linear takes cat[x_i, x_j - x_i], so its in_features must be even, got %d" % lin.in_features)
+    if who[0] == "PPFConv" and lin.in_features < 4:
+        raise ValueError("PPFConv: the Linear takes cat[x_j, f_ij] with four point-pair features, so its in_features must be >= 4, "
+                         "got %d" % lin.in_features)
     for m in rest:
         if not (type(m) in (nn.ReLU, nn.Identity) or (type(m) is nn.LeakyReLU and m.negative_slope >= 0)):
-            raise ValueError(_EDGE_NN_MSG % (module,))
+            raise ValueError(_EDGE_NN_MSG % (who + (module,)))
     return lin, rest
 
 
@@ -1425,6 +1430,180 @@ class EdgeConv(nn.Module):
 
     def extra_repr(self):
         return "aggr=%s" % self.aggr
+
+
+def point_pair_features(pos: torch.Tensor, normal: torch.Tensor, edge_index: torch.Tensor) -> torch.Tensor:
+    """The four rigid-motion-invariant point-pair features of PyG's ``PointPairFeatures`` transform in plain torch (any device; not
+    on the hot path), one row per INPUT edge, in ``PPFConv``'s orientation -- ``edge_index[0] = j`` the source, ``edge_index[1] = i``
+    the target: ``d = pos[j] - pos[i]``, ``[|d|, angle(n_i, d), angle(n_j, d), angle(n_i, n_j)]`` with ``angle(a, b) =
+    atan2(|a x b|, a . b)`` -> [E, 4].  Usable as ``edge_attr`` of ``GMMConv`` / ``CGConv`` (``dim=4``)."""
+    j, i = edge_index[0], edge_index[1]
+    d = pos[j] - pos[i]
+    ni, nj = normal[i], normal[j]
+    angle = lambda a, b: torch.atan2(torch.cross(a, b, dim=1).norm(dim=1), (a * b).sum(1))
+    return torch.stack([d.norm(dim=1), angle(ni, d), angle(nj, d), angle(ni, nj)], 1)
+
+
+class _PPFConvFn(_Fn):
+    """With ``W = [Wx | Wp]`` ([out, in + 4]): ONE GEMM gives ``B = x Wx^T + b`` (none when ``x`` is None: the message is
+    ``Wp f``), then ONE launch takes the per-column maximum of ``B[j] + F[e] Wp^T`` over the entries and who won
+    (``ops.gather_max_attr`` with ``E = Wp^T``).  Saved: the padded x, the packed weight, arg [N, out] and F [entries, 4] -- not the
+    row buffer and nothing out-wide per edge.  Backward: ONE launch writes dB and the 8-row partials of dE
+    (``ops.gather_max_attr_bwd``), ``dWp = gatv2_datt(parts, 4)^T``, ``db = colsum(dB)`` (every non-empty output lands on exactly
+    one winner), ONE wgrad GEMM (dWx) and ONE dgrad GEMM (dx).  ``want_arg``: whether a backward can follow (``_ppf_conv``)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, f, graph, want_arg):
+        C, cin = weight.shape[0], weight.shape[1] - 4
+        w = weight.detach()
+        e = w[:, cin:].t().contiguous()                          # [4, out]
+        xp = wp = b = spans = None
+        if x is not None:
+            xp, wp, buf, spans = _packed_gemm(x, (w[:, :cin],), (bias,))   # buf [N, out rounded up to 4]: B | zero padding
+            b = _cols(buf, spans[0])
+        want = bool(want_arg) and any(ctx.needs_input_grad[:3])
+        y, arg = ops.gather_max_attr(graph, b, f, e, want_arg=want)
+        ctx.save_for_backward(xp, wp, arg, f)
+        ctx.graph, ctx.spans, ctx.dims = graph, spans, (cin, C)
+        return y
+
+    @staticmethod
+    def _backward(ctx, dy):
+        xp, wp, arg, f = ctx.saved_tensors
+        need, (cin, C) = ctx.needs_input_grad, ctx.dims
+        dy = dy.contiguous().to(torch.float32)
+        g = out = None
+        if xp is not None:
+            g = _grad_rows(dy.shape[0], ctx.spans, wp.shape[0], dy.device)
+            out = _cols(g, ctx.spans[0])                         # g = [dB | 0]
+        db_rows, parts = ops.gather_max_attr_bwd(ctx.graph, dy, arg, f, out=out, want_parts=need[1])
+        dwp = ops.gatv2_datt(parts, 4).t() if need[1] else None  # [out, 4]
+        db = _bias_grad(db_rows) if need[2] else None
+        dx = dw = None
+        if xp is not None:
+            dx, (dwx,), _ = _packed_grads(g, xp, wp, ctx.spans, cin, (need[1],), None, need[0])
+            dw = torch.cat([dwx, dwp], 1) if need[1] else None
+        elif need[1]:
+            dw = dwp.contiguous()
+        return dx, dw, db, None, None, None
+
+
+def _ppf_conv(x, weight, bias, f, graph):
+    want = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias))
+    return _PPFConvFn.apply(x, weight, bias, f, graph, want)
+
+
+_PPF_NN = ("PPFConv", "local_nn", "in + 4")
+
+
+def _ppf_geometry(name, t, n):
+    if isinstance(t, (tuple, list)):
+        raise ValueError("PPFConv: a tuple %s (bipartite graphs) is not implemented on the HIP path" % name)
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3 or (n is not None and t.shape[0] != n):
+        raise ValueError("PPFConv: %s must be a tensor of shape [N, 3], got %s" % (name, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__))
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError("PPFConv: %s must be float32 or float64, got %s" % (name, t.dtype))
+    if t.requires_grad:
+        raise ValueError("PPFConv: the gradient with respect to %s is not implemented on the HIP path: pass %s.detach()" % (name, name))
+
+
+class PPFConv(nn.Module):
+    """``torch_geometric.nn.PPFConv`` 2.2.0 (Deng et al., PPFNet, CVPR 2018) on the HIP kernels,
+    ``PPFConv(local_nn=None, global_nn=None, add_self_loops=True)``, ``forward(x, pos, normal, edge_index)`` (written from the
+    published source from memory -- PyG cannot be installed here, so this could not be checked against it; the pin is the float64
+    restatement ``tests/ppf_ref.py``):
+
+    * ``out[i] = global_nn(max over the edges j -> i of local_nn(cat[x_j, f_ij]))`` with the point-pair features
+      ``f_ij = [|d|, angle(n_i, d), angle(n_j, d), angle(n_i, n_j)]``, ``d = pos_j - pos_i``, ``angle(a, b) = atan2(|a x b|, a . b)``
+      (``point_pair_features``).  ``x`` may be None: the message is ``local_nn(f_ij)``.  With ``add_self_loops`` explicit loops are
+      removed and every node gets exactly one loop, whose features are 0; without it an explicit loop is an ordinary edge (its
+      features are 0 too), and a node without incoming edges gets ``global_nn(0)``.  A duplicate edge changes nothing.
+    * accepted ``local_nn``: a float32 ``torch.nn.Linear(in + 4, out)`` with or without bias, or a ``torch.nn.Sequential`` whose
+      first module is one and whose other modules are all ``ReLU``, ``LeakyReLU(negative_slope >= 0)`` or ``Identity`` (EdgeConv's
+      rule: they commute with the maximum bit for bit and keep an empty neighbourhood at 0, and run as torch modules after the
+      fused core).  It is kept as given under ``self.local_nn``: ``state_dict()`` has PyG's keys (``local_nn.weight`` or
+      ``local_nn.0.weight`` ..., ``global_nn.*``) and ``parameters()`` are the user's own tensors.  ``global_nn``: any module or
+      None; torch runs it on the result.
+    * with ``W = [Wx | Wp]``: ``W [x_j ; f_ij] + b = B[j] + Wp f_ij``, ``B = x Wx^T + b``: one GEMM, one launch for the maximum and
+      its winner (``ops.gather_max_attr``), one launch for the graph part of the backward (``ops.gather_max_attr_bwd``), the column
+      sum of its 8-row partials for ``dWp``, one wgrad and one dgrad GEMM.  The features of the coalesced entries come from ONE
+      launch (``ops.ppf_entries``) cached on the graph by the identity and version of ``pos`` and ``normal``: keep the tensors
+      (float64 geometry is rounded to float32 once per call, which defeats that cache).  No [E, out] tensor exists at any point.
+      The graph is GATConv's: ``ops.graph_for(edge_index, N, norm="gat", add_self_loops=...)``.  Symmetric edge STRUCTURE only.
+    * differentiable w.r.t. x and the ``Linear``'s weight and bias, NOT w.r.t. ``pos`` / ``normal`` (refused when they require
+      grad); float32, bitwise reproducible.  Deviation: with exact ties PyG's winner is unspecified, ours is the smallest source id.
+    * refused with ``ValueError`` before any launch: ``local_nn=None`` (the raw ``cat[x_j, f_ij]`` maximum), any other
+      ``local_nn``, ``aggr != "max"``, tuple ``x`` / ``pos`` / ``normal`` (bipartite), bf16 features, ``pos`` / ``normal`` that are
+      not [N, 3] float32 / float64 or require grad, an ``x`` whose width is not ``in``, CPU tensors."""
+
+    def __init__(self, local_nn=None, global_nn=None, add_self_loops: bool = True, **kwargs):
+        super().__init__()
+        _check_aggr("PPFConv", kwargs.pop("aggr", "max"), ("max",), kwargs)
+        if local_nn is None:
+            raise ValueError("PPFConv: local_nn=None (the maximum of the raw cat[x_j, f_ij]) is not implemented on the HIP path: "
+                             "pass a torch.nn.Linear(in + 4, out)")
+        lin, _ = _edge_nn(local_nn, _PPF_NN)
+        self.aggr = "max"
+        self.in_channels, self.out_channels = lin.in_features - 4, lin.out_features
+        self.local_nn = local_nn                                 # kept as given: PyG's state_dict keys, the user's own parameters
+        self.global_nn = global_nn
+        self.add_self_loops = bool(add_self_loops)
+
+    def reset_parameters(self):
+        for top in (self.local_nn, self.global_nn):
+            if top is None:
+                continue
+            for m in top.modules():
+                if hasattr(m, "reset_parameters"):
+                    m.reset_parameters()
+
+    def forward(self, x, pos, normal, edge_index) -> torch.Tensor:
+        """``edge_index`` must have a symmetric structure (both directions of every edge present); ``x``: [N, in] or None;
+        ``pos``, ``normal``: [N, 3], float32 or float64 (rounded to float32 once), not requiring grad."""
+        _no_tuple_x("PPFConv", x)
+        _ppf_geometry("pos", pos, None)
+        _ppf_geometry("normal", normal, pos.shape[0])
+        lin, _ = _edge_nn(self.local_nn, _PPF_NN)                # (the module is the user's: it may have been edited since)
+        if x is None:
+            if self.in_channels != 0:
+                raise ValueError("PPFConv: x=None needs a local_nn of in_features 4, got %d: expected x of shape [N, %d]"
+                                 % (lin.in_features, self.in_channels))
+        else:
+            _check_x("PPFConv", x, self.in_channels)
+            if self.in_channels == 0 or x.shape[0] != pos.shape[0]:
+                raise ValueError("PPFConv: expected x of shape [%d, %d] (None for a local_nn of in_features 4), got %s"
+                                 % (pos.shape[0], self.in_channels, tuple(x.shape)))
+        for t in (x, pos, normal):
+            if t is not None:
+                _need_gpu("PPFConv", t, exc=ValueError)
+        _need_entries("PPFConv", edge_index, loops=self.add_self_loops)
+        return self._core(x, pos, normal, edge_index)
+
+    def _core(self, x, pos, normal, edge_index):
+        lin, rest = _edge_nn(self.local_nn, _PPF_NN)
+        n = pos.shape[0]
+        with ops.on_device(pos):
+            graph = ops.graph_for(edge_index, n, norm="gat", add_self_loops=self.add_self_loops)
+            with torch.no_grad():
+                f = ops.ppf_entries(graph, pos if pos.dtype == torch.float32 else pos.to(torch.float32),
+                                    normal if normal.dtype == torch.float32 else normal.to(torch.float32))
+            if x is not None:
+                y = _ppf_conv(x, lin.weight, lin.bias, f, graph)
+            else:
+                y = _ppf_conv(None, lin.weight, None, f, graph)
+                if lin.bias is not None:                         # after the launch; an empty neighbourhood stays 0
+                    if self.add_self_loops:
+                        y = y + lin.bias
+                    else:
+                        has = torch.zeros(n, dtype=torch.bool, device=y.device)
+                        has[edge_index[1]] = True
+                        y = torch.where(has.unsqueeze(1), y + lin.bias, y)
+        for m in rest:
+            y = m(y)
+        return y if self.global_nn is None else self.global_nn(y)
+
+    def extra_repr(self):
+        return "add_self_loops=%s" % self.add_self_loops
 
 
 _SAGE_AGGRS = ("mean", "add", "sum", "max", "min")

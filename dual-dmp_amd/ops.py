@@ -1433,6 +1433,92 @@ def gather_max_bwd(g: Graph, dg, arg, out=None):
     return da, db
 
 
+# ---------------------------------------------------------------------------------------- max aggregation of an edge-conditioned
+# message over point-pair features
+def ppf_entries(g: Graph, pos, normal):
+    """Point-pair features of the COALESCED entries in one launch (``ddmp_ppf_entries_f32``) -> F float32 [g.nnz, 4]:
+    ``F[e] = [|d|, angle(n_i, d), angle(n_j, d), angle(n_i, n_j)]`` for the entry e = (i, j = col e), ``d = pos[j] - pos[i]``,
+    ``angle(a, b) = atan2(|a x b|, a . b)``; a loop entry is exactly 0.  ``pos``, ``normal``: float32 [n, 3] (column blocks of a
+    wider row buffer are fine).  The result is cached on ``g`` by the identity and ``_version`` of the two tensors (weak
+    references, like ``graph_for``): every layer of a net and every training step share one evaluation -- keep the tensors."""
+    _gat_graph(g)
+    hit = getattr(g, "_ppf", None)
+    if (hit is not None and hit[0]() is pos and hit[1]() is normal and isinstance(pos, torch.Tensor) and isinstance(normal, torch.Tensor)
+            and hit[2] == (pos._version, normal._version)):
+        return hit[3]
+    n = g.n_rows
+    pos, ldp = _rows(pos, "pos", n, 3)
+    normal, ldn = _rows(normal, "normal", n, 3)
+    if pos.shape[0] != n or normal.shape[0] != n:
+        raise DdmpError("pos and normal must be [%d, 3], got %s and %s" % (n, tuple(pos.shape), tuple(normal.shape)))
+    f = torch.empty((g.nnz, 4), dtype=torch.float32, device=pos.device)
+    # algorithmic bytes: pos and normal read once, F written, col + mirror
+    with _timed("ppf_entries", (int(round(g.nnz / max(n, 1))),), 24.0 * n + 24.0 * g.nnz, 90.0 * g.nnz):
+        st = _lib.lib().ddmp_ppf_entries_f32(g.handle, _p(pos), ldp, _p(normal), ldn, _p(f), _stream())
+    check(st, "ddmp_ppf_entries_f32")
+    g._ppf = (weakref.ref(pos), weakref.ref(normal), (pos._version, normal._version), f)
+    return f
+
+
+def _ppf_f(g, f):
+    _chk(f, torch.float32, "f")
+    if f.dim() != 2 or tuple(f.shape) != (g.nnz, 4) or not f.is_contiguous():
+        raise DdmpError("f must be a contiguous float32 [%d, 4] (one row per coalesced entry: ops.ppf_entries), got %s"
+                        % (g.nnz, tuple(f.shape)))
+    return f
+
+
+def gather_max_attr(g: Graph, b, f, e, out=None, want_arg=True):
+    """Arg-max gather of an edge-conditioned message in one launch (``ddmp_gather_max_attr_f32``) -> (y [n, C], arg int32 [n, C]
+    | None): ``y[i, c] = max_{entry t in row i} (b[col t, c] + sum_d f[t, d] e[d, c])``, ``arg[i, c]`` the source node id of the
+    winning entry (ties: the smallest id).  A row without entries gets y = 0 and arg = -1.  ``b``: [n, C] (a column block of a
+    row buffer is fine) or None = 0; ``f``: contiguous [g.nnz, 4] (``ppf_entries``); ``e``: contiguous [4, C] (the edge weights
+    TRANSPOSED); ``want_arg=False`` skips the store of ``arg`` (a forward without a backward)."""
+    _gat_graph(g)
+    n = g.n_rows
+    f = _ppf_f(g, f)
+    _chk(e, torch.float32, "e")
+    if e.dim() != 2 or e.shape[0] != 4 or e.shape[1] < 1 or not e.is_contiguous():
+        raise DdmpError("e must be a contiguous float32 [4, C], got %s" % (tuple(e.shape),))
+    C = e.shape[1]
+    ldb = 0
+    if b is not None:
+        b, ldb = _rows(b, "b", n, C)
+    out, ldy = _out(out, "out", n, C, f.device)
+    arg, ldg = None, 0
+    if want_arg:
+        arg, ldg = _gmax_arg(torch.empty((n, C), dtype=torch.int32, device=f.device), n, C)
+    # algorithmic bytes: every gathered row read once, y (and arg) written, F, E, col, rowptr
+    nb = (1 if b is not None else 0) + 1 + (1 if want_arg else 0)
+    alg = 4.0 * n * C * nb + 20.0 * g.nnz + 16.0 * C + 4.0 * (n + 1)
+    with _timed("gather_max_attr", (C, int(round(g.nnz / max(n, 1)))), alg, 9.0 * g.nnz * C):
+        st = _lib.lib().ddmp_gather_max_attr_f32(g.handle, _p(b), ldb, _p(f), _p(e), C, _p(out), ldy, _p(arg), ldg, _stream())
+    check(st, "ddmp_gather_max_attr_f32")
+    return out, arg
+
+
+def gather_max_attr_bwd(g: Graph, dg, arg, f, out=None, want_parts=True):
+    """Backward of ``gather_max_attr`` in ONE launch (``ddmp_gather_max_attr_bwd_f32``) -> (dB [n, C], parts | None):
+    ``dB[j, c] = sum_{e' in row j} (arg[col e', c] == j ? dg[col e', c] : 0)``; ``parts`` (``want_parts``): float32
+    [ceil(n / 8), 4 * C], the shares of ``dE[d, c] = sum_i dg[i, c] f[entry(i, arg[i, c]), d]`` of every 8 consecutive rows -- their
+    column sum ``gatv2_datt(parts, 4)`` is dE [4, C].  ``out``: where dB goes (a column block of a row buffer is fine)."""
+    _gat_graph(g)
+    n = g.n_rows
+    dg, lddg = _rows(dg, "dg", n)
+    C = dg.shape[1]
+    arg, ldg = _gmax_arg(arg, n, C)
+    f = _ppf_f(g, f)
+    out, lddb = _out(out, "out", n, C, dg.device)
+    parts = torch.empty(((n + 7) // 8, 4 * C), dtype=torch.float32, device=dg.device) if want_parts else None
+    # algorithmic bytes: dg and arg read once each, dB (and the partials) written, F, col, rowptr
+    alg = 12.0 * n * C + (2.0 * n * C if want_parts else 0.0) + (20.0 if want_parts else 4.0) * g.nnz + 4.0 * (n + 1)
+    with _timed("gather_max_attr_bwd", (C, int(round(g.nnz / max(n, 1)))), alg, (5.0 if want_parts else 1.0) * g.nnz * C):
+        st = _lib.lib().ddmp_gather_max_attr_bwd_f32(g.handle, _p(dg), lddg, _p(arg), ldg, _p(f), C, _p(out), lddb, _p(parts),
+                                                     _stream())
+    check(st, "ddmp_gather_max_attr_bwd_f32")
+    return out, parts
+
+
 # ---------------------------------------------------------------------------------------- neighbour statistics and moments
 # (DESIGN.md 4.16, 4.17.)  Written once for both operators: the ``want`` validation, the (pointer, leading dimension) table of
 # the forward's blocks and args, and the backward's operand table with its refusals.

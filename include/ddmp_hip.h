@@ -419,6 +419,30 @@ int ddmp_gather_max_f32(const ddmp_graph* g, const float* B, int64_t ldb, const 
 int ddmp_gather_max_bwd_f32(const ddmp_graph* g, const float* dG, int64_t lddg, const int32_t* arg, int64_t ldarg, int C, float* dA,
                             int64_t ldda, float* dB, int64_t lddb, ddmp_stream stream);
 
+/* ------------------------------------------------------------------ max aggregation of an edge-conditioned message
+ * (torch_geometric PPFConv with a Linear local_nn).  float32.  The graph is the attention graph above (a VALUED graph
+ * with its mirror map); an unvalued graph is DDMP_EINVAL.  No atomics, no LDS, fixed orders: two calls give the same bits.  The
+ * vector kernels need C % 4 == 0, leading dimensions % 4 == 0 and 16-byte aligned matrices; anything else takes scalar kernels.
+ *
+ * features:  F[e,:] = [ |d|, angle(n_i, d), angle(n_j, d), angle(n_i, n_j) ] for every COALESCED entry e = (i, j = col e), with
+ *            d = pos[j] - pos[i] and angle(a, b) = atan2(|a x b|, a . b); the cross products are compensated differences of
+ *            products.  An entry with j == i gets exactly 0.  pos, normal: [n, 3] with leading dimensions ldp, ldn >= 3; F:
+ *            contiguous [entries, 4], 16-byte aligned.  One thread per entry, one launch. */
+int ddmp_ppf_entries_f32(const ddmp_graph* g, const float* pos, int64_t ldp, const float* normal, int64_t ldn, float* F,
+                         ddmp_stream stream);
+/* forward:   Y[i,c] = max_{e in row i} (B[col e, c] + sum_d F[e,d] E[d,c]) (B nullable: 0; E: contiguous [4, C]), arg[i,c] = col e
+ *            of the winning entry (int32 [n, C]; nullable: not stored).  The message is fma(F3, E3, fma(F2, E2, fma(F1, E1,
+ *            F0 * E0))) + B, in that order.  Ties go to the first entry in CSR order (strict > from the row's first entry).  A row
+ *            without entries gets Y = 0 and arg = -1.  One launch. */
+int ddmp_gather_max_attr_f32(const ddmp_graph* g, const float* B /*nullable*/, int64_t ldb, const float* F, const float* E, int C,
+                             float* Y, int64_t ldy, int32_t* arg /*nullable*/, int64_t ldarg, ddmp_stream stream);
+/* backward:  dB[j,c] = sum_{e' in row j} (arg[col e', c] == j ? dG[col e', c] : 0) in CSR order (the structure is symmetric, as
+ *            for ddmp_gather_max_bwd_f32) and, P non-null, the shares of dE[d,c] = sum_i dG[i,c] F[entry(i, arg[i,c]), d] of every
+ *            8 consecutive rows: P contiguous [ceil(n / 8), 4, C]; its column sum (ddmp_gatv2_datt_f32 with heads = 4) is dE.
+ *            One launch. */
+int ddmp_gather_max_attr_bwd_f32(const ddmp_graph* g, const float* dG, int64_t lddg, const int32_t* arg, int64_t ldarg,
+                                 const float* F, int C, float* dB, int64_t lddb, float* P /*nullable*/, ddmp_stream stream);
+
 /* ------------------------------------------------------------------ neighbour statistics (torch_geometric SAGEConv with mean, add,
  * max and min aggregation, one of them or several at once).  float32.  The graph is the one of the Gaussian-mixture
  * kernels: the attention graph created with flags 0 (no loop handling, so a_e is the number of input edges of entry e) and left at

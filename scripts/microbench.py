@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Kernel micro-benchmarks at bench scale (HIP-event timing); also the target of rocprofv3 --pmc runs.
-usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|spline|sage|pna|gen|cg|all] [--rows N] [--iters K]
+usage: microbench.py [gemm|spmm|bn|hd|cheb|sddmm|gat|gatv2|transformer|resgated|feast|edge|gmm|spline|sage|pna|gen|cg|ppf|all] [--rows N] [--iters K]
+ppf (not part of all): the point-pair launches (ops.ppf_entries on its own; ops.gather_max_attr with and without the winners' store,
+ops.gather_max_attr_bwd with and without the 8-row partials, the gatv2_datt column sum of the partials) at C = 64, 128
+on the vertex graph of a torus with --rows vertices in RCB order with one loop per node, alternating in one loop with
+ops.gather_max / ops.gather_max_bwd at the same width; the figures, the algorithmic byte counts and the size of the partials go to
+--out (profiles/ppf_microbench.txt).
 cg (not part of all): the crystal-gate launches (ops.cgate_fwd with the root block, cgate_bwd_row with and without the partials,
 cgate_bwd_node with the root block's gradient) at C = 64, 128 and dim = 0, 3 on the vertex graph of a torus with --rows
 vertices in RCB order, without loops, each alternating in one loop with the rgate_* launch of the same role at the same width; then
@@ -657,6 +662,73 @@ if a.what == "cg":
             print("\n".join(lines[-(len(q) + 2 + (1 if dim else 0)):]), flush=True)
             del Af, As, Bf, Bs, Rs, Ds, Out, Out2, Out3, leaves, yt, attr, ef, es, kw, fns
     out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "cg_microbench.txt")
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if a.what == "ppf":
+    nu_ = int(round(n ** 0.5)); nv_ = n // nu_
+    v, f = synth.rcb_relabel(*synth.torus(nu_, nv_))
+    nn_ = len(v)
+    f64 = np.asarray(f, dtype=np.int64)
+    e = np.concatenate([f64[:, [0, 1]], f64[:, [1, 2]], f64[:, [2, 0]]])
+    key = np.unique(np.concatenate([e[:, 0] * nn_ + e[:, 1], e[:, 1] * nn_ + e[:, 0]]))
+    ei = torch.from_numpy(np.stack([key // nn_, key % nn_])).contiguous().to(dev)
+    g = ops.graph_for(ei, nn_, norm="gat")
+    reps = max(a.iters, 20)
+    lines = ["point-pair-feature convolution (PPFConv) on the vertex graph of torus(%d, %d) in RCB order with one loop per node: N=%d, "
+             "entries=%d, float32; median of %d launches [min q1 q3 max], one HIP-event pair per launch, forms alternating in one loop, "
+             "rotating buffer sets; bytes = the algorithmic counts of ops.py (MB); gather_max / gather_max_bwd = the arg-max gather "
+             "without an edge term at the same width on the same graph (the in-tree yardstick; its backward also writes the dA "
+             "copy); fwd-arg = without the winners' store; bwd-P = without the partials" % (nu_, nv_, nn_, g.nnz, reps)]
+    print(lines[0], flush=True)
+    pos = torch.tensor(np.asarray(v), dtype=torch.float32, device=dev)
+    nrm = torch.randn(nn_, 3, device=dev)
+    nrm = nrm / nrm.norm(dim=1, keepdim=True)
+    P2 = [pos.clone() for _ in range(2)]
+
+    def entries(i):
+        g._ppf = None                                            # (defeat the cache: time the launch)
+        return ops.ppf_entries(g, P2[i], nrm)
+
+    q = alternate({"ppf_entries": entries}, reps, 2)
+    alg_e = 24.0 * nn_ + 24.0 * g.nnz
+    lines.append("ppf_entries        %s  %7.0f MB  %.2f TB/s alg" % (fmt(q["ppf_entries"]), alg_e / 1e6, alg_e / q["ppf_entries"][2] / 1e6))
+    print(lines[-1], flush=True)
+    F = ops.ppf_entries(g, pos, nrm)
+    for C in (64, 128):
+        R = 2 if nn_ * C * 4 >= (1 << 29) else 4
+        B, Ds = ([torch.randn(nn_, C, device=dev) for _ in range(R)] for _ in range(2))
+        E = torch.randn(4, C, device=dev) * 0.5
+        Out = torch.empty(nn_, C, device=dev)
+        Out2 = torch.empty(nn_, 2 * C, device=dev)
+        _, arg = ops.gather_max_attr(g, B[0], F, E)
+        fns = {
+            "gather_max": lambda i: ops.gather_max(g, B[i], out=Out),
+            "fwd": lambda i: ops.gather_max_attr(g, B[i], F, E, out=Out),
+            "fwd-arg": lambda i: ops.gather_max_attr(g, B[i], F, E, out=Out, want_arg=False),
+            "gather_max_bwd": lambda i: ops.gather_max_bwd(g, Ds[i], arg, out=Out2),
+            "bwd": lambda i: ops.gather_max_attr_bwd(g, Ds[i], arg, F, out=Out),
+            "bwd-P": lambda i: ops.gather_max_attr_bwd(g, Ds[i], arg, F, out=Out, want_parts=False)}
+        q = alternate(fns, reps, R)
+        parts = ops.gather_max_attr_bwd(g, Ds[0], arg, F)[1]
+        q.update(alternate({"gatv2_datt": lambda i: ops.gatv2_datt(parts, 4)}, reps, 1))
+        feat, ent, node = 4.0 * nn_ * C, 4.0 * g.nnz, 4.0 * nn_
+        pbytes = 4.0 * parts.numel()
+        alg = {"gather_max": 3 * feat + ent + node, "fwd": 3 * feat + 5 * ent + 16.0 * C + node, "fwd-arg": 2 * feat + 5 * ent + 16.0 * C + node,
+               "gather_max_bwd": 4 * feat + ent + node, "bwd": 3 * feat + pbytes + 5 * ent + node, "bwd-P": 3 * feat + ent + node,
+               "gatv2_datt": pbytes}
+        base = {"fwd": "gather_max", "fwd-arg": "gather_max", "bwd": "gather_max_bwd", "bwd-P": "gather_max_bwd"}
+        lines.append("C=%d (%d buffer sets):" % (C, R))
+        for k in q:
+            tail = "  x%.2f of %s" % (q[k][2] / q[base[k]][2], base[k]) if k in base else ""
+            lines.append("  %-15s %s  %7.0f MB  %.2f TB/s alg = %4.1f%% of 8 TB/s%s" % (
+                k, fmt(q[k]), alg[k] / 1e6, alg[k] / q[k][2] / 1e6, alg[k] / q[k][2] / 1e6 / 8.0 * 100.0, tail))
+        lines.append("  the partials: [N / 8, 4 C] = %.0f MB (per-row partials would be %.0f MB); %.0f us = %.0f%% of bwd" % (
+            pbytes / 1e6, 8 * pbytes / 1e6, q["bwd"][2] - q["bwd-P"][2], 100.0 * (q["bwd"][2] - q["bwd-P"][2]) / q["bwd"][2]))
+        print("\n".join(lines[-(len(q) + 2):]), flush=True)
+        del B, Ds, Out, Out2, arg, parts, fns
+    out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ppf_microbench.txt")
     with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
 
